@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- scan-pairs/s of the MI355X scan-matching core on BASELINE.json's workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: under python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ..., or plainly: without a launcher the
      script starts its N ranks itself, as a child process; a launcher whose WORLD_SIZE is not N is an error)
 
@@ -11,16 +11,23 @@ frame k+1 of drive i against frame k -- the previous frame, registered as source
 the ring clouds already resident in HBM, the initial guess is the constant-velocity prediction from the drive's last two poses
 (main.cpp:311-331; the start-up guess {0,0,0,0,0,1} for a drive's first pair, main.cpp:170) -- target index build, query list and
 frame_to_frame (6 association rounds + 6 Levenberg-Marquardt solves to Ceres-default tolerances) of every pair, through ONE library
-call (velo_register_batch).  Every timed registration is a pair its context has never seen (steps x B different pairs; synth.drive:
+call (velo_register_batch).  Every timed registration of a walk is a pair its context has not seen in it (B different pairs per step; synth.drive:
 own scene, noise and speed / yaw profile per drive), so the lock-step groups diverge and the chain's launch prediction is a real
 prediction; `chain` reports its calls and misses.  `--same-pairs` re-registers B fixed pairs every step (what round 3 measured).
 The headline (`value`) is workload configs[1] of BASELINE.json: synthetic HDL-64E pairs, 64 x 1875 = 120,000 points each,
 icp_skip = 1; at N > 1 every rank registers its own pairs (replicas, no data-path collective -> "scaling": "weak").
 
-The same JSON line also carries
+A plain run sets up, warms up, times its K steps and prints the line; past 42 frames per drive (LAP_FRAMES) it walks the drives again from
+their first frame, each walk warmed up like the first, so that setting up does not grow with K.  --dump-outputs DIR writes what the last
+timed step returned (poses, solve statistics: dump_outputs) as .npy files; the inputs are seeded, so two builds compare output for output.
+
+The line carries
   roofline  the kernel with the largest share of the timed region's kernel time (HIP events on the launching stream, per kernel
             name, velo_set_timing(ctx, 2)) with its algorithmic bytes, achieved GB/s and fraction of the HBM peak; `kernels` = the
             same for the top three
+and, with --full only:
+  cpu_baseline  the CPU restatement (oracle) on the workload's first pair, all cores and one thread, with its pose against the GPU's
+  timed_pairs_vs_oracle  two timed pairs replayed through the CPU oracle;  single_pair  the latency of ONE pair in flight
   configs   short legs of the other single-GPU workloads (c1: reference constants -- on KITTI frames when VELO_KITTI_ROOT names a
             dataset root --, c3: + 2,000 stereo blocks, c4: 2M-point map shared by the B contexts, canonical_pair: the start-up-guess pair of
             rounds 1-3), each a complete bench of its own IN A CHILD PROCESS of its own, each with its cpu_baseline                (N = 1)
@@ -89,7 +96,16 @@ def parse():
     ap.add_argument("--force-device", type=int, default=None, help="testing only: every rank uses this device (with --dist-backend gloo)")
     ap.add_argument("--detail-out", default=None, help="where the FULL record of the run goes (default: bench_detail.json next to this script); stdout carries the compact line only")
     ap.add_argument("--timing", type=int, default=2, help="velo_set_timing level inside the timed region (2: per-kernel brackets; 1: association only)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the c1 / c3 / c4 / host-inputs / canonical-pair legs (N = 1), the multi-GPU mode legs (N > 1), "
+                         "the CPU baseline, the timed pairs replayed through the CPU oracle, the single-pair latency, the drives' poses against their "
+                         "simulated motion.  Without it a run sets up, warms up, times its steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float64)")
+    a = ap.parse_args()
+    if not a.full:                                           # a plain run: only what the headline needs
+        a.no_legs = a.no_cpu_baseline = a.no_oracle_check = True
+    return a
 
 
 _cache = {}
@@ -126,6 +142,9 @@ def kitti_pairs(root, n):
 
 
 _drives = {}
+# Frames per drive a run synthesises at most (drives of up to 42 frames share their scene and their first poses, see make_drives): a run
+# with more steps walks its drives again from the first frame, each walk warmed up and timed like the first one
+LAP_FRAMES = 42
 
 
 def _drive_frame_job(job):
@@ -550,19 +569,25 @@ class DriveWalker:
         return xs, Ts, Ss
 
 
-def run_leg(rig, a, workload, mode, B, steps, warmup, single_leg=True, comm="peer", drives=None):
+def run_leg(rig, a, workload, mode, B, steps, warmup, single_leg=True, comm="peer", drives=None, outputs_to=None):
     """One timed leg: `steps` steps of B registrations (B = 1 in the sharded modes) bracketed by barrier + synchronize, max over ranks.
-    drives (replicas, c1 / c2 / c3): B planned drives with their frames -- every step registers the next frame of every drive."""
+    drives (replicas, c1 / c2 / c3): B planned drives with their frames -- every step registers the next frame of every drive.
+    outputs_to: a dict that receives what the last timed step returned (poses, solve statistics) as float64 arrays."""
     import velo_amd  # noqa: F401
     from velo_amd import api
     torch = rig.torch
     world, rank = rig.world, rig.rank
     B = 1 if mode != "replicas" else max(1, B)
     drive = drives is not None and mode == "replicas" and workload in ("c1", "c2", "c3") and len(drives) >= B
+    lap_steps = steps
     if drive:
         from velo_amd import synth
         n_frames = min(len(p["frames"]) for p in drives[:B])
-        steps = max(1, min(steps, n_frames - 2 - warmup))      # (the last timed step still announces a frame: main.cpp:216 loads one per step)
+        # timed steps per walk of the drives (the last timed step still announces a frame: main.cpp:216 loads one per step).  A run with more
+        # steps than the frames allow walks the drives again from their first frame (see LAP_FRAMES); the sequence form walks once.
+        lap_steps = max(1, n_frames - 2 - warmup)
+        if getattr(a, "sequences", False) or getattr(a, "sequences_lockstep", False):
+            steps = min(steps, lap_steps)
         label, icp_skip = {
             "c1": ("configs[0] stand-in: synthetic 120k-pt drives in the KITTI ring layout, reference constants (icp_skip=200)", 200),
             "c2": ("synthetic HDL-64E 64x1875=120k-pt drives (configs[1]): frame k+1 -> frame k, icp_skip=1, point-to-plane ICP", 1),
@@ -573,7 +598,7 @@ def run_leg(rig, a, workload, mode, B, steps, warmup, single_leg=True, comm="pee
             vis_all = [[synth.stereo_matches(1000, seed=3 + 1000 * i + k, x_true=drives[i]["x_true"][k]) for k in range(n_frames - 1)] for i in range(B)]
         first_pairs = [dict(tgt_xyz=p["frames"][0][0], tgt_off=p["frames"][0][1], src_xyz=p["frames"][1][0], src_off=p["frames"][1][1],
                             x0=synth.INITIAL_GUESS.copy(), x_true=p["x_true"][0], vis=(vis_all[i][0] if vis_all else None)) for i, p in enumerate(drives[:B])]
-        W = dict(label=label, icp_skip=icp_skip, pairs=first_pairs, shared_map=False, distinct=steps * B)
+        W = dict(label=label, icp_skip=icp_skip, pairs=first_pairs, shared_map=False, distinct=min(steps, lap_steps) * B)
     else:
         W = make_workload(workload, B, a.same_pair or mode != "replicas")
     pairs, icp_skip, label = W["pairs"], W["icp_skip"], W["label"]
@@ -707,46 +732,106 @@ def run_leg(rig, a, workload, mode, B, steps, warmup, single_leg=True, comm="pee
         # (what timeit does); nothing the library does is affected.
         gc.collect()
         gc.disable()
-        for c in ctxs:
-            c.kernel_times(reset=True)                       # the per-kernel log starts with the timed region
-        chain0 = [c.chain_stats() for c in ctxs]
+        check_oracle = walker is not None and not seq and not getattr(a, "no_oracle_check", False) and rank == 0
+        need_evals = check_oracle or bool(os.environ.get("VELO_BENCH_DUMP_EVALS"))
+        tot = {"assoc_ms": 0.0, "assoc_n": 0, "alg_bytes": 0, "assoc_bytes": 0, "evals": 0}
+        kacc, chain_delta = {}, [0, 0]
+        evals_log = []                                       # per timed step and context: the evaluations of every solve
+        xs_log = []                                          # per timed step: the B solved poses (copies)
+
+        def open_lap():
+            for c in ctxs:
+                c.kernel_times(reset=True)                   # the per-kernel log starts with the timed region
+            return [c.chain_stats() for c in ctxs]
+
+        def close_lap(kept, xs_steps, chain0):
+            """off the clock: the timed steps' summaries (150 ctypes reads per step), kernel times and chain counts added up before a next
+            walk of the drives reuses the result blocks"""
+            for step_summaries in kept:
+                for s in step_summaries:
+                    tot["assoc_ms"] += s.assoc_kernel_ms
+                    tot["assoc_n"] += s.assoc_kernel_launches
+                    tot["alg_bytes"] += s.algorithmic_bytes
+                    tot["assoc_bytes"] += s.assoc_bytes
+                    tot["evals"] += sum(s.solves[k].evaluations for k in range(s.n_solves))
+                if need_evals:
+                    evals_log.append([[s.solves[k].evaluations for k in range(s.n_solves)] for s in step_summaries])
+            xs_log.extend(np.array([np.asarray(x, dtype=np.float64) for x in xs]) for xs in xs_steps)
+            for c in ctxs:
+                for name, (ms, n, b) in c.kernel_times(reset=True).items():
+                    e = kacc.setdefault(name, [0.0, 0, 0])
+                    e[0] += ms; e[1] += n; e[2] += b
+            for c, c0 in zip(ctxs, chain0):
+                c1 = c.chain_stats()
+                chain_delta[0] += c1[0] - c0[0]
+                chain_delta[1] += c1[1] - c0[1]
+
+        chain0 = open_lap()
         rig.barrier(ctxs)
-        k_timed_first = walker.k if walker is not None else 0     # the drives' frame index the timed region starts from
         t0 = time.perf_counter()
-        assoc_ms, assoc_n, alg_bytes, assoc_bytes, evals = 0.0, 0, 0, 0, 0
-        kept = []                                            # the steps' summaries: added up behind the timed region (150 ctypes reads per step)
-        xs_seq = None
+        dt = 0.0
+        timed_k = []                                         # the drives' frame each timed step registered (against the frame before it)
+        guess_first = None                                   # the guesses of the first walk, kept for the oracle replay
         if seq:
             xs_seq, Ts_seq, kept = walker.walk(prep, lockstep=getattr(a, "sequences_lockstep", False))
             for i in range(B):
                 results[i] = (xs_seq[-1][i], Ts_seq[-1][i], kept[-1][i])
+            rig.barrier(ctxs)
+            dt = rig.max_over_ranks(time.perf_counter() - t0)
+            timed_k = list(range(walker.k - steps + 1, walker.k + 1))
+            close_lap(kept, xs_seq, chain0)
         else:
-            xs_steps = []
-            for _ in range(steps):
-                step()
-                kept.append([r[2] for r in results])
-                xs_steps.append([r[0] for r in results])
-            if walker is not None:
-                xs_seq = xs_steps
-        rig.barrier(ctxs)
-        dt = rig.max_over_ranks(time.perf_counter() - t0)
-        kept_pick = {(i, f): kept[f][i] for f in range(len(kept)) for i in range(len(kept[f]))} if (walker is not None and not seq) else {}
+            done = 0
+            while True:
+                n = min(steps - done, lap_steps) if walker is not None else steps
+                kept, xs_steps = [], []
+                for _ in range(n):
+                    step()
+                    kept.append([r[2] for r in results])
+                    xs_steps.append([r[0] for r in results])
+                rig.barrier(ctxs)
+                dt += rig.max_over_ranks(time.perf_counter() - t0)
+                done += n
+                if walker is not None:
+                    timed_k.extend(range(walker.k - n + 1, walker.k + 1))
+                close_lap(kept, xs_steps, chain0)
+                if done >= steps:
+                    break
+                # more steps than the drives have frames: off the clock, the frame the last step announced is registered, the drives start
+                # again from their first frame and warm up as at the start, and the next walk's steps are timed like the first walk's
+                if guess_first is None:
+                    guess_first = walker.guess_log.copy()
+                while walker.k + 1 < walker.n_frames:
+                    walker.step()
+                walker.restart()
+                for _ in range(warmup):
+                    step()
+                chain0 = open_lap()
+                rig.barrier(ctxs)
+                t0 = time.perf_counter()
+        # what the last timed step handed its caller (--dump-outputs), copied before anything else reuses the result blocks
+        last_summaries = [r[2] for r in results]
+        n_solves_max = max(int(s.n_solves) for s in last_summaries)
+        solve_stats = np.full((B, n_solves_max, 6), np.nan)
+        for i, s in enumerate(last_summaries):
+            for k in range(s.n_solves):
+                v = s.solves[k]
+                solve_stats[i, k] = (v.termination, v.lm_iterations, v.evaluations, v.n_icp_valid, v.initial_cost, v.final_cost)
+        outputs = {"pose_x": np.array([np.asarray(r[0], dtype=np.float64) for r in results]),
+                   "pose_T": np.array([np.asarray(r[1], dtype=np.float64).reshape(4, 4) for r in results]),
+                   "solve_stats": solve_stats}
+        if walker is not None:
+            outputs["next_guess"] = np.array(walker.x0, dtype=np.float64)
+        if outputs_to is not None:
+            outputs_to.update(outputs)
         if os.environ.get("VELO_BENCH_DUMP_EVALS"):              # dev aid: evaluations per step, context and solve (what the chain's launch prediction has to guess)
-            np.save(os.environ["VELO_BENCH_DUMP_EVALS"], np.array([[[s.solves[k].evaluations for k in range(s.n_solves)] for s in ss] for ss in kept], dtype=np.int32))
-        for step_summaries in kept:
-            for s in step_summaries:
-                assoc_ms += s.assoc_kernel_ms
-                assoc_n += s.assoc_kernel_launches
-                alg_bytes += s.algorithmic_bytes
-                assoc_bytes += s.assoc_bytes
-                evals += sum(s.solves[k].evaluations for k in range(s.n_solves))
+            np.save(os.environ["VELO_BENCH_DUMP_EVALS"], np.array(evals_log, dtype=np.int32))
         # every timed registration against the drive's simulated motion (off the clock): a drive that diverged -- a bad registration feeding a
         # bad constant-velocity guess -- would change the iteration counts and still report a valid-looking rate
         truth = None
-        if walker is not None and xs_seq is not None:
-            k_first = k_timed_first
-            et = max(float(np.linalg.norm(xs_seq[f][i][3:] - np.asarray(drives[i]["x_true"][k_first + f])[3:])) for f in range(steps) for i in range(B))
-            er = max(float(np.linalg.norm(xs_seq[f][i][:3] - np.asarray(drives[i]["x_true"][k_first + f])[:3])) for f in range(steps) for i in range(B))
+        if walker is not None and xs_log and getattr(a, "full", False):
+            et = max(float(np.linalg.norm(xs_log[f][i][3:] - np.asarray(drives[i]["x_true"][timed_k[f] - 1])[3:])) for f in range(steps) for i in range(B))
+            er = max(float(np.linalg.norm(xs_log[f][i][:3] - np.asarray(drives[i]["x_true"][timed_k[f] - 1])[:3])) for f in range(steps) for i in range(B))
             truth = {"max_dt_m": et, "max_dw_rad": er, "pairs": steps * B,
                      "note": "largest difference between a timed pair's solved pose and the drive's SIMULATED relative pose: the registration's own noise "
                              "(range noise sigma = 0.02 m; 640 queries at icp_skip = 200), reported, not a pass/fail bound -- the check on the timed pairs is "
@@ -754,43 +839,39 @@ def run_leg(rig, a, workload, mode, B, steps, warmup, single_leg=True, comm="pee
         # TIMED pairs against the CPU oracle (off the clock): the frames a timed step registered -- loaded ahead behind the previous chain, the
         # target promoted by buffer rotation -- and the guess it started from, replayed through the oracle.  north_star: 1e-4 m / 1e-5 rad.
         vs_oracle = None
-        if walker is not None and xs_seq is not None and not seq and not getattr(a, "no_oracle_check", False) and rank == 0:
+        if check_oracle:
             import oracle_lib
-            k_first = k_timed_first
-            picks = sorted({(min(3, B - 1), min(7, steps - 1)), (min(6, B - 1), min(15, steps - 1))})
+            n_first = min(steps, lap_steps)                      # (picked from the first walk of the drives)
+            guesses = guess_first if guess_first is not None else walker.guess_log
+            picks = sorted({(min(3, B - 1), min(7, n_first - 1)), (min(6, B - 1), min(15, n_first - 1))})
             worst_t = worst_r = 0.0
             counts_equal, which = True, []
             for (i, f) in picks:
-                kk = k_first + f + 1                             # the step that registered frame kk against frame kk - 1
+                kk = timed_k[f]                                  # the step that registered frame kk against frame kk - 1
                 o = oracle_lib.Oracle(threads=oracle_lib.max_threads(), icp_skip=icp_skip)
                 o.set_target(*drives[i]["frames"][kk - 1])
                 o.set_source(*drives[i]["frames"][kk])
                 if vis_all is not None:
                     o.set_visual(vis_all[i][kk - 1])
-                xo, _To, so = o.frame_to_frame(walker.guess_log[kk][i])
-                xg, sg = np.asarray(xs_seq[f][i]), kept_pick[(i, f)]
+                xo, _To, so = o.frame_to_frame(guesses[kk][i])
+                xg = xs_log[f][i]
                 worst_t = max(worst_t, float(np.linalg.norm(xo[3:] - xg[3:])))
                 worst_r = max(worst_r, float(np.linalg.norm(xo[:3] - xg[:3])))
-                counts_equal = counts_equal and [sg.solves[j].evaluations for j in range(sg.n_solves)] == [so.solves[j].evaluations for j in range(so.n_solves)]
+                counts_equal = counts_equal and evals_log[f][i] == [so.solves[j].evaluations for j in range(so.n_solves)]
                 which.append(f"drive {i} timed step {f}")
             vs_oracle = {"dt_m": worst_t, "dw_rad": worst_r, "counts_equal": bool(counts_equal), "pairs": len(picks), "which": which,
                          "ok": bool(worst_t <= 1e-4 and worst_r <= 1e-5),
                          "note": "timed pairs replayed through the CPU oracle on the same two frames and the same guess; bound = north_star's 1e-4 m / 1e-5 rad"}
             if not vs_oracle["ok"]:
                 raise RuntimeError(f"timed pairs differ from the oracle beyond the north_star tolerance: {vs_oracle}")
-        del kept
-        chain1 = [c.chain_stats() for c in ctxs]
-        kacc = {}
-        for c in ctxs:
-            for name, (ms, n, b) in c.kernel_times(reset=True).items():
-                e = kacc.setdefault(name, [0.0, 0, 0])
-                e[0] += ms; e[1] += n; e[2] += b
+        assoc_ms, assoc_n, alg_bytes, assoc_bytes, evals = tot["assoc_ms"], tot["assoc_n"], tot["alg_bytes"], tot["assoc_bytes"], tot["evals"]
         solutions = [[float(v) for v in r[0]] for r in results]
         first_pair_solutions = [[float(v) for v in x] for x in walker.first] if (walker is not None and walker.first is not None) else None
 
-        if walker is not None and not seq and walker.k + 1 < walker.n_frames:
-            # off the clock and behind the kernel log's read-out: the frame the last timed step announced and loaded ahead is registered by one more step (the drive's last frame:
-            # nothing announced behind it), so that the contexts hold no frame loaded ahead when the single-pair walk restarts them
+        while walker is not None and not seq and walker.k + 1 < walker.n_frames:
+            # off the clock and behind the kernel log's read-out: the frame the last timed step announced and loaded ahead is registered, and
+            # so is every frame after it up to the drive's last (nothing announced behind that one), so that the contexts hold no frame loaded
+            # ahead when the single-pair walk restarts them -- one step when the timed steps ended a walk, more when they ended inside one
             walker.step()
         single = None
         if single_leg and world == 1 and walker is not None and B > 1 and walker.n_frames >= 8:
@@ -839,7 +920,7 @@ def run_leg(rig, a, workload, mode, B, steps, warmup, single_leg=True, comm="pee
             one_pair(0, 0)                                   # context 0 holds its own pair again
 
         shared = None
-        if W["shared_map"] and mode == "replicas" and B > 1 and a.batch_api:
+        if W["shared_map"] and mode == "replicas" and B > 1 and a.batch_api and getattr(a, "full", False):
             # the other way of holding the map, next to the timed one (shared by default; see use_shared)
             refs_sh = (api.scan_refs([tgts[0]] * B, rig.local_rank, shared=not use_shared), batch_refs[1])
             for _ in range(2):
@@ -880,7 +961,7 @@ def run_leg(rig, a, workload, mode, B, steps, warmup, single_leg=True, comm="pee
             "valid_correspondences_last_round": int(s0.solves[s0.n_solves - 1].n_icp_valid),
             "algorithmic_bytes_per_pair": per_pair_bytes,
             "achieved_hbm_GBs_whole_path": per_pair_bytes * (total_pairs / dt) / 1e9,
-            "chain": {"calls": sum(b[0] - a_[0] for a_, b in zip(chain0, chain1)), "misses": sum(b[1] - a_[1] for a_, b in zip(chain0, chain1)),
+            "chain": {"calls": chain_delta[0], "misses": chain_delta[1],
                       "note": "calls enqueued as one chain of launches / calls whose predicted launch count was too short and were repeated host-driven"},
             "roofline": rf,
             "kernels": ktab[:3],
@@ -912,6 +993,15 @@ def run_leg(rig, a, workload, mode, B, steps, warmup, single_leg=True, comm="pee
             c.close()
         dev_of.clear()
         torch.cuda.empty_cache()
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs DIR: what the last timed step returned to its caller, one float64 .npy per array (a few KB in all): pose_x (B, 6) and
+    pose_T (B, 4, 4) of every pair, solve_stats (B, solves, 6: termination, LM iterations, evaluations, valid ICP correspondences, initial
+    and final cost; NaN where a pair ran fewer solves) and, for the drives, next_guess (B, 6), the constant-velocity guess of the next frame"""
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def self_launch(a):
@@ -950,11 +1040,18 @@ def main():
             os.environ["VELO_DRIVE_CACHE"] = tempfile.mkdtemp(prefix="velo_drives_")
             a._own_cache = os.environ["VELO_DRIVE_CACHE"]
         # frames per drive: 1 held at the start + one per warm-up and timed step + ONE MORE, so that the last timed step announces and loads its
-        # next frame like every other (round 5 timed 19 frame loads for 20 steps)
-        drives = make_drives(max(1, a.batch), a.warmup + a.steps + 2, a.gen_procs)
+        # next frame like every other (round 5 timed 19 frame loads for 20 steps) -- at most LAP_FRAMES of them (or warm-up + 3): a longer run
+        # walks the drives again from their first frame, so that setting up does not grow with --steps
+        n_frames = a.warmup + a.steps + 2
+        if n_frames > LAP_FRAMES and not (a.sequences or a.sequences_lockstep):
+            n_frames = max(LAP_FRAMES, a.warmup + 3)
+        drives = make_drives(max(1, a.batch), n_frames, a.gen_procs)
     rig = Rig(a)
     world, rank = rig.world, rig.rank
-    main_leg = run_leg(rig, a, a.workload, a.mode, a.batch, a.steps, a.warmup, comm=a.comm, drives=drives)
+    outputs = {}
+    main_leg = run_leg(rig, a, a.workload, a.mode, a.batch, a.steps, a.warmup, single_leg=a.full, comm=a.comm, drives=drives, outputs_to=outputs)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, outputs)
     legs, modes = {}, {}
     if not a.no_legs:
         if world == 1 and a.mode == "replicas":
@@ -972,7 +1069,7 @@ def main():
                 fd, dpath = tempfile.mkstemp(prefix=f"velo_leg_{workload}_", suffix=".json")
                 os.close(fd)
                 cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", workload, "--steps", str(steps), "--warmup", str(warmup), "--batch", str(a.batch),
-                       "--timing", str(a.timing), "--no-legs", "--no-cpu-baseline", "--detail-out", dpath, *extra]
+                       "--timing", str(a.timing), "--full", "--no-legs", "--no-cpu-baseline", "--detail-out", dpath, *extra]
                 try:
                     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
                     rows = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")]
@@ -1114,7 +1211,7 @@ def main():
                       "committed PMC passes of this same command (profiles/*_traffic.json: FETCH_SIZE x 2 + WRITE_SIZE, separate passes, the bench's "
                       "own pairs in flight; rocprofv3 serialises the dispatches while it counts), or null when that instantiation was not measured")
         single = main_leg.get("single_pair")
-        if sq and sq.get("SQ_INSTS_VALU"):
+        if sq and sq.get("SQ_INSTS_VALU") and single is not None:        # (the launch time alone comes from the single-pair leg: --full)
             t_alone = (single or {}).get("assoc_avg_launch_us", 0.0) * 1e-6
             rf["valu"] = {"kernel": "assoc_search_v5_kernel", "wave_insts_per_launch": sq["SQ_INSTS_VALU"], "salu": sq.get("SQ_INSTS_SALU"), "lds": sq.get("SQ_INSTS_LDS"),
                           "issue_slots_per_launch_at_2p4GHz": 1024 * 2.4e9 / 2 * t_alone,

@@ -56,6 +56,28 @@ def test_bench_does_not_import_torch_before_launching():
     assert out.returncode == 0, out.stderr[-500:]
 
 
+def test_plain_run_leaves_the_extras_to_full(monkeypatch):
+    """a plain run does what its headline needs; the legs, the CPU baseline and the oracle replay come with --full"""
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = b.parse()
+    assert not a.full and a.no_legs and a.no_cpu_baseline and a.no_oracle_check and a.dump_outputs is None and a.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--full", "--dump-outputs", "out"])
+    a = b.parse()
+    assert a.full and not (a.no_legs or a.no_cpu_baseline or a.no_oracle_check) and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_one_float64_file_per_array(tmp_path):
+    import numpy as np
+    b = _bench()
+    outs = {"pose_x": np.arange(48, dtype=np.float64).reshape(8, 6), "solve_stats": np.full((8, 6, 6), np.nan)}
+    b.dump_outputs(str(tmp_path / "d"), outs)
+    assert sorted(os.listdir(tmp_path / "d")) == ["pose_x.npy", "solve_stats.npy"]
+    for name, want in outs.items():
+        got = np.load(tmp_path / "d" / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, want, equal_nan=True)
+
+
 def _fat_leg(name, with_cpu=True):
     """a leg as run_leg / child_leg return it, with everything that made round 5's line 20 KB: notes, kernel tables, poses of every context"""
     rf = {"kernel": f"{name}_dominant_kernel", "share": 0.5612345678, "launches": 3100, "avg_launch_us": 27.123456789, "algorithmic_bytes_per_launch": 5109440.0,

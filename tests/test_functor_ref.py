@@ -1,11 +1,12 @@
 """Rows R1-R5 of SURVEY.md 8(a) (and the triangulation functors of 8(f) row 4) against vectors produced FROM THE REFERENCE'S OWN FUNCTOR
-TEXT: tests/golden/functors_ref.npz, made by tests/golden/make_functor_ref.py, which reads /root/reference/costfunctions.h at run time,
+TEXT: tests/golden/functors_ref.npz, made by tests/golden/make_functor_ref.py, which reads the reference's costfunctions.h at run time,
 turns every operator() body into Python statement by statement and evaluates it in double (Jacobians by complex step).  This is the one
 place where the oracle and the HIP path are held to something the reference itself wrote, not to this repository's reading of it;
 ceres::AngleAxisRotatePoint stays [3P] (restated from Ceres' published rotation.h in the generating script).
 
   CPU, everywhere        the oracle's functors (values + dual-number Jacobians) equal the fixture;
-  CPU, authoring box     the committed fixture is bit for bit what the script produces from the reference today;
+  CPU, everywhere        the committed fixture is bit for bit what the script produced from the reference (digests recorded in
+                         tests/golden/reference_facts.json);
   GPU                    velo_evaluate_functors (seam 2) equals the fixture."""
 import os
 import sys
@@ -48,19 +49,23 @@ def test_oracle_triangulation_functors_equal_the_reference_derived_vectors():
         assert _rel(ro, r[:d]) <= 1e-14 and _rel(Jo, J[:d]) <= 1e-13, (bool(is3d), cam)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/costfunctions.h"), reason="the reference checkout is not on this box")
 def test_committed_fixture_is_what_the_reference_text_yields_today():
+    """the committed fixture is, array for array, what make_functor_ref.py produced from costfunctions.h when the reference was last read
+    (tests/golden/reference_facts.json, made and re-checked by tests/golden/make_reference_facts.py)"""
+    import json
     sys.path.insert(0, os.path.join(HERE, "golden"))
-    import make_functor_ref as M
-    fresh = M.generate()
+    import make_reference_facts as R
+    facts = json.load(open(os.path.join(HERE, "golden", "reference_facts.json")))
+    fresh = facts["functor_vector_digests"]
     z = np.load(FIX)
     assert set(fresh) == set(z.files)
     for k in z.files:
-        assert np.array_equal(np.asarray(fresh[k]), z[k]), k
+        assert R.array_digest(z[k]) == fresh[k], k
     # the transpiler saw what it should: seven functors, the frame ones with the parameter counts of costfunctions.h:19-28,58-64,89-97,128-136,170-177
-    parsed = M.parse_functors(open(M.REF_HEADER).read())
-    assert {n: len(parsed[n][0]) for n in M.FRAME_FUNCTORS} == {"cost3D3D": 6, "cost3D2D": 8, "cost2D3D": 8, "cost2D2D": 7, "cost3DPD": 9}
-    assert len(parsed["triangulation2D"][0]) == 11 and len(parsed["triangulation3D"][0]) == 9
+    parsed = facts["functor_parameter_counts"]
+    import make_functor_ref as M
+    assert {n: parsed[n] for n in M.FRAME_FUNCTORS} == {"cost3D3D": 6, "cost3D2D": 8, "cost2D3D": 8, "cost2D2D": 7, "cost3DPD": 9}
+    assert parsed["triangulation2D"] == 11 and parsed["triangulation3D"] == 9
 
 
 def test_transpiler_refuses_anything_but_arithmetic():

@@ -14,11 +14,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.timeout(900)
 def test_single_gpu_bench_line_meets_the_contract(hip_lib, tmp_path):
-    # the driver's command shape WITH the legs (their steps capped): round 5's line was only ever checked with --no-legs, grew to 20 KB with
-    # them and the driver could not parse it (BENCH_r05.json: parsed null)
+    # the driver's command shape WITH the legs (--full, their steps capped): round 5's line was only ever checked with --no-legs, grew to 20 KB
+    # with them and the driver could not parse it (BENCH_r05.json: parsed null)
     detail = tmp_path / "detail.json"
     env = dict(os.environ, VELO_DRIVE_CACHE=str(tmp_path), VELO_BENCH_LEG_STEPS="3")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--detail-out", str(detail)],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--full", "--detail-out", str(detail)],
                          capture_output=True, text=True, timeout=850, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     all_lines = out.stdout.strip().splitlines()

@@ -24,7 +24,7 @@ def _free_port():
 def test_two_rank_bench_line_reports_both_sharded_modes(hip_lib):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--dist-backend", "gloo", "--force-device", "0", "--no-cpu-baseline"]
+           "--dist-backend", "gloo", "--force-device", "0", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     text = out.stdout.strip().splitlines()[-1]
@@ -55,7 +55,7 @@ def test_bench_starts_its_own_ranks_when_no_launcher_wraps_it(hip_lib):
     never measure one GPU and print n_gpus: 1)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--force-device", "0", "--dist-backend", "gloo",
-           "--steps", "4", "--warmup", "1", "--no-cpu-baseline"]
+           "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     text = out.stdout.strip().splitlines()[-1]
@@ -73,7 +73,7 @@ def test_eight_rank_bench_line_is_one_small_line(hip_lib):
     (BENCH_r05.json: parsed null was a line that had outgrown the driver), with both modes' communicators reporting eight ranks."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--force-device", "0", "--dist-backend", "gloo",
-           "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-oracle-check"]
+           "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-oracle-check", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=850, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     rows = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")]

@@ -1,30 +1,26 @@
-"""CPU, in the authoring container only: row P1 of SURVEY.md 8(a) -- the constants the path reads -- checked against the REFERENCE'S OWN
-TEXT (/root/reference/kitti.h:3-35, main.cpp:170, lru.h:5-6) instead of against this repository's recollection of it.  The reference is
-read at test time and nothing of it is kept here; on a box without /root/reference (the GPU box) the tests skip -- the same constants are
-held together by tests/test_abi.py::test_default_params_match_header_python_and_oracle everywhere."""
+"""CPU: row P1 of SURVEY.md 8(a) -- the constants the path reads -- checked against the REFERENCE'S OWN TEXT (kitti.h:3-35, main.cpp:170,
+lru.h:5-6) instead of against this repository's recollection of it.  The reference is not part of this repository: what its text says is
+recorded as data in tests/golden/reference_facts.json by tests/golden/make_reference_facts.py (which re-reads a checkout of it with
+--check); the same constants are held together by tests/test_abi.py::test_default_params_match_header_python_and_oracle as well."""
+import json
 import os
-import re
 
 import numpy as np
-import pytest
 
 import oracle_lib as ol
 import velo_amd  # noqa: F401
 from velo_amd import api, odometry, synth
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(REF, "kitti.h")), reason="the reference checkout is not on this box")
+FACTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_facts.json")
+
+
+def _facts():
+    return json.load(open(FACTS))
 
 
 def _constants():
-    """`name = value` pairs of the two constant lists at the top of kitti.h (const int ...; const double ...;)."""
-    text = open(os.path.join(REF, "kitti.h")).read()
-    out = {}
-    for block in re.findall(r"const\s+(?:int|double)\s+(.*?);", text, flags=re.S):
-        block = re.sub(r"//[^\n]*", "", block)
-        for name, value in re.findall(r"(\w+)\s*=\s*([-+0-9.eE]+)", block):
-            out[name] = float(value)
-    return out
+    """`name = value` pairs of the two constant lists at the top of kitti.h (const int ...; const double ...;), as recorded."""
+    return _facts()["kitti_constants"]
 
 
 def test_default_params_are_the_references_constants():
@@ -41,23 +37,18 @@ def test_default_params_are_the_references_constants():
 
 
 def test_start_up_guess_and_cache_capacity_are_the_references():
-    main = open(os.path.join(REF, "main.cpp")).read()
-    m = re.search(r"double\s+transform\[6\]\s*=\s*\{([^}]*)\}", main)
-    assert m, "main.cpp no longer declares the start-up transform"
-    guess = [float(v) for v in m.group(1).split(",")]
+    F = _facts()
+    guess = F["startup_transform"]
     assert guess == list(synth.INITIAL_GUESS) == list(odometry.FIRST_GUESS)        # main.cpp:170
-    lru = open(os.path.join(REF, "lru.h")).read()
-    m = re.search(r"class\s+ScansLRU\s*\{.*?const\s+int\s+size\s*=\s*(\d+)", lru, flags=re.S)      # lru.h:33
-    assert m, "lru.h no longer declares ScansLRU::size"
+    size = F["scans_lru_size"]                                                      # lru.h:33, ScansLRU::size
     import inspect
-    assert inspect.signature(api.ScanCache.__init__).parameters["capacity"].default == int(m.group(1)) == 50
-    assert inspect.signature(odometry.LidarOdometer.__init__).parameters["cache_capacity"].default == int(m.group(1))
+    assert inspect.signature(api.ScanCache.__init__).parameters["capacity"].default == size == 50
+    assert inspect.signature(odometry.LidarOdometer.__init__).parameters["cache_capacity"].default == size
 
 
 def test_velo_h_gates_the_squared_distance_by_iter_to_the_fourth():
     """velo.h:829: the correspondence gate is correspondence_thresh_icp / iter^4 on the SQUARED distance -- the line itself."""
-    velo = open(os.path.join(REF, "velo.h")).read()
-    assert re.search(r"correspondence_thresh_icp\s*/\s*iter\s*/\s*iter\s*/\s*iter\s*/\s*iter", velo)
+    assert _facts()["as_written"]["icp_gate_divides_by_iter_four_times"] is True
     d = synth.scan_pair(n_beams=8, n_azimuth=64)
     o = ol.Oracle(icp_skip=1)
     o.set_target(d["tgt_xyz"], d["tgt_off"])

@@ -16,6 +16,7 @@ for w in c2 c1 c3 c4; do
 done
 mkdir -p $R/gpurun_out/${TAG}_profiles
 cp $R/profiles/${TAG}* $R/gpurun_out/${TAG}_profiles/ 2>/dev/null
-cd $R && python3 bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
-tail -2 gpurun_out/${TAG}_bench.err
+OUT=$(dirname "$(ls -d $R/*/${TAG}_profiles | head -1)")     # the folder the profiles were copied to, above
+cd $R && python3 bench.py --steps 20 --warmup 5 --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+tail -2 $OUT/${TAG}_bench.err
 du -sh gpurun_out
