@@ -506,6 +506,26 @@ int velo_triangulate_points(velo_ctx* ctx, const double* camera_poses, int32_t n
                             const velo_tri_obs* obs, const int32_t* obs_offsets, int32_t n_landmarks, float* points_xyz,
                             const uint8_t* initial_guess, velo_tri_result* results);
 
+/* --- descriptor matching: matchFeatures (velo.h:499-560), the stage the reference runs on cv::cuda (USE_CUDA, velo.h:517-525) ----
+ * One job = one (query set, train set) pair of 64-byte descriptors (FREAK, 512 bits), rows contiguous.  Per job, like
+ * cv::BFMatcher(NORM_HAMMING).match and the filter after it (velo.h:527-549):
+ *   train_idx[q] / distance[q]: the train row t with the smallest popcount(query[q] ^ train[t]), the LOWEST t on ties (the strict `<`
+ *       of cv::BFMatcher); -1 / -1 when the job's train set is empty.
+ *   min_dist: the smallest distance of the job (-1 when it has no match: an empty set; the reference's 1e9 then filters nothing).
+ *   kept pairs (queryIdx, trainIdx), query order: distance <= max(1.5 * min_dist, match_thresh) (kitti.h:27: match_thresh = 29).
+ * Outputs: train_idx / distance [sum n_query] (job-major, query order); min_dist / n_kept [n_jobs]; pairs [sum n_query][2], job j's
+ * kept pairs starting at pair sum(n_kept[0..j-1]).  Every job of a call goes through ONE upload (a set named by several jobs --
+ * the same pointer and row count -- travels once), one launch set and one copy back.  Train sets hold at most 2^22 rows.  The
+ * context's registration state is untouched. */
+typedef struct velo_desc_job {
+    const uint8_t* query;   /* n_query x 64 bytes */
+    int32_t n_query;
+    const uint8_t* train;   /* n_train x 64 bytes */
+    int32_t n_train;
+} velo_desc_job;
+int velo_match_descriptors(velo_ctx* ctx, const velo_desc_job* jobs, int32_t n_jobs, double match_thresh,
+                           int32_t* train_idx, int32_t* distance, int32_t* min_dist, int32_t* n_kept, int32_t* pairs);
+
 #ifdef __cplusplus
 }
 #endif

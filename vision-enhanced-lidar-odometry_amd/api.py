@@ -62,6 +62,11 @@ VELO_MAX_STATS = 4
 RESIDUAL_TYPE_NAMES = ("3D3D", "3D2D", "2D3D", "2D2D", "3DPD")
 
 
+class VeloDescJob(C.Structure):
+    """velo_desc_job: one (query, train) pair of 64-byte descriptor sets"""
+    _fields_ = [("query", C.c_void_p), ("n_query", C.c_int32), ("train", C.c_void_p), ("n_train", C.c_int32)]
+
+
 class VeloResidualStat(C.Structure):
     _fields_ = [("median", C.c_double), ("mean", C.c_double), ("count", C.c_int64)]
 
@@ -233,6 +238,8 @@ SIGNATURES = {
     "velo_depth_association": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, _P(C.c_int32)]),
     "velo_triangulate_points": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "velo_match_descriptors": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
 }
 
 _lib = None
@@ -581,6 +588,58 @@ class Context:
         self._check(self._lib.velo_triangulate_points(self._h, vp(poses), len(poses), vp(ct), len(ct), vp(ob), vp(off), n,
                                                       vp(pts), vp(init), vp(res)))
         return pts, res
+
+    # -- descriptor matching: matchFeatures (velo.h:499-560) ----------------------------------------------------
+    def match_descriptors(self, query, train, match_thresh: float = 29.0):
+        """BFMatcher(NORM_HAMMING).match + the velo.h:536-549 filter for one (query, train) pair of uint8 (n, 64) arrays:
+        (train_idx [nq] i32, distance [nq] i32, min_dist int, pairs [k, 2] i32 (queryIdx, trainIdx))."""
+        idx, dist, md, pairs = self.match_descriptor_jobs([(query, train)], match_thresh)
+        return idx[0], dist[0], int(md[0]), pairs[0]
+
+    def match_descriptor_jobs(self, jobs, match_thresh: float = 29.0):
+        """Every (query, train) pair of `jobs` in ONE call (one upload, one launch set, one copy back; a set passed as the same array
+        object to several jobs travels once): per job lists (train_idx [nq], distance [nq]), min_dist [n_jobs] i32 (-1: no match) and
+        a list of the kept (queryIdx, trainIdx) pairs [k, 2]."""
+        sets = {}                                             # id(array) -> contiguous uint8 (n, 64): the C side dedupes by pointer
+        held = []
+
+        def rows(a):
+            key = id(a)
+            if key not in sets:
+                arr = np.ascontiguousarray(np.asarray(a, dtype=np.uint8))
+                if arr.size == 0:
+                    arr = arr.reshape(0, 64)
+                if arr.ndim != 2 or arr.shape[1] != 64:
+                    raise ValueError(f"descriptors must be uint8 (n, 64), got shape {arr.shape}")
+                sets[key] = arr
+                held.append(a)                                # ids stay unique while the call runs
+            return sets[key]
+
+        n_jobs = len(jobs)
+        arr = (VeloDescJob * max(n_jobs, 1))()
+        nqs = []
+        for j, (q, t) in enumerate(jobs):
+            qa, ta = rows(q), rows(t)
+            arr[j].query = qa.ctypes.data if len(qa) else None
+            arr[j].n_query = len(qa)
+            arr[j].train = ta.ctypes.data if len(ta) else None
+            arr[j].n_train = len(ta)
+            nqs.append(len(qa))
+        nq = int(sum(nqs))
+        idx = np.full(max(nq, 1), -1, dtype=np.int32)
+        dist = np.full(max(nq, 1), -1, dtype=np.int32)
+        pairs = np.zeros((max(nq, 1), 2), dtype=np.int32)
+        md = np.full(max(n_jobs, 1), -1, dtype=np.int32)
+        nk = np.zeros(max(n_jobs, 1), dtype=np.int32)
+        vp = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+        self._check(self._lib.velo_match_descriptors(self._h, C.cast(arr, C.c_void_p), n_jobs, float(match_thresh), vp(idx), vp(dist),
+                                                     vp(md), vp(nk), vp(pairs)))
+        q_off = np.concatenate([[0], np.cumsum(nqs)]).astype(np.int64)
+        k_off = np.concatenate([[0], np.cumsum(nk[:n_jobs])]).astype(np.int64)
+        idx_l = [idx[q_off[j]:q_off[j + 1]].copy() for j in range(n_jobs)]
+        dist_l = [dist[q_off[j]:q_off[j + 1]].copy() for j in range(n_jobs)]
+        pairs_l = [pairs[k_off[j]:k_off[j + 1]].copy() for j in range(n_jobs)]
+        return idx_l, dist_l, md[:n_jobs].copy(), pairs_l
 
     # -- multi-GPU -------------------------------------------------------------------------------------------
     def set_query_shard(self, rank: int, world: int):

@@ -38,6 +38,7 @@ int velo_create(velo_ctx** out, int device) {
         if (const char* e = dev_env("VELO_ASSOC_VARIANT")) c->assoc_variant = atoi(e);
         if (const char* e = dev_env("VELO_CLUSTER_W")) { c->cluster_w = std::max(atoi(e), 0); c->cluster_w_set = true; }
         if (const char* e = dev_env("VELO_TRI_VARIANT")) c->tri_variant = atoi(e);
+        if (const char* e = dev_env("VELO_MATCH_VARIANT")) c->match_variant = atoi(e);
 #ifdef VELO_DIAGNOSTICS
         if (dev_env("VELO_LM_TRACE") && atoi(dev_env("VELO_LM_TRACE"))) {
             c->lm_trace_on = true;
@@ -184,6 +185,9 @@ int velo_destroy(velo_ctx* c) {
     if (c->h_status) (void)hipHostFree(c->h_status);
     if (c->h_x) (void)hipHostFree(c->h_x);
     if (c->h_int) (void)hipHostFree(c->h_int);
+    c->md_in.release(); c->md_keys.release(); c->md_out.release();
+    if (c->h_md_in) (void)hipHostFree(c->h_md_in);
+    if (c->h_md_out) (void)hipHostFree(c->h_md_out);
     for (auto& ps : c->pin) { if (ps.ev) (void)hipEventDestroy(ps.ev); if (ps.p) (void)hipHostFree(ps.p); }
     if (c->src_bbox_ev) (void)hipEventDestroy(c->src_bbox_ev);
     if (c->ev0) (void)hipEventDestroy(c->ev0);

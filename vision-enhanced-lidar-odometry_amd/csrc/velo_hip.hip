@@ -36,6 +36,7 @@
 #include "velo_kernels.h"
 #include "velo_depth_kernels.h"
 #include "velo_tri_kernels.h"
+#include "velo_match_kernels.h"
 
 using namespace velo;
 
@@ -58,3 +59,4 @@ extern "C" int velo_launch_lm_solve_ag(int nb_max, int n, void* stream, const vo
 #include "velo_host_batch.inl"   // the lock-step batch driver: group association launches, the next frame loaded behind the chain, f2f_batch_lockstep, jobs, sequences, velo_register_*
 #include "velo_api_pose_comm.inl"   // C-ABI: pose helpers and hand-off, the communicators (RCCL, peer slabs), shards, synchronize
 #include "velo_api_next_rows.inl"   // C-ABI: SURVEY 8(f) rows 3 and 4 -- projection, keypoint depth, batched triangulation
+#include "velo_api_match.inl"   // C-ABI: batched Hamming matching of 64-byte descriptors (matchFeatures, velo.h:499-560)

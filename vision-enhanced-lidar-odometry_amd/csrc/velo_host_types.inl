@@ -378,6 +378,16 @@ struct velo_ctx {
     DevBuf<velo_tri_result> tri_res;
     int tri_variant = 1;                 // 1 = one wave per landmark (default), 0 = one thread per landmark (VELO_TRI_VARIANT)
 
+    // descriptor matching (velo_match_descriptors): buffers of its own, which no registration reads or writes
+    DevBuf<unsigned char> md_in;         // one staged upload: job table | the distinct descriptor rows (64 bytes each)
+    DevBuf<unsigned> md_keys;            // [sum n_query] nearest-row keys | [n_jobs] min_dist
+    DevBuf<int> md_out;                  // train_idx | distance | pairs (per job from its first query) | {min_dist, n_kept} per job
+    unsigned char* h_md_in = nullptr;    // pinned staging of md_in
+    size_t h_md_in_cap = 0;
+    int* h_md_out = nullptr;             // pinned landing of md_out
+    size_t h_md_out_cap = 0;
+    int match_variant = 1;               // 1 = int8 MFMA (product), 0 = XOR + popcount (VELO_MATCH_VARIANT, diagnostics build only)
+
     // lock-step batch driver (velo_frame_to_frame_batch): scratch owned by the FIRST context of a batch
     DevBuf<LMBatchItem> batch_items;
     DevBuf<PoseRecord> batch_pose;       // chain mode of the lock-step driver: per-context records, logs, failure flags

@@ -1,0 +1,11 @@
+// velo_unit_match.hip -- the translation unit that DEFINES the kernels of the VELO_DEF_MATCH family (velo_match_kernels.h: batched Hamming
+// matching of 64-byte descriptors): their device code is generated here and nowhere else; velo_hip.hip (the host side of the C-ABI) sees
+// declarations and launches through the host stubs this unit exports.  No host logic lives here.
+#include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+#include <stdint.h>
+
+#include "../../include/velo_hip.h"
+
+#define VELO_DEF_MATCH 1
+#include "velo_match_kernels.h"
