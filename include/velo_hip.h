@@ -526,6 +526,42 @@ typedef struct velo_desc_job {
 int velo_match_descriptors(velo_ctx* ctx, const velo_desc_job* jobs, int32_t n_jobs, double match_thresh,
                            int32_t* train_idx, int32_t* distance, int32_t* min_dist, int32_t* n_kept, int32_t* pairs);
 
+/* --- feature tracking: trackFeatures (velo.h:28-116), cv::calcOpticalFlowPyrLK four times per frame (main.cpp:220-245) -------------
+ * Resident images: every context holds two image slots per camera, current and previous.  velo_set_images turns the current images
+ * into the previous ones (a buffer rotation, no copy), uploads the new 8-bit grayscale frames (n_cams <= 8, all width x height,
+ * rows `stride` bytes apart) in one copy and builds on the device each image's pyramid (cv::pyrDown, reflect-101) and the Scharr
+ * derivatives of every level (calcSharrDeriv), which tracking reads once the image has become the previous one.  The levels kept are
+ * those a 5-wide window would build, at most 7; every level is stored padded by 32 pixels (image reflect-101, derivatives zero).
+ * The call is asynchronous (the next call on the context's stream waits for it).  The registration state is untouched. */
+int velo_set_images(velo_ctx* ctx, const uint8_t* const* imgs, int32_t n_cams, int32_t width, int32_t height, int32_t stride);
+/* Read-back of one padded level: kind 0 = image (uint8), 1 = dx, 2 = dy (int16); (height + 2 pad) x (width + 2 pad) values, row-major.
+ * dims[4] receives the level's width, height, pad and the number of stored levels; out == NULL fills dims only. */
+int velo_get_image_level(velo_ctx* ctx, int32_t cam, int32_t previous, int32_t level, int32_t kind, void* out, int64_t capacity_bytes,
+                         int32_t* dims);
+/* One job tracks n points (pixels, [n][2] floats) from the PREVIOUS image of prev_cam into the CURRENT image of cam, like
+ * calcOpticalFlowPyrLK(img_prev, img, points1, points2, status, err, Size(window, window), max_level,
+ * TermCriteria(COUNT | EPS, max_count, epsilon), 0, min_eig_threshold).  Outputs, job-major in job order: next_xy [sum n][2],
+ * status [sum n] (calcOpticalFlowPyrLK's), kept [sum n] = the filters of velo.h:72-84: status set, util::dist2(p1, p2) (float
+ * arithmetic, compared as double) <= flow_outlier, and p2 inside [0, width) x [0, height).  All jobs of a call share one upload,
+ * one launch and one copy back.  The window sums are exact (int64) and rounded once to float. */
+typedef struct velo_track_job {
+    int32_t prev_cam;
+    int32_t cam;
+    const float* prev_xy;   /* n x 2 floats, pixels */
+    int32_t n;
+} velo_track_job;
+typedef struct velo_lk_params {
+    int32_t window;             /* odd, 5..31 (kitti.h:5: 21) */
+    int32_t max_level;          /* 0..7 (kitti.h:6: 4) */
+    int32_t max_count;          /* 0..100 (velo.h:64: 30) */
+    int32_t reserved;
+    double epsilon;             /* velo.h:65: 0.01 (compared squared, like OpenCV) */
+    double min_eig_threshold;   /* OpenCV's default 1e-4 */
+    double flow_outlier;        /* kitti.h:17: 20000 (pixels^2) */
+} velo_lk_params;
+int velo_track_features(velo_ctx* ctx, const velo_track_job* jobs, int32_t n_jobs, const velo_lk_params* p, float* next_xy,
+                        uint8_t* status, uint8_t* kept);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,25 @@ class VeloDescJob(C.Structure):
     _fields_ = [("query", C.c_void_p), ("n_query", C.c_int32), ("train", C.c_void_p), ("n_train", C.c_int32)]
 
 
+class VeloTrackJob(C.Structure):
+    """velo_track_job: n points tracked from the previous image of prev_cam into the current image of cam"""
+    _fields_ = [("prev_cam", C.c_int32), ("cam", C.c_int32), ("prev_xy", C.c_void_p), ("n", C.c_int32)]
+
+
+class VeloLkParams(C.Structure):
+    """velo_lk_params: calcOpticalFlowPyrLK's window, levels and termination as trackFeatures uses them (kitti.h:5-6,17; velo.h:60-67)"""
+    _fields_ = [("window", C.c_int32), ("max_level", C.c_int32), ("max_count", C.c_int32), ("reserved", C.c_int32),
+                ("epsilon", C.c_double), ("min_eig_threshold", C.c_double), ("flow_outlier", C.c_double)]
+
+
+def lk_params(window: int = 21, max_level: int = 4, max_count: int = 30, epsilon: float = 0.01, min_eig_threshold: float = 1e-4,
+              flow_outlier: float = 20000.0) -> VeloLkParams:
+    return VeloLkParams(int(window), int(max_level), int(max_count), 0, float(epsilon), float(min_eig_threshold), float(flow_outlier))
+
+
+IMAGE_KINDS = {"img": 0, "dx": 1, "dy": 2}
+
+
 class VeloResidualStat(C.Structure):
     _fields_ = [("median", C.c_double), ("mean", C.c_double), ("count", C.c_int64)]
 
@@ -240,6 +259,9 @@ SIGNATURES = {
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "velo_match_descriptors": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    "velo_set_images": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "velo_get_image_level": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "velo_track_features": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(VeloLkParams), C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -640,6 +662,54 @@ class Context:
         dist_l = [dist[q_off[j]:q_off[j + 1]].copy() for j in range(n_jobs)]
         pairs_l = [pairs[k_off[j]:k_off[j + 1]].copy() for j in range(n_jobs)]
         return idx_l, dist_l, md[:n_jobs].copy(), pairs_l
+
+    # -- feature tracking: trackFeatures (velo.h:28-116) -----------------------------------------------------------------
+    def set_images(self, imgs):
+        """The frame's grayscale images (one 2-D uint8 array per camera, all the same shape) become the current ones; the current
+        ones become the previous ones.  Pyramids and derivatives are built on the device."""
+        arrs = [np.ascontiguousarray(np.asarray(im, dtype=np.uint8)) for im in imgs]
+        if not arrs or any(a.ndim != 2 or a.shape != arrs[0].shape for a in arrs):
+            raise ValueError("set_images: one or more 2-D uint8 images of one shape")
+        h, w = arrs[0].shape
+        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        self._check(self._lib.velo_set_images(self._h, C.cast(ptrs, C.c_void_p), len(arrs), w, h, w))
+
+    def get_image_level(self, cam: int, level: int = 0, kind: str = "img", previous: bool = False):
+        """One stored level, padded: uint8 (image) or int16 (dx / dy) of shape (h + 2 pad, w + 2 pad); returns (array, pad)."""
+        dims = np.zeros(4, dtype=np.int32)
+        k = IMAGE_KINDS[kind]
+        self._check(self._lib.velo_get_image_level(self._h, int(cam), int(bool(previous)), int(level), k, None, 0,
+                                                   C.c_void_p(dims.ctypes.data)))
+        w, h, pad = int(dims[0]), int(dims[1]), int(dims[2])
+        out = np.zeros((h + 2 * pad, w + 2 * pad), dtype=np.uint8 if k == 0 else np.int16)
+        self._check(self._lib.velo_get_image_level(self._h, int(cam), int(bool(previous)), int(level), k, C.c_void_p(out.ctypes.data),
+                                                   out.nbytes, C.c_void_p(dims.ctypes.data)))
+        return out, pad
+
+    def image_levels(self, previous: bool = False) -> int:
+        dims = np.zeros(4, dtype=np.int32)
+        self._check(self._lib.velo_get_image_level(self._h, 0, int(bool(previous)), 0, 0, None, 0, C.c_void_p(dims.ctypes.data)))
+        return int(dims[3])
+
+    def track_features(self, jobs, **params):
+        """Every (prev_cam, cam, prev_xy [n, 2] pixels) job in ONE call: per job lists of next_xy [n, 2] f32, status [n] bool and
+        kept [n] bool (the filters of velo.h:72-84).  params: lk_params keywords."""
+        p = lk_params(**params)
+        pts = [np.ascontiguousarray(np.asarray(xy, dtype=np.float32).reshape(-1, 2)) for _, _, xy in jobs]
+        arr = (VeloTrackJob * max(len(jobs), 1))()
+        for j, ((pc, cc, _), a) in enumerate(zip(jobs, pts)):
+            arr[j].prev_cam, arr[j].cam = int(pc), int(cc)
+            arr[j].prev_xy = a.ctypes.data if len(a) else None
+            arr[j].n = len(a)
+        n = int(sum(len(a) for a in pts))
+        nxt = np.zeros((max(n, 1), 2), dtype=np.float32)
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        kp = np.zeros(max(n, 1), dtype=np.uint8)
+        vp = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+        self._check(self._lib.velo_track_features(self._h, C.cast(arr, C.c_void_p), len(jobs), C.byref(p), vp(nxt), vp(st), vp(kp)))
+        off = np.concatenate([[0], np.cumsum([len(a) for a in pts])]).astype(np.int64)
+        return ([nxt[off[j]:off[j + 1]].copy() for j in range(len(jobs))], [st[off[j]:off[j + 1]].astype(bool) for j in range(len(jobs))],
+                [kp[off[j]:off[j + 1]].astype(bool) for j in range(len(jobs))])
 
     # -- multi-GPU -------------------------------------------------------------------------------------------
     def set_query_shard(self, rank: int, world: int):

@@ -188,6 +188,12 @@ int velo_destroy(velo_ctx* c) {
     c->md_in.release(); c->md_keys.release(); c->md_out.release();
     if (c->h_md_in) (void)hipHostFree(c->h_md_in);
     if (c->h_md_out) (void)hipHostFree(c->h_md_out);
+    for (auto& sl : c->lk_slot) { sl.pix.release(); sl.der.release(); }
+    c->lk_raw.release(); c->lk_in.release(); c->lk_out.release(); c->lk_diag.release();
+    if (c->lk_upload_ev) (void)hipEventDestroy(c->lk_upload_ev);
+    if (c->h_lk_raw) (void)hipHostFree(c->h_lk_raw);
+    if (c->h_lk_in) (void)hipHostFree(c->h_lk_in);
+    if (c->h_lk_out) (void)hipHostFree(c->h_lk_out);
     for (auto& ps : c->pin) { if (ps.ev) (void)hipEventDestroy(ps.ev); if (ps.p) (void)hipHostFree(ps.p); }
     if (c->src_bbox_ev) (void)hipEventDestroy(c->src_bbox_ev);
     if (c->ev0) (void)hipEventDestroy(c->ev0);

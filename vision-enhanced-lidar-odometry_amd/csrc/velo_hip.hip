@@ -37,6 +37,7 @@
 #include "velo_depth_kernels.h"
 #include "velo_tri_kernels.h"
 #include "velo_match_kernels.h"
+#include "velo_track_kernels.h"
 
 using namespace velo;
 
@@ -60,3 +61,4 @@ extern "C" int velo_launch_lm_solve_ag(int nb_max, int n, void* stream, const vo
 #include "velo_api_pose_comm.inl"   // C-ABI: pose helpers and hand-off, the communicators (RCCL, peer slabs), shards, synchronize
 #include "velo_api_next_rows.inl"   // C-ABI: SURVEY 8(f) rows 3 and 4 -- projection, keypoint depth, batched triangulation
 #include "velo_api_match.inl"   // C-ABI: batched Hamming matching of 64-byte descriptors (matchFeatures, velo.h:499-560)
+#include "velo_api_track.inl"   // C-ABI: resident camera images and pyramidal Lucas-Kanade tracking (trackFeatures, velo.h:28-116)

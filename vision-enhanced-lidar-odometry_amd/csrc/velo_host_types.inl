@@ -162,6 +162,16 @@ struct TargetData {
     bool dimg_built = false;
 };
 
+// one image slot of a context (velo_set_images): every camera's pyramid, camera-major, cam_pix elements apart
+struct LkSlot {
+    DevBuf<unsigned char> pix;           // padded levels, uint8
+    DevBuf<int> der;                     // padded Scharr derivatives, dx | dy << 16
+    LkPyr pyr{};
+    long long cam_pix = 0;
+    int n_cams = 0, w = 0, h = 0;
+    bool valid = false;
+};
+
 struct velo_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -387,6 +397,23 @@ struct velo_ctx {
     int* h_md_out = nullptr;             // pinned landing of md_out
     size_t h_md_out_cap = 0;
     int match_variant = 1;               // 1 = int8 MFMA (product), 0 = XOR + popcount (VELO_MATCH_VARIANT, diagnostics build only)
+
+    // resident camera images and Lucas-Kanade tracking (velo_set_images / velo_track_features): buffers of their own, which no
+    // registration reads or writes
+    LkSlot lk_slot[2];                   // current = lk_slot[lk_cur], previous = the other (velo_set_images rotates them)
+    int lk_cur = 0;
+    DevBuf<unsigned char> lk_raw;        // the frame's raw images, one upload
+    unsigned char* h_lk_raw = nullptr;   // pinned staging of lk_raw
+    size_t h_lk_raw_cap = 0;
+    hipEvent_t lk_upload_ev = nullptr;   // h_lk_raw may be rewritten once this has passed
+    DevBuf<unsigned char> lk_in;         // job table | points
+    DevBuf<unsigned char> lk_out;        // next_xy | status | kept
+    unsigned char* h_lk_in = nullptr;
+    size_t h_lk_in_cap = 0;
+    unsigned char* h_lk_out = nullptr;
+    size_t h_lk_out_cap = 0;
+    DevBuf<unsigned long long> lk_diag;  // diagnostics build: iterations / entries per level (velo_diag_track_counters)
+    bool lk_diag_init = false;
 
     // lock-step batch driver (velo_frame_to_frame_batch): scratch owned by the FIRST context of a batch
     DevBuf<LMBatchItem> batch_items;

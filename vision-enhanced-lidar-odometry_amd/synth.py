@@ -522,3 +522,81 @@ def triangulation_problem(n_landmarks: int = 2000, n_frames: int = 12, seed: int
     points0 = (truth + 0.5 * normal01(seed, 3 * n_landmarks, stream=3).reshape(n_landmarks, 3)).astype(np.float32)
     return dict(camera_poses=poses, cam_trans=CAM_TRANS.copy(), obs=obs, obs_offsets=np.asarray(off, dtype=np.int32),
                 points0=points0, initial_guess=init, truth=truth)
+
+
+# --- camera images for feature tracking (velo_set_images / velo_track_features) ------------------------------------------------
+# A seeded, band-limited texture: a continuous function of the plane (Gaussian blobs of sigma >= 2.5 px plus cosine gratings of
+# period >= 9 px around mid-grey), sampled at pixel positions after a known motion, rounded to uint8.  Because the motion is known, a
+# tracker's output can be checked against ground truth.  Streams 40.. of the counter-based generator; nothing above uses them.
+LK_FLAT_VALUE = 100
+
+
+def _texture_terms(seed: int, width: int, height: int, n_blobs: int):
+    u = uniform01(seed, 5 * n_blobs, stream=40).reshape(n_blobs, 5)
+    blobs = np.stack([-40 + u[:, 0] * (width + 80), -40 + u[:, 1] * (height + 80), 2.5 + 9.5 * u[:, 2], (u[:, 3] - 0.5) * 160.0,
+                      u[:, 4]], axis=1)
+    g = uniform01(seed, 4 * 8, stream=41).reshape(8, 4)
+    ang = g[:, 0] * np.pi
+    period = 9.0 + 40.0 * g[:, 1]
+    gratings = np.stack([np.cos(ang) / period, np.sin(ang) / period, 2 * np.pi * g[:, 2], 6.0 + 10.0 * g[:, 3]], axis=1)
+    return blobs, gratings
+
+
+def texture_motion(xy, width: int, height: int, tx: float = 0.0, ty: float = 0.0, angle: float = 0.0, scale: float = 1.0):
+    """where a point of the unmoved frame lies after the motion: p' = s R(angle) (p - c) + c + t, c the image centre (float64 [n,2])"""
+    p = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    c = np.array([0.5 * (width - 1), 0.5 * (height - 1)])
+    ca, sa = np.cos(angle), np.sin(angle)
+    d = p - c
+    return np.stack([scale * (ca * d[:, 0] - sa * d[:, 1]), scale * (sa * d[:, 0] + ca * d[:, 1])], axis=1) + c + np.array([tx, ty])
+
+
+def render_texture(width: int, height: int, seed: int = 0, tx: float = 0.0, ty: float = 0.0, angle: float = 0.0, scale: float = 1.0,
+                   flat=(), n_blobs: int = 1500) -> np.ndarray:
+    """uint8 (height, width): the seed's texture seen after the motion of texture_motion.  flat: rectangles (x0, y0, x1, y1) of the
+    unmoved frame painted LK_FLAT_VALUE (no gradient: a window inside one fails the minimum-eigenvalue test)."""
+    blobs, gratings = _texture_terms(seed, width, height, n_blobs)
+    ys, xs = np.mgrid[0:height, 0:width].astype(np.float64)
+    c = np.array([0.5 * (width - 1), 0.5 * (height - 1)])
+    ca, sa = np.cos(angle), np.sin(angle)
+    dx, dy = (xs - c[0] - tx) / scale, (ys - c[1] - ty) / scale      # inverse motion: the unmoved-frame position of every pixel
+    px, py = ca * dx + sa * dy + c[0], -sa * dx + ca * dy + c[1]
+    f = np.full((height, width), 128.0)
+    for gx, gy, ph, amp in gratings:
+        f += amp * np.cos(2 * np.pi * (gx * px + gy * py) + ph)
+    for bx, by, s, amp, _ in blobs:
+        q = texture_motion([[bx, by]], width, height, tx, ty, angle, scale)[0]
+        r = 4.0 * s * scale + 2.0
+        x0, x1 = max(int(q[0] - r), 0), min(int(q[0] + r) + 1, width)
+        y0, y1 = max(int(q[1] - r), 0), min(int(q[1] + r) + 1, height)
+        if x0 >= x1 or y0 >= y1:
+            continue
+        sx, sy = px[y0:y1, x0:x1] - bx, py[y0:y1, x0:x1] - by
+        f[y0:y1, x0:x1] += amp * np.exp(-(sx * sx + sy * sy) / (2.0 * s * s))
+    img = np.clip(np.rint(f), 0, 255).astype(np.uint8)
+    for x0, y0, x1, y1 in flat:
+        img[(px >= x0) & (px < x1) & (py >= y0) & (py < y1)] = LK_FLAT_VALUE
+    return img
+
+
+LK_MOTION = dict(tx=2.6, ty=-1.4, angle=0.004, scale=1.006)       # camera 0, frame k -> k + 1
+LK_DISPARITY = 9.35                                                  # camera 1 sees the scene shifted left by this many pixels
+
+
+def tracking_frames(width: int = IMG_WIDTH, height: int = IMG_HEIGHT, seed: int = 0, motion=None, disparity: float = LK_DISPARITY,
+                    flat: bool = True):
+    """Two frames of a two-camera rig over one textured plane: prev[cam] / next[cam] uint8 images, the motion of each camera
+    (texture_motion keywords; camera 1 = camera 0 shifted by -disparity in x) and the flat rectangles (unmoved-frame coordinates)."""
+    m = dict(LK_MOTION if motion is None else motion)
+    rects = [(0.1 * width, 0.3 * height, 0.1 * width + 60, 0.3 * height + 60), (0.6 * width, 0.5 * height, 0.6 * width + 48,
+             0.5 * height + 70)] if flat else []
+    cams = [dict(tx=0.0, ty=0.0), dict(tx=-disparity, ty=0.0)]
+    prev = [render_texture(width, height, seed, c["tx"], c["ty"], 0.0, 1.0, rects) for c in cams]
+    nxt = [render_texture(width, height, seed, c["tx"] + m["tx"], c["ty"] + m["ty"], m["angle"], m["scale"], rects) for c in cams]
+    return dict(prev=prev, next=nxt, motion=m, cams=cams, flat=rects)
+
+
+def tracking_points(n: int, width: int = IMG_WIDTH, height: int = IMG_HEIGHT, seed: int = 5, margin: float = 0.0) -> np.ndarray:
+    """n keypoints (pixels, float32 [n,2]) uniform over [margin, width - margin) x [margin, height - margin)"""
+    u = uniform01(seed, 2 * n, stream=42).reshape(n, 2)
+    return np.stack([margin + u[:, 0] * (width - 2 * margin), margin + u[:, 1] * (height - 2 * margin)], axis=1).astype(np.float32)
