@@ -562,6 +562,36 @@ typedef struct velo_lk_params {
 int velo_track_features(velo_ctx* ctx, const velo_track_job* jobs, int32_t n_jobs, const velo_lk_params* p, float* next_xy,
                         uint8_t* status, uint8_t* kept);
 
+/* --- corner detection: detectFeatures (velo.h:118-177), cv::GFTTDetector(corner_count, quality_level, min_distance) + the occupancy
+ * filter against the frame's existing points, once per camera and frame (main.cpp:543-557) -----------------------------------------
+ * Works on the CURRENT images of velo_set_images (an error if none was set): nothing is uploaded except the jobs' existing points.
+ * One job detects on camera `cam`: cv::goodFeaturesToTrack(img, max_corners, quality_level, min_distance, noArray(), 3, false) --
+ * the minimum-eigenvalue map (3 x 3 Sobel, 3 x 3 box sums, reflect-101), candidates above max * quality_level that are 3 x 3 local
+ * maxima, in descending order of value (equal values: the higher row-major index first), greedy minimum-distance selection, at most
+ * max_corners (<= 0: no cap) -- and flags every corner FRESH unless one of the job's existing points (pixels, [n][2] floats) lies at
+ * util::dist2 (float arithmetic, compared as double) < (float)(min_distance^2) of it.  Existing points outside [0, width) x
+ * [0, height) or non-finite take no part.  The box sums are exact integers.
+ * Outputs, per job `capacity` entries apart: xy [n_jobs][capacity][2] (pixels, integral), response [n_jobs][capacity] (the map's
+ * value), fresh [n_jobs][capacity], in selection order; counts [n_jobs][3] = corners, fresh corners, candidates.  A job whose corners
+ * exceed `capacity` reports so in counts; the first `capacity` are written, entries past min(corners, capacity) are left untouched.
+ * All jobs of a call share every launch and one synchronisation.  Registration state, image slots and pyramids are untouched. */
+typedef struct velo_detect_job {
+    int32_t cam;
+    int32_t n_existing;
+    const float* existing_xy;   /* n_existing x 2 floats, pixels */
+} velo_detect_job;
+typedef struct velo_gftt_params {
+    int32_t max_corners;        /* kitti.h:7: 3000; <= 0: no cap */
+    int32_t block_size;         /* 3 (GFTTDetector::create's default; the only supported value) */
+    double quality_level;       /* kitti.h:18: 0.001; (0, 1] */
+    double min_distance;        /* kitti.h:19: 12; [1, 64] */
+} velo_gftt_params;
+int velo_default_gftt_params(velo_gftt_params* p);
+int velo_detect_features(velo_ctx* ctx, const velo_detect_job* jobs, int32_t n_jobs, const velo_gftt_params* p, int32_t capacity,
+                         float* xy, float* response, uint8_t* fresh, int32_t* counts);
+/* The minimum-eigenvalue map of the current image of `cam`: height x width floats, row-major (tests). */
+int velo_get_corner_response(velo_ctx* ctx, int32_t cam, float* out, int64_t capacity_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,20 @@ def lk_params(window: int = 21, max_level: int = 4, max_count: int = 30, epsilon
 IMAGE_KINDS = {"img": 0, "dx": 1, "dy": 2}
 
 
+class VeloDetectJob(C.Structure):
+    """velo_detect_job: corners of the current image of cam, flagged against n_existing points of the frame"""
+    _fields_ = [("cam", C.c_int32), ("n_existing", C.c_int32), ("existing_xy", C.c_void_p)]
+
+
+class VeloGfttParams(C.Structure):
+    """velo_gftt_params: cv::GFTTDetector's arguments as detectFeatures uses them (main.cpp:84-87; kitti.h:7,18,19)"""
+    _fields_ = [("max_corners", C.c_int32), ("block_size", C.c_int32), ("quality_level", C.c_double), ("min_distance", C.c_double)]
+
+
+def gftt_params(max_corners: int = 3000, quality_level: float = 0.001, min_distance: float = 12.0, block_size: int = 3) -> VeloGfttParams:
+    return VeloGfttParams(int(max_corners), int(block_size), float(quality_level), float(min_distance))
+
+
 class VeloResidualStat(C.Structure):
     _fields_ = [("median", C.c_double), ("mean", C.c_double), ("count", C.c_int64)]
 
@@ -262,6 +276,10 @@ SIGNATURES = {
     "velo_set_images": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "velo_get_image_level": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "velo_track_features": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(VeloLkParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "velo_default_gftt_params": (C.c_int, [_P(VeloGfttParams)]),
+    "velo_detect_features": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(VeloGfttParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "velo_get_corner_response": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_int64]),
 }
 
 _lib = None
@@ -710,6 +728,55 @@ class Context:
         off = np.concatenate([[0], np.cumsum([len(a) for a in pts])]).astype(np.int64)
         return ([nxt[off[j]:off[j + 1]].copy() for j in range(len(jobs))], [st[off[j]:off[j + 1]].astype(bool) for j in range(len(jobs))],
                 [kp[off[j]:off[j + 1]].astype(bool) for j in range(len(jobs))])
+
+    # -- corner detection: detectFeatures (velo.h:118-177) ---------------------------------------------------------------
+    def current_image_size(self):
+        """(width, height) of the current images"""
+        dims = np.zeros(4, dtype=np.int32)
+        self._check(self._lib.velo_get_image_level(self._h, 0, 0, 0, 0, None, 0, C.c_void_p(dims.ctypes.data)))
+        return int(dims[0]), int(dims[1])
+
+    def corner_response(self, cam: int) -> np.ndarray:
+        """The minimum-eigenvalue map (cornerMinEigenVal, 3 x 3 / 3 x 3) of the current image of cam: float32 [height, width]"""
+        w, h = self.current_image_size()
+        out = np.zeros((h, w), dtype=np.float32)
+        self._check(self._lib.velo_get_corner_response(self._h, int(cam), C.c_void_p(out.ctypes.data), out.nbytes))
+        return out
+
+    def detect_features_raw(self, jobs, capacity: int, xy=None, response=None, fresh=None, **params):
+        """velo_detect_features as it is: jobs = [(cam, existing_xy [n, 2] or None)]; returns the caller-sized arrays
+        (xy [n_jobs, capacity, 2], response, fresh, counts [n_jobs, 3]); arrays handed in are written in place"""
+        p = gftt_params(**params)
+        n_jobs = len(jobs)
+        pts = [np.ascontiguousarray(np.asarray(np.zeros((0, 2)) if e is None else e, dtype=np.float32).reshape(-1, 2)) for _, e in jobs]
+        arr = (VeloDetectJob * max(n_jobs, 1))()
+        for j, ((cam, _), a) in enumerate(zip(jobs, pts)):
+            arr[j].cam, arr[j].n_existing = int(cam), len(a)
+            arr[j].existing_xy = a.ctypes.data if len(a) else None
+        cap = int(capacity)
+        xy = np.zeros((max(n_jobs, 1), max(cap, 1), 2), dtype=np.float32) if xy is None else xy
+        response = np.zeros((max(n_jobs, 1), max(cap, 1)), dtype=np.float32) if response is None else response
+        fresh = np.zeros((max(n_jobs, 1), max(cap, 1)), dtype=np.uint8) if fresh is None else fresh
+        counts = np.zeros((max(n_jobs, 1), 3), dtype=np.int32)
+        vp = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+        self._check(self._lib.velo_detect_features(self._h, C.cast(arr, C.c_void_p), n_jobs, C.byref(p), cap, vp(xy), vp(response),
+                                                   vp(fresh), vp(counts)))
+        return xy, response, fresh, counts[:n_jobs]
+
+    def detect_features(self, jobs, return_counts: bool = False, **params):
+        """Every (cam, existing_xy [n, 2] pixels or None) job in ONE call on the current images: per job (xy [k, 2] f32, response [k]
+        f32, fresh [k] bool) in selection order.  params: gftt_params keywords (max_corners, quality_level, min_distance)."""
+        p = gftt_params(**params)
+        w, h = self.current_image_size()
+        cap = p.max_corners if p.max_corners > 0 else 4096
+        while True:
+            xy, resp, fr, counts = self.detect_features_raw(jobs, cap, **params)
+            need = int(counts[:, 0].max()) if len(jobs) else 0
+            if need <= cap:
+                break
+            cap = min(need, w * h)                  # no cap on the corners and more of them than assumed: once more, sized right
+        res = [(xy[j, :counts[j, 0]].copy(), resp[j, :counts[j, 0]].copy(), fr[j, :counts[j, 0]].astype(bool)) for j in range(len(jobs))]
+        return (res, counts.copy()) if return_counts else res
 
     # -- multi-GPU -------------------------------------------------------------------------------------------
     def set_query_shard(self, rank: int, world: int):

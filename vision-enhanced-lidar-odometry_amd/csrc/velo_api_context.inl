@@ -194,6 +194,10 @@ int velo_destroy(velo_ctx* c) {
     if (c->h_lk_raw) (void)hipHostFree(c->h_lk_raw);
     if (c->h_lk_in) (void)hipHostFree(c->h_lk_in);
     if (c->h_lk_out) (void)hipHostFree(c->h_lk_out);
+    c->gf_eig.release(); c->gf_state.release(); c->gf_cand.release(); c->gf_keys.release(); c->gf_hdr.release();
+    c->gf_in.release(); c->gf_out.release();
+    if (c->h_gf_in) (void)hipHostFree(c->h_gf_in);
+    if (c->h_gf_out) (void)hipHostFree(c->h_gf_out);
     for (auto& ps : c->pin) { if (ps.ev) (void)hipEventDestroy(ps.ev); if (ps.p) (void)hipHostFree(ps.p); }
     if (c->src_bbox_ev) (void)hipEventDestroy(c->src_bbox_ev);
     if (c->ev0) (void)hipEventDestroy(c->ev0);

@@ -38,6 +38,7 @@
 #include "velo_tri_kernels.h"
 #include "velo_match_kernels.h"
 #include "velo_track_kernels.h"
+#include "velo_detect_kernels.h"
 
 using namespace velo;
 
@@ -62,3 +63,4 @@ extern "C" int velo_launch_lm_solve_ag(int nb_max, int n, void* stream, const vo
 #include "velo_api_next_rows.inl"   // C-ABI: SURVEY 8(f) rows 3 and 4 -- projection, keypoint depth, batched triangulation
 #include "velo_api_match.inl"   // C-ABI: batched Hamming matching of 64-byte descriptors (matchFeatures, velo.h:499-560)
 #include "velo_api_track.inl"   // C-ABI: resident camera images and pyramidal Lucas-Kanade tracking (trackFeatures, velo.h:28-116)
+#include "velo_api_detect.inl"   // C-ABI: GFTT corner detection on the current images (detectFeatures, velo.h:118-177)

@@ -415,6 +415,20 @@ struct velo_ctx {
     DevBuf<unsigned long long> lk_diag;  // diagnostics build: iterations / entries per level (velo_diag_track_counters)
     bool lk_diag_init = false;
 
+    // corner detection on the current images (velo_detect_features): buffers of its own, which nothing else reads or writes
+    DevBuf<float> gf_eig;                // units x (h x w): the minimum-eigenvalue map
+    DevBuf<unsigned char> gf_state;      // units x padded state map (velo_detect_kernels.h)
+    DevBuf<unsigned> gf_cand;            // units x (h x w) candidate indices | units x (h x w) undecided at the finish
+    DevBuf<unsigned long long> gf_keys;  // units x keys_cap accepted keys
+    DevBuf<int> gf_hdr;                  // units x kGfHdr
+    DevBuf<unsigned char> gf_in;         // job table | existing points
+    DevBuf<unsigned char> gf_out;        // counts | per job xy, response, fresh
+    unsigned char* h_gf_in = nullptr;
+    size_t h_gf_in_cap = 0;
+    unsigned char* h_gf_out = nullptr;
+    size_t h_gf_out_cap = 0;
+    int gf_units = 0;                    // units of the last call (velo_diag_detect_counters)
+
     // lock-step batch driver (velo_frame_to_frame_batch): scratch owned by the FIRST context of a batch
     DevBuf<LMBatchItem> batch_items;
     DevBuf<PoseRecord> batch_pose;       // chain mode of the lock-step driver: per-context records, logs, failure flags

@@ -600,3 +600,23 @@ def tracking_points(n: int, width: int = IMG_WIDTH, height: int = IMG_HEIGHT, se
     """n keypoints (pixels, float32 [n,2]) uniform over [margin, width - margin) x [margin, height - margin)"""
     u = uniform01(seed, 2 * n, stream=42).reshape(n, 2)
     return np.stack([margin + u[:, 0] * (width - 2 * margin), margin + u[:, 1] * (height - 2 * margin)], axis=1).astype(np.float32)
+
+
+# ---- corner detection (velo_detect_features): crafted images for the tie rule and for long selection chains ----------------------
+
+def detect_tiles(width: int = IMG_WIDTH, height: int = IMG_HEIGHT, tile: int = 16, seed: int = 0) -> np.ndarray:
+    """One seeded tile x tile pattern repeated over the whole image: every interior tile has exactly the same corner responses, so
+    thousands of candidates tie and only the tie rule orders them."""
+    t = (uniform01(seed, tile * tile, stream=77).reshape(tile, tile) * 200 + 20).astype(np.uint8)
+    reps = (-(-height // tile), -(-width // tile))
+    return np.ascontiguousarray(np.tile(t, reps)[:height, :width])
+
+
+def detect_ramp(width: int = IMG_WIDTH, height: int = IMG_HEIGHT, period: int = 8) -> np.ndarray:
+    """Bright 2 x 2 dots every `period` pixels whose contrast grows with x: neighbouring corners are closer than the reference's
+    min_distance and each is weaker than its right neighbour, so the greedy selection is one dependency chain per row as long as the
+    image is wide."""
+    y, x = np.mgrid[0:height, 0:width]
+    dot = ((x % period) // 2 == 1) & ((y % period) // 2 == 1)
+    amp = 30.0 + 200.0 * x / max(width - 1, 1)
+    return np.where(dot, 20.0 + amp, 20.0).astype(np.uint8)
