@@ -10,6 +10,10 @@
 //   d.detectFeaturesFrame<KeyPoint>(keypoints, keypoints_p, keypoint_ids, descriptors, extractor, imgs, id_counter, frame)
 //                                                main.cpp:543-557: every camera of the frame, detection as ONE library call, the
 //                                                extraction and the appends camera by camera in the reference's order
+//   CornerDetector::detectFeaturesFrameBatch<KeyPoint>(detectors, keypoints, keypoints_p, keypoint_ids, descriptors, extractors, imgs,
+//   id_counters, frames)                         several sequences (one detector and one context each, lists indexed by sequence, the
+//                                                containers and id counters by pointer) with detection as ONE library call
+//                                                (velo_detect_features_batch); per sequence exactly what detectFeaturesFrame does
 //
 // The descriptor extractor stays the caller's object (cv::Ptr<cv::DescriptorExtractor>, or anything with
 // compute(img, std::vector<KeyPoint>&, Mat&) reachable through ->).  As in the reference, "compute MUTATES cvKP": the extractor may
@@ -27,6 +31,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -91,12 +96,57 @@ public:
                              cam, frame);
     }
 
+    // detectFeaturesFrame of several detectors (one per sequence, distinct contexts on one device) in ONE library call
+    // (velo_detect_features_batch): element i of every list is what detector i's detectFeaturesFrame takes (extractors[i] and
+    // id_counters[i] stay sequence i's own; the extractors run on the host afterwards, sequence by sequence).  Per sequence the
+    // containers receive exactly what its own detectFeaturesFrame appends.  The detectors must share one set of velo_gftt_params.
+    template <typename KeyPoint, typename Point, typename Mat, typename ExtractorPtr, typename Image>
+    static void detectFeaturesFrameBatch(const std::vector<CornerDetector*>& detectors,
+                                         const std::vector<std::vector<std::vector<std::vector<Point> > >*>& keypoints,
+                                         const std::vector<std::vector<std::vector<std::vector<Point> > >*>& keypoints_p,
+                                         const std::vector<std::vector<std::vector<std::vector<int> > >*>& keypoint_ids,
+                                         const std::vector<std::vector<std::vector<Mat> >*>& descriptors, const std::vector<ExtractorPtr>& extractors,
+                                         const std::vector<std::vector<Image> >& imgs, const std::vector<int*>& id_counters,
+                                         const std::vector<int>& frames) {
+        const size_t n = detectors.size();
+        if (n == 0 || keypoints.size() != n || keypoints_p.size() != n || keypoint_ids.size() != n || descriptors.size() != n ||
+            extractors.size() != n || imgs.size() != n || id_counters.size() != n || frames.size() != n)
+            throw std::runtime_error("detectFeaturesFrameBatch: one entry per detector in every list");
+        std::vector<velo_ctx*> ctxs;
+        std::vector<Detected> det;
+        std::vector<velo_detect_job> jobs;
+        std::vector<int32_t> job_ctx;
+        for (size_t i = 0; i < n; i++) {
+            if (std::memcmp(&detectors[i]->p_, &detectors[0]->p_, sizeof(velo_gftt_params)) != 0)
+                throw std::runtime_error("detectFeaturesFrameBatch: the detectors of one call must share their velo_gftt_params");
+            ctxs.push_back(detectors[i]->ctx_);
+            std::vector<const std::vector<Point>*> existing;
+            std::vector<int> cams;
+            for (int cam = 0; cam < (int)imgs[i].size(); cam++) { cams.push_back(cam); existing.push_back(&keypoints_p[i]->at(cam).at(frames[i])); }
+            detectors[i]->prepare(cams, existing, det);
+            job_ctx.insert(job_ctx.end(), cams.size(), (int32_t)i);
+        }
+        jobs.resize(det.size());
+        for (size_t j = 0; j < det.size(); j++) det[j].job(&jobs[j]);      // after the last push_back: det's buffers no longer move
+        detectors[0]->collect(det, jobs, ctxs, &job_ctx);
+        size_t j = 0;
+        for (size_t i = 0; i < n; i++)
+            for (int cam = 0; cam < (int)imgs[i].size(); cam++, j++)
+                detectors[i]->template append<KeyPoint>(det[j], (*keypoints[i])[cam], (*keypoints_p[i])[cam], (*keypoint_ids[i])[cam], (*descriptors[i])[cam],
+                                                        extractors[i], imgs[i][cam], *id_counters[i], cam, frames[i]);
+    }
+
 private:
     struct Detected {
         std::vector<float> xy;
         std::vector<uint8_t> fresh;
         std::vector<float> existing;       // the frame's points when detection ran (the occupancy of velo.h:132-137)
-        int width, height;
+        int width, height, cam;
+        void job(velo_detect_job* j) const {
+            j->cam = cam;
+            j->n_existing = (int32_t)((existing.size() - 2) / 2);
+            j->existing_xy = j->n_existing ? existing.data() : NULL;
+        }
     };
     static void check(int s, const char* what) {
         if (s != VELO_OK) throw std::runtime_error(std::string(what) + ": " + velo_last_error());
@@ -104,28 +154,45 @@ private:
 
     template <typename Point>
     void run(const std::vector<int>& cams, const std::vector<const std::vector<Point>*>& existing, std::vector<Detected>& det) {
-        const size_t n = cams.size();
+        det.clear();
+        prepare(cams, existing, det);
+        std::vector<velo_detect_job> jobs(det.size());
+        for (size_t j = 0; j < det.size(); j++) det[j].job(&jobs[j]);
+        collect(det, jobs, std::vector<velo_ctx*>(1, ctx_), NULL);
+    }
+
+    // appends one Detected per camera to det: the image size of this detector's context and the frame's existing points
+    template <typename Point>
+    void prepare(const std::vector<int>& cams, const std::vector<const std::vector<Point>*>& existing, std::vector<Detected>& det) const {
         int32_t dims[4] = {0, 0, 0, 0};
         check(velo_get_image_level(ctx_, 0, 0, 0, 0, NULL, 0, dims), "velo_get_image_level");
-        det.assign(n, Detected());
-        std::vector<velo_detect_job> jobs(n);
-        for (size_t j = 0; j < n; j++) {
+        for (size_t j = 0; j < cams.size(); j++) {
             const std::vector<Point>& e = *existing[j];
-            det[j].width = dims[0]; det[j].height = dims[1];
-            det[j].existing.resize(2 * e.size() + 2);
-            for (size_t i = 0; i < e.size(); i++) { det[j].existing[2 * i] = e[i].x; det[j].existing[2 * i + 1] = e[i].y; }
-            jobs[j].cam = cams[j];
-            jobs[j].n_existing = (int32_t)e.size();
-            jobs[j].existing_xy = e.empty() ? NULL : det[j].existing.data();
+            Detected d;
+            d.width = dims[0]; d.height = dims[1]; d.cam = cams[j];
+            d.existing.resize(2 * e.size() + 2);
+            for (size_t i = 0; i < e.size(); i++) { d.existing[2 * i] = e[i].x; d.existing[2 * i + 1] = e[i].y; }
+            det.push_back(d);
         }
+    }
+
+    // the library call (job_ctx == NULL: this detector's context alone; else the batch entry over ctxs) and its results into det
+    void collect(std::vector<Detected>& det, const std::vector<velo_detect_job>& jobs, const std::vector<velo_ctx*>& ctxs,
+                 const std::vector<int32_t>* job_ctx) const {
+        const size_t n = jobs.size();
         size_t cap = p_.max_corners > 0 ? (size_t)p_.max_corners : 4096;
         std::vector<float> xy, resp;
         std::vector<uint8_t> fresh;
         std::vector<int32_t> counts(3 * n);
+        std::vector<velo_ctx*> cs(ctxs);
         for (;;) {
             xy.assign(2 * n * cap, 0.f); resp.assign(n * cap, 0.f); fresh.assign(n * cap, 0);
-            check(velo_detect_features(ctx_, jobs.data(), (int32_t)n, &p_, (int32_t)cap, xy.data(), resp.data(), fresh.data(), counts.data()),
-                  "velo_detect_features");
+            if (job_ctx)
+                check(velo_detect_features_batch(cs.data(), (int32_t)cs.size(), job_ctx->data(), jobs.data(), (int32_t)n, &p_, (int32_t)cap, xy.data(),
+                                                 resp.data(), fresh.data(), counts.data()), "velo_detect_features_batch");
+            else
+                check(velo_detect_features(ctx_, jobs.data(), (int32_t)n, &p_, (int32_t)cap, xy.data(), resp.data(), fresh.data(), counts.data()),
+                      "velo_detect_features");
             size_t need = 0;
             for (size_t j = 0; j < n; j++) if ((size_t)counts[3 * j] > need) need = (size_t)counts[3 * j];
             if (need <= cap) break;

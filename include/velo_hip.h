@@ -592,6 +592,31 @@ int velo_detect_features(velo_ctx* ctx, const velo_detect_job* jobs, int32_t n_j
 /* The minimum-eigenvalue map of the current image of `cam`: height x width floats, row-major (tests). */
 int velo_get_corner_response(velo_ctx* ctx, int32_t cam, float* out, int64_t capacity_bytes);
 
+/* --- the visual front end of several contexts in one call each ---------------------------------------------------------------------
+ * A host thread that drives n sequences on one GPU calls these once per frame instead of the single-context entries n times.  The
+ * contexts of a call must be distinct and on one device (at most 256); the FIRST one lends its stream, staging and scratch buffers.
+ * A call runs after everything already enqueued on the stream of every context it names, and whatever is enqueued on any of them
+ * later runs after the call's use of their buffers.  Every context ends in exactly the state, and every output byte is exactly the
+ * one, that the single-context entries give when each context's share is handed to them in the same relative order; batch and single
+ * calls may be mixed freely.  n_ctx == 1 IS the single-context entry.  Contexts may hold images of different sizes: the same launches
+ * serve all of them (each unit's size travels in a device table), one launch set whatever n_ctx.  All arguments are checked before
+ * any context is touched.
+ *
+ * velo_set_images_batch: imgs[i * n_cams + k] is camera k of context i; all images of ONE context share a size, sizes[3 i ..] =
+ * {width, height, stride} of context i.  Per context what velo_set_images does, with one staged upload and one launch per pyramid
+ * level for all of them.  Asynchronous like velo_set_images. */
+int velo_set_images_batch(velo_ctx** ctxs, int32_t n_ctx, const uint8_t* const* imgs, int32_t n_cams, const int32_t* sizes /* n_ctx x 3 */);
+/* velo_track_features / velo_detect_features over several contexts: job j runs on ctxs[job_ctx[j]] (its previous / current images).
+ * Outputs are laid out exactly as by the single-context entries over the same job list (job-major, job order).  A context that no
+ * job names is not touched and needs no images.  One upload, one launch (tracking) or one launch set (detection), one copy back, one
+ * synchronisation.  A detection launch set carries at most 64 distinct cameras: a call that names more runs set after set, each with
+ * its own upload, copy back and synchronisation, and if a later set fails (an allocation, a device error) the call returns the error
+ * after the jobs of the earlier sets have already been written to the caller's arrays. */
+int velo_track_features_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* job_ctx, const velo_track_job* jobs, int32_t n_jobs,
+                              const velo_lk_params* p, float* next_xy, uint8_t* status, uint8_t* kept);
+int velo_detect_features_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* job_ctx, const velo_detect_job* jobs, int32_t n_jobs,
+                               const velo_gftt_params* p, int32_t capacity, float* xy, float* response, uint8_t* fresh, int32_t* counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,10 @@
 //   t.trackFeaturesFrame(keypoints, keypoints_p, keypoint_ids, descriptors, frame)
 //                                                main.cpp:222-235: every (cam, prev_cam) pair from frame - 1 into frame, in the reference's
 //                                                order (cam outer, prev_cam inner), as ONE call
+//   FeatureTracker::setImagesBatch(trackers, imgs) / FeatureTracker::trackFeaturesFrameBatch(trackers, keypoints, keypoints_p,
+//   keypoint_ids, descriptors, frames)           several sequences (one tracker and one context each, lists indexed by sequence) in ONE
+//                                                library call each (velo_set_images_batch / velo_track_features_batch); per sequence
+//                                                exactly what setImages / trackFeaturesFrame do
 //   t.consolidateFeatures(keypoints, keypoints_p, keypoint_ids, descriptors, cam)
 //                                                velo.h:179-230, host code in the reference's float arithmetic (geomedian: utility.h:105-131)
 //   pixel2canonical / canonical2pixel / geomedian velo.h:10-26, utility.h:105-131
@@ -27,6 +31,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -101,17 +106,31 @@ public:
     // the frame's images, one per camera (8-bit, one size): current -> previous, these -> current
     template <typename Image>
     void setImages(const std::vector<Image>& imgs) {
-        if (imgs.empty()) throw std::runtime_error("setImages: no image");
-        std::vector<const uint8_t*> planes;
-        for (size_t k = 0; k < imgs.size(); k++) {
-            if (imgs[k].rows != imgs[0].rows || imgs[k].cols != imgs[0].cols || (size_t)imgs[k].step != (size_t)imgs[0].step)
-                throw std::runtime_error("setImages: every camera's image must have one size and row step");
-            planes.push_back((const uint8_t*)imgs[k].data);
-        }
+        const std::vector<const uint8_t*> planes = planes_of(imgs);
         check(velo_set_images(ctx_, planes.data(), (int32_t)planes.size(), (int32_t)imgs[0].cols, (int32_t)imgs[0].rows,
                               (int32_t)(size_t)imgs[0].step), "velo_set_images");
         prev_ = cur_;
         cur_ = planes;
+    }
+
+    // setImages of several trackers (one per sequence, distinct contexts on one device) in ONE library call (velo_set_images_batch):
+    // imgs[i] are tracker i's images; the sequences may have different image sizes, the number of cameras is the same for all
+    template <typename Image>
+    static void setImagesBatch(const std::vector<FeatureTracker*>& trackers, const std::vector<std::vector<Image> >& imgs) {
+        if (trackers.empty() || trackers.size() != imgs.size()) throw std::runtime_error("setImagesBatch: one image list per tracker");
+        std::vector<velo_ctx*> ctxs;
+        std::vector<std::vector<const uint8_t*> > planes;
+        std::vector<const uint8_t*> all;
+        std::vector<int32_t> sizes;
+        for (size_t i = 0; i < trackers.size(); i++) {
+            planes.push_back(planes_of(imgs[i]));
+            if (planes[i].size() != planes[0].size()) throw std::runtime_error("setImagesBatch: every tracker must bring the same number of cameras");
+            ctxs.push_back(trackers[i]->ctx_);
+            all.insert(all.end(), planes[i].begin(), planes[i].end());
+            sizes.push_back((int32_t)imgs[i][0].cols); sizes.push_back((int32_t)imgs[i][0].rows); sizes.push_back((int32_t)(size_t)imgs[i][0].step);
+        }
+        check(velo_set_images_batch(ctxs.data(), (int32_t)ctxs.size(), all.data(), (int32_t)planes[0].size(), sizes.data()), "velo_set_images_batch");
+        for (size_t i = 0; i < trackers.size(); i++) { trackers[i]->prev_ = trackers[i]->cur_; trackers[i]->cur_ = planes[i]; }
     }
 
     // velo.h:28-116
@@ -136,6 +155,48 @@ public:
         for (int cam = 0; cam < (int)cur_.size(); cam++)
             for (int prev_cam = 0; prev_cam < (int)prev_.size(); prev_cam++) jobs.push_back(Job(prev_cam, cam, frame - 1, frame));
         run(keypoints, keypoints_p, keypoint_ids, descriptors, jobs);
+    }
+
+    // trackFeaturesFrame of several trackers in ONE library call (velo_track_features_batch): element i of every list is what tracker
+    // i's trackFeaturesFrame takes; per tracker the containers receive exactly what its own trackFeaturesFrame appends.  The trackers
+    // must share one set of velo_lk_params (the call has one).
+    template <typename Point, typename Mat>
+    static void trackFeaturesFrameBatch(const std::vector<FeatureTracker*>& trackers,
+                                        const std::vector<std::vector<std::vector<std::vector<Point> > >*>& keypoints,
+                                        const std::vector<std::vector<std::vector<std::vector<Point> > >*>& keypoints_p,
+                                        const std::vector<std::vector<std::vector<std::vector<int> > >*>& keypoint_ids,
+                                        const std::vector<std::vector<std::vector<Mat> >*>& descriptors, const std::vector<int>& frames) {
+        const size_t n = trackers.size();
+        if (n == 0 || keypoints.size() != n || keypoints_p.size() != n || keypoint_ids.size() != n || descriptors.size() != n || frames.size() != n)
+            throw std::runtime_error("trackFeaturesFrameBatch: one entry per tracker in every list");
+        std::vector<velo_ctx*> ctxs;
+        std::vector<Job> jobs;
+        std::vector<int32_t> job_ctx;
+        for (size_t i = 0; i < n; i++) {
+            const FeatureTracker& t = *trackers[i];
+            if (std::memcmp(&t.p_, &trackers[0]->p_, sizeof(velo_lk_params)) != 0)
+                throw std::runtime_error("trackFeaturesFrameBatch: the trackers of one call must share their velo_lk_params");
+            ctxs.push_back(t.ctx_);
+            for (int cam = 0; cam < (int)t.cur_.size(); cam++)
+                for (int prev_cam = 0; prev_cam < (int)t.prev_.size(); prev_cam++) {
+                    jobs.push_back(Job(prev_cam, cam, frames[i] - 1, frames[i]));
+                    job_ctx.push_back((int32_t)i);
+                }
+        }
+        std::vector<velo_track_job> cj(jobs.size());
+        std::vector<size_t> first(jobs.size() + 1, 0);
+        for (size_t j = 0; j < jobs.size(); j++) first[j + 1] = first[j] + keypoints_p[job_ctx[j]]->at(jobs[j].cam1).at(jobs[j].frame1).size();
+        std::vector<float> xy(2 * first.back() + 2);
+        for (size_t j = 0; j < jobs.size(); j++) fill_job(&cj[j], &xy[2 * first[j]], (*keypoints_p[job_ctx[j]])[jobs[j].cam1][jobs[j].frame1], jobs[j]);
+        std::vector<float> next(2 * first.back() + 2);
+        std::vector<uint8_t> status(first.back() + 1), kept(first.back() + 1);
+        check(velo_track_features_batch(ctxs.data(), (int32_t)n, job_ctx.data(), cj.data(), (int32_t)cj.size(), &trackers[0]->p_, next.data(),
+                                        status.data(), kept.data()), "velo_track_features_batch");
+        for (size_t j = 0; j < jobs.size(); j++) {
+            const size_t i = (size_t)job_ctx[j];
+            trackers[i]->append_job(*keypoints[i], *keypoints_p[i], *keypoint_ids[i], *descriptors[i], jobs[j], (size_t)cj[j].n, &next[2 * first[j]],
+                                    &kept[first[j]]);
+        }
     }
 
     // velo.h:179-230 (host code): entries merged per id, ids ascending (std::map); n > 2: geomedian, n == 2: the pair mean; the pixel
@@ -188,28 +249,49 @@ private:
         std::vector<size_t> first(jobs.size() + 1, 0);
         for (size_t j = 0; j < jobs.size(); j++) first[j + 1] = first[j] + keypoints_p.at(jobs[j].cam1).at(jobs[j].frame1).size();
         std::vector<float> xy(2 * first.back() + 2);
-        for (size_t j = 0; j < jobs.size(); j++) {
-            const std::vector<Point>& p1 = keypoints_p[jobs[j].cam1][jobs[j].frame1];
-            for (size_t i = 0; i < p1.size(); i++) { xy[2 * (first[j] + i)] = p1[i].x; xy[2 * (first[j] + i) + 1] = p1[i].y; }
-            cj[j].prev_cam = jobs[j].cam1;
-            cj[j].cam = jobs[j].cam2;
-            cj[j].prev_xy = p1.empty() ? NULL : &xy[2 * first[j]];
-            cj[j].n = (int32_t)p1.size();
-        }
+        for (size_t j = 0; j < jobs.size(); j++) fill_job(&cj[j], &xy[2 * first[j]], keypoints_p[jobs[j].cam1][jobs[j].frame1], jobs[j]);
         std::vector<float> next(2 * first.back() + 2);
         std::vector<uint8_t> status(first.back() + 1), kept(first.back() + 1);
         check(velo_track_features(ctx_, cj.data(), (int32_t)cj.size(), &p_, next.data(), status.data(), kept.data()), "velo_track_features");
-        for (size_t j = 0; j < jobs.size(); j++) {                     // velo.h:107-114, in job order
-            const Job& J = jobs[j];
-            const Matrix3& Kinv2 = Kinv_.at(J.cam2);
-            for (size_t i = 0; i < (size_t)cj[j].n; i++) {
-                if (!kept[first[j] + i]) continue;
-                const Point p2(next[2 * (first[j] + i)], next[2 * (first[j] + i) + 1]);
-                keypoints_p[J.cam2][J.frame2].push_back(p2);
-                keypoints[J.cam2][J.frame2].push_back(pixel2canonical(p2, Kinv2));
-                keypoint_ids[J.cam2][J.frame2].push_back(keypoint_ids[J.cam1][J.frame1][i]);
-                descriptors[J.cam2][J.frame2].push_back(descriptors[J.cam1][J.frame1].row((int)i).clone());
-            }
+        for (size_t j = 0; j < jobs.size(); j++)                       // in job order
+            append_job(keypoints, keypoints_p, keypoint_ids, descriptors, jobs[j], (size_t)cj[j].n, &next[2 * first[j]], &kept[first[j]]);
+    }
+
+    template <typename Image>
+    static std::vector<const uint8_t*> planes_of(const std::vector<Image>& imgs) {
+        if (imgs.empty()) throw std::runtime_error("setImages: no image");
+        std::vector<const uint8_t*> planes;
+        for (size_t k = 0; k < imgs.size(); k++) {
+            if (imgs[k].rows != imgs[0].rows || imgs[k].cols != imgs[0].cols || (size_t)imgs[k].step != (size_t)imgs[0].step)
+                throw std::runtime_error("setImages: every camera's image must have one size and row step");
+            planes.push_back((const uint8_t*)imgs[k].data);
+        }
+        return planes;
+    }
+
+    // one velo_track_job: the points of (cam1, frame1), copied to xy
+    template <typename Point>
+    static void fill_job(velo_track_job* cj, float* xy, const std::vector<Point>& p1, const Job& J) {
+        for (size_t i = 0; i < p1.size(); i++) { xy[2 * i] = p1[i].x; xy[2 * i + 1] = p1[i].y; }
+        cj->prev_cam = J.cam1;
+        cj->cam = J.cam2;
+        cj->prev_xy = p1.empty() ? NULL : xy;
+        cj->n = (int32_t)p1.size();
+    }
+
+    // velo.h:107-114 for one job: next [n][2] and kept [n] as the library returned them
+    template <typename Point, typename Mat>
+    void append_job(std::vector<std::vector<std::vector<Point> > >& keypoints, std::vector<std::vector<std::vector<Point> > >& keypoints_p,
+                    std::vector<std::vector<std::vector<int> > >& keypoint_ids, std::vector<std::vector<Mat> >& descriptors, const Job& J,
+                    size_t n, const float* next, const uint8_t* kept) const {
+        const Matrix3& Kinv2 = Kinv_.at(J.cam2);
+        for (size_t i = 0; i < n; i++) {
+            if (!kept[i]) continue;
+            const Point p2(next[2 * i], next[2 * i + 1]);
+            keypoints_p[J.cam2][J.frame2].push_back(p2);
+            keypoints[J.cam2][J.frame2].push_back(pixel2canonical(p2, Kinv2));
+            keypoint_ids[J.cam2][J.frame2].push_back(keypoint_ids[J.cam1][J.frame1][i]);
+            descriptors[J.cam2][J.frame2].push_back(descriptors[J.cam1][J.frame1].row((int)i).clone());
         }
     }
 

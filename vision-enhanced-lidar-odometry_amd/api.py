@@ -280,6 +280,11 @@ SIGNATURES = {
     "velo_detect_features": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(VeloGfttParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
     "velo_get_corner_response": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_int64]),
+    "velo_set_images_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "velo_track_features_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, _P(VeloLkParams), C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
+    "velo_detect_features_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, _P(VeloGfttParams), C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -902,6 +907,104 @@ def frame_to_frame_batch(ctxs, x0s):
         msg = lib.velo_last_error()
         raise VeloError(f"velo status {st}: {msg.decode() if msg else ''}")
     return x, T.reshape(n, 4, 4), list(S)
+
+
+# -- the visual front end of several contexts in one call each (velo_set_images_batch / velo_track_features_batch /
+#    velo_detect_features_batch): what Context.set_images / track_features / detect_features do, for n sequences on one GPU ---------
+def _batch_lib_and_handles(ctxs):
+    if not len(ctxs):
+        raise ValueError("a batch call needs at least one context")
+    lib = ctxs[0]._lib                                          # the build the contexts were created on
+    return lib, (_ctx * len(ctxs))(*[c.handle for c in ctxs])
+
+
+def _batch_check(lib, st):
+    if st != 0:
+        msg = lib.velo_last_error()
+        raise VeloError(f"velo status {st}: {msg.decode() if msg else ''}")
+
+
+def set_images_batch(ctxs, imgs_per_ctx):
+    """Context.set_images for every context in ONE call: imgs_per_ctx[i] is the list of context i's grayscale images (2-D uint8, one
+    shape per context, the same number of cameras for all; shapes may differ between contexts)."""
+    lib, arr = _batch_lib_and_handles(ctxs)
+    if len(imgs_per_ctx) != len(ctxs):
+        raise ValueError("set_images_batch: one image list per context")
+    per = [[np.ascontiguousarray(np.asarray(im, dtype=np.uint8)) for im in imgs] for imgs in imgs_per_ctx]
+    n_cams = len(per[0])
+    if n_cams < 1 or any(len(a) != n_cams for a in per):
+        raise ValueError("set_images_batch: the same number of cameras (>= 1) for every context")
+    if any(im.ndim != 2 or im.shape != a[0].shape for a in per for im in a):
+        raise ValueError("set_images_batch: per context one or more 2-D uint8 images of one shape")
+    ptrs = (C.c_void_p * (len(per) * n_cams))(*[im.ctypes.data for a in per for im in a])
+    sizes = np.array([[a[0].shape[1], a[0].shape[0], a[0].shape[1]] for a in per], dtype=np.int32)
+    _batch_check(lib, lib.velo_set_images_batch(C.cast(arr, C.c_void_p), len(ctxs), C.cast(ptrs, C.c_void_p), n_cams,
+                                                C.c_void_p(sizes.ctypes.data)))
+
+
+def track_features_batch(ctxs, jobs, **params):
+    """Every (ctx_index, prev_cam, cam, prev_xy [n, 2] pixels) job in ONE call over all contexts: per job lists of next_xy [n, 2] f32,
+    status [n] bool and kept [n] bool, as Context.track_features gives them.  params: lk_params keywords."""
+    p = lk_params(**params)
+    lib, arr = _batch_lib_and_handles(ctxs)
+    pts = [np.ascontiguousarray(np.asarray(xy, dtype=np.float32).reshape(-1, 2)) for _, _, _, xy in jobs]
+    jarr = (VeloTrackJob * max(len(jobs), 1))()
+    jctx = np.zeros(max(len(jobs), 1), dtype=np.int32)
+    for j, ((ci, pc, cc, _), a) in enumerate(zip(jobs, pts)):
+        jctx[j] = int(ci)
+        jarr[j].prev_cam, jarr[j].cam = int(pc), int(cc)
+        jarr[j].prev_xy = a.ctypes.data if len(a) else None
+        jarr[j].n = len(a)
+    n = int(sum(len(a) for a in pts))
+    nxt = np.zeros((max(n, 1), 2), dtype=np.float32)
+    st = np.zeros(max(n, 1), dtype=np.uint8)
+    kp = np.zeros(max(n, 1), dtype=np.uint8)
+    vp = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+    _batch_check(lib, lib.velo_track_features_batch(C.cast(arr, C.c_void_p), len(ctxs), vp(jctx), C.cast(jarr, C.c_void_p), len(jobs),
+                                                    C.byref(p), vp(nxt), vp(st), vp(kp)))
+    off = np.concatenate([[0], np.cumsum([len(a) for a in pts])]).astype(np.int64)
+    return ([nxt[off[j]:off[j + 1]].copy() for j in range(len(jobs))], [st[off[j]:off[j + 1]].astype(bool) for j in range(len(jobs))],
+            [kp[off[j]:off[j + 1]].astype(bool) for j in range(len(jobs))])
+
+
+def detect_features_batch_raw(ctxs, jobs, capacity: int, xy=None, response=None, fresh=None, **params):
+    """velo_detect_features_batch as it is: jobs = [(ctx_index, cam, existing_xy [n, 2] or None)]; returns the caller-sized arrays
+    (xy [n_jobs, capacity, 2], response, fresh, counts [n_jobs, 3]); arrays handed in are written in place"""
+    p = gftt_params(**params)
+    lib, arr = _batch_lib_and_handles(ctxs)
+    n_jobs = len(jobs)
+    pts = [np.ascontiguousarray(np.asarray(np.zeros((0, 2)) if e is None else e, dtype=np.float32).reshape(-1, 2)) for _, _, e in jobs]
+    jarr = (VeloDetectJob * max(n_jobs, 1))()
+    jctx = np.zeros(max(n_jobs, 1), dtype=np.int32)
+    for j, ((ci, cam, _), a) in enumerate(zip(jobs, pts)):
+        jctx[j] = int(ci)
+        jarr[j].cam, jarr[j].n_existing = int(cam), len(a)
+        jarr[j].existing_xy = a.ctypes.data if len(a) else None
+    cap = int(capacity)
+    xy = np.zeros((max(n_jobs, 1), max(cap, 1), 2), dtype=np.float32) if xy is None else xy
+    response = np.zeros((max(n_jobs, 1), max(cap, 1)), dtype=np.float32) if response is None else response
+    fresh = np.zeros((max(n_jobs, 1), max(cap, 1)), dtype=np.uint8) if fresh is None else fresh
+    counts = np.zeros((max(n_jobs, 1), 3), dtype=np.int32)
+    vp = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+    _batch_check(lib, lib.velo_detect_features_batch(C.cast(arr, C.c_void_p), len(ctxs), vp(jctx), C.cast(jarr, C.c_void_p), n_jobs,
+                                                     C.byref(p), cap, vp(xy), vp(response), vp(fresh), vp(counts)))
+    return xy, response, fresh, counts[:n_jobs]
+
+
+def detect_features_batch(ctxs, jobs, return_counts: bool = False, **params):
+    """Every (ctx_index, cam, existing_xy [n, 2] pixels or None) job in ONE call on the current images of the contexts: per job
+    (xy [k, 2] f32, response [k] f32, fresh [k] bool) in selection order, as Context.detect_features gives them.  params:
+    gftt_params keywords (max_corners, quality_level, min_distance)."""
+    p = gftt_params(**params)
+    cap = p.max_corners if p.max_corners > 0 else 4096
+    while True:
+        xy, resp, fr, counts = detect_features_batch_raw(ctxs, jobs, cap, **params)
+        need = int(counts[:, 0].max()) if len(jobs) else 0
+        if need <= cap:
+            break
+        cap = need                                  # no cap on the corners and more of them than assumed: once more, sized right
+    res = [(xy[j, :counts[j, 0]].copy(), resp[j, :counts[j, 0]].copy(), fr[j, :counts[j, 0]].astype(bool)) for j in range(len(jobs))]
+    return (res, counts.copy()) if return_counts else res
 
 
 SCAN_ON_DEVICE, SCAN_SHARED, SCAN_PROMOTE = 1, 2, 4

@@ -191,6 +191,8 @@ int velo_destroy(velo_ctx* c) {
     for (auto& sl : c->lk_slot) { sl.pix.release(); sl.der.release(); }
     c->lk_raw.release(); c->lk_in.release(); c->lk_out.release(); c->lk_diag.release();
     if (c->lk_upload_ev) (void)hipEventDestroy(c->lk_upload_ev);
+    if (c->fb_here_ev) (void)hipEventDestroy(c->fb_here_ev);
+    if (c->fb_done_ev) (void)hipEventDestroy(c->fb_done_ev);
     if (c->h_lk_raw) (void)hipHostFree(c->h_lk_raw);
     if (c->h_lk_in) (void)hipHostFree(c->h_lk_in);
     if (c->h_lk_out) (void)hipHostFree(c->h_lk_out);

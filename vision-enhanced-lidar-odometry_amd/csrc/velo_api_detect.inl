@@ -25,9 +25,39 @@ int gf_prepare(velo_ctx* c, const LkSlot& S, const int* cams, int n_units, GfArg
     A->keys = c->gf_keys.p; A->keys_cap = (long long)keys_cap;
     A->hdr = c->gf_hdr.p;
     const float s = (float)(1.0 / (255.0 * 4.0 * 3.0));       // cornerMinEigenVal: 1 / (255 * 2^(ksize - 1) * blockSize)
-    A->scale2 = s * s;
+    A->K.scale2 = s * s;
     HIP_TRY(hipMemsetAsync(c->gf_hdr.p, 0, sizeof(int) * kGfHdr * kGfMaxUnits, c->stream));
     c->gf_units = n_units;
+    return VELO_OK;
+}
+
+// the argument checks of velo_detect_features that read no context (shared with velo_detect_features_batch)
+int gf_check_params(int32_t n_jobs, const velo_gftt_params* p, int32_t capacity) {
+    if (n_jobs < 0) return fail(VELO_ERR_INVALID, "negative job count %d", n_jobs);
+    if (!p) return fail(VELO_ERR_INVALID, "null params");
+    if (p->block_size != 3) return fail(VELO_ERR_INVALID, "block_size %d; only 3 is supported", p->block_size);
+    if (!(p->min_distance >= 1.0 && p->min_distance <= (double)kGfMaxDist))
+        return fail(VELO_ERR_INVALID, "min_distance %g; 1..%d", p->min_distance, kGfMaxDist);
+    if (!(p->quality_level > 0.0 && p->quality_level <= 1.0)) return fail(VELO_ERR_INVALID, "quality_level %g; (0, 1]", p->quality_level);
+    if (capacity < 0) return fail(VELO_ERR_INVALID, "negative capacity %d", capacity);
+    return VELO_OK;
+}
+
+// n_jobs > 0: the job list and the output arrays; *total = existing points of the call
+int gf_check_jobs(const velo_detect_job* jobs, int32_t n_jobs, int32_t capacity, const float* xy, const float* response, const uint8_t* fresh,
+                  const int32_t* counts, int64_t* total) {
+    if (!jobs) return fail(VELO_ERR_INVALID, "null jobs");
+    if (!counts) return fail(VELO_ERR_INVALID, "null counts");
+    if (capacity > 0 && (!xy || !response || !fresh)) return fail(VELO_ERR_INVALID, "null xy / response / fresh");
+    *total = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        if (jobs[j].n_existing < 0) return fail(VELO_ERR_INVALID, "job %d: negative point count %d", j, jobs[j].n_existing);
+        if (jobs[j].n_existing > 0 && !jobs[j].existing_xy) return fail(VELO_ERR_INVALID, "job %d: null points", j);
+        if (jobs[j].cam < 0 || jobs[j].cam >= kLkMaxCams) return fail(VELO_ERR_INVALID, "job %d: camera %d; 0..%d", j, jobs[j].cam, kLkMaxCams - 1);
+        *total += jobs[j].n_existing;
+    }
+    if (n_jobs > 4096) return fail(VELO_ERR_INVALID, "%d jobs in one call; at most 4096", n_jobs);
+    if (*total > (int64_t)(INT32_MAX / 16)) return fail(VELO_ERR_INVALID, "%lld points in one call; at most %d", (long long)*total, INT32_MAX / 16);
     return VELO_OK;
 }
 
@@ -49,26 +79,10 @@ int velo_detect_features(velo_ctx* c, const velo_detect_job* jobs, int32_t n_job
                          float* response, uint8_t* fresh, int32_t* counts) {
     // every argument is checked before the context is touched
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
-    if (n_jobs < 0) return fail(VELO_ERR_INVALID, "negative job count %d", n_jobs);
-    if (!p) return fail(VELO_ERR_INVALID, "null params");
-    if (p->block_size != 3) return fail(VELO_ERR_INVALID, "block_size %d; only 3 is supported", p->block_size);
-    if (!(p->min_distance >= 1.0 && p->min_distance <= (double)kGfMaxDist))
-        return fail(VELO_ERR_INVALID, "min_distance %g; 1..%d", p->min_distance, kGfMaxDist);
-    if (!(p->quality_level > 0.0 && p->quality_level <= 1.0)) return fail(VELO_ERR_INVALID, "quality_level %g; (0, 1]", p->quality_level);
-    if (capacity < 0) return fail(VELO_ERR_INVALID, "negative capacity %d", capacity);
+    VELO_TRY(gf_check_params(n_jobs, p, capacity));
     if (n_jobs == 0) return VELO_OK;
-    if (!jobs) return fail(VELO_ERR_INVALID, "null jobs");
-    if (!counts) return fail(VELO_ERR_INVALID, "null counts");
-    if (capacity > 0 && (!xy || !response || !fresh)) return fail(VELO_ERR_INVALID, "null xy / response / fresh");
     int64_t total = 0;
-    for (int j = 0; j < n_jobs; j++) {
-        if (jobs[j].n_existing < 0) return fail(VELO_ERR_INVALID, "job %d: negative point count %d", j, jobs[j].n_existing);
-        if (jobs[j].n_existing > 0 && !jobs[j].existing_xy) return fail(VELO_ERR_INVALID, "job %d: null points", j);
-        if (jobs[j].cam < 0 || jobs[j].cam >= kLkMaxCams) return fail(VELO_ERR_INVALID, "job %d: camera %d; 0..%d", j, jobs[j].cam, kLkMaxCams - 1);
-        total += jobs[j].n_existing;
-    }
-    if (n_jobs > 4096) return fail(VELO_ERR_INVALID, "%d jobs in one call; at most 4096", n_jobs);
-    if (total > (int64_t)(INT32_MAX / 16)) return fail(VELO_ERR_INVALID, "%lld points in one call; at most %d", (long long)total, INT32_MAX / 16);
+    VELO_TRY(gf_check_jobs(jobs, n_jobs, capacity, xy, response, fresh, counts, &total));
     const LkSlot& S = *lk_slot(c, false);
     if (!S.valid) return fail(VELO_ERR_STATE, "no current images: velo_set_images first");
     int cams[kGfMaxUnits], unit_of[kLkMaxCams], n_units = 0;
@@ -83,12 +97,12 @@ int velo_detect_features(velo_ctx* c, const velo_detect_job* jobs, int32_t n_job
     HIP_TRY(hipSetDevice(c->device));
     GfArgs A;
     VELO_TRY(gf_prepare(c, S, cams, n_units, &A));
-    A.radius = (int)std::ceil(p->min_distance) - 1;
-    A.max_corners = p->max_corners;
-    A.capacity = cap_d;
-    A.quality = p->quality_level;
-    A.md2 = p->min_distance * p->min_distance;
-    A.md2f = (float)(p->min_distance * p->min_distance);
+    A.K.radius = (int)std::ceil(p->min_distance) - 1;
+    A.K.max_corners = p->max_corners;
+    A.K.capacity = cap_d;
+    A.K.quality = p->quality_level;
+    A.K.md2 = p->min_distance * p->min_distance;
+    A.K.md2f = (float)(p->min_distance * p->min_distance);
     const size_t job_bytes = (sizeof(GfJob) * (size_t)n_jobs + 63) & ~(size_t)63;
     const size_t in_bytes = job_bytes + sizeof(float2) * (size_t)total;
     const size_t cnt_bytes = (sizeof(int) * 3 * (size_t)n_jobs + 63) & ~(size_t)63;

@@ -29,6 +29,33 @@ void lk_plan(LkPyr* P, int w, int h, long long* cam_pix) {
 
 LkSlot* lk_slot(velo_ctx* c, bool previous) { return &c->lk_slot[previous ? (c->lk_cur ^ 1) : c->lk_cur]; }
 
+// the argument checks of velo_track_features that read no context (shared with velo_track_features_batch)
+int lk_check_params(int32_t n_jobs, const velo_lk_params* p) {
+    if (n_jobs < 0) return fail(VELO_ERR_INVALID, "negative job count %d", n_jobs);
+    if (!p) return fail(VELO_ERR_INVALID, "null params");
+    if (p->window < kLkMinWin || p->window > kLkMaxWin || (p->window & 1) == 0)
+        return fail(VELO_ERR_INVALID, "window %d; odd, %d..%d", p->window, kLkMinWin, kLkMaxWin);
+    if (p->max_level < 0 || p->max_level > kLkMaxLevel) return fail(VELO_ERR_INVALID, "max_level %d; 0..%d", p->max_level, kLkMaxLevel);
+    if (p->max_count < 0 || p->max_count > 100) return fail(VELO_ERR_INVALID, "max_count %d; 0..100", p->max_count);
+    if (!(p->epsilon >= 0.0 && p->epsilon <= 10.0)) return fail(VELO_ERR_INVALID, "epsilon %g; 0..10", p->epsilon);
+    if (!std::isfinite(p->min_eig_threshold) || std::isnan(p->flow_outlier)) return fail(VELO_ERR_INVALID, "min_eig_threshold / flow_outlier not a number");
+    return VELO_OK;
+}
+
+// n_jobs > 0: the job list and the output arrays; *total = points of the call
+int lk_check_jobs(const velo_track_job* jobs, int32_t n_jobs, const float* next_xy, const uint8_t* status, const uint8_t* kept, int64_t* total) {
+    if (!jobs) return fail(VELO_ERR_INVALID, "null jobs");
+    *total = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        if (jobs[j].n < 0) return fail(VELO_ERR_INVALID, "job %d: negative point count %d", j, jobs[j].n);
+        if (jobs[j].n > 0 && !jobs[j].prev_xy) return fail(VELO_ERR_INVALID, "job %d: null points", j);
+        *total += jobs[j].n;
+    }
+    if (*total > (int64_t)(INT32_MAX / 16)) return fail(VELO_ERR_INVALID, "%lld points in one call; at most %d", (long long)*total, INT32_MAX / 16);
+    if (*total > 0 && (!next_xy || !status || !kept)) return fail(VELO_ERR_INVALID, "null next_xy / status / kept");
+    return VELO_OK;
+}
+
 }  // namespace
 
 extern "C" {   // (continued from the previous part)
@@ -102,24 +129,10 @@ int velo_track_features(velo_ctx* c, const velo_track_job* jobs, int32_t n_jobs,
                         uint8_t* kept) {
     // every argument is checked before the context is touched
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
-    if (n_jobs < 0) return fail(VELO_ERR_INVALID, "negative job count %d", n_jobs);
-    if (!p) return fail(VELO_ERR_INVALID, "null params");
-    if (p->window < kLkMinWin || p->window > kLkMaxWin || (p->window & 1) == 0)
-        return fail(VELO_ERR_INVALID, "window %d; odd, %d..%d", p->window, kLkMinWin, kLkMaxWin);
-    if (p->max_level < 0 || p->max_level > kLkMaxLevel) return fail(VELO_ERR_INVALID, "max_level %d; 0..%d", p->max_level, kLkMaxLevel);
-    if (p->max_count < 0 || p->max_count > 100) return fail(VELO_ERR_INVALID, "max_count %d; 0..100", p->max_count);
-    if (!(p->epsilon >= 0.0 && p->epsilon <= 10.0)) return fail(VELO_ERR_INVALID, "epsilon %g; 0..10", p->epsilon);
-    if (!std::isfinite(p->min_eig_threshold) || std::isnan(p->flow_outlier)) return fail(VELO_ERR_INVALID, "min_eig_threshold / flow_outlier not a number");
+    VELO_TRY(lk_check_params(n_jobs, p));
     if (n_jobs == 0) return VELO_OK;
-    if (!jobs) return fail(VELO_ERR_INVALID, "null jobs");
     int64_t total = 0;
-    for (int j = 0; j < n_jobs; j++) {
-        if (jobs[j].n < 0) return fail(VELO_ERR_INVALID, "job %d: negative point count %d", j, jobs[j].n);
-        if (jobs[j].n > 0 && !jobs[j].prev_xy) return fail(VELO_ERR_INVALID, "job %d: null points", j);
-        total += jobs[j].n;
-    }
-    if (total > (int64_t)(INT32_MAX / 16)) return fail(VELO_ERR_INVALID, "%lld points in one call; at most %d", (long long)total, INT32_MAX / 16);
-    if (total > 0 && (!next_xy || !status || !kept)) return fail(VELO_ERR_INVALID, "null next_xy / status / kept");
+    VELO_TRY(lk_check_jobs(jobs, n_jobs, next_xy, status, kept, &total));
     const LkSlot& Sp = *lk_slot(c, true);
     const LkSlot& Sc = *lk_slot(c, false);
     if (!Sp.valid || !Sc.valid) return fail(VELO_ERR_STATE, "tracking needs a previous and a current frame: velo_set_images twice");
@@ -155,10 +168,10 @@ int velo_track_features(velo_ctx* c, const velo_track_job* jobs, int32_t n_jobs,
     if (Sp.cam_pix != Sc.cam_pix) return fail(VELO_ERR_STATE, "slot layouts differ");
     A.P = Sc.pyr;
     A.top = std::min(lk_level_count(Sc.w, Sc.h, p->window, p->max_level), Sc.pyr.n_levels - 1);
-    A.win = p->window; A.max_count = p->max_count;
-    A.min_eig = (float)p->min_eig_threshold;
-    A.eps2 = p->epsilon * p->epsilon;
-    A.flow_outlier = p->flow_outlier;
+    A.K.win = p->window; A.K.max_count = p->max_count;
+    A.K.min_eig = (float)p->min_eig_threshold;
+    A.K.eps2 = p->epsilon * p->epsilon;
+    A.K.flow_outlier = p->flow_outlier;
     const LkJob* djobs = (const LkJob*)c->lk_in.p;
     const float2* dpts = (const float2*)(c->lk_in.p + job_bytes);
     float2* oxy = (float2*)c->lk_out.p;

@@ -22,6 +22,13 @@
 //   in LDS up to 4,096 keys, in global memory above) and applies the cap.
 // gf_output_kernel: per job and accepted corner the fresh flag against the job's existing points (LDS chunks, brute force), written in
 //   key order; counts per job.
+//
+// Every kernel body works on ONE unit through a GfUnit (the unit's image plane, size and its share of every scratch buffer) and the
+// call's GfParams.  The single-context kernels derive the GfUnit from their arguments (GfArgs: one slot, one size, unit * plane); the
+// batch kernels (gf_*_batch_kernel, velo_detect_features_batch: units of several contexts and of different image sizes in the same
+// launches) read it from a device table uploaded with the jobs, at an index that is uniform per workgroup -- scalar loads, once.  Grids
+// of the batch kernels are sized for the largest unit; a workgroup outside its unit's image leaves at once.  The selection stays per
+// unit: verdicts depend on that unit's keys and states only, so gf_finish's proof of progress holds for every unit independently.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -48,8 +55,29 @@ constexpr int kGfHdr = 8;                  // ints per unit: max bits, candidate
 enum { kGfNone = 0, kGfUndecided = 1, kGfAccepted = 2, kGfDropped = 3 };
 
 struct GfJob {
-    int unit;                              // index into GfArgs::cams
+    int unit;                              // index into GfArgs::cams (batch: into the unit table)
     int first, n;                          // the job's existing points [first, first + n) of the call
+    int pad_;
+};
+
+struct GfUnit {                            // one camera of one context, and its share of the call's scratch
+    const unsigned char* plane;            // padded level 0 of the current image (element 0 = padded pixel (0, 0))
+    float* eig;                            // h x w
+    unsigned char* state;                  // padded state map, rows sstride apart
+    unsigned* cand;                        // h x w: candidate pixel indices
+    unsigned* und;                         // h x w: undecided at the start of the finish kernel
+    unsigned long long* keys;              // a power of two >= h x w
+    int* hdr;                              // kGfHdr
+    int w, h, stride, sstride;             // stride: elements per padded image row
+};
+
+struct GfParams {                          // what every unit of a call shares
+    float scale2;
+    int radius;                            // ceil(min_distance) - 1: the largest |dx| in range
+    int max_corners;
+    int capacity;                          // corners written per job
+    double quality, md2;
+    float md2f;                            // (float)(min_distance^2), the reference's md2
     int pad_;
 };
 
@@ -68,29 +96,41 @@ struct GfArgs {
     unsigned long long* keys;              // units x keys_cap (a power of two >= h x w)
     long long keys_cap;
     int* hdr;                              // units x kGfHdr
-    float scale2;
-    int radius;                            // ceil(min_distance) - 1: the largest |dx| in range
-    int max_corners;
-    int capacity;                          // corners written per job
-    double quality, md2;
-    float md2f;                            // (float)(min_distance^2), the reference's md2
+    GfParams K;
 };
 
-__global__ void __launch_bounds__(kGfTile * kGfTile) gf_response_kernel(GfArgs A)
-#if VELO_DEF_DETECT
-{
-    __shared__ int img[kGfTile + 4][kGfTile + 4];
-    __shared__ int pxx[kGfTile + 2][kGfTile + 2], pxy[kGfTile + 2][kGfTile + 2], pyy[kGfTile + 2][kGfTile + 2];
-    __shared__ unsigned smax;
-    const int u = blockIdx.z;
-    const int w = A.w, h = A.h;
-    const unsigned char* plane = A.pix + A.cams[u] * A.cam_pix + A.L0.off;
+// unit u of a single-context call
+__device__ __forceinline__ GfUnit gf_unit_of(const GfArgs& A, int u) {
+    GfUnit U;
+    const long long plane = (long long)A.w * A.h;
+    U.plane = A.pix + A.cams[u] * A.cam_pix + A.L0.off;
+    U.eig = A.eig + u * plane;
+    U.state = A.state + u * A.splane;
+    U.cand = A.cand + u * plane;
+    U.und = A.und + u * plane;
+    U.keys = A.keys + u * A.keys_cap;
+    U.hdr = A.hdr + u * kGfHdr;
+    U.w = A.w; U.h = A.h; U.stride = A.L0.stride; U.sstride = A.sstride;
+    return U;
+}
+
+struct GfResponseLds {
+    int img[kGfTile + 4][kGfTile + 4];
+    int pxx[kGfTile + 2][kGfTile + 2], pxy[kGfTile + 2][kGfTile + 2], pyy[kGfTile + 2][kGfTile + 2];
+    unsigned smax;
+};
+
+__device__ __forceinline__ void gf_response_body(const GfUnit& U, const GfParams& A, GfResponseLds& S) {
+    auto& img = S.img; auto& pxx = S.pxx; auto& pxy = S.pxy; auto& pyy = S.pyy;
+    unsigned& smax = S.smax;
+    const int w = U.w, h = U.h;
+    const unsigned char* plane = U.plane;
     const int X0 = (int)blockIdx.x * kGfTile, Y0 = (int)blockIdx.y * kGfTile;
     if (threadIdx.x == 0) smax = 0u;
     // x in [X0 - 2, X0 + 18) lies within [-2, w + 16]: inside the 32-pixel border
     for (int i = threadIdx.x; i < (kGfTile + 4) * (kGfTile + 4); i += kGfTile * kGfTile) {
         const int ty = i / (kGfTile + 4), tx = i - ty * (kGfTile + 4);
-        img[ty][tx] = plane[(long long)(Y0 - 2 + ty + kLkPad) * A.L0.stride + (X0 - 2 + tx + kLkPad)];
+        img[ty][tx] = plane[(long long)(Y0 - 2 + ty + kLkPad) * U.stride + (X0 - 2 + tx + kLkPad)];
     }
     __syncthreads();
     for (int i = threadIdx.x; i < (kGfTile + 2) * (kGfTile + 2); i += kGfTile * kGfTile) {
@@ -123,32 +163,48 @@ __global__ void __launch_bounds__(kGfTile * kGfTile) gf_response_kernel(GfArgs A
         const float c = ((float)syy * A.scale2) * 0.5f;
         const float d = a - c;
         const float v = (a + c) - sqrtf(d * d + b * b);
-        A.eig[(long long)u * w * h + (long long)y * w + x] = v;
+        U.eig[(long long)y * w + x] = v;
         if (v > 0.f) atomicMax(&smax, __float_as_uint(v));
     }
     __syncthreads();
-    if (threadIdx.x == 0 && smax != 0u) atomicMax((unsigned*)&A.hdr[u * kGfHdr + 0], smax);
+    if (threadIdx.x == 0 && smax != 0u) atomicMax((unsigned*)&U.hdr[0], smax);
+}
+
+__global__ void __launch_bounds__(kGfTile * kGfTile) gf_response_kernel(GfArgs A)
+#if VELO_DEF_DETECT
+{
+    __shared__ GfResponseLds S;
+    gf_response_body(gf_unit_of(A, blockIdx.z), A.K, S);
 }
 #else
 ;
 #endif
 
-__device__ __forceinline__ unsigned char* gf_state_at(const GfArgs& A, int u, int x, int y) {
-    return A.state + u * A.splane + (long long)(y + kGfStatePad) * A.sstride + (x + kGfStatePad);
+// grid (tiles x, tiles y, units) for the largest unit
+__global__ void __launch_bounds__(kGfTile * kGfTile) gf_response_batch_kernel(const GfUnit* __restrict__ units, GfParams K)
+#if VELO_DEF_DETECT
+{
+    __shared__ GfResponseLds S;
+    const GfUnit U = units[blockIdx.z];
+    if ((int)blockIdx.x * kGfTile >= U.w || (int)blockIdx.y * kGfTile >= U.h) return;
+    gf_response_body(U, K, S);
+}
+#else
+;
+#endif
+
+__device__ __forceinline__ unsigned char* gf_state_at(const GfUnit& U, int x, int y) {
+    return U.state + (long long)(y + kGfStatePad) * U.sstride + (x + kGfStatePad);
 }
 
 // 64 x 4 pixels per workgroup
-__global__ void __launch_bounds__(256) gf_candidates_kernel(GfArgs A)
-#if VELO_DEF_DETECT
-{
-    __shared__ int s_n, s_base;
-    const int u = blockIdx.z;
-    const int w = A.w, h = A.h;
-    const float* eig = A.eig + (long long)u * w * h;
+__device__ __forceinline__ void gf_candidates_body(const GfUnit& U, const GfParams& A, int& s_n, int& s_base) {
+    const int w = U.w, h = U.h;
+    const float* eig = U.eig;
     const int x = (int)blockIdx.x * 64 + (threadIdx.x & 63), y = (int)blockIdx.y * 4 + (threadIdx.x >> 6);
     if (threadIdx.x == 0) s_n = 0;
     __syncthreads();
-    const float maxv = __uint_as_float((unsigned)A.hdr[u * kGfHdr + 0]);
+    const float maxv = __uint_as_float((unsigned)U.hdr[0]);
     const float thr = (float)((double)maxv * A.quality);
     bool is = false;
     int slot = 0;
@@ -163,28 +219,48 @@ __global__ void __launch_bounds__(256) gf_candidates_kernel(GfArgs A)
                     for (int i = -1; i <= 1; i++) is = is && (v >= eig[(long long)(y + j) * w + (x + i)]);
             }
         }
-        *gf_state_at(A, u, x, y) = is ? kGfUndecided : kGfNone;
+        *gf_state_at(U, x, y) = is ? kGfUndecided : kGfNone;
         if (is) slot = atomicAdd(&s_n, 1);
     }
     __syncthreads();
-    if (threadIdx.x == 0 && s_n > 0) s_base = atomicAdd(&A.hdr[u * kGfHdr + 1], s_n);
+    if (threadIdx.x == 0 && s_n > 0) s_base = atomicAdd(&U.hdr[1], s_n);
     __syncthreads();
-    if (is) A.cand[(long long)u * w * h + s_base + slot] = (unsigned)(y * w + x);
+    if (is) U.cand[s_base + slot] = (unsigned)(y * w + x);
+}
+
+__global__ void __launch_bounds__(256) gf_candidates_kernel(GfArgs A)
+#if VELO_DEF_DETECT
+{
+    __shared__ int s_n, s_base;
+    gf_candidates_body(gf_unit_of(A, blockIdx.z), A.K, s_n, s_base);
+}
+#else
+;
+#endif
+
+// grid (cdiv(w, 64), cdiv(h, 4), units) for the largest unit
+__global__ void __launch_bounds__(256) gf_candidates_batch_kernel(const GfUnit* __restrict__ units, GfParams K)
+#if VELO_DEF_DETECT
+{
+    __shared__ int s_n, s_base;
+    const GfUnit U = units[blockIdx.z];
+    if ((int)blockIdx.x * 64 >= U.w || (int)blockIdx.y * 4 >= U.h) return;
+    gf_candidates_body(U, K, s_n, s_base);
 }
 #else
 ;
 #endif
 
 // the verdict on one undecided candidate from the states around it: kGfAccepted, kGfDropped or still kGfUndecided
-__device__ __forceinline__ int gf_decide(const GfArgs& A, int u, unsigned idx) {
-    const int w = A.w, r = A.radius;
+__device__ __forceinline__ int gf_decide(const GfUnit& U, const GfParams& A, unsigned idx) {
+    const int w = U.w, r = A.radius;
     const int y = (int)(idx / (unsigned)w), x = (int)(idx - (unsigned)y * (unsigned)w);
-    const float* eig = A.eig + (long long)u * w * A.h;
+    const float* eig = U.eig;
     const float v = eig[idx];
     const int w0 = (x + kGfStatePad - r) >> 2, w1 = (x + kGfStatePad + r) >> 2;   // words of a padded row; >= 0, < sstride / 4
     bool blocked = false;
     for (int dy = -r; dy <= r; dy++) {
-        const unsigned* row = (const unsigned*)(A.state + u * A.splane + (long long)(y + dy + kGfStatePad) * A.sstride);
+        const unsigned* row = (const unsigned*)(U.state + (long long)(y + dy + kGfStatePad) * U.sstride);
         for (int wb = w0; wb <= w1; wb += 8) {
             unsigned wv[8];                                    // eight independent loads in flight (a row of the reference's radius is 6-7 words)
 #pragma unroll
@@ -219,42 +295,57 @@ __device__ __forceinline__ void gf_store_state(unsigned char* p, int s) {
 }
 
 // one pass over every candidate of every unit: grid (kGfRoundBlocks, units)
+__device__ __forceinline__ void gf_round_body(const GfUnit& U, const GfParams& A) {
+    const int n = U.hdr[1];
+    const unsigned* cand = U.cand;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const unsigned idx = cand[i];
+        unsigned char* sp = gf_state_at(U, (int)(idx % (unsigned)U.w), (int)(idx / (unsigned)U.w));
+        if (gf_load_state(sp) != kGfUndecided) continue;
+        const int s = gf_decide(U, A, idx);
+        if (s != kGfUndecided) gf_store_state(sp, s);
+    }
+}
+
 __global__ void __launch_bounds__(256) gf_round_kernel(GfArgs A)
 #if VELO_DEF_DETECT
 {
-    const int u = blockIdx.y;
-    const int n = A.hdr[u * kGfHdr + 1];
-    const unsigned* cand = A.cand + (long long)u * A.w * A.h;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const unsigned idx = cand[i];
-        unsigned char* sp = gf_state_at(A, u, (int)(idx % (unsigned)A.w), (int)(idx / (unsigned)A.w));
-        if (gf_load_state(sp) != kGfUndecided) continue;
-        const int s = gf_decide(A, u, idx);
-        if (s != kGfUndecided) gf_store_state(sp, s);
-    }
+    gf_round_body(gf_unit_of(A, blockIdx.y), A.K);
+}
+#else
+;
+#endif
+
+__global__ void __launch_bounds__(256) gf_round_batch_kernel(const GfUnit* __restrict__ units, GfParams K)
+#if VELO_DEF_DETECT
+{
+    const GfUnit U = units[blockIdx.y];
+    gf_round_body(U, K);
 }
 #else
 ;
 #endif
 
 // one workgroup per unit: the rest of the selection, the sort of the accepted keys and the cap
-__global__ void __launch_bounds__(kGfFinishThreads) gf_finish_kernel(GfArgs A)
-#if VELO_DEF_DETECT
-{
-    __shared__ unsigned long long skeys[kGfSortLds];
-    __shared__ int s_n, s_left, s_acc;
-    const int u = blockIdx.x, tid = threadIdx.x;
-    const int w = A.w;
-    const long long plane = (long long)w * A.h;
-    const int n = A.hdr[u * kGfHdr + 1];
-    const unsigned* cand = A.cand + u * plane;
-    unsigned* und = A.und + u * plane;
-    const float* eig = A.eig + u * plane;
+struct GfFinishLds {
+    unsigned long long skeys[kGfSortLds];
+    int s_n, s_left, s_acc;
+};
+
+__device__ __forceinline__ void gf_finish_body(const GfUnit& U, const GfParams& A, GfFinishLds& S) {
+    auto& skeys = S.skeys;
+    int& s_n = S.s_n; int& s_left = S.s_left; int& s_acc = S.s_acc;
+    const int tid = threadIdx.x;
+    const int w = U.w;
+    const int n = U.hdr[1];
+    const unsigned* cand = U.cand;
+    unsigned* und = U.und;
+    const float* eig = U.eig;
     if (tid == 0) { s_n = 0; s_acc = 0; }
     __syncthreads();
     for (int i = tid; i < n; i += kGfFinishThreads) {
         const unsigned idx = cand[i];
-        if (gf_load_state(gf_state_at(A, u, (int)(idx % (unsigned)w), (int)(idx / (unsigned)w))) == kGfUndecided) und[atomicAdd(&s_n, 1)] = idx;
+        if (gf_load_state(gf_state_at(U, (int)(idx % (unsigned)w), (int)(idx / (unsigned)w))) == kGfUndecided) und[atomicAdd(&s_n, 1)] = idx;
     }
     __syncthreads();
     const int n_und = s_n;
@@ -264,9 +355,9 @@ __global__ void __launch_bounds__(kGfFinishThreads) gf_finish_kernel(GfArgs A)
         __syncthreads();
         for (int i = tid; i < n_und; i += kGfFinishThreads) {
             const unsigned idx = und[i];
-            unsigned char* sp = gf_state_at(A, u, (int)(idx % (unsigned)w), (int)(idx / (unsigned)w));
+            unsigned char* sp = gf_state_at(U, (int)(idx % (unsigned)w), (int)(idx / (unsigned)w));
             if (gf_load_state(sp) != kGfUndecided) continue;
-            const int s = gf_decide(A, u, idx);
+            const int s = gf_decide(U, A, idx);
             if (s != kGfUndecided) gf_store_state(sp, s);
             else atomicAdd(&s_left, 1);
         }
@@ -277,10 +368,10 @@ __global__ void __launch_bounds__(kGfFinishThreads) gf_finish_kernel(GfArgs A)
         __syncthreads();
     }
     // the accepted keys, in any order
-    unsigned long long* gkeys = A.keys + u * A.keys_cap;
+    unsigned long long* gkeys = U.keys;
     for (int i = tid; i < n; i += kGfFinishThreads) {
         const unsigned idx = cand[i];
-        if (gf_load_state(gf_state_at(A, u, (int)(idx % (unsigned)w), (int)(idx / (unsigned)w))) == kGfAccepted)
+        if (gf_load_state(gf_state_at(U, (int)(idx % (unsigned)w), (int)(idx / (unsigned)w))) == kGfAccepted)
             gkeys[atomicAdd(&s_acc, 1)] = ((unsigned long long)__float_as_uint(eig[idx]) << 32) | idx;
     }
     __syncthreads();
@@ -310,33 +401,45 @@ __global__ void __launch_bounds__(kGfFinishThreads) gf_finish_kernel(GfArgs A)
         }
     if (in_lds) for (int i = tid; i < n_acc; i += kGfFinishThreads) gkeys[i] = skeys[i];
     if (tid == 0) {
-        A.hdr[u * kGfHdr + 2] = n_acc;
-        A.hdr[u * kGfHdr + 3] = (A.max_corners > 0 && n_acc > A.max_corners) ? A.max_corners : n_acc;
-        A.hdr[u * kGfHdr + 4] = passes;
-        A.hdr[u * kGfHdr + 5] = n_und;
+        U.hdr[2] = n_acc;
+        U.hdr[3] = (A.max_corners > 0 && n_acc > A.max_corners) ? A.max_corners : n_acc;
+        U.hdr[4] = passes;
+        U.hdr[5] = n_und;
     }
+}
+
+__global__ void __launch_bounds__(kGfFinishThreads) gf_finish_kernel(GfArgs A)
+#if VELO_DEF_DETECT
+{
+    __shared__ GfFinishLds S;
+    gf_finish_body(gf_unit_of(A, blockIdx.x), A.K, S);
+}
+#else
+;
+#endif
+
+__global__ void __launch_bounds__(kGfFinishThreads) gf_finish_batch_kernel(const GfUnit* __restrict__ units, GfParams K)
+#if VELO_DEF_DETECT
+{
+    __shared__ GfFinishLds S;
+    const GfUnit U = units[blockIdx.x];
+    gf_finish_body(U, K, S);
 }
 #else
 ;
 #endif
 
 // grid (kGfOutBlocks, jobs): xy / response / fresh of the first `capacity` corners in key order; counts [job][3] = corners, fresh, candidates
-__global__ void __launch_bounds__(256) gf_output_kernel(GfArgs A, const GfJob* __restrict__ jobs, const float2* __restrict__ existing,
-                                                        int* __restrict__ counts, float2* __restrict__ out_xy, float* __restrict__ out_resp,
-                                                        unsigned char* __restrict__ out_fresh)
-#if VELO_DEF_DETECT
-{
-    __shared__ float2 pts[256];
-    __shared__ int s_fresh;
+__device__ __forceinline__ void gf_output_body(const GfUnit& U, const GfParams& A, const GfJob J, const float2* __restrict__ existing,
+                                               int* __restrict__ counts, float2* __restrict__ out_xy, float* __restrict__ out_resp,
+                                               unsigned char* __restrict__ out_fresh, float2* pts, int& s_fresh) {
     const int j = blockIdx.y;
-    const GfJob J = jobs[j];
-    const int u = J.unit;
-    const int n_out = A.hdr[u * kGfHdr + 3];
-    const unsigned long long* keys = A.keys + u * A.keys_cap;
-    const float fw = (float)A.w, fh = (float)A.h;
+    const int n_out = U.hdr[3];
+    const unsigned long long* keys = U.keys;
+    const float fw = (float)U.w, fh = (float)U.h;
     const float md2 = A.md2f;                  // util::dist2 is a float converted to double: (double)d2 < (double)md2f <=> d2 < md2f
     if (threadIdx.x == 0) s_fresh = 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { counts[3 * j + 0] = n_out; counts[3 * j + 2] = A.hdr[u * kGfHdr + 1]; }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { counts[3 * j + 0] = n_out; counts[3 * j + 2] = U.hdr[1]; }
     for (int base = blockIdx.x * 256; base < n_out; base += gridDim.x * 256) {       // uniform per workgroup
         const int i = base + threadIdx.x;
         unsigned long long key = 0ull;
@@ -344,8 +447,8 @@ __global__ void __launch_bounds__(256) gf_output_kernel(GfArgs A, const GfJob* _
         if (i < n_out) {
             key = keys[i];
             const unsigned idx = (unsigned)(key & 0xFFFFFFFFull);
-            const unsigned y = idx / (unsigned)A.w;
-            cx = (float)(idx - y * (unsigned)A.w); cy = (float)y;
+            const unsigned y = idx / (unsigned)U.w;
+            cx = (float)(idx - y * (unsigned)U.w); cy = (float)y;
         }
         bool bad = false;
         for (int e0 = 0; e0 < J.n; e0 += 256) {
@@ -377,6 +480,33 @@ __global__ void __launch_bounds__(256) gf_output_kernel(GfArgs A, const GfJob* _
     }
     __syncthreads();
     if (threadIdx.x == 0 && s_fresh > 0) atomicAdd(&counts[3 * j + 1], s_fresh);
+}
+
+__global__ void __launch_bounds__(256) gf_output_kernel(GfArgs A, const GfJob* __restrict__ jobs, const float2* __restrict__ existing,
+                                                        int* __restrict__ counts, float2* __restrict__ out_xy, float* __restrict__ out_resp,
+                                                        unsigned char* __restrict__ out_fresh)
+#if VELO_DEF_DETECT
+{
+    __shared__ float2 pts[256];
+    __shared__ int s_fresh;
+    const GfJob J = jobs[blockIdx.y];
+    gf_output_body(gf_unit_of(A, J.unit), A.K, J, existing, counts, out_xy, out_resp, out_fresh, pts, s_fresh);
+}
+#else
+;
+#endif
+
+__global__ void __launch_bounds__(256) gf_output_batch_kernel(const GfUnit* __restrict__ units, GfParams K, const GfJob* __restrict__ jobs,
+                                                              const float2* __restrict__ existing, int* __restrict__ counts,
+                                                              float2* __restrict__ out_xy, float* __restrict__ out_resp,
+                                                              unsigned char* __restrict__ out_fresh)
+#if VELO_DEF_DETECT
+{
+    __shared__ float2 pts[256];
+    __shared__ int s_fresh;
+    const GfJob J = jobs[blockIdx.y];
+    const GfUnit U = units[J.unit];
+    gf_output_body(U, K, J, existing, counts, out_xy, out_resp, out_fresh, pts, s_fresh);
 }
 #else
 ;

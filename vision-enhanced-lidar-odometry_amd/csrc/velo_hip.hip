@@ -64,3 +64,4 @@ extern "C" int velo_launch_lm_solve_ag(int nb_max, int n, void* stream, const vo
 #include "velo_api_match.inl"   // C-ABI: batched Hamming matching of 64-byte descriptors (matchFeatures, velo.h:499-560)
 #include "velo_api_track.inl"   // C-ABI: resident camera images and pyramidal Lucas-Kanade tracking (trackFeatures, velo.h:28-116)
 #include "velo_api_detect.inl"   // C-ABI: GFTT corner detection on the current images (detectFeatures, velo.h:118-177)
+#include "velo_api_frontend_batch.inl"   // C-ABI: images, tracking and detection of several contexts in one call each (velo_*_batch)

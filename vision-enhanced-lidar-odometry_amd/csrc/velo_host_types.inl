@@ -428,6 +428,9 @@ struct velo_ctx {
     unsigned char* h_gf_out = nullptr;
     size_t h_gf_out_cap = 0;
     int gf_units = 0;                    // units of the last call (velo_diag_detect_counters)
+    // front-end batch calls (velo_api_frontend_batch.inl): the FIRST context of a call lends its stream, staging and scratch buffers
+    hipEvent_t fb_here_ev = nullptr;     // "everything enqueued on this context's stream so far": the lending stream waits for it
+    hipEvent_t fb_done_ev = nullptr;     // recorded on the lending stream after an asynchronous batch call: the other streams wait for it
 
     // lock-step batch driver (velo_frame_to_frame_batch): scratch owned by the FIRST context of a batch
     DevBuf<LMBatchItem> batch_items;

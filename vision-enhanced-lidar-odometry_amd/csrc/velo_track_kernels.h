@@ -17,6 +17,12 @@
 // |Ix| <= 4080: a lane's sum stays below 2^31) and the wave adds the 64 partial sums in int64 (butterfly: every lane ends with the same
 // exact total).  The float steps after the sums are computed redundantly by every lane from identical inputs, so control flow is
 // uniform.  Integer sums are exact, hence independent of the reduction order: what lets the result equal the restatement bit for bit.
+//
+// Batch variants (velo_set_images_batch / velo_track_features_batch: several contexts, possibly of different image sizes, in one launch):
+// lk_build_batch_kernel and lk_track_batch_kernel_<N> run the SAME bodies; what the single-context kernels take from their kernel
+// arguments (slot bases, level table) they take from small device tables uploaded with the call -- one LkBuildUnit per camera of every
+// context, one LkBatchJob per job, and the distinct LkPyr level tables both index.  The index is uniform per workgroup (build) or made
+// uniform per wave (track: readfirstlane), so the tables are read with scalar loads, once, outside the loops.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,6 +56,15 @@ struct LkJob {                             // one velo_track_job as the kernel s
     int first, n;                          // the job's points [first, first + n) of the call
 };
 
+struct LkParams {                          // what every point of a call shares
+    int win;
+    int max_count;
+    float min_eig;
+    int pad_;
+    double eps2;                           // epsilon^2 (calcOpticalFlowPyrLK squares it)
+    double flow_outlier;
+};
+
 struct LkTrackArgs {
     const unsigned char* prev_pix;         // slot of the previous images
     const int* prev_der;
@@ -57,11 +72,22 @@ struct LkTrackArgs {
     long long cam_pix;                     // elements per camera in a slot
     LkPyr P;                               // level sizes (both slots: the same image size)
     int top;                               // deepest level tracked (buildOpticalFlowPyramid's count for this window, - 1)
-    int win;
-    int max_count;
-    float min_eig;
-    double eps2;                           // epsilon^2 (calcOpticalFlowPyrLK squares it)
-    double flow_outlier;
+    LkParams K;
+};
+
+struct LkBuildUnit {                       // batch build: one camera of one context
+    const unsigned char* raw;              // its w0 x h0 upload
+    unsigned char* pix;                    // its share of the context's current slot
+    int* der;
+    int pyr, pad_;                         // index into the call's table of distinct LkPyr
+};
+
+struct LkBatchJob {                        // batch tracking: one velo_track_job with the bases of its context's cameras resolved
+    int first, n;                          // the job's points [first, first + n) of the call
+    int pyr, top;                          // level table of its context's image size; deepest level tracked at that size
+    const unsigned char* prev_pix;         // previous image of prev_cam (camera base inside the previous slot)
+    const int* prev_der;
+    const unsigned char* cur_pix;          // current image of cam
 };
 
 __device__ __forceinline__ int lk_refl(int i, int n) {       // borderInterpolate(BORDER_REFLECT_101), any offset
@@ -91,20 +117,9 @@ __device__ __forceinline__ int lk_value(const unsigned char* __restrict__ raw, c
     return (s + 128) >> 8;
 }
 
-// one level of every camera: grid (tiles x, tiles y, cameras); raw: cameras x (w0 x h0) bytes
-__global__ void __launch_bounds__(kLkTile * kLkTile)
-lk_build_kernel(const unsigned char* __restrict__ raw, unsigned char* __restrict__ pix, int* __restrict__ der, LkPyr P, int lev,
-                long long cam_pix)
-#if VELO_DEF_TRACK
-{
-    __shared__ int tile[kLkTile + 2][kLkTile + 2];
-    const int cam = blockIdx.z;
-    const LkLevel L = P.lv[lev];
-    const int w0 = P.lv[0].w, h0 = P.lv[0].h;
-    const unsigned char* craw = raw + (size_t)cam * w0 * h0;
-    unsigned char* cpix = pix + cam * cam_pix;
-    int* cder = der + cam * cam_pix;
-    const LkLevel B = P.lv[lev > 0 ? lev - 1 : 0];
+// one 16 x 16 tile of one level of one camera: craw its upload, cpix / cder its share of the slot, L the level, B the level below
+__device__ __forceinline__ void lk_build_body(const unsigned char* __restrict__ craw, unsigned char* __restrict__ cpix, int* __restrict__ cder,
+                                              const LkLevel L, const LkLevel B, int lev, int w0, int (*tile)[kLkTile + 2]) {
     const int X0 = (int)blockIdx.x * kLkTile - 1, Y0 = (int)blockIdx.y * kLkTile - 1;      // padded coordinates of tile[0][0]
     for (int i = threadIdx.x; i < (kLkTile + 2) * (kLkTile + 2); i += kLkTile * kLkTile) {
         const int ty = i / (kLkTile + 2), tx = i - ty * (kLkTile + 2);
@@ -133,6 +148,36 @@ lk_build_kernel(const unsigned char* __restrict__ raw, unsigned char* __restrict
     }
     cder[o] = d;
 }
+
+// one level of every camera: grid (tiles x, tiles y, cameras); raw: cameras x (w0 x h0) bytes
+__global__ void __launch_bounds__(kLkTile * kLkTile)
+lk_build_kernel(const unsigned char* __restrict__ raw, unsigned char* __restrict__ pix, int* __restrict__ der, LkPyr P, int lev,
+                long long cam_pix)
+#if VELO_DEF_TRACK
+{
+    __shared__ int tile[kLkTile + 2][kLkTile + 2];
+    const int cam = blockIdx.z;
+    const int w0 = P.lv[0].w, h0 = P.lv[0].h;
+    lk_build_body(raw + (size_t)cam * w0 * h0, pix + cam * cam_pix, der + cam * cam_pix, P.lv[lev], P.lv[lev > 0 ? lev - 1 : 0], lev, w0, tile);
+}
+#else
+;
+#endif
+
+// one level of every camera of every context: grid (tiles x, tiles y, units), sized for the largest unit; a unit that has no such level
+// or no such tile leaves at once (uniform per workgroup, before any barrier)
+__global__ void __launch_bounds__(kLkTile * kLkTile)
+lk_build_batch_kernel(const LkBuildUnit* __restrict__ units, const LkPyr* __restrict__ pyrs, int lev)
+#if VELO_DEF_TRACK
+{
+    __shared__ int tile[kLkTile + 2][kLkTile + 2];
+    const LkBuildUnit U = units[blockIdx.z];
+    const LkPyr* __restrict__ P = pyrs + U.pyr;
+    if (lev >= P->n_levels) return;
+    const LkLevel L = P->lv[lev];
+    if ((int)blockIdx.x * kLkTile >= L.w + 2 * kLkPad || (int)blockIdx.y * kLkTile >= L.h + 2 * kLkPad) return;
+    lk_build_body(U.raw, U.pix, U.der, L, P->lv[lev > 0 ? lev - 1 : 0], lev, P->lv[0].w, tile);
+}
 #else
 ;
 #endif
@@ -156,8 +201,9 @@ __device__ __forceinline__ void lk_weights(float a, float b, int* w00, int* w01,
     *w11 = (1 << kLkWBits) - *w00 - *w01 - *w10;
 }
 
-// the job that owns point i: the last job whose first <= i (empty jobs share their first with the next job)
-__device__ __forceinline__ int lk_job_of(const LkJob* __restrict__ jobs, int n_jobs, int i) {
+// the job that owns point i: the last job whose first <= i (empty jobs share their first with the next job); Job: LkJob or LkBatchJob
+template <typename Job>
+__device__ __forceinline__ int lk_job_of(const Job* __restrict__ jobs, int n_jobs, int i) {
     int lo = 0, hi = n_jobs;
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
@@ -167,17 +213,15 @@ __device__ __forceinline__ int lk_job_of(const LkJob* __restrict__ jobs, int n_j
 }
 
 // diag (diagnostics build only, else null): [level] iterations taken, [kLkLevels + level] points that entered the iteration loop
+// point gi of the call: I0 / D0 the previous image and derivatives of its job's prev_cam, J0 the current image of its cam (camera bases),
+// P the level table of that image size, top the deepest level tracked
 template <int N>
-__device__ __forceinline__ void lk_track_body(const LkJob* __restrict__ jobs, int n_jobs, const float2* __restrict__ pts, int total,
-                                              const LkTrackArgs& A, float2* __restrict__ out_xy, unsigned char* __restrict__ out_status,
-                                              unsigned char* __restrict__ out_kept, unsigned long long* __restrict__ diag) {
+__device__ __forceinline__ void lk_track_point(int gi, const unsigned char* __restrict__ I0, const int* __restrict__ D0,
+                                               const unsigned char* __restrict__ J0, const LkPyr& P, int top, const LkParams& A,
+                                               const float2* __restrict__ pts, float2* __restrict__ out_xy,
+                                               unsigned char* __restrict__ out_status, unsigned char* __restrict__ out_kept,
+                                               unsigned long long* __restrict__ diag) {
     const int lane = threadIdx.x & 63;
-    const int gi = (int)blockIdx.x * (kLkThreads / 64) + (int)(threadIdx.x >> 6);
-    if (gi >= total) return;                                   // the whole wave leaves together
-    const LkJob J = jobs[lk_job_of(jobs, n_jobs, gi)];
-    const unsigned char* I0 = A.prev_pix + J.prev_cam * A.cam_pix;
-    const int* D0 = A.prev_der + J.prev_cam * A.cam_pix;
-    const unsigned char* J0 = A.cur_pix + J.cam * A.cam_pix;
     const float2 p = pts[gi];
     const int win = A.win, npix = win * win;
     const float hw = (float)(win - 1) * 0.5f;
@@ -190,11 +234,11 @@ __device__ __forceinline__ void lk_track_body(const LkJob* __restrict__ jobs, in
     }
     bool status = true;
     float sx = 0.f, sy = 0.f;                                  // nextPts[i]
-    for (int lev = A.top; lev >= 0; lev--) {
-        const LkLevel L = A.P.lv[lev];
+    for (int lev = top; lev >= 0; lev--) {
+        const LkLevel L = P.lv[lev];
         const float scale = 1.f / (float)(1 << lev);
         const float px = p.x * scale, py = p.y * scale;
-        if (lev == A.top) { sx = px; sy = py; } else { sx = sx * 2.f; sy = sy * 2.f; }
+        if (lev == top) { sx = px; sy = py; } else { sx = sx * 2.f; sy = sy * 2.f; }
         const float ppx = px - hw, ppy = py - hw;
         // floor(v) in [-win, n) <=> v in [-win, n) (integer bounds): tested on the float, so NaN fails and no out-of-range value is converted
         if (!lk_in_bounds(ppx, ppy, win, L.w, L.h)) {
@@ -285,24 +329,58 @@ __device__ __forceinline__ void lk_track_body(const LkJob* __restrict__ jobs, in
         // velo.h:72-84: status, util::dist2 (float) against flow_outlier as double, inside [0, width) x [0, height)
         const float ex = p.x - sx, ey = p.y - sy;
         const double d2 = (double)(ex * ex + ey * ey);
-        const bool inside = !(sx < 0.f || sy < 0.f || sx >= (float)A.P.lv[0].w || sy >= (float)A.P.lv[0].h);
+        const bool inside = !(sx < 0.f || sy < 0.f || sx >= (float)P.lv[0].w || sy >= (float)P.lv[0].h);
         out_kept[gi] = (status && !(d2 > A.flow_outlier) && inside) ? 1 : 0;
     }
+}
+
+template <int N>
+__device__ __forceinline__ void lk_track_body(const LkJob* __restrict__ jobs, int n_jobs, const float2* __restrict__ pts, int total,
+                                              const LkTrackArgs& A, float2* __restrict__ out_xy, unsigned char* __restrict__ out_status,
+                                              unsigned char* __restrict__ out_kept, unsigned long long* __restrict__ diag) {
+    const int gi = (int)blockIdx.x * (kLkThreads / 64) + (int)(threadIdx.x >> 6);
+    if (gi >= total) return;                                   // the whole wave leaves together
+    const LkJob J = jobs[lk_job_of(jobs, n_jobs, gi)];
+    lk_track_point<N>(gi, A.prev_pix + J.prev_cam * A.cam_pix, A.prev_der + J.prev_cam * A.cam_pix, A.cur_pix + J.cam * A.cam_pix, A.P, A.top,
+                      A.K, pts, out_xy, out_status, out_kept, diag);
+}
+
+template <int N>
+__device__ __forceinline__ void lk_track_batch_body(const LkBatchJob* __restrict__ jobs, int n_jobs, const LkPyr* __restrict__ pyrs,
+                                                    const float2* __restrict__ pts, int total, const LkParams& K, float2* __restrict__ out_xy,
+                                                    unsigned char* __restrict__ out_status, unsigned char* __restrict__ out_kept) {
+    // a wave is one point: its index is the same in every lane; saying so keeps the search, the job record and the level table in
+    // scalar registers and scalar loads
+    const int gi = __builtin_amdgcn_readfirstlane((int)blockIdx.x * (kLkThreads / 64) + (int)(threadIdx.x >> 6));
+    if (gi >= total) return;                                   // the whole wave leaves together
+    const LkBatchJob J = jobs[lk_job_of(jobs, n_jobs, gi)];
+    lk_track_point<N>(gi, J.prev_pix, J.prev_der, J.cur_pix, pyrs[J.pyr], J.top, K, pts, out_xy, out_status, out_kept, nullptr);
 }
 
 #define VELO_LK_TRACK_KERNEL(NAME, N)                                                                                                   \
     __global__ void __launch_bounds__(kLkThreads)                                                                                       \
     NAME(const LkJob* __restrict__ jobs, int n_jobs, const float2* __restrict__ pts, int total, LkTrackArgs A, float2* __restrict__ out_xy, \
          unsigned char* __restrict__ out_status, unsigned char* __restrict__ out_kept, unsigned long long* __restrict__ diag)
+#define VELO_LK_TRACK_BATCH_KERNEL(NAME, N)                                                                                             \
+    __global__ void __launch_bounds__(kLkThreads)                                                                                       \
+    NAME(const LkBatchJob* __restrict__ jobs, int n_jobs, const LkPyr* __restrict__ pyrs, const float2* __restrict__ pts, int total,    \
+         LkParams K, float2* __restrict__ out_xy, unsigned char* __restrict__ out_status, unsigned char* __restrict__ out_kept)
 #if VELO_DEF_TRACK
 VELO_LK_TRACK_KERNEL(lk_track_kernel_4, 4) { lk_track_body<4>(jobs, n_jobs, pts, total, A, out_xy, out_status, out_kept, diag); }
 VELO_LK_TRACK_KERNEL(lk_track_kernel_8, 8) { lk_track_body<8>(jobs, n_jobs, pts, total, A, out_xy, out_status, out_kept, diag); }
 VELO_LK_TRACK_KERNEL(lk_track_kernel_16, 16) { lk_track_body<16>(jobs, n_jobs, pts, total, A, out_xy, out_status, out_kept, diag); }
+VELO_LK_TRACK_BATCH_KERNEL(lk_track_batch_kernel_4, 4) { lk_track_batch_body<4>(jobs, n_jobs, pyrs, pts, total, K, out_xy, out_status, out_kept); }
+VELO_LK_TRACK_BATCH_KERNEL(lk_track_batch_kernel_8, 8) { lk_track_batch_body<8>(jobs, n_jobs, pyrs, pts, total, K, out_xy, out_status, out_kept); }
+VELO_LK_TRACK_BATCH_KERNEL(lk_track_batch_kernel_16, 16) { lk_track_batch_body<16>(jobs, n_jobs, pyrs, pts, total, K, out_xy, out_status, out_kept); }
 #else
 VELO_LK_TRACK_KERNEL(lk_track_kernel_4, 4);
 VELO_LK_TRACK_KERNEL(lk_track_kernel_8, 8);
 VELO_LK_TRACK_KERNEL(lk_track_kernel_16, 16);
+VELO_LK_TRACK_BATCH_KERNEL(lk_track_batch_kernel_4, 4);
+VELO_LK_TRACK_BATCH_KERNEL(lk_track_batch_kernel_8, 8);
+VELO_LK_TRACK_BATCH_KERNEL(lk_track_batch_kernel_16, 16);
 #endif
 #undef VELO_LK_TRACK_KERNEL
+#undef VELO_LK_TRACK_BATCH_KERNEL
 
 }  // namespace velo
