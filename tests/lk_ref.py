@@ -136,12 +136,26 @@ def _accum(prod, mode):
     return acc * FLT_SCALE
 
 
+def _lane_max(stats, name, prod):
+    """stats["lane_max"][name]: the largest |sum| any lane of the GPU's wave holds -- lane l owns window pixels l, l + 64, ... in
+    row-major order (velo_track_kernels.h), which is the column order of prod [points, win * win]"""
+    if len(prod) == 0:
+        return
+    n, k = prod.shape
+    padded = np.zeros((n, -(-k // 64) * 64), dtype=np.int64)
+    padded[:, :k] = prod
+    m = int(np.abs(padded.reshape(n, -1, 64).sum(1)).max())
+    stats["lane_max"][name] = max(stats["lane_max"].get(name, 0), m)
+
+
 def track(prev_pyr, next_pyr, pts, win: int = 21, max_level: int = 4, max_count: int = 30, epsilon: float = 0.01,
           min_eig_threshold: float = 1e-4, accumulate: str = "int64", stats=None):
     """calcOpticalFlowPyrLK(prev, next, pts) without initial flow: (next_xy [n,2] f32, status [n] bool).
     accumulate="float": the window sums in float, row-major sequential (OpenCV's scalar order) -- the budget of the unpinned choice.
     stats: optional dict; receives iterations[level] (J samples taken), entered[level] (points that reached the iteration loop) and
-    oscillations[level] (points stopped by the |delta + prev_delta| < 0.01 rule)."""
+    oscillations[level] (points stopped by the |delta + prev_delta| < 0.01 rule).  A stats dict that arrives with a "lane_max" dict
+    also receives there, per product (IxIx, IxIy, IyIy, dIx, dIy), the largest |partial sum| of one lane of the GPU's wave over every
+    point, level and iteration: what the kernel holds in an int32."""
     pts = np.ascontiguousarray(np.asarray(pts, dtype=np.float32).reshape(-1, 2))
     n = len(pts)
     status = np.ones(n, dtype=bool)
@@ -177,6 +191,10 @@ def track(prev_pyr, next_pyr, pts, win: int = 21, max_level: int = 4, max_count:
         Ix = _descale(_bilinear(P["dx"].reshape(-1), idx, S, w4), W_BITS)
         Iy = _descale(_bilinear(P["dy"].reshape(-1), idx, S, w4), W_BITS)
         A11, A12, A22 = _accum(Ix * Ix, accumulate), _accum(Ix * Iy, accumulate), _accum(Iy * Iy, accumulate)
+        lanes = stats is not None and "lane_max" in stats
+        if lanes:
+            for name, prod in (("IxIx", Ix * Ix), ("IxIy", Ix * Iy), ("IyIy", Iy * Iy)):
+                _lane_max(stats, name, prod)
         D = A11 * A22 - A12 * A12
         minEig = (A22 + A11 - np.sqrt((A11 - A22) * (A11 - A22) + f32(4.0) * A12 * A12)) / f32(2 * win * win)
         bad = (minEig < min_eig) | (D < FLT_EPSILON)
@@ -210,6 +228,9 @@ def track(prev_pyr, next_pyr, pts, win: int = 21, max_level: int = 4, max_count:
             diff = _descale(_bilinear(Jflat, jdx, S, _weights(a, b)), W_BITS - 5) - Ipatch[live]
             b1 = _accum(diff * Ix[live], accumulate)
             b2 = _accum(diff * Iy[live], accumulate)
+            if lanes:
+                _lane_max(stats, "dIx", diff * Ix[live])
+                _lane_max(stats, "dIy", diff * Iy[live])
             dlx = (A12[live] * b2 - A22[live] * b1) * Dinv[live]
             dly = (A12[live] * b1 - A11[live] * b2) * Dinv[live]
             nx[live, 0] += dlx
