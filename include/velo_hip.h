@@ -617,6 +617,61 @@ int velo_track_features_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* job
 int velo_detect_features_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* job_ctx, const velo_detect_job* jobs, int32_t n_jobs,
                                const velo_gftt_params* p, int32_t capacity, float* xy, float* response, uint8_t* fresh, int32_t* counts);
 
+/* --- the resident landmark store: the bookkeeping between the stages of a frame (main.cpp:376-386, main.cpp:614-679, velo.h:1132-1160) ---
+ * Every context can hold one store: per landmark id keypoint_obs_count, keypoint_added and the landmark itself, every observation
+ * (the entries of keypoint_obs2 / keypoint_obs3) in a log, and the Rodrigues constants of every frame's pose -- all on the device.
+ * Per frame the caller hands over that frame's observations and pose only (one small upload per camera, one per pose) and the
+ * triangulation is two launches.  How the cost of a frame compares with the stateless velo_triangulate_points as a sequence grows
+ * has not been measured yet (tools/landmarks_bench.py is the measurement).  Both forms of the solve give the same bits.
+ *
+ * velo_landmarks_reset empties the store and fixes the cameras: cam_trans [n_cams][3] floats, n_cams 1..8.  log_capacity: entries
+ * the observation log holds before it is first reallocated (0: the default, 65536; the ids of one landmark store cost 21 bytes of
+ * device memory per id of the id space, so ids should be dense); the log, the id tables and the frame table all
+ * grow geometrically.  A reallocation is the only time an observe / set_pose call waits for the device. */
+int velo_landmarks_reset(velo_ctx* ctx, int32_t n_cams, const float* cam_trans, int32_t log_capacity);
+/* ceres_poses_vec[frame] = pose6 (angle-axis, translation).  Frames may arrive in any order and may be set again; a triangulation
+ * uses what was set last.  frame < 2^22. */
+int velo_landmarks_set_pose(velo_ctx* ctx, int32_t frame, const double pose6[6]);
+/* The loop body of main.cpp:622-645 for keypoints[cam][frame]: for entry i, obs_count[ids[i]]++ and the observation is kept as
+ * keypoint_obs3[id][cam][frame] = kp_with_depth[has_depth[i]] when has_depth[i] != -1, else as keypoint_obs2[id][cam][frame] =
+ * keypoints_xy[i] (canonical coordinates).  The id space grows as needed (main.cpp:614-621), ids < 2^26.  Refused with VELO_ERR_INVALID
+ * before anything changes: a second call for the same (frame, cam), a negative id, an id twice in one call, a has_depth entry
+ * outside [-1, n_with_depth).  n == 0 is a camera that saw nothing.  Asynchronous: the arrays are copied before the call returns. */
+int velo_landmarks_observe(velo_ctx* ctx, int32_t frame, int32_t cam, const int32_t* ids, const float* keypoints_xy /* n x 2 */,
+                           const int32_t* has_depth /* n */, const float* kp_with_depth_xyz /* n_with_depth x 3 */, int32_t n_with_depth,
+                           int32_t n);
+/* main.cpp:654-679 for `frame`: every id some camera observed in it, ascending (the std::set), with obs_count >= 3 is triangulated
+ * from ALL its observations in the reference's block order (3-D observations camera-major and frame-ascending, then the 2-D ones
+ * likewise), starting from its stored point when it was added before, else from (0, 0, 10) with the early solve on the first 3-D
+ * block; the point is stored (float) and the id marked added.  Every frame that holds an observation needs its pose
+ * (VELO_ERR_STATE otherwise).  Outputs in that id order: ids_out [capacity], points_out [capacity][3], results_out [capacity]
+ * (each may be NULL); *n_out = the number triangulated -- when it exceeds `capacity` all of them are still solved and stored, the
+ * first `capacity` are written.  One upload, one gather launch, one solve launch, one copy back, one synchronisation. */
+int velo_landmarks_triangulate(velo_ctx* ctx, int32_t frame, int32_t* ids_out, float* points_out, velo_tri_result* results_out,
+                               int32_t capacity, int32_t* n_out);
+/* The same for frames[i] of ctxs[i], i < n_ctx, in ONE gather launch and ONE solve launch: a device table carries every context's
+ * store, camera translations and velo_params (LM settings, loss), read per workgroup.  The rules of the front-end batch entries hold
+ * (distinct contexts on one device, the first lends its stream and staging, batch and single calls mix freely, n_ctx == 1 IS the
+ * single entry).  Outputs are context-major, `capacity` entries apart: ids_out [n_ctx][capacity], points_out [n_ctx][capacity][3],
+ * results_out [n_ctx][capacity], n_out [n_ctx].  Every context's outputs and store are byte-identical to the single entry's. */
+int velo_landmarks_triangulate_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* frames, int32_t* ids_out, float* points_out,
+                                     velo_tri_result* results_out, int32_t capacity, int32_t* n_out);
+/* getLandmarksAtFrame (velo.h:1132-1160): for every id observed in `frame` that is added, p = pose_inv (x, y, z, 1) in double, each
+ * row summed left to right, divided by p[3] and rounded to float; ascending id order (the std::map).  pose_inv16 is the row-major
+ * INVERSE of the frame's pose, computed by the caller (the reference's Eigen inverse() is third-party arithmetic).
+ * *n_out = the number of such landmarks; the first `capacity` are written. */
+int velo_landmarks_at_frame(velo_ctx* ctx, int32_t frame, const double pose_inv16[16], int32_t* ids_out, float* xyz_out, int32_t capacity,
+                            int32_t* n_out);
+/* Read-back of landmarks->at(id), keypoint_added[id] and keypoint_obs_count[id] for n ids, from the device (outputs may be NULL);
+ * an id beyond the store's id space reads as never seen. */
+int velo_landmarks_get(velo_ctx* ctx, const int32_t* ids, int32_t n, float* xyz /* n x 3 */, uint8_t* added, int32_t* obs_count);
+/* Host bookkeeping only, no device work: the distinct ids observed in `frame` and how many of them velo_landmarks_triangulate would
+ * solve now (obs_count >= 3) -- the size its outputs need.  Either output may be NULL. */
+int velo_landmarks_frame_count(velo_ctx* ctx, int32_t frame, int32_t* n_seen, int32_t* n_to_triangulate);
+/* info[8] = ids in the id space, log entries, log capacity, log reallocations, frames in the frame table, cameras, (frame, cam)
+ * pairs observed, 0. */
+int velo_landmarks_info(velo_ctx* ctx, int32_t* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -285,6 +285,16 @@ SIGNATURES = {
                                             C.c_void_p, C.c_void_p]),
     "velo_detect_features_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, _P(VeloGfttParams), C.c_int32,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "velo_landmarks_reset": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_int32]),
+    "velo_landmarks_set_pose": (C.c_int, [_ctx, C.c_int32, _dp]),
+    "velo_landmarks_observe": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "velo_landmarks_triangulate": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _P(C.c_int32)]),
+    "velo_landmarks_triangulate_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                   C.c_void_p]),
+    "velo_landmarks_at_frame": (C.c_int, [_ctx, C.c_int32, _dp, C.c_void_p, C.c_void_p, C.c_int32, _P(C.c_int32)]),
+    "velo_landmarks_get": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "velo_landmarks_frame_count": (C.c_int, [_ctx, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
+    "velo_landmarks_info": (C.c_int, [_ctx, C.c_void_p]),
 }
 
 _lib = None
@@ -633,6 +643,76 @@ class Context:
         self._check(self._lib.velo_triangulate_points(self._h, vp(poses), len(poses), vp(ct), len(ct), vp(ob), vp(off), n,
                                                       vp(pts), vp(init), vp(res)))
         return pts, res
+
+    # -- the resident landmark store (main.cpp:614-679, getLandmarksAtFrame velo.h:1132-1160) ---------------------------
+    def landmarks_reset(self, cam_trans, log_capacity: int = 0):
+        """Empties the store; cam_trans [n_cams, 3] fixes the cameras.  log_capacity: entries before the observation log first
+        reallocates (0: the library's default)."""
+        ct = np.ascontiguousarray(np.asarray(cam_trans, dtype=np.float32).reshape(-1, 3))
+        self._check(self._lib.velo_landmarks_reset(self._h, len(ct), C.c_void_p(ct.ctypes.data), int(log_capacity)))
+
+    def landmarks_set_pose(self, frame: int, pose6):
+        x = _dvec(pose6, 6)
+        self._check(self._lib.velo_landmarks_set_pose(self._h, int(frame), _ptr(x)))
+
+    def landmarks_observe(self, frame: int, cam: int, ids, keypoints_xy, has_depth, kp_with_depth_xyz=None):
+        """keypoints[cam][frame] with their ids, has_depth (-1 or an index into kp_with_depth_xyz [m, 3]) -- main.cpp:622-645"""
+        i = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+        k = np.ascontiguousarray(np.asarray(keypoints_xy, dtype=np.float32).reshape(-1, 2))
+        h = np.ascontiguousarray(np.asarray(has_depth, dtype=np.int32).reshape(-1))
+        d = np.ascontiguousarray(np.asarray(np.zeros((0, 3)) if kp_with_depth_xyz is None else kp_with_depth_xyz, dtype=np.float32).reshape(-1, 3))
+        if not len(i) == len(k) == len(h):
+            raise ValueError("landmarks_observe: one keypoint and one has_depth entry per id")
+        vp = lambda a: C.c_void_p(a.ctypes.data) if a.size else None   # noqa: E731
+        self._check(self._lib.velo_landmarks_observe(self._h, int(frame), int(cam), vp(i), vp(k), vp(h), vp(d), len(d), len(i)))
+
+    def landmarks_triangulate(self, frame: int, capacity: Optional[int] = None):
+        """main.cpp:654-679 for `frame`: (ids [k] i32 ascending, points [k, 3] f32, results [k] TRI_RESULT_DTYPE).  capacity: the
+        raw call with caller-sized outputs, which also returns the count: (ids, points, results, n)."""
+        ids, pts, res, n = landmarks_triangulate_batch([self], [frame], capacity=capacity, raw=True)
+        if capacity is not None:
+            return ids[0], pts[0], res[0], int(n[0])
+        return ids[0][:n[0]].copy(), pts[0][:n[0]].copy(), res[0][:n[0]].copy()
+
+    def landmarks_at_frame(self, frame: int, pose_inv, capacity: Optional[int] = None):
+        """getLandmarksAtFrame: (ids [k] i32 ascending, xyz [k, 3] f32) of the added landmarks seen in `frame`, in the frame whose
+        INVERSE pose (4 x 4) is given.  capacity: caller-sized outputs, returns (ids, xyz, n)."""
+        M = _dvec(pose_inv, 16)
+        n = C.c_int32(0)
+        cap = int(capacity) if capacity is not None else 0
+        if capacity is None:                         # the count first: it needs no device work
+            self._check(self._lib.velo_landmarks_at_frame(self._h, int(frame), _ptr(M), None, None, 0, C.byref(n)))
+            cap = n.value
+        ids = np.zeros(max(cap, 1), dtype=np.int32)
+        xyz = np.zeros((max(cap, 1), 3), dtype=np.float32)
+        self._check(self._lib.velo_landmarks_at_frame(self._h, int(frame), _ptr(M), C.c_void_p(ids.ctypes.data), C.c_void_p(xyz.ctypes.data),
+                                                      cap, C.byref(n)))
+        if capacity is not None:
+            return ids[:cap], xyz[:cap], n.value
+        return ids[:n.value].copy(), xyz[:n.value].copy()
+
+    def landmarks_get(self, ids):
+        """(xyz [n, 3] f32, added [n] bool, obs_count [n] i32) of the given ids, read from the device"""
+        i = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+        n = len(i)
+        xyz = np.zeros((max(n, 1), 3), dtype=np.float32)
+        added = np.zeros(max(n, 1), dtype=np.uint8)
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        vp = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+        self._check(self._lib.velo_landmarks_get(self._h, vp(i) if n else None, n, vp(xyz), vp(added), vp(cnt)))
+        return xyz[:n], added[:n].astype(bool), cnt[:n]
+
+    def landmarks_frame_count(self, frame: int):
+        """(distinct ids observed in `frame`, how many of them landmarks_triangulate would solve now); host bookkeeping only"""
+        a, b = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.velo_landmarks_frame_count(self._h, int(frame), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def landmarks_info(self) -> dict:
+        a = np.zeros(8, dtype=np.int32)
+        self._check(self._lib.velo_landmarks_info(self._h, C.c_void_p(a.ctypes.data)))
+        return dict(n_ids=int(a[0]), log_entries=int(a[1]), log_capacity=int(a[2]), log_reallocations=int(a[3]), frame_capacity=int(a[4]),
+                    n_cams=int(a[5]), observed=int(a[6]))
 
     # -- descriptor matching: matchFeatures (velo.h:499-560) ----------------------------------------------------
     def match_descriptors(self, query, train, match_thresh: float = 29.0):
@@ -1005,6 +1085,33 @@ def detect_features_batch(ctxs, jobs, return_counts: bool = False, **params):
         cap = need                                  # no cap on the corners and more of them than assumed: once more, sized right
     res = [(xy[j, :counts[j, 0]].copy(), resp[j, :counts[j, 0]].copy(), fr[j, :counts[j, 0]].astype(bool)) for j in range(len(jobs))]
     return (res, counts.copy()) if return_counts else res
+
+
+def landmarks_triangulate_batch(ctxs, frames, capacity: Optional[int] = None, raw: bool = False):
+    """Context.landmarks_triangulate for frames[i] of ctxs[i] in ONE call (one gather launch, one solve launch): per context
+    (ids, points, results).  capacity / raw: the call as it is -- context-major arrays ids [n_ctx, capacity], points
+    [n_ctx, capacity, 3], results [n_ctx, capacity] and the counts n [n_ctx] (a count above `capacity` means truncated outputs;
+    every landmark is solved and stored all the same)."""
+    lib, arr = _batch_lib_and_handles(ctxs)
+    if len(frames) != len(ctxs):
+        raise ValueError("landmarks_triangulate_batch: one frame per context")
+    fr = np.ascontiguousarray(np.asarray(frames, dtype=np.int32).reshape(-1))
+    n_ctx = len(ctxs)
+    if capacity is None:                             # what the largest context of the call will solve: host bookkeeping, no device work
+        cap = max(c.landmarks_frame_count(f)[1] for c, f in zip(ctxs, fr))
+    else:
+        cap = int(capacity)
+    if cap < 0:
+        raise ValueError("landmarks_triangulate_batch: capacity >= 0")
+    ids = np.zeros((n_ctx, max(cap, 1)), dtype=np.int32)
+    pts = np.zeros((n_ctx, max(cap, 1), 3), dtype=np.float32)
+    res = np.zeros((n_ctx, max(cap, 1)), dtype=TRI_RESULT_DTYPE)
+    n = np.zeros(n_ctx, dtype=np.int32)
+    vp = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+    _batch_check(lib, lib.velo_landmarks_triangulate_batch(C.cast(arr, C.c_void_p), n_ctx, vp(fr), vp(ids), vp(pts), vp(res), cap, vp(n)))
+    if raw or capacity is not None:
+        return ids[:, :cap], pts[:, :cap], res[:, :cap], n
+    return [(ids[i, :n[i]].copy(), pts[i, :n[i]].copy(), res[i, :n[i]].copy()) for i in range(n_ctx)]
 
 
 SCAN_ON_DEVICE, SCAN_SHARED, SCAN_PROMOTE = 1, 2, 4

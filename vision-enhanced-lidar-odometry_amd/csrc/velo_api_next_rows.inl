@@ -1,5 +1,38 @@
 // velo_api_next_rows.inl -- part of the host side of the C-ABI, included by velo_hip.hip (ONE translation unit; the order of the parts is the order of
 // definition).  C-ABI: SURVEY 8(f) rows 3 and 4 -- projection, keypoint depth, batched triangulation.
+namespace {
+
+// The per-frame constants of the triangulation kernels from one entry of ceres_poses_vec, in double with the host libm:
+// rot = -pose[0..2] (costfunctions.h:318-320), Rodrigues scalars, R columns.  Shared by velo_triangulate_points and the resident
+// landmark store (velo_api_landmarks.inl): one code path, one arithmetic.
+void tri_frame_from_pose(const double* cp, TriFrame* out) {
+    const double xr[6] = {-cp[0], -cp[1], -cp[2], 0.0, 0.0, 0.0};
+    PoseScalars S;
+    pose_scalars(xr, &S);
+    TriFrame& F = *out;
+    std::memset(&F, 0, sizeof(F));
+    for (int k = 0; k < 3; k++) { F.w[k] = S.w[k]; F.u[k] = S.u[k]; F.center[k] = cp[3 + k]; }
+    F.c = S.c; F.s = S.s; F.omc = S.omc; F.small = S.small;
+    for (int j = 0; j < 3; j++) {                                // column j = rotation of e_j, same operation order as the device form
+        double e[3] = {0.0, 0.0, 0.0}, o[3];
+        e[j] = 1.0;
+        if (!F.small) {
+            const double c0 = F.u[1] * e[2] - F.u[2] * e[1], c1 = F.u[2] * e[0] - F.u[0] * e[2], c2 = F.u[0] * e[1] - F.u[1] * e[0];
+            const double tmp = (F.u[0] * e[0] + F.u[1] * e[1] + F.u[2] * e[2]) * F.omc;
+            o[0] = e[0] * F.c + c0 * F.s + F.u[0] * tmp;
+            o[1] = e[1] * F.c + c1 * F.s + F.u[1] * tmp;
+            o[2] = e[2] * F.c + c2 * F.s + F.u[2] * tmp;
+        } else {
+            o[0] = e[0] + (F.w[1] * e[2] - F.w[2] * e[1]);
+            o[1] = e[1] + (F.w[2] * e[0] - F.w[0] * e[2]);
+            o[2] = e[2] + (F.w[0] * e[1] - F.w[1] * e[0]);
+        }
+        F.R[0 * 3 + j] = o[0]; F.R[1 * 3 + j] = o[1]; F.R[2 * 3 + j] = o[2];
+    }
+}
+
+}  // namespace
+
 extern "C" {   // (continued from the previous part)
 // ---- projectLidarToCamera + featureDepthAssociation (velo.h:329-497) ---------------------------------
 int velo_project_lidar(velo_ctx* c, int32_t of_target, const float cam_t[3], const double bounds[4], int32_t* n_valid_total) {
@@ -116,34 +149,8 @@ int velo_triangulate_points(velo_ctx* c, const double* camera_poses, int32_t n_f
         if (o.kind == VELO_TRI_OBS_2D && (o.cam < 0 || o.cam >= n_cams || !cam_trans)) return fail(VELO_ERR_INVALID, "observation %d: camera %d outside [0, %d)", k, o.cam, n_cams);
     }
     HIP_TRY(hipSetDevice(c->device));
-    // per-frame constants in double with the host libm: rot = -pose[0..2] (costfunctions.h:318-320), Rodrigues scalars, R columns
     std::vector<TriFrame> hf((size_t)std::max(n_frames, 1));
-    for (int f = 0; f < n_frames; f++) {
-        const double* cp = camera_poses + 6 * (size_t)f;
-        const double xr[6] = {-cp[0], -cp[1], -cp[2], 0.0, 0.0, 0.0};
-        PoseScalars S;
-        pose_scalars(xr, &S);
-        TriFrame& F = hf[(size_t)f];
-        std::memset(&F, 0, sizeof(F));
-        for (int k = 0; k < 3; k++) { F.w[k] = S.w[k]; F.u[k] = S.u[k]; F.center[k] = cp[3 + k]; }
-        F.c = S.c; F.s = S.s; F.omc = S.omc; F.small = S.small;
-        for (int j = 0; j < 3; j++) {                                // column j = rotation of e_j, same operation order as the device form
-            double e[3] = {0.0, 0.0, 0.0}, o[3];
-            e[j] = 1.0;
-            if (!F.small) {
-                const double c0 = F.u[1] * e[2] - F.u[2] * e[1], c1 = F.u[2] * e[0] - F.u[0] * e[2], c2 = F.u[0] * e[1] - F.u[1] * e[0];
-                const double tmp = (F.u[0] * e[0] + F.u[1] * e[1] + F.u[2] * e[2]) * F.omc;
-                o[0] = e[0] * F.c + c0 * F.s + F.u[0] * tmp;
-                o[1] = e[1] * F.c + c1 * F.s + F.u[1] * tmp;
-                o[2] = e[2] * F.c + c2 * F.s + F.u[2] * tmp;
-            } else {
-                o[0] = e[0] + (F.w[1] * e[2] - F.w[2] * e[1]);
-                o[1] = e[1] + (F.w[2] * e[0] - F.w[0] * e[2]);
-                o[2] = e[2] + (F.w[0] * e[1] - F.w[1] * e[0]);
-            }
-            F.R[0 * 3 + j] = o[0]; F.R[1 * 3 + j] = o[1]; F.R[2 * 3 + j] = o[2];
-        }
-    }
+    for (int f = 0; f < n_frames; f++) tri_frame_from_pose(camera_poses + 6 * (size_t)f, &hf[(size_t)f]);
     std::vector<double> hct((size_t)std::max(3 * n_cams, 3), 0.0);
     for (int k = 0; k < 3 * n_cams; k++) hct[(size_t)k] = (double)cam_trans[k];
     VELO_TRY(c->tri_frames.reserve(hf.size())); VELO_TRY(c->tri_cam_t.reserve(hct.size()));

@@ -172,6 +172,8 @@ struct LkSlot {
     bool valid = false;
 };
 
+struct LmStore;   // the resident landmark store (velo_api_landmarks.inl)
+
 struct velo_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -428,6 +430,8 @@ struct velo_ctx {
     unsigned char* h_gf_out = nullptr;
     size_t h_gf_out_cap = 0;
     int gf_units = 0;                    // units of the last call (velo_diag_detect_counters)
+    // the resident landmark store (velo_landmarks_*): created by velo_landmarks_reset, buffers of its own, which no registration reads or writes
+    std::shared_ptr<LmStore> lm;
     // front-end batch calls (velo_api_frontend_batch.inl): the FIRST context of a call lends its stream, staging and scratch buffers
     hipEvent_t fb_here_ev = nullptr;     // "everything enqueued on this context's stream so far": the lending stream waits for it
     hipEvent_t fb_done_ev = nullptr;     // recorded on the lending stream after an asynchronous batch call: the other streams wait for it

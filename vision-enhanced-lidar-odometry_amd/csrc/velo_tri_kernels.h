@@ -351,6 +351,26 @@ __device__ __forceinline__ void tri_evaluate_wave(TriShared& sh, const TriFrame*
     E->cost = __shfl(acc, 9);
 }
 
+// The wave's whole work on ONE landmark whose observations obs[b .. b + n_obs) arrive 3-D first: the early solve on the first 3-D block
+// (velo.h:1080-1083) when there is no initial guess, then the full problem (velo.h:1123), both from / into x; S receives the summary.
+// Shared by triangulate_wave_kernel below and the resident landmark store's solve (velo_landmark_kernels.h) as TEXT: as an inlined
+// function the same statements cost the existing kernel 14 more VGPRs (248 against 234), as a macro its code is what it was.  Needs
+// `sh` (TriShared) and `lane` in scope.
+#define VELO_TRI_WAVE_LANDMARK(frames, cam_t, obs, b, n_obs, guess, P, x, S)                                                                  \
+    S.n_solves = 0; S.termination = VELO_CONVERGENCE; S.lm_iterations = 0; S.evaluations = 0; S.final_cost = 0.0;                             \
+    TriLane mine;                                                                                                                              \
+    mine.kind = VELO_TRI_OBS_3D;                                                                                                               \
+    if (lane < n_obs) tri_load_obs(frames, cam_t, obs[b + lane], &mine);                                                                       \
+    int n3d = 0;                                                      /* 3-D observations come first (host partition / device gather) */      \
+    for (int k0 = 0; k0 < n_obs; k0 += 64) {                                                                                                   \
+        const int k = k0 + lane;                                                                                                               \
+        n3d += (int)__popcll(__ballot(k < n_obs && obs[b + k].kind == VELO_TRI_OBS_3D));                                                       \
+    }                                                                                                                                          \
+    if (!guess && n3d > 0)                                            /* velo.h:1080-1083 */                                                   \
+        tri_solve([&](const double* xx, TriEval* E) { tri_evaluate_wave(sh, frames, cam_t, obs + b, n_obs, n3d, true, mine, P, xx, E); }, P, x, &S); \
+    if (n_obs > 0)                                                    /* velo.h:1123 */                                                        \
+        tri_solve([&](const double* xx, TriEval* E) { tri_evaluate_wave(sh, frames, cam_t, obs + b, n_obs, n3d, false, mine, P, xx, E); }, P, x, &S);
+
 __global__ void __launch_bounds__(64)
 triangulate_wave_kernel(const TriFrame* __restrict__ frames, const double* __restrict__ cam_t, const velo_tri_obs* __restrict__ obs,
                         const int* __restrict__ off, int n, TriParams P, float* __restrict__ pts, const unsigned char* __restrict__ init,
@@ -366,19 +386,7 @@ triangulate_wave_kernel(const TriFrame* __restrict__ frames, const double* __res
     double x[3] = {0.0, 0.0, 10.0};                                   // velo.h:1043
     if (guess) { x[0] = pts[3 * l]; x[1] = pts[3 * l + 1]; x[2] = pts[3 * l + 2]; }   // velo.h:1044-1049
     velo_tri_result S;
-    S.n_solves = 0; S.termination = VELO_CONVERGENCE; S.lm_iterations = 0; S.evaluations = 0; S.final_cost = 0.0;
-    TriLane mine;
-    mine.kind = VELO_TRI_OBS_3D;
-    if (lane < n_obs) tri_load_obs(frames, cam_t, obs[b + lane], &mine);
-    int n3d = 0;                                                      // 3-D observations come first (host partition)
-    for (int k0 = 0; k0 < n_obs; k0 += 64) {
-        const int k = k0 + lane;
-        n3d += (int)__popcll(__ballot(k < n_obs && obs[b + k].kind == VELO_TRI_OBS_3D));
-    }
-    if (!guess && n3d > 0)                                            // velo.h:1080-1083
-        tri_solve([&](const double* xx, TriEval* E) { tri_evaluate_wave(sh, frames, cam_t, obs + b, n_obs, n3d, true, mine, P, xx, E); }, P, x, &S);
-    if (n_obs > 0)                                                    // velo.h:1123
-        tri_solve([&](const double* xx, TriEval* E) { tri_evaluate_wave(sh, frames, cam_t, obs + b, n_obs, n3d, false, mine, P, xx, E); }, P, x, &S);
+    VELO_TRI_WAVE_LANDMARK(frames, cam_t, obs, b, n_obs, guess, P, x, S)
     if (lane == 0) {
         pts[3 * l] = (float)x[0]; pts[3 * l + 1] = (float)x[1]; pts[3 * l + 2] = (float)x[2];        // velo.h:1124-1126
         if (results) results[l] = S;
