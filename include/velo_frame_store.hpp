@@ -1,0 +1,128 @@
+// velo_frame_store.hpp -- header-only C++11 adaptor of the resident keypoint frames (velo_frames_*, velo_build_matches in velo_hip.h)
+// over the reference's containers: what main.cpp:366-405 does between tracking and frameToFrame, with the visual matches assembled
+// on the device.
+//
+//     velo_hip::FrameStore frames(ctx.get(), num_cams, &cam_trans[0][0]);
+//     per frame, once its keypoints, ids and depth are final for a registration (again when they change):
+//                 frames.putFrame(keypoints, keypoint_ids, has_depth, keypoints_with_depth, frame);
+//     instead of matchUsingId + getLandmarksAtFrame + frameToFrame (main.cpp:366-405):
+//                 dpose = velo_hip::frameToFrameResident<Eigen::Matrix4d>(ctx, frames, frame, frame - dframe, &pose_inverse,
+//                             scans_M, scans_S, kd_trees, transform, matches, good_matches, residual_type, enable_icp);
+//     frames.dropFrame(frame) when a frame leaves the window.
+//
+// Templated over the container types like the other adaptors (cv::Point2f, pcl::PointCloud<pcl::PointXYZ>::Ptr, Eigen::Matrix4d or
+// stand-ins): a keypoint needs .x / .y, a cloud pointer ->points (a vector of points with .x / .y / .z), a matrix operator()(row, col).
+#ifndef VELO_FRAME_STORE_HPP_
+#define VELO_FRAME_STORE_HPP_
+#include <utility>
+#include <vector>
+
+#include "velo_frame_to_frame.hpp"
+
+namespace velo_hip {
+
+class FrameStore {
+public:
+    FrameStore(velo_ctx* ctx, int num_cams, const float* cam_trans, int arena_capacity = 0) : ctx_(ctx), num_cams_(num_cams) {
+        status_ = velo_frames_reset(ctx, num_cams, cam_trans, arena_capacity);
+    }
+    int status() const { return status_; }
+    int numCams() const { return num_cams_; }
+    velo_ctx* ctx() const { return ctx_; }
+
+    // keypoints[cam][frame][i], keypoint_ids[cam][frame][i], has_depth[cam][frame][i], keypoints_with_depth[cam][frame]->points[j];
+    // a frame put before is replaced
+    template <class Keypoints, class Ids, class HasDepth, class Clouds>
+    int putFrame(const Keypoints& keypoints, const Ids& keypoint_ids, const HasDepth& has_depth, const Clouds& keypoints_with_depth, int frame) {
+        for (int cam = 0; cam < num_cams_; cam++) {
+            const size_t n = keypoints[cam][frame].size();
+            std::vector<int32_t> ids(n), hd(n);
+            std::vector<float> xy(2 * n), cloud;
+            for (size_t i = 0; i < n; i++) {
+                ids[i] = keypoint_ids[cam][frame][i];
+                hd[i] = has_depth[cam][frame][i];
+                xy[2 * i] = keypoints[cam][frame][i].x;
+                xy[2 * i + 1] = keypoints[cam][frame][i].y;
+            }
+            size_t m = 0;
+            if (keypoints_with_depth[cam][frame]) {
+                m = keypoints_with_depth[cam][frame]->points.size();
+                cloud.resize(3 * m);
+                for (size_t j = 0; j < m; j++) {
+                    cloud[3 * j] = keypoints_with_depth[cam][frame]->points[j].x;
+                    cloud[3 * j + 1] = keypoints_with_depth[cam][frame]->points[j].y;
+                    cloud[3 * j + 2] = keypoints_with_depth[cam][frame]->points[j].z;
+                }
+            }
+            status_ = velo_frames_put(ctx_, frame, cam, n ? &ids[0] : 0, n ? &xy[0] : 0, n ? &hd[0] : 0, m ? &cloud[0] : 0, (int32_t)m, (int32_t)n);
+            if (status_ != VELO_OK) return status_;
+        }
+        return status_;
+    }
+
+    int dropFrame(int frame) { return status_ = velo_frames_drop(ctx_, frame); }
+
+    // keypoints of `frame` over all cameras as the library holds them: no match list of a registration against it is longer
+    int32_t frameSize(int frame) {
+        int32_t n = 0;
+        status_ = velo_frames_count(ctx_, frame, 0, &n);
+        return status_ == VELO_OK ? n : 0;
+    }
+
+private:
+    velo_ctx* ctx_;
+    int num_cams_;
+    int status_;
+};
+
+// frameToFrame (velo.h:598-614) for two frames of `frames`, which lives in `ctx`: the matches (matchUsingId, velo.h:562-590), the
+// landmarks of frame2 (getLandmarksAtFrame with the INVERSE pose handed in; null: no landmarks) and the gather of velo.h:627-654 run
+// on the device, then the registration as in frameToFrame.  `matches` receives matchUsingId's result for the caller's min_matches
+// tests (main.cpp:366-371); good_matches / residual_type as frameToFrame fills them.
+template <typename Mat4, typename CloudPtr, typename KdTrees, typename ResidualT>
+Mat4 frameToFrameResident(Context& ctx, FrameStore& frames, const int frame1, const int frame2, const Mat4* pose2_inverse,
+                          const std::vector<CloudPtr>& scans_M, const std::vector<CloudPtr>& scans_S,
+                          const KdTrees& /*kd_trees: superseded by the device grid*/,
+                          double transform[6],
+                          std::vector<std::vector<std::pair<int, int> > >& matches,
+                          std::vector<std::vector<std::pair<int, int> > >& good_matches,
+                          std::vector<std::vector<ResidualT> >& residual_type,
+                          const bool enable_icp) {
+    velo_params P = ctx.params();
+    P.enable_icp = enable_icp ? 1 : 0;                                            // velo.h:806
+    ctx.set_params(P);
+    if (!scans_S.empty()) ctx.set_target(scans_S);                                // empty: the scan the context already holds
+    if (!scans_M.empty()) ctx.set_source(scans_M);
+
+    const int num_cams = frames.numCams();
+    double M[16];
+    if (pose2_inverse) for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) M[4 * r + c] = (*pose2_inverse)(r, c);
+    const int32_t cap = frames.frameSize(frame2);
+    std::vector<int32_t> per_cam((size_t)num_cams, 0), pairs(2 * (size_t)(cap > 0 ? cap : 1));
+    int32_t n = 0;
+    check(velo_build_matches(ctx.get(), frame1, frame2, pose2_inverse ? M : 0, &per_cam[0], &pairs[0], cap, &n), "velo_build_matches");
+    matches.assign((size_t)num_cams, std::vector<std::pair<int, int> >());
+    for (int cam = 0, k = 0; cam < num_cams; cam++)
+        for (int32_t i = 0; i < per_cam[(size_t)cam] && k < cap; i++, k++) matches[(size_t)cam].push_back(std::make_pair((int)pairs[2 * (size_t)k], (int)pairs[2 * (size_t)k + 1]));
+
+    double T[16];
+    check(velo_frame_to_frame(ctx.get(), transform, T, 0), "velo_frame_to_frame");
+
+    int32_t ng = 0;
+    check(velo_get_good_matches(ctx.get(), 0, 0, &ng), "velo_get_good_matches");
+    std::vector<velo_good_match> gm((size_t)ng);
+    if (ng > 0) check(velo_get_good_matches(ctx.get(), &gm[0], ng, &ng), "velo_get_good_matches");
+    good_matches.resize((size_t)num_cams);
+    residual_type.resize((size_t)num_cams);
+    for (int cam = 0; cam < num_cams; cam++) { good_matches[(size_t)cam].clear(); residual_type[(size_t)cam].clear(); }
+    for (size_t k = 0; k < gm.size(); k++) {
+        good_matches[(size_t)gm[k].cam].push_back(std::make_pair(gm[k].point1, gm[k].point2));
+        residual_type[(size_t)gm[k].cam].push_back((ResidualT)gm[k].residual_type);
+    }
+    Mat4 out;
+    for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) out(i, j) = T[i * 4 + j];
+    return out;
+}
+
+}  // namespace velo_hip
+#endif  // VELO_FRAME_STORE_HPP_

@@ -672,6 +672,63 @@ int velo_landmarks_frame_count(velo_ctx* ctx, int32_t frame, int32_t* n_seen, in
  * pairs observed, 0. */
 int velo_landmarks_info(velo_ctx* ctx, int32_t* info);
 
+/* --- resident keypoint frames and the visual matches assembled from them (velo.h:562-590, velo.h:627-654, main.cpp:366-405) ---
+ * Every context can hold one frame store: for every (frame, camera) put so far keypoints[cam][frame], keypoint_ids[cam][frame],
+ * has_depth[cam][frame] and keypoints_with_depth[cam][frame], in one device arena; the host keeps a directory (frame, cam) ->
+ * offset, n, n_with_depth, largest id, and the list of free blocks (first-fit, blocks are neither split nor merged: made for a
+ * sliding window of frames of similar size) -- no copy of the arrays.  velo_build_matches joins two such frames by id (matchUsingId), substitutes the
+ * landmarks of the context's landmark store (velo.h:634-644), gathers every match's operands (velo.h:645-654) and leaves the
+ * records in the context's visual set, as velo_set_visual would: the records never exist on the host, and a landmark triangulated
+ * on the device is not read back only to be sent down again.  What the host work it replaces costs has not been measured yet
+ * (tools/visual_assembly_bench.py is the measurement).
+ *
+ * velo_frames_reset empties the store and fixes the cameras: cam_trans [n_cams][3] floats, n_cams 1..8 (as the landmark store).
+ * arena_capacity: bytes the arena holds before it is first reallocated (0: the default, 1 MiB); it grows geometrically, and a
+ * reallocation is the only time velo_frames_put waits for the device. */
+int velo_frames_reset(velo_ctx* ctx, int32_t n_cams, const float* cam_trans, int32_t arena_capacity);
+/* keypoints[cam][frame] with their ids, has_depth (-1 or an index into kp_with_depth_xyz) and the cloud: the argument list of
+ * velo_landmarks_observe, so a caller hands both the same arrays.  A second call for the same (frame, cam) REPLACES the entry (the
+ * reference mutates a frame's arrays until the frame ends), in place when it fits.  n == 0 is valid and counts as put.  An id may
+ * occur more than once (matchUsingId has a rule for it, below).  Refused with VELO_ERR_INVALID before anything changes: a negative
+ * id, an id >= 2^26, a has_depth entry outside [-1, n_with_depth).  frame < 2^22.  Asynchronous: the arrays are copied into pinned
+ * memory before the call returns, one upload, no synchronisation and no device allocation in the steady state. */
+int velo_frames_put(velo_ctx* ctx, int32_t frame, int32_t cam, const int32_t* ids, const float* keypoints_xy /* n x 2 */,
+                    const int32_t* has_depth /* n */, const float* kp_with_depth_xyz /* n_with_depth x 3 */, int32_t n_with_depth,
+                    int32_t n);
+/* Frees every camera's entry of `frame` for reuse (a frame that is not held: nothing happens). */
+int velo_frames_drop(velo_ctx* ctx, int32_t frame);
+/* Host bookkeeping only: n_per_cam [n_cams] (may be NULL) = the keypoints of every camera's entry of `frame` as put (-1: never put
+ * or dropped), *n_total (may be NULL) their sum -- no registration against `frame` as frame2 has more matches, which sizes pairs_out. */
+int velo_frames_count(velo_ctx* ctx, int32_t frame, int32_t* n_per_cam, int32_t* n_total);
+/* info[8] = frames held, (frame, cam) entries, arena bytes, arena reallocations, arena bytes handed out so far, cameras, ids per
+ * camera the slot table holds, free blocks.  The two byte counts saturate at 2^31 - 1. */
+int velo_frames_info(velo_ctx* ctx, int32_t* info);
+/* The visual set of frameToFrame(frame1, frame2) (frame1 the current frame, frame2 the previous one).  Per camera, in camera order:
+ * matchUsingId -- for ind2 ascending over frame2's ids, when the id occurs in frame1, the match (ind1, ind2) with ind1 the LAST
+ * index of frame1 that holds it (the id2ind[id] = ind overwrite of velo.h:571-574); an id twice in frame2 gives two matches.  Per
+ * match the velo_match record of velo.h:630-654: d1 / p3_1 from frame1's has_depth; p3_2 = the landmark of that id moved by
+ * pose2_inv16 (the arithmetic and the bits of velo_landmarks_at_frame) and d2 = 1 when pose2_inv16 is given, the context has a
+ * landmark store and the id is added there (an id beyond the store's id space is not), else frame2's depth point when it has one;
+ * p2_1, p2_2, t_cam, cam, point1, point2 always; every other byte zero.  The records become the context's visual set exactly as
+ * after velo_set_visual (velo_frame_to_frame[_batch], velo_register_batch and velo_get_good_matches work on it unchanged).
+ * Outputs: n_per_cam [n_cams] (may be NULL) the matches of every camera; pairs_out [capacity][2] (may be NULL) the (point1, point2)
+ * of the first `capacity` records; *n_out the total -- when it exceeds `capacity` the visual set is complete all the same.
+ * VELO_ERR_STATE, with nothing changed: no velo_frames_reset, or a (frame, cam) of either frame that was never put.  Four launches,
+ * one copy back (the chunk counts and 8 bytes per keypoint of frame2: the matches are not counted before it), one synchronisation; no cost depends on the size of the id space. */
+int velo_build_matches(velo_ctx* ctx, int32_t frame1, int32_t frame2, const double* pose2_inv16 /* may be NULL */, int32_t* n_per_cam,
+                       int32_t* pairs_out, int32_t capacity, int32_t* n_out);
+/* The same for (frames1[i], frames2[i]) of ctxs[i], i < n_ctx, in the SAME four launches: a device table carries every context's
+ * frames, slot tables, landmark store and pose, read per workgroup.  The rules of the other batch entries hold (distinct contexts on
+ * one device, the first lends its stream and staging and waits for the others' streams, batch and single calls mix freely, n_ctx == 1
+ * IS the single entry); contexts may differ in their camera counts and some may have no landmark store.  pose2_inv [n_ctx][16] or
+ * NULL (no substitution anywhere); n_per_cam [n_ctx][8] (a context's first n_cams entries are written), pairs_out
+ * [n_ctx][capacity][2], n_out [n_ctx].  Every context's visual set and outputs are byte-identical to the single entry's. */
+int velo_build_matches_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* frames1, const int32_t* frames2, const double* pose2_inv,
+                             int32_t* n_per_cam, int32_t* pairs_out, int32_t capacity, int32_t* n_out);
+/* Read-back of the context's device-side visual set, whoever wrote it (velo_set_visual or velo_build_matches): *n = its records,
+ * the first `capacity` are written (out may be NULL). */
+int velo_get_visual(velo_ctx* ctx, velo_match* out, int32_t capacity, int32_t* n);
+
 #ifdef __cplusplus
 }
 #endif

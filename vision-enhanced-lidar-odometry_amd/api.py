@@ -295,6 +295,15 @@ SIGNATURES = {
     "velo_landmarks_get": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "velo_landmarks_frame_count": (C.c_int, [_ctx, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
     "velo_landmarks_info": (C.c_int, [_ctx, C.c_void_p]),
+    "velo_frames_reset": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_int32]),
+    "velo_frames_put": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "velo_frames_drop": (C.c_int, [_ctx, C.c_int32]),
+    "velo_frames_count": (C.c_int, [_ctx, C.c_int32, C.c_void_p, _P(C.c_int32)]),
+    "velo_frames_info": (C.c_int, [_ctx, C.c_void_p]),
+    "velo_build_matches": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _P(C.c_int32)]),
+    "velo_build_matches_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_void_p]),
+    "velo_get_visual": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(C.c_int32)]),
 }
 
 _lib = None
@@ -714,6 +723,63 @@ class Context:
         return dict(n_ids=int(a[0]), log_entries=int(a[1]), log_capacity=int(a[2]), log_reallocations=int(a[3]), frame_capacity=int(a[4]),
                     n_cams=int(a[5]), observed=int(a[6]))
 
+    # -- resident keypoint frames and the visual matches assembled from them (velo.h:562-590, velo.h:627-654) ---------------
+    def frames_reset(self, cam_trans, arena_capacity: int = 0):
+        """Empties the frame store; cam_trans [n_cams, 3] fixes the cameras.  arena_capacity: bytes before the arena first
+        reallocates (0: the library's default)."""
+        ct = np.ascontiguousarray(np.asarray(cam_trans, dtype=np.float32).reshape(-1, 3))
+        self._check(self._lib.velo_frames_reset(self._h, len(ct), C.c_void_p(ct.ctypes.data), int(arena_capacity)))
+        self._fr_cams = len(ct)
+
+    def frames_put(self, frame: int, cam: int, ids, keypoints_xy, has_depth, kp_with_depth_xyz=None):
+        """keypoints[cam][frame] with their ids, has_depth and the depth cloud (the arguments of landmarks_observe); a second put of
+        the same (frame, cam) replaces the entry"""
+        i = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+        k = np.ascontiguousarray(np.asarray(keypoints_xy, dtype=np.float32).reshape(-1, 2))
+        h = np.ascontiguousarray(np.asarray(has_depth, dtype=np.int32).reshape(-1))
+        d = np.ascontiguousarray(np.asarray(np.zeros((0, 3)) if kp_with_depth_xyz is None else kp_with_depth_xyz, dtype=np.float32).reshape(-1, 3))
+        if not len(i) == len(k) == len(h):
+            raise ValueError("frames_put: one keypoint and one has_depth entry per id")
+        vp = lambda a: C.c_void_p(a.ctypes.data) if a.size else None   # noqa: E731
+        self._check(self._lib.velo_frames_put(self._h, int(frame), int(cam), vp(i), vp(k), vp(h), vp(d), len(d), len(i)))
+
+    def frames_drop(self, frame: int):
+        self._check(self._lib.velo_frames_drop(self._h, int(frame)))
+
+    def frames_info(self) -> dict:
+        a = np.zeros(8, dtype=np.int32)
+        self._check(self._lib.velo_frames_info(self._h, C.c_void_p(a.ctypes.data)))
+        return dict(frames=int(a[0]), entries=int(a[1]), arena_bytes=int(a[2]), arena_reallocations=int(a[3]), arena_used=int(a[4]),
+                    n_cams=int(a[5]), slot_ids=int(a[6]), free_blocks=int(a[7]))
+
+    def frames_count(self, frame: int):
+        """(keypoints per camera of `frame` as put, -1 where never put; their sum): host bookkeeping only"""
+        a = np.full(8, -1, dtype=np.int32)
+        n = C.c_int32(0)
+        self._check(self._lib.velo_frames_count(self._h, int(frame), C.c_void_p(a.ctypes.data), C.byref(n)))
+        if getattr(self, "_fr_cams", None) is None:
+            self._fr_cams = self.frames_info()["n_cams"]
+        return a[:self._fr_cams].copy(), n.value
+
+    def build_matches(self, frame1: int, frame2: int, pose2_inv=None, capacity: Optional[int] = None):
+        """The visual set of frameToFrame(frame1, frame2) assembled on the device from the frame store (and the landmark store when
+        pose2_inv, the 4 x 4 INVERSE pose of frame2, is given): (n_per_cam [n_cams] i32, pairs [n, 2] i32 (point1, point2)), both as
+        the call wrote them.  capacity: caller-sized pairs, returns (n_per_cam, pairs [capacity, 2], n)."""
+        per_cam, pairs, n, n_cams = build_matches_batch([self], [frame1], [frame2], None if pose2_inv is None else [pose2_inv],
+                                                        capacity=capacity, raw=True, _with_cams=True)
+        if capacity is not None:
+            return per_cam[0, :n_cams[0]].copy(), pairs[0], int(n[0])
+        return per_cam[0, :n_cams[0]].copy(), pairs[0, :n[0]].copy()
+
+    def get_visual(self, capacity: Optional[int] = None) -> np.ndarray:
+        """The context's device-side visual set (velo_match records), whoever wrote it"""
+        n = C.c_int32(0)
+        self._check(self._lib.velo_get_visual(self._h, None, 0, C.byref(n)))
+        cap = n.value if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 1), dtype=MATCH_DTYPE)
+        self._check(self._lib.velo_get_visual(self._h, C.c_void_p(out.ctypes.data), cap, C.byref(n)))
+        return out[:min(cap, n.value)]
+
     # -- descriptor matching: matchFeatures (velo.h:499-560) ----------------------------------------------------
     def match_descriptors(self, query, train, match_thresh: float = 29.0):
         """BFMatcher(NORM_HAMMING).match + the velo.h:536-549 filter for one (query, train) pair of uint8 (n, 64) arrays:
@@ -1112,6 +1178,40 @@ def landmarks_triangulate_batch(ctxs, frames, capacity: Optional[int] = None, ra
     if raw or capacity is not None:
         return ids[:, :cap], pts[:, :cap], res[:, :cap], n
     return [(ids[i, :n[i]].copy(), pts[i, :n[i]].copy(), res[i, :n[i]].copy()) for i in range(n_ctx)]
+
+
+def build_matches_batch(ctxs, frames1, frames2, poses2_inv=None, capacity: Optional[int] = None, raw: bool = False, _with_cams: bool = False):
+    """Context.build_matches for (frames1[i], frames2[i]) of ctxs[i] in ONE call (the same four launches for all): per context
+    (n_per_cam, pairs), as the call wrote them.  poses2_inv: one 4 x 4 inverse pose per context, or None (no landmark substitution
+    anywhere).  capacity: the pairs every context gets room for (default: the keypoints of the largest frame2, which bounds every
+    count; host bookkeeping, no device work).  capacity / raw: the call's arrays as they are -- n_per_cam [n_ctx, 8], pairs
+    [n_ctx, capacity, 2] and the counts n [n_ctx] (a count above `capacity` means truncated pairs; the visual set is complete all
+    the same)."""
+    lib, arr = _batch_lib_and_handles(ctxs)
+    n_ctx = len(ctxs)
+    if len(frames1) != n_ctx or len(frames2) != n_ctx:
+        raise ValueError("build_matches_batch: one frame pair per context")
+    f1 = np.ascontiguousarray(np.asarray(frames1, dtype=np.int32).reshape(-1))
+    f2 = np.ascontiguousarray(np.asarray(frames2, dtype=np.int32).reshape(-1))
+    M = None
+    if poses2_inv is not None:
+        M = np.ascontiguousarray(np.asarray(poses2_inv, dtype=np.float64).reshape(-1))
+        if M.size != 16 * n_ctx:
+            raise ValueError("build_matches_batch: one 4 x 4 inverse pose per context")
+    vp = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+    sizes = [c.frames_count(f) for c, f in zip(ctxs, f2)]      # also raises when a context has no frame store
+    cap = max(s[1] for s in sizes) if capacity is None else int(capacity)
+    per_cam = np.zeros((n_ctx, 8), dtype=np.int32)
+    n = np.zeros(n_ctx, dtype=np.int32)
+    pairs = np.zeros((n_ctx, max(cap, 1), 2), dtype=np.int32)
+    _batch_check(lib, lib.velo_build_matches_batch(C.cast(arr, C.c_void_p), n_ctx, vp(f1), vp(f2), vp(M) if M is not None else None,
+                                                   vp(per_cam), vp(pairs), cap, vp(n)))
+    n_cams = [len(s[0]) for s in sizes]
+    if _with_cams:
+        return per_cam, pairs[:, :cap], n, n_cams
+    if raw or capacity is not None:
+        return per_cam, pairs[:, :cap], n
+    return [(per_cam[i, :n_cams[i]].copy(), pairs[i, :n[i]].copy()) for i in range(n_ctx)]
 
 
 SCAN_ON_DEVICE, SCAN_SHARED, SCAN_PROMOTE = 1, 2, 4

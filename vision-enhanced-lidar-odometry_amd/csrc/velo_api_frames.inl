@@ -1,0 +1,392 @@
+// velo_api_frames.inl -- part of the host side of the C-ABI, included by velo_hip.hip (ONE translation unit; the order of the parts is the order of
+// definition).  C-ABI: resident keypoint frames (velo_frames_*) and the assembly of frameToFrame's visual matches from them
+// (velo_build_matches[_batch], velo_get_visual): matchUsingId (velo.h:562-590), the landmark substitution and the gather of
+// velo.h:627-654 on the device; the kernels are in velo_frame_kernels.h.
+//
+// Who knows what: the DEVICE holds the arrays of every (frame, camera) in one arena of 4-byte words and one slot table per camera;
+// the HOST keeps the directory (frame, cam) -> block, n, n_with_depth, the largest id of the block (which sizes the slot table
+// without asking the device) and the list of free blocks.  The free list is first-fit and neither splits nor merges blocks: it is
+// made for the reference's use, a sliding window of frames of similar size (3,000 keypoints per camera, kitti.h) in which a dropped
+// frame's blocks are taken by the next frame's entries of about the same size; a caller that mixes very different sizes pays with
+// arena growth (velo_frames_info shows it), never with wrong results.
+struct FrStore {
+    int n_cams = 0;
+    float cam_t[3 * 8] = {};
+    // device
+    DevBuf<int> arena;
+    size_t used = 0, cap = 0;                       // words handed out from the front / words before the arena reallocates
+    int reallocs = 0;
+    DevBuf<int> slots;                              // n_cams tables of slot_ids entries, all -1 between calls
+    size_t slot_ids = 0;
+    bool slots_dirty = false;                       // a call failed between the fill and the clear launch: refill before the next one
+    // host
+    struct Entry { size_t off = 0, cap = 0; int n = 0, n_wd = 0, max_id = -1; };
+    std::unordered_map<int64_t, Entry> dir;         // frame * 8 + cam
+    std::vector<std::pair<size_t, size_t>> free_blocks;   // {offset, words} of dropped and outgrown blocks
+    // staging of velo_frames_put: two pinned slots used alternately, so that a put waits only for the upload before the previous one
+    unsigned char* h_put[2] = {nullptr, nullptr};
+    size_t h_put_cap[2] = {0, 0};
+    hipEvent_t put_ev[2] = {nullptr, nullptr};
+    int put_k = 0;
+    // staging of velo_build_matches (a batch call uses the first context's); every call ends in a synchronisation, so nothing guards it
+    unsigned char* h_in = nullptr; size_t h_in_cap = 0;
+    unsigned char* h_out = nullptr; size_t h_out_cap = 0;
+    DevBuf<unsigned char> d_in, d_out;
+    ~FrStore() {
+        for (int k = 0; k < 2; k++) { if (h_put[k]) (void)hipHostFree(h_put[k]); if (put_ev[k]) (void)hipEventDestroy(put_ev[k]); }
+        if (h_in) (void)hipHostFree(h_in);
+        if (h_out) (void)hipHostFree(h_out);
+    }
+};
+
+namespace {
+
+constexpr size_t kFrDefaultArena = (1u << 20) / sizeof(int);   // words
+constexpr size_t kFrAlign = 16;                                 // words: every block starts on a 64-byte line
+
+inline size_t fr_round(size_t words) { return (words + kFrAlign - 1) / kFrAlign * kFrAlign; }
+
+int fr_need_store(velo_ctx* c, const char* who) {
+    if (!c->fr) return fail(VELO_ERR_STATE, "%s: velo_frames_reset has not run on this context", who);
+    return VELO_OK;
+}
+
+int fr_event_wait(hipEvent_t* ev) {
+    if (*ev) HIP_TRY(hipEventSynchronize(*ev));
+    else HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    return VELO_OK;
+}
+
+void fr_side(const FrStore& S, const FrStore::Entry& e, FrSide* out) {
+    const int* b = S.arena.p + e.off;
+    out->ids = b;
+    out->has_depth = b + e.n;
+    out->xy = reinterpret_cast<const float*>(b + 2 * (size_t)e.n);
+    out->cloud = reinterpret_cast<const float*>(b + 4 * (size_t)e.n);
+    out->n = e.n; out->pad = 0;
+}
+
+int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32_t* frames2, const double* pose2_inv, int32_t* n_per_cam,
+                 int32_t* pairs_out, int32_t capacity, int32_t* n_out) {
+    // state first: nothing changes when a frame is missing
+    for (int i = 0; i < n_ctx; i++) {
+        VELO_TRY(fr_need_store(ctxs[i], "velo_build_matches"));
+        const FrStore& S = *ctxs[i]->fr;
+        for (int cam = 0; cam < S.n_cams; cam++)
+            for (int f : {frames1[i], frames2[i]})
+                if (!S.dir.count(lm_key(f, cam))) return fail(VELO_ERR_STATE, "context %d: frame %d, camera %d has not been put", i, f, cam);
+    }
+    velo_ctx* c0 = ctxs[0];
+    FrStore* L = c0->fr.get();
+    HIP_TRY(hipSetDevice(c0->device));
+    // the units of the call, context-major and camera-major, and every context's share of the outputs
+    int n_units = 0, n_chunks = 0, max_n1 = 0, max_chunks = 0;
+    size_t all_n2 = 0;
+    std::vector<int> unit0(n_ctx + 1, 0), chunk0;
+    std::vector<size_t> pair0(n_ctx + 1, 0);
+    for (int i = 0; i < n_ctx; i++) {
+        const FrStore& S = *ctxs[i]->fr;
+        for (int cam = 0; cam < S.n_cams; cam++) {
+            const FrStore::Entry& e1 = S.dir.at(lm_key(frames1[i], cam));
+            const FrStore::Entry& e2 = S.dir.at(lm_key(frames2[i], cam));
+            const int ch = cdiv(e2.n, kFrChunk);
+            chunk0.push_back(n_chunks);
+            n_chunks += ch;
+            max_chunks = std::max(max_chunks, ch);
+            max_n1 = std::max(max_n1, e1.n);
+            all_n2 += (size_t)e2.n;
+            n_units++;
+        }
+        unit0[i + 1] = n_units;
+        pair0[i + 1] = all_n2;
+    }
+    chunk0.push_back(n_chunks);
+    // room: slot tables, the visual sets, the staging
+    std::vector<char> refill(n_ctx, 0);
+    for (int i = 0; i < n_ctx; i++) {
+        velo_ctx* c = ctxs[i];
+        FrStore& S = *c->fr;
+        int max_id = -1;
+        for (int cam = 0; cam < S.n_cams; cam++) max_id = std::max(max_id, S.dir.at(lm_key(frames1[i], cam)).max_id);
+        if ((size_t)(max_id + 1) > S.slot_ids) {
+            // the tables hold -1 everywhere between calls, so a larger one is filled, not copied
+            const size_t ids = std::max<size_t>({(size_t)max_id + 1, 2 * S.slot_ids, 4096});
+            S.slot_ids = 0;
+            VELO_TRY(S.slots.reserve(ids * (size_t)S.n_cams));
+            S.slot_ids = ids;
+            S.slots_dirty = true;                                    // uninitialised until this call's fill is queued and the call ends well
+        }
+        if (S.slots_dirty) refill[i] = 1;
+        const size_t n2 = pair0[i + 1] - pair0[i];
+        // records of an earlier velo_register_batch_visual may still be on their way into vm (set_visual_impl without a wait)
+        if (c->pin[3].pending) { HIP_TRY(hipEventSynchronize(c->pin[3].ev)); c->pin[3].pending = false; }
+        if (n2 > 0) {
+            VELO_TRY(c->vm.reserve(n2));
+            VELO_TRY(c->vflags.reserve(3 * n2));
+        }
+    }
+    const size_t unit_bytes = fb_align64(sizeof(FrUnit) * (size_t)n_units);
+    const size_t in_bytes = unit_bytes + sizeof(FrCtx) * (size_t)n_ctx;
+    const size_t cnt_bytes = fb_align64(sizeof(int) * (size_t)n_chunks);
+    const size_t out_bytes = cnt_bytes + sizeof(int) * 2 * all_n2;
+    VELO_TRY(match_pinned((void**)&L->h_in, &L->h_in_cap, in_bytes));
+    VELO_TRY(match_pinned((void**)&L->h_out, &L->h_out_cap, std::max<size_t>(out_bytes, 64)));
+    VELO_TRY(L->d_in.reserve(in_bytes));
+    VELO_TRY(L->d_out.reserve(std::max<size_t>(out_bytes, 64)));
+    int* d_counts = (int*)L->d_out.p;
+    int* d_pairs = (int*)(L->d_out.p + cnt_bytes);
+    {
+        FrUnit* hu = (FrUnit*)L->h_in;
+        FrCtx* hc = (FrCtx*)(L->h_in + unit_bytes);
+        std::memset(L->h_in, 0, in_bytes);
+        for (int i = 0; i < n_ctx; i++) {
+            velo_ctx* c = ctxs[i];
+            const FrStore& S = *c->fr;
+            for (int cam = 0; cam < S.n_cams; cam++) {
+                FrUnit& U = hu[unit0[i] + cam];
+                fr_side(S, S.dir.at(lm_key(frames1[i], cam)), &U.f1);
+                fr_side(S, S.dir.at(lm_key(frames2[i], cam)), &U.f2);
+                U.slots = S.slots.p + (size_t)cam * S.slot_ids;
+                U.slot_ids = (int)S.slot_ids;
+                U.ctx = i; U.cam = cam;
+                U.chunk0 = chunk0[(size_t)(unit0[i] + cam)];
+                U.ctx_chunk0 = chunk0[(size_t)unit0[i]];
+                for (int k = 0; k < 3; k++) U.t_cam[k] = S.cam_t[3 * cam + k];
+            }
+            FrCtx& K = hc[i];
+            K.vm = c->vm.p;
+            K.pairs = d_pairs + 2 * pair0[i];
+            if (pose2_inv && c->lm && c->lm->n_ids > 0) {
+                K.lm_pts = c->lm->pts.p; K.lm_added = c->lm->added.p; K.lm_ids = (int)c->lm->n_ids;
+                std::memcpy(K.pose2_inv.m, pose2_inv + 16 * (size_t)i, sizeof(K.pose2_inv.m));
+            }
+        }
+    }
+    VELO_TRY(fb_gather(ctxs, n_ctx, nullptr));
+    hipStream_t st = c0->stream;
+    for (int i = 0; i < n_ctx; i++) {
+        FrStore& S = *ctxs[i]->fr;
+        if (refill[i] && S.slot_ids > 0) HIP_TRY(hipMemsetAsync(S.slots.p, 0xFF, sizeof(int) * S.slot_ids * (size_t)S.n_cams, st));
+        S.slots_dirty = true;                                        // until the clear launch is known to have run
+        const size_t n2 = pair0[i + 1] - pair0[i];
+        if (n2 > 0) HIP_TRY(hipMemsetAsync(ctxs[i]->vflags.p, 0, 3 * n2, st));
+    }
+    HIP_TRY(hipMemcpyAsync(L->d_in.p, L->h_in, in_bytes, hipMemcpyHostToDevice, st));
+    const FrUnit* d_units = (const FrUnit*)L->d_in.p;
+    const FrCtx* d_ctxs = (const FrCtx*)(L->d_in.p + unit_bytes);
+    if (n_chunks > 0) {
+        const dim3 g1((unsigned)std::max(cdiv(max_n1, 256), 1), (unsigned)n_units), g2((unsigned)max_chunks, (unsigned)n_units);
+        if (max_n1 > 0) hipLaunchKernelGGL(fr_fill_kernel, g1, dim3(256), 0, st, d_units);
+        hipLaunchKernelGGL(fr_count_kernel, g2, dim3(kFrChunk), 0, st, d_units, d_counts);
+        hipLaunchKernelGGL(fr_emit_kernel, g2, dim3(kFrChunk), 0, st, d_units, d_ctxs, (const int*)d_counts);
+        if (max_n1 > 0) hipLaunchKernelGGL(fr_clear_kernel, g1, dim3(256), 0, st, d_units);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(L->h_out, L->d_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    const int* h_counts = (const int*)L->h_out;
+    const int* h_pairs = (const int*)(L->h_out + cnt_bytes);
+    velo_match zero;
+    std::memset(&zero, 0, sizeof(zero));
+    for (int i = 0; i < n_ctx; i++) {
+        velo_ctx* c = ctxs[i];
+        FrStore& S = *c->fr;
+        S.slots_dirty = false;
+        // the state velo_set_visual leaves; the host copy of the records holds what velo_get_good_matches reads
+        c->h_matches.clear();
+        int total = 0;
+        for (int cam = 0; cam < S.n_cams; cam++) {
+            const int u = unit0[i] + cam;
+            int m = 0;
+            for (int k = chunk0[(size_t)u]; k < chunk0[(size_t)u + 1]; k++) m += h_counts[k];
+            if (n_per_cam) n_per_cam[(size_t)i * kLmMaxCams + cam] = m;
+            for (int k = 0; k < m; k++) {
+                const int* pr = h_pairs + 2 * (pair0[i] + (size_t)total + (size_t)k);
+                velo_match r = zero;
+                r.cam = cam; r.point1 = pr[0]; r.point2 = pr[1];
+                c->h_matches.push_back(r);
+            }
+            total += m;
+        }
+        c->n_matches = total;
+        c->vflags_valid = false;
+        c->h_vflags.clear();
+        n_out[i] = total;
+        const int w = std::min(total, (int)capacity);
+        if (pairs_out && w > 0) std::memcpy(pairs_out + 2 * (size_t)i * capacity, h_pairs + 2 * pair0[i], sizeof(int32_t) * 2 * (size_t)w);
+    }
+    return VELO_OK;
+}
+
+}  // namespace
+
+extern "C" {   // (continued from the previous part)
+int velo_frames_reset(velo_ctx* c, int32_t n_cams, const float* cam_trans, int32_t arena_capacity) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (n_cams < 1 || n_cams > kLmMaxCams) return fail(VELO_ERR_INVALID, "%d cameras; 1..%d", n_cams, kLmMaxCams);
+    if (!cam_trans) return fail(VELO_ERR_INVALID, "null cam_trans");
+    if (arena_capacity < 0) return fail(VELO_ERR_INVALID, "negative arena capacity");
+    for (int k = 0; k < 3 * n_cams; k++) if (!std::isfinite(cam_trans[k])) return fail(VELO_ERR_INVALID, "cam_trans[%d] is not finite", k);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));           // nothing of the old store is in flight when it goes
+    c->fr.reset();
+    std::shared_ptr<FrStore> S = std::make_shared<FrStore>();
+    S->n_cams = n_cams;
+    std::memcpy(S->cam_t, cam_trans, sizeof(float) * 3 * (size_t)n_cams);
+    const size_t want = arena_capacity > 0 ? fr_round(((size_t)arena_capacity + sizeof(int) - 1) / sizeof(int)) : kFrDefaultArena;
+    VELO_TRY(S->arena.reserve(want));
+    S->cap = want;                                      // the buffer holds a little more; the arena reallocates at what was asked for
+    c->fr = S;
+    return VELO_OK;
+}
+
+int velo_frames_put(velo_ctx* c, int32_t frame, int32_t cam, const int32_t* ids, const float* keypoints_xy, const int32_t* has_depth,
+                    const float* kp_with_depth_xyz, int32_t n_with_depth, int32_t n) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
+    if (cam < 0 || cam >= kLmMaxCams) return fail(VELO_ERR_INVALID, "camera %d; 0..%d", cam, kLmMaxCams - 1);
+    if (n < 0 || n_with_depth < 0) return fail(VELO_ERR_INVALID, "negative count");
+    if (n > 0 && (!ids || !keypoints_xy || !has_depth)) return fail(VELO_ERR_INVALID, "null ids / keypoints / has_depth");
+    if (n_with_depth > 0 && !kp_with_depth_xyz) return fail(VELO_ERR_INVALID, "a cloud of %d points and a null pointer", n_with_depth);
+    int32_t max_id = -1;
+    for (int i = 0; i < n; i++) {
+        if (ids[i] < 0) return fail(VELO_ERR_INVALID, "entry %d: negative id %d", i, ids[i]);
+        if (ids[i] >= kLmMaxId) return fail(VELO_ERR_INVALID, "entry %d: id %d; below %d", i, ids[i], kLmMaxId);
+        if (has_depth[i] < -1 || has_depth[i] >= n_with_depth)
+            return fail(VELO_ERR_INVALID, "entry %d: has_depth %d outside the cloud of %d points", i, has_depth[i], n_with_depth);
+        max_id = std::max(max_id, ids[i]);
+    }
+    VELO_TRY(fr_need_store(c, "velo_frames_put"));
+    FrStore& S = *c->fr;
+    if (cam >= S.n_cams) return fail(VELO_ERR_INVALID, "camera %d; the store has %d", cam, S.n_cams);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t words = 4 * (size_t)n + 3 * (size_t)n_with_depth, need = fr_round(words);
+    const int64_t key = lm_key(frame, cam);
+    auto old = S.dir.find(key);
+    // where the block goes: in place when it fits, else the first free block that is large enough, else the front of the arena
+    FrStore::Entry e;
+    e.n = n; e.n_wd = n_with_depth; e.max_id = max_id;
+    int from_free = -1;
+    bool in_place = false;
+    if (old != S.dir.end() && old->second.cap >= need) { e.off = old->second.off; e.cap = old->second.cap; in_place = true; }
+    else if (need == 0) { in_place = true; }                         // an empty entry owns no block
+    else {
+        for (size_t k = 0; k < S.free_blocks.size() && from_free < 0; k++) if (S.free_blocks[k].second >= need) from_free = (int)k;
+        if (from_free >= 0) { e.off = S.free_blocks[(size_t)from_free].first; e.cap = S.free_blocks[(size_t)from_free].second; }
+        else {
+            if (S.used + need > S.cap) {
+                const size_t cap = std::max(S.used + need, 2 * S.cap);
+                VELO_TRY(lm_regrow(c, &S.arena, S.used, cap, 0));
+                S.cap = cap;
+                S.reallocs++;
+            }
+            e.off = S.used; e.cap = need;
+        }
+    }
+    if (words > 0) {
+        const int k = S.put_k;
+        VELO_TRY(fr_event_wait(&S.put_ev[k]));
+        VELO_TRY(match_pinned((void**)&S.h_put[k], &S.h_put_cap[k], sizeof(int) * words));
+        int* h = (int*)S.h_put[k];
+        if (n > 0) {
+            std::memcpy(h, ids, sizeof(int) * (size_t)n);
+            std::memcpy(h + n, has_depth, sizeof(int) * (size_t)n);
+            std::memcpy(h + 2 * (size_t)n, keypoints_xy, sizeof(float) * 2 * (size_t)n);
+        }
+        if (n_with_depth > 0) std::memcpy(h + 4 * (size_t)n, kp_with_depth_xyz, sizeof(float) * 3 * (size_t)n_with_depth);
+        HIP_TRY(hipMemcpyAsync(S.arena.p + e.off, h, sizeof(int) * words, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipEventRecord(S.put_ev[k], c->stream));
+        S.put_k = k ^ 1;
+    }
+    // the directory after the last call that can fail
+    if (!in_place) {
+        if (from_free >= 0) S.free_blocks.erase(S.free_blocks.begin() + from_free);
+        else S.used += need;
+        if (old != S.dir.end() && old->second.cap > 0) S.free_blocks.push_back(std::make_pair(old->second.off, old->second.cap));
+    }
+    S.dir[key] = e;
+    return VELO_OK;
+}
+
+int velo_frames_drop(velo_ctx* c, int32_t frame) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
+    VELO_TRY(fr_need_store(c, "velo_frames_drop"));
+    FrStore& S = *c->fr;
+    for (int cam = 0; cam < S.n_cams; cam++) {
+        auto it = S.dir.find(lm_key(frame, cam));
+        if (it == S.dir.end()) continue;
+        if (it->second.cap > 0) S.free_blocks.push_back(std::make_pair(it->second.off, it->second.cap));
+        S.dir.erase(it);
+    }
+    return VELO_OK;
+}
+
+int velo_frames_count(velo_ctx* c, int32_t frame, int32_t* n_per_cam, int32_t* n_total) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
+    VELO_TRY(fr_need_store(c, "velo_frames_count"));
+    const FrStore& S = *c->fr;
+    int total = 0;
+    for (int cam = 0; cam < S.n_cams; cam++) {
+        auto it = S.dir.find(lm_key(frame, cam));
+        const int n = it == S.dir.end() ? -1 : it->second.n;
+        if (n_per_cam) n_per_cam[cam] = n;
+        total += std::max(n, 0);
+    }
+    if (n_total) *n_total = total;
+    return VELO_OK;
+}
+
+int velo_frames_info(velo_ctx* c, int32_t* info) {
+    if (!c || !info) return fail(VELO_ERR_INVALID, "null argument");
+    VELO_TRY(fr_need_store(c, "velo_frames_info"));
+    const FrStore& S = *c->fr;
+    auto sat = [](size_t v) { return (int32_t)std::min<size_t>(v, 0x7fffffff); };    // an arena of 2 GiB or more reads as 2^31 - 1
+    std::vector<int> frames;
+    for (const auto& kv : S.dir) frames.push_back((int)(kv.first / kLmMaxCams));
+    std::sort(frames.begin(), frames.end());
+    frames.erase(std::unique(frames.begin(), frames.end()), frames.end());
+    info[0] = (int32_t)frames.size(); info[1] = (int32_t)S.dir.size(); info[2] = sat(S.cap * sizeof(int)); info[3] = S.reallocs;
+    info[4] = sat(S.used * sizeof(int)); info[5] = S.n_cams; info[6] = (int32_t)S.slot_ids; info[7] = (int32_t)S.free_blocks.size();
+    return VELO_OK;
+}
+
+int velo_build_matches_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* frames1, const int32_t* frames2, const double* pose2_inv,
+                             int32_t* n_per_cam, int32_t* pairs_out, int32_t capacity, int32_t* n_out) {
+    // every argument is checked before any context is touched
+    VELO_TRY(fb_check_list(ctxs, n_ctx));
+    if (!frames1 || !frames2) return fail(VELO_ERR_INVALID, "null frames");
+    if (!n_out) return fail(VELO_ERR_INVALID, "null n_out");
+    if (capacity < 0) return fail(VELO_ERR_INVALID, "negative capacity");
+    for (int i = 0; i < n_ctx; i++)
+        for (int f : {frames1[i], frames2[i]})
+            if (f < 0 || f >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "context %d: frame %d; 0..%d", i, f, kLmMaxFrame - 1);
+    if (pose2_inv)
+        for (int k = 0; k < 16 * n_ctx; k++) if (!std::isfinite(pose2_inv[k])) return fail(VELO_ERR_INVALID, "context %d: pose2_inv[%d] is not finite", k / 16, k % 16);
+    VELO_TRY(fb_check_devices(ctxs, n_ctx));
+    return fr_build_run(ctxs, n_ctx, frames1, frames2, pose2_inv, n_per_cam, pairs_out, capacity, n_out);
+}
+
+int velo_build_matches(velo_ctx* c, int32_t frame1, int32_t frame2, const double* pose2_inv16, int32_t* n_per_cam, int32_t* pairs_out,
+                       int32_t capacity, int32_t* n_out) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    return velo_build_matches_batch(&c, 1, &frame1, &frame2, pose2_inv16, n_per_cam, pairs_out, capacity, n_out);
+}
+
+int velo_get_visual(velo_ctx* c, velo_match* out, int32_t capacity, int32_t* n) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (!n) return fail(VELO_ERR_INVALID, "null n");
+    if (capacity < 0) return fail(VELO_ERR_INVALID, "negative capacity");
+    *n = c->n_matches;
+    const int w = std::min(c->n_matches, (int)capacity);
+    if (!out || w <= 0) return VELO_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->pin[3].pending) { HIP_TRY(hipEventSynchronize(c->pin[3].ev)); c->pin[3].pending = false; }   // records still on their way (set_visual_impl without a wait)
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    static_assert(sizeof(VisualMatch) == sizeof(velo_match), "device/host match layout");
+    HIP_TRY(hipMemcpy(out, c->vm.p, sizeof(velo_match) * (size_t)w, hipMemcpyDeviceToHost));
+    return VELO_OK;
+}
+
+}  // extern "C"

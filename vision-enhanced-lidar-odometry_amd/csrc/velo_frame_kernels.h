@@ -1,0 +1,164 @@
+// velo_frame_kernels.h -- frameToFrame's visual matches assembled on the device from resident keypoint frames: matchUsingId
+// (reference velo.h:562-590), the landmark substitution (velo.h:634-644) and the gather of a match's operands (velo.h:645-654).
+// Included by velo_hip.hip (declarations) and by velo_unit_frames.hip (VELO_DEF_FRAMES: the definitions); gfx950 only.
+//
+// What a context keeps on the device (velo_api_frames.inl owns the buffers): an arena of 4-byte words in which every (frame, camera)
+// put so far owns one block  ids[n] | has_depth[n] | keypoints[n][2] | kp_with_depth[n_with_depth][3],  and one slot table per camera,
+// slots[cam][id] = -1 between calls.  A call is four launches for all contexts and cameras it names (a UNIT is one camera of one
+// context, read from a device table at a workgroup-uniform index):
+//     fr_fill_kernel    slots[id] = the LAST index of frame1 that holds id (atomicMax: whatever the thread order)
+//     fr_count_kernel   per chunk of kFrChunk entries of frame2: how many of their ids frame1 holds
+//     fr_emit_kernel    a chunk's first record = the matches of the context's chunks before it (cameras in order, ind2 ascending); inside
+//                       the chunk a workgroup scan keeps ind2 order; every match writes its 68-byte record and its (point1, point2) pair
+//     fr_clear_kernel   walks frame1's ids again and sets their slots back to -1: no cost depends on the size of the id space
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/velo_hip.h"
+#include "velo_kernels.h"
+#include "velo_landmark_kernels.h"
+
+#ifndef VELO_DEF_FRAMES
+#define VELO_DEF_FRAMES 0
+#endif
+
+namespace velo {
+
+constexpr int kFrChunk = 256;          // entries of frame2 per workgroup: one per thread of the compaction's scan (kScanThreads)
+
+// one (frame, camera) block of the arena
+struct FrSide {
+    const int* ids;
+    const int* has_depth;
+    const float* xy;
+    const float* cloud;
+    int n, pad;
+};
+
+// one camera of one context of a call
+struct FrUnit {
+    FrSide f1, f2;
+    int* slots;                        // this camera's slot table, slot_ids entries
+    int slot_ids;
+    int ctx, cam;
+    int chunk0;                        // index of this unit's first chunk in the call's count array ...
+    int ctx_chunk0;                    // ... and of the first chunk of its context's camera 0
+    float t_cam[3];
+};
+
+// one context of a call: where its records go and where its landmarks are
+struct FrCtx {
+    VisualMatch* vm;
+    int* pairs;                        // (point1, point2) per record, in record order
+    const float* lm_pts;               // null: no substitution (no landmark store, or no pose given)
+    const unsigned char* lm_added;
+    int lm_ids, pad;
+    LmPose pose2_inv;
+};
+
+__global__ void __launch_bounds__(256)
+fr_fill_kernel(const FrUnit* __restrict__ units)
+#if VELO_DEF_FRAMES
+{
+    const FrUnit& U = units[blockIdx.y];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= U.f1.n) return;
+    const int id = U.f1.ids[i];
+    if (id >= 0 && id < U.slot_ids) atomicMax(U.slots + id, i);      // velo.h:571-574: a later index overwrites an earlier one
+}
+#else
+;
+#endif
+
+__global__ void __launch_bounds__(256)
+fr_clear_kernel(const FrUnit* __restrict__ units)
+#if VELO_DEF_FRAMES
+{
+    const FrUnit& U = units[blockIdx.y];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= U.f1.n) return;
+    const int id = U.f1.ids[i];
+    if (id >= 0 && id < U.slot_ids) U.slots[id] = -1;
+}
+#else
+;
+#endif
+
+// the index of frame1 that entry ind2 of frame2 matches, or -1 (velo.h:575-579)
+__device__ __forceinline__ int fr_lookup(const FrUnit& U, int ind2) {
+    if (ind2 >= U.f2.n) return -1;
+    const int id = U.f2.ids[ind2];
+    return (id >= 0 && id < U.slot_ids) ? U.slots[id] : -1;
+}
+
+__global__ void __launch_bounds__(kFrChunk)
+fr_count_kernel(const FrUnit* __restrict__ units, int* __restrict__ counts)
+#if VELO_DEF_FRAMES
+{
+    const FrUnit& U = units[blockIdx.y];
+    const int first = blockIdx.x * kFrChunk;
+    if (first >= U.f2.n) return;                                      // workgroup-uniform
+    const int hit = fr_lookup(U, first + (int)threadIdx.x) >= 0 ? 1 : 0;
+    int total;
+    (void)block_exclusive_scan(hit, &total);
+    if (threadIdx.x == 0) counts[U.chunk0 + blockIdx.x] = total;
+}
+#else
+;
+#endif
+
+__global__ void __launch_bounds__(kFrChunk)
+fr_emit_kernel(const FrUnit* __restrict__ units, const FrCtx* __restrict__ ctxs, const int* __restrict__ counts)
+#if VELO_DEF_FRAMES
+{
+    __shared__ int part[kFrChunk / kWave];
+    const FrUnit& U = units[blockIdx.y];
+    const int first = blockIdx.x * kFrChunk;
+    if (first >= U.f2.n) return;                                      // workgroup-uniform
+    const FrCtx& C = ctxs[U.ctx];
+    // records of the context's chunks before this one: earlier cameras, then earlier chunks of this camera
+    const int mine = U.chunk0 + blockIdx.x;
+    int before = 0;
+    for (int k = U.ctx_chunk0 + (int)threadIdx.x; k < mine; k += kFrChunk) before += counts[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = before;
+    __syncthreads();
+    int base = 0;
+#pragma unroll
+    for (int w = 0; w < kFrChunk / kWave; w++) base += part[w];
+    const int ind2 = first + (int)threadIdx.x;
+    const int ind1 = fr_lookup(U, ind2);
+    int total;
+    const int pos = base + block_exclusive_scan(ind1 >= 0 ? 1 : 0, &total);
+    if (ind1 < 0) return;
+    static_assert(sizeof(VisualMatch) == 13 * sizeof(float) + 3 * sizeof(int) + 4, "no padding between the members: zeroing them zeroes the record");
+    VisualMatch m = {};                                               // every byte that is not written below is zero, pad included
+    const int id = U.f2.ids[ind2];
+    const int h1 = U.f1.has_depth[ind1], h2 = U.f2.has_depth[ind2];
+    bool d2 = h2 != -1;                                               // velo.h:631-632
+    if (C.lm_pts != nullptr && id < C.lm_ids && C.lm_added[id] != 0) {  // velo.h:634-644: landmarks_at_frame.count(id)
+        lm_move_point(C.lm_pts + 3 * (size_t)id, C.pose2_inv.m, m.p3_2);
+        d2 = true;
+    } else if (d2) {                                                  // velo.h:645-648
+        const float* p = U.f2.cloud + 3 * (size_t)h2;
+        m.p3_2[0] = p[0]; m.p3_2[1] = p[1]; m.p3_2[2] = p[2];
+    }
+    if (h1 != -1) {                                                   // velo.h:649-652
+        const float* p = U.f1.cloud + 3 * (size_t)h1;
+        m.p3_1[0] = p[0]; m.p3_1[1] = p[1]; m.p3_1[2] = p[2];
+    }
+    m.p2_1[0] = U.f1.xy[2 * (size_t)ind1]; m.p2_1[1] = U.f1.xy[2 * (size_t)ind1 + 1];     // velo.h:653-654
+    m.p2_2[0] = U.f2.xy[2 * (size_t)ind2]; m.p2_2[1] = U.f2.xy[2 * (size_t)ind2 + 1];
+    m.t_cam[0] = U.t_cam[0]; m.t_cam[1] = U.t_cam[1]; m.t_cam[2] = U.t_cam[2];
+    m.cam = U.cam; m.point1 = ind1; m.point2 = ind2;
+    m.d1 = h1 != -1 ? 1 : 0; m.d2 = d2 ? 1 : 0;
+    C.vm[pos] = m;
+    C.pairs[2 * (size_t)pos] = ind1;
+    C.pairs[2 * (size_t)pos + 1] = ind2;
+}
+#else
+;
+#endif
+
+}  // namespace velo

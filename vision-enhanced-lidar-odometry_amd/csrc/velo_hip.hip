@@ -40,6 +40,7 @@
 #include "velo_track_kernels.h"
 #include "velo_detect_kernels.h"
 #include "velo_landmark_kernels.h"
+#include "velo_frame_kernels.h"
 
 using namespace velo;
 
@@ -67,3 +68,4 @@ extern "C" int velo_launch_lm_solve_ag(int nb_max, int n, void* stream, const vo
 #include "velo_api_detect.inl"   // C-ABI: GFTT corner detection on the current images (detectFeatures, velo.h:118-177)
 #include "velo_api_frontend_batch.inl"   // C-ABI: images, tracking and detection of several contexts in one call each (velo_*_batch)
 #include "velo_api_landmarks.inl"   // C-ABI: the resident landmark store (main.cpp:614-679, getLandmarksAtFrame) and its batch triangulation (velo_landmarks_*)
+#include "velo_api_frames.inl"   // C-ABI: resident keypoint frames and the assembly of frameToFrame's visual matches from them (velo_frames_*, velo_build_matches*)

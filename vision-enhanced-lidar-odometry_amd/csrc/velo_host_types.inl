@@ -173,6 +173,7 @@ struct LkSlot {
 };
 
 struct LmStore;   // the resident landmark store (velo_api_landmarks.inl)
+struct FrStore;   // the resident keypoint frames (velo_api_frames.inl)
 
 struct velo_ctx {
     int device = 0;
@@ -432,6 +433,8 @@ struct velo_ctx {
     int gf_units = 0;                    // units of the last call (velo_diag_detect_counters)
     // the resident landmark store (velo_landmarks_*): created by velo_landmarks_reset, buffers of its own, which no registration reads or writes
     std::shared_ptr<LmStore> lm;
+    // the resident keypoint frames (velo_frames_*): created by velo_frames_reset; velo_build_matches writes the visual set (vm, n_matches) from them
+    std::shared_ptr<FrStore> fr;
     // front-end batch calls (velo_api_frontend_batch.inl): the FIRST context of a call lends its stream, staging and scratch buffers
     hipEvent_t fb_here_ev = nullptr;     // "everything enqueued on this context's stream so far": the lending stream waits for it
     hipEvent_t fb_done_ev = nullptr;     // recorded on the lending stream after an asynchronous batch call: the other streams wait for it

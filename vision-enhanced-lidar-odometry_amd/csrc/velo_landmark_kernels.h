@@ -135,22 +135,27 @@ lm_solve_kernel(const LmUnit* __restrict__ units, const LmItem* __restrict__ ite
 ;
 #endif
 
-// getLandmarksAtFrame (velo.h:1146-1153) for n added landmarks: p = M (x, y, z, 1) in double, every row summed left to right,
-// divided by p[3] and rounded to float
+// getLandmarksAtFrame (velo.h:1146-1153) for one added landmark: p = M (x, y, z, 1) in double, every row summed left to right,
+// divided by p[3] and rounded to float.  Shared with the match assembly (velo_frame_kernels.h), whose landmark points must have
+// the bits velo_landmarks_at_frame gives.
+__device__ __forceinline__ void lm_move_point(const float* __restrict__ pt, const double* __restrict__ m, float* __restrict__ out) {
+    const double q0 = (double)pt[0], q1 = (double)pt[1], q2 = (double)pt[2];
+    double p[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) p[r] = ((m[4 * r] * q0 + m[4 * r + 1] * q1) + m[4 * r + 2] * q2) + m[4 * r + 3] * 1.0;
+    out[0] = (float)(p[0] / p[3]);
+    out[1] = (float)(p[1] / p[3]);
+    out[2] = (float)(p[2] / p[3]);
+}
+
+// ... for n added landmarks
 __global__ void __launch_bounds__(256)
 lm_at_frame_kernel(const int* __restrict__ ids, int n, const float* __restrict__ pts, LmPose M, float* __restrict__ out)
 #if VELO_DEF_LANDMARKS
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float* pt = pts + 3 * (size_t)ids[i];
-    const double q0 = (double)pt[0], q1 = (double)pt[1], q2 = (double)pt[2];
-    double p[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) p[r] = ((M.m[4 * r] * q0 + M.m[4 * r + 1] * q1) + M.m[4 * r + 2] * q2) + M.m[4 * r + 3] * 1.0;
-    out[3 * (size_t)i] = (float)(p[0] / p[3]);
-    out[3 * (size_t)i + 1] = (float)(p[1] / p[3]);
-    out[3 * (size_t)i + 2] = (float)(p[2] / p[3]);
+    lm_move_point(pts + 3 * (size_t)ids[i], M.m, out + 3 * (size_t)i);
 }
 #else
 ;
