@@ -30,7 +30,7 @@ HEADERS = ["velo_kernels.h", "velo_lm_ag_kernels.h", "velo_depth_kernels.h", "ve
            # the parts of the host side (velo_hip.hip includes them in this order: one translation unit)
            "velo_host_types.inl", "velo_host_index.inl", "velo_host_assoc.inl", "velo_host_lm.inl", "velo_host_loaders.inl", "velo_host_pool.inl",
            "velo_api_context.inl", "velo_api_solve.inl", "velo_host_chain.inl", "velo_host_batch.inl", "velo_api_pose_comm.inl", "velo_api_next_rows.inl",
-           "velo_api_match.inl", "velo_api_track.inl", "velo_api_detect.inl", "velo_api_frontend_batch.inl", "velo_api_landmarks.inl", "velo_api_frames.inl"]
+           "velo_api_match.inl", "velo_api_track.inl", "velo_api_detect.inl", "velo_api_landmarks.inl", "velo_api_frames.inl"]
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",

@@ -1,37 +1,17 @@
 // velo_api_detect.inl -- part of the host side of the C-ABI, included by velo_hip.hip (ONE translation unit; the order of the parts is the order of
-// definition).  C-ABI: GFTT corner detection on the current resident images (velo_detect_features: detectFeatures, velo.h:118-177;
-// velo_get_corner_response); kernels in velo_detect_kernels.h.
+// definition).  C-ABI: GFTT corner detection on the current resident images (velo_detect_features[_batch]: detectFeatures,
+// velo.h:118-177; velo_get_corner_response); kernels in velo_detect_kernels.h.  One implementation over a list of contexts, which the
+// single-context entry hands a list of one (velo_api_track.inl says who lends what).
 namespace {
 
-// buffers and kernel arguments for `n_units` cameras of the current slot; everything a call zeroes is zeroed here (stream-ordered)
-int gf_prepare(velo_ctx* c, const LkSlot& S, const int* cams, int n_units, GfArgs* A) {
-    std::memset(A, 0, sizeof(*A));
-    const size_t plane = (size_t)S.w * S.h;
-    const int sstride = (S.w + 2 * kGfStatePad + 3) & ~3;
-    const size_t splane = (size_t)sstride * (S.h + 2 * kGfStatePad);
-    size_t keys_cap = 1;
-    while (keys_cap < plane) keys_cap <<= 1;
-    VELO_TRY(c->gf_eig.reserve(plane * n_units));
-    VELO_TRY(c->gf_state.reserve(splane * n_units));
-    VELO_TRY(c->gf_cand.reserve(2 * plane * n_units));
-    VELO_TRY(c->gf_keys.reserve(keys_cap * n_units));
-    VELO_TRY(c->gf_hdr.reserve((size_t)kGfHdr * kGfMaxUnits));
-    A->pix = S.pix.p; A->cam_pix = S.cam_pix; A->L0 = S.pyr.lv[0];
-    A->w = S.w; A->h = S.h; A->n_units = n_units;
-    for (int u = 0; u < n_units; u++) A->cams[u] = cams[u];
-    A->eig = c->gf_eig.p;
-    A->state = c->gf_state.p; A->sstride = sstride; A->splane = (long long)splane;
-    A->cand = c->gf_cand.p; A->und = c->gf_cand.p + plane * n_units;
-    A->keys = c->gf_keys.p; A->keys_cap = (long long)keys_cap;
-    A->hdr = c->gf_hdr.p;
-    const float s = (float)(1.0 / (255.0 * 4.0 * 3.0));       // cornerMinEigenVal: 1 / (255 * 2^(ksize - 1) * blockSize)
-    A->K.scale2 = s * s;
-    HIP_TRY(hipMemsetAsync(c->gf_hdr.p, 0, sizeof(int) * kGfHdr * kGfMaxUnits, c->stream));
-    c->gf_units = n_units;
-    return VELO_OK;
+constexpr int kGfDetectUnits = 64;         // cameras per detection launch set (a call with more runs in chunks)
+
+inline float gf_scale2() {                 // cornerMinEigenVal: 1 / (255 * 2^(ksize - 1) * blockSize), squared
+    const float s = (float)(1.0 / (255.0 * 4.0 * 3.0));
+    return s * s;
 }
 
-// the argument checks of velo_detect_features that read no context (shared with velo_detect_features_batch)
+// the argument checks of detection that read no context
 int gf_check_params(int32_t n_jobs, const velo_gftt_params* p, int32_t capacity) {
     if (n_jobs < 0) return fail(VELO_ERR_INVALID, "negative job count %d", n_jobs);
     if (!p) return fail(VELO_ERR_INVALID, "null params");
@@ -61,9 +41,153 @@ int gf_check_jobs(const velo_detect_job* jobs, int32_t n_jobs, int32_t capacity,
     return VELO_OK;
 }
 
-void gf_launch_response(velo_ctx* c, const GfArgs& A) {
-    const dim3 grid((unsigned)cdiv(A.w, kGfTile), (unsigned)cdiv(A.h, kGfTile), (unsigned)A.n_units);
-    hipLaunchKernelGGL(gf_response_kernel, grid, dim3(kGfTile * kGfTile), 0, c->stream, A);
+// one launch set of detection: the units [u0, u0 + nu) of the call and the jobs `sel` that name them (call order)
+struct GfUnitRef { int ctx, cam; };
+int gf_run(velo_ctx** ctxs, int n_ctx, const std::vector<GfUnitRef>& units, int u0, int nu, const std::vector<int>& unit_of_job, const std::vector<int>& sel,
+           const velo_detect_job* jobs, const velo_gftt_params* p, int32_t capacity, float* xy, float* response, uint8_t* fresh, int32_t* counts) {
+    velo_ctx* c = ctxs[0];
+    const int nj = (int)sel.size();
+    // every unit's share of the scratch buffers: sizes differ, so offsets are summed, not multiplied
+    std::vector<size_t> plane(nu), splane(nu), kcap(nu), o_plane(nu), o_state(nu), o_keys(nu);
+    std::vector<int> sstride(nu);
+    size_t t_plane = 0, t_state = 0, t_keys = 0, max_plane = 0;
+    int max_w = 0, max_h = 0;
+    for (int u = 0; u < nu; u++) {
+        const LkSlot& S = *lk_slot(ctxs[units[u0 + u].ctx], false);
+        plane[u] = (size_t)S.w * S.h;
+        sstride[u] = (S.w + 2 * kGfStatePad + 3) & ~3;
+        splane[u] = (size_t)sstride[u] * (S.h + 2 * kGfStatePad);
+        kcap[u] = 1;
+        while (kcap[u] < plane[u]) kcap[u] <<= 1;
+        o_plane[u] = t_plane; o_state[u] = t_state; o_keys[u] = t_keys;
+        t_plane += plane[u]; t_state += splane[u]; t_keys += kcap[u];
+        max_plane = std::max(max_plane, plane[u]);
+        max_w = std::max(max_w, S.w); max_h = std::max(max_h, S.h);
+    }
+    const int cap_d = (int)std::min<size_t>((size_t)capacity, max_plane);     // a camera has at most one corner per pixel
+    VELO_TRY(c->gf_eig.reserve(t_plane));
+    VELO_TRY(c->gf_state.reserve(t_state));
+    VELO_TRY(c->gf_cand.reserve(2 * t_plane));
+    VELO_TRY(c->gf_keys.reserve(t_keys));
+    VELO_TRY(c->gf_hdr.reserve((size_t)kGfHdrStride * nu));
+    GfParams K;
+    std::memset(&K, 0, sizeof(K));
+    K.scale2 = gf_scale2();
+    K.radius = (int)std::ceil(p->min_distance) - 1;
+    K.max_corners = p->max_corners;
+    K.capacity = cap_d;
+    K.quality = p->quality_level;
+    K.md2 = p->min_distance * p->min_distance;
+    K.md2f = (float)(p->min_distance * p->min_distance);
+    int64_t total = 0;
+    for (int k = 0; k < nj; k++) total += jobs[sel[k]].n_existing;
+    const size_t unit_bytes = fb_align64(sizeof(GfUnit) * (size_t)nu);
+    const size_t job_bytes = fb_align64(sizeof(GfJob) * (size_t)nj);
+    const size_t in_bytes = unit_bytes + job_bytes + sizeof(float2) * (size_t)total;
+    const size_t cnt_bytes = fb_align64(sizeof(int) * 3 * (size_t)nj);
+    const size_t n_slots = (size_t)nj * cap_d;
+    const size_t out_bytes = cnt_bytes + n_slots * (sizeof(float2) + sizeof(float) + 1);
+    VELO_TRY(match_pinned((void**)&c->h_gf_in, &c->h_gf_in_cap, in_bytes));
+    VELO_TRY(match_pinned((void**)&c->h_gf_out, &c->h_gf_out_cap, out_bytes));
+    VELO_TRY(c->gf_in.reserve(in_bytes));
+    VELO_TRY(c->gf_out.reserve(out_bytes));
+    {
+        GfUnit* hu = (GfUnit*)c->h_gf_in;
+        for (int u = 0; u < nu; u++) {
+            const LkSlot& S = *lk_slot(ctxs[units[u0 + u].ctx], false);
+            GfUnit& U = hu[u];
+            U.plane = S.pix.p + (size_t)units[u0 + u].cam * S.cam_pix + S.pyr.lv[0].off;
+            U.eig = c->gf_eig.p + o_plane[u];
+            U.state = c->gf_state.p + o_state[u];
+            U.cand = c->gf_cand.p + o_plane[u];
+            U.und = c->gf_cand.p + t_plane + o_plane[u];
+            U.keys = c->gf_keys.p + o_keys[u];
+            U.hdr = c->gf_hdr.p + (size_t)u * kGfHdrStride;
+            U.w = S.w; U.h = S.h; U.stride = S.pyr.lv[0].stride; U.sstride = sstride[u];
+        }
+        GfJob* hj = (GfJob*)(c->h_gf_in + unit_bytes);
+        float* hp = (float*)(c->h_gf_in + unit_bytes + job_bytes);
+        int first = 0;
+        for (int k = 0; k < nj; k++) {
+            const velo_detect_job& J = jobs[sel[k]];
+            hj[k].unit = unit_of_job[sel[k]] - u0; hj[k].first = first; hj[k].n = J.n_existing; hj[k].pad_ = 0;
+            if (J.n_existing > 0) std::memcpy(hp + 2 * (size_t)first, J.existing_xy, sizeof(float) * 2 * (size_t)J.n_existing);
+            first += J.n_existing;
+        }
+    }
+    std::vector<char> used(n_ctx, 0);
+    for (int u = 0; u < nu; u++) used[units[u0 + u].ctx] = 1;
+    VELO_TRY(fb_gather(ctxs, n_ctx, &used));
+    HIP_TRY(hipMemcpyAsync(c->gf_in.p, c->h_gf_in, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->gf_hdr.p, 0, sizeof(int) * kGfHdrStride * (size_t)nu, c->stream));
+    HIP_TRY(hipMemsetAsync(c->gf_state.p, 0, t_state, c->stream));                          // the zero border of the state maps
+    HIP_TRY(hipMemsetAsync(c->gf_out.p, 0, cnt_bytes, c->stream));
+    const GfUnit* d_units = (const GfUnit*)c->gf_in.p;
+    hipLaunchKernelGGL(gf_response_kernel, dim3((unsigned)cdiv(max_w, kGfTile), (unsigned)cdiv(max_h, kGfTile), (unsigned)nu), dim3(kGfTile * kGfTile), 0,
+                       c->stream, d_units, K);
+    hipLaunchKernelGGL(gf_candidates_kernel, dim3((unsigned)cdiv(max_w, 64), (unsigned)cdiv(max_h, 4), (unsigned)nu), dim3(256), 0, c->stream, d_units, K);
+    for (int r = 0; r < kGfRoundLaunches; r++)
+        hipLaunchKernelGGL(gf_round_kernel, dim3(kGfRoundBlocks, (unsigned)nu), dim3(256), 0, c->stream, d_units, K);
+    hipLaunchKernelGGL(gf_finish_kernel, dim3((unsigned)nu), dim3(kGfFinishThreads), 0, c->stream, d_units, K);
+    int* d_counts = (int*)c->gf_out.p;
+    float2* d_xy = (float2*)(c->gf_out.p + cnt_bytes);
+    float* d_resp = (float*)(c->gf_out.p + cnt_bytes + n_slots * sizeof(float2));
+    unsigned char* d_fresh = c->gf_out.p + cnt_bytes + n_slots * (sizeof(float2) + sizeof(float));
+    hipLaunchKernelGGL(gf_output_kernel, dim3(kGfOutBlocks, (unsigned)nj), dim3(256), 0, c->stream, d_units, K, (const GfJob*)(c->gf_in.p + unit_bytes),
+                       (const float2*)(c->gf_in.p + unit_bytes + job_bytes), d_counts, d_xy, d_resp, d_fresh);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->h_gf_out, c->gf_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->gf_units = nu;
+    const int* h_counts = (const int*)c->h_gf_out;
+    const unsigned char* h_xy = c->h_gf_out + cnt_bytes;
+    const unsigned char* h_resp = h_xy + n_slots * sizeof(float2);
+    const unsigned char* h_fresh = h_resp + n_slots * sizeof(float);
+    for (int k = 0; k < nj; k++) {
+        const size_t j = (size_t)sel[k];
+        std::memcpy(counts + 3 * j, h_counts + 3 * k, sizeof(int) * 3);
+        const size_t m = (size_t)std::min(h_counts[3 * k], cap_d);            // what lies past it in the caller's arrays stays as it was
+        if (m == 0) continue;
+        std::memcpy(xy + 2 * j * capacity, h_xy + sizeof(float2) * (size_t)k * cap_d, sizeof(float2) * m);
+        std::memcpy(response + j * capacity, h_resp + sizeof(float) * (size_t)k * cap_d, sizeof(float) * m);
+        std::memcpy(fresh + j * capacity, h_fresh + (size_t)k * cap_d, m);
+    }
+    return VELO_OK;
+}
+
+
+// velo_detect_features[_batch]: job j runs on the current images of ctxs[job_ctx[j]] (job_ctx null: of ctxs[0])
+int gf_detect(velo_ctx** ctxs, int n_ctx, const int32_t* job_ctx, const velo_detect_job* jobs, int32_t n_jobs, const velo_gftt_params* p, int32_t capacity,
+              float* xy, float* response, uint8_t* fresh, int32_t* counts) {
+    // every argument is checked before any context is touched
+    VELO_TRY(fb_check_list(ctxs, n_ctx));
+    VELO_TRY(gf_check_params(n_jobs, p, capacity));
+    if (n_jobs == 0) return VELO_OK;
+    int64_t total = 0;
+    VELO_TRY(gf_check_jobs(jobs, n_jobs, capacity, xy, response, fresh, counts, &total));
+    VELO_TRY(fb_check_job_ctx(job_ctx, n_jobs, n_ctx));
+    VELO_TRY(fb_check_devices(ctxs, n_ctx));
+    // the units: the distinct (context, camera) pairs, in the order the jobs name them
+    std::vector<GfUnitRef> units;
+    std::vector<int> unit_of_job(n_jobs), unit_at((size_t)n_ctx * kLkMaxCams, -1);
+    for (int j = 0; j < n_jobs; j++) {
+        const int i = fb_ctx_of(job_ctx, j);
+        const LkSlot& S = *lk_slot(ctxs[i], false);
+        if (!S.valid) return fail(VELO_ERR_STATE, "context %d: no current images: velo_set_images first", i);
+        if (jobs[j].cam >= S.n_cams) return fail(VELO_ERR_INVALID, "job %d: camera %d outside the %d that context %d uploaded", j, jobs[j].cam, S.n_cams, i);
+        int& u = unit_at[(size_t)i * kLkMaxCams + jobs[j].cam];
+        if (u < 0) { u = (int)units.size(); units.push_back(GfUnitRef{i, jobs[j].cam}); }
+        unit_of_job[j] = u;
+    }
+    HIP_TRY(hipSetDevice(ctxs[0]->device));
+    std::vector<int> sel;
+    for (int u0 = 0; u0 < (int)units.size(); u0 += kGfDetectUnits) {
+        const int nu = std::min(kGfDetectUnits, (int)units.size() - u0);
+        sel.clear();
+        for (int j = 0; j < n_jobs; j++) if (unit_of_job[j] >= u0 && unit_of_job[j] < u0 + nu) sel.push_back(j);
+        VELO_TRY(gf_run(ctxs, n_ctx, units, u0, nu, unit_of_job, sel, jobs, p, capacity, xy, response, fresh, counts));
+    }
+    return VELO_OK;
 }
 
 }  // namespace
@@ -77,81 +201,14 @@ int velo_default_gftt_params(velo_gftt_params* p) {
 
 int velo_detect_features(velo_ctx* c, const velo_detect_job* jobs, int32_t n_jobs, const velo_gftt_params* p, int32_t capacity, float* xy,
                          float* response, uint8_t* fresh, int32_t* counts) {
-    // every argument is checked before the context is touched
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
-    VELO_TRY(gf_check_params(n_jobs, p, capacity));
-    if (n_jobs == 0) return VELO_OK;
-    int64_t total = 0;
-    VELO_TRY(gf_check_jobs(jobs, n_jobs, capacity, xy, response, fresh, counts, &total));
-    const LkSlot& S = *lk_slot(c, false);
-    if (!S.valid) return fail(VELO_ERR_STATE, "no current images: velo_set_images first");
-    int cams[kGfMaxUnits], unit_of[kLkMaxCams], n_units = 0;
-    for (int k = 0; k < kLkMaxCams; k++) unit_of[k] = -1;
-    for (int j = 0; j < n_jobs; j++) {
-        if (jobs[j].cam >= S.n_cams) return fail(VELO_ERR_INVALID, "job %d: camera %d outside the uploaded %d", j, jobs[j].cam, S.n_cams);
-        if (unit_of[jobs[j].cam] < 0) { unit_of[jobs[j].cam] = n_units; cams[n_units++] = jobs[j].cam; }
-    }
-    const size_t plane = (size_t)S.w * S.h;
-    const int cap_d = (int)std::min<size_t>((size_t)capacity, plane);        // a camera has at most one corner per pixel
+    return gf_detect(&c, 1, nullptr, jobs, n_jobs, p, capacity, xy, response, fresh, counts);
+}
 
-    HIP_TRY(hipSetDevice(c->device));
-    GfArgs A;
-    VELO_TRY(gf_prepare(c, S, cams, n_units, &A));
-    A.K.radius = (int)std::ceil(p->min_distance) - 1;
-    A.K.max_corners = p->max_corners;
-    A.K.capacity = cap_d;
-    A.K.quality = p->quality_level;
-    A.K.md2 = p->min_distance * p->min_distance;
-    A.K.md2f = (float)(p->min_distance * p->min_distance);
-    const size_t job_bytes = (sizeof(GfJob) * (size_t)n_jobs + 63) & ~(size_t)63;
-    const size_t in_bytes = job_bytes + sizeof(float2) * (size_t)total;
-    const size_t cnt_bytes = (sizeof(int) * 3 * (size_t)n_jobs + 63) & ~(size_t)63;
-    const size_t n_slots = (size_t)n_jobs * cap_d;
-    const size_t out_bytes = cnt_bytes + n_slots * (sizeof(float2) + sizeof(float) + 1);
-    VELO_TRY(match_pinned((void**)&c->h_gf_in, &c->h_gf_in_cap, in_bytes));
-    VELO_TRY(match_pinned((void**)&c->h_gf_out, &c->h_gf_out_cap, out_bytes));
-    VELO_TRY(c->gf_in.reserve(in_bytes));
-    VELO_TRY(c->gf_out.reserve(out_bytes));
-    {
-        GfJob* hj = (GfJob*)c->h_gf_in;
-        float* hp = (float*)(c->h_gf_in + job_bytes);
-        int first = 0;
-        for (int j = 0; j < n_jobs; j++) {
-            hj[j].unit = unit_of[jobs[j].cam]; hj[j].first = first; hj[j].n = jobs[j].n_existing; hj[j].pad_ = 0;
-            if (jobs[j].n_existing > 0) std::memcpy(hp + 2 * (size_t)first, jobs[j].existing_xy, sizeof(float) * 2 * (size_t)jobs[j].n_existing);
-            first += jobs[j].n_existing;
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(c->gf_in.p, c->h_gf_in, in_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->gf_state.p, 0, (size_t)A.splane * n_units, c->stream));      // the zero border of the state maps
-    HIP_TRY(hipMemsetAsync(c->gf_out.p, 0, cnt_bytes, c->stream));
-    gf_launch_response(c, A);
-    hipLaunchKernelGGL(gf_candidates_kernel, dim3((unsigned)cdiv(A.w, 64), (unsigned)cdiv(A.h, 4), (unsigned)n_units), dim3(256), 0, c->stream, A);
-    for (int r = 0; r < kGfRoundLaunches; r++)
-        hipLaunchKernelGGL(gf_round_kernel, dim3(kGfRoundBlocks, (unsigned)n_units), dim3(256), 0, c->stream, A);
-    hipLaunchKernelGGL(gf_finish_kernel, dim3((unsigned)n_units), dim3(kGfFinishThreads), 0, c->stream, A);
-    int* d_counts = (int*)c->gf_out.p;
-    float2* d_xy = (float2*)(c->gf_out.p + cnt_bytes);
-    float* d_resp = (float*)(c->gf_out.p + cnt_bytes + n_slots * sizeof(float2));
-    unsigned char* d_fresh = c->gf_out.p + cnt_bytes + n_slots * (sizeof(float2) + sizeof(float));
-    hipLaunchKernelGGL(gf_output_kernel, dim3(kGfOutBlocks, (unsigned)n_jobs), dim3(256), 0, c->stream, A, (const GfJob*)c->gf_in.p,
-                       (const float2*)(c->gf_in.p + job_bytes), d_counts, d_xy, d_resp, d_fresh);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_gf_out, c->gf_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const int* h_counts = (const int*)c->h_gf_out;
-    const unsigned char* h_xy = c->h_gf_out + cnt_bytes;
-    const unsigned char* h_resp = h_xy + n_slots * sizeof(float2);
-    const unsigned char* h_fresh = h_resp + n_slots * sizeof(float);
-    std::memcpy(counts, h_counts, sizeof(int) * 3 * (size_t)n_jobs);
-    for (int j = 0; j < n_jobs; j++) {
-        const size_t m = (size_t)std::min(h_counts[3 * j], cap_d);            // what lies past it in the caller's arrays stays as it was
-        if (m == 0) continue;
-        std::memcpy(xy + 2 * (size_t)j * capacity, h_xy + sizeof(float2) * (size_t)j * cap_d, sizeof(float2) * m);
-        std::memcpy(response + (size_t)j * capacity, h_resp + sizeof(float) * (size_t)j * cap_d, sizeof(float) * m);
-        std::memcpy(fresh + (size_t)j * capacity, h_fresh + (size_t)j * cap_d, m);
-    }
-    return VELO_OK;
+int velo_detect_features_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* job_ctx, const velo_detect_job* jobs, int32_t n_jobs,
+                               const velo_gftt_params* p, int32_t capacity, float* xy, float* response, uint8_t* fresh, int32_t* counts) {
+    if (!job_ctx && n_jobs > 0) return fail(VELO_ERR_INVALID, "null job_ctx");
+    return gf_detect(ctxs, n_ctx, job_ctx, jobs, n_jobs, p, capacity, xy, response, fresh, counts);
 }
 
 int velo_get_corner_response(velo_ctx* c, int32_t cam, float* out, int64_t capacity_bytes) {
@@ -164,10 +221,25 @@ int velo_get_corner_response(velo_ctx* c, int32_t cam, float* out, int64_t capac
     const size_t bytes = sizeof(float) * (size_t)S.w * S.h;
     if ((size_t)capacity_bytes < bytes) return fail(VELO_ERR_INVALID, "capacity %lld bytes < %zu", (long long)capacity_bytes, bytes);
     HIP_TRY(hipSetDevice(c->device));
-    GfArgs A;
-    const int cams[1] = {cam};
-    VELO_TRY(gf_prepare(c, S, cams, 1, &A));
-    gf_launch_response(c, A);
+    // a table of one unit whose only live fields are the image, the map and the header (the response kernel reads nothing else)
+    VELO_TRY(c->gf_eig.reserve((size_t)S.w * S.h));
+    VELO_TRY(c->gf_hdr.reserve(kGfHdrStride));
+    VELO_TRY(match_pinned((void**)&c->h_gf_in, &c->h_gf_in_cap, sizeof(GfUnit)));
+    VELO_TRY(c->gf_in.reserve(sizeof(GfUnit)));
+    GfUnit& U = *(GfUnit*)c->h_gf_in;
+    std::memset(&U, 0, sizeof(U));
+    U.plane = S.pix.p + (size_t)cam * S.cam_pix + S.pyr.lv[0].off;
+    U.eig = c->gf_eig.p;
+    U.hdr = c->gf_hdr.p;
+    U.w = S.w; U.h = S.h; U.stride = S.pyr.lv[0].stride;
+    GfParams K;
+    std::memset(&K, 0, sizeof(K));
+    K.scale2 = gf_scale2();
+    HIP_TRY(hipMemcpyAsync(c->gf_in.p, c->h_gf_in, sizeof(GfUnit), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->gf_hdr.p, 0, sizeof(int) * kGfHdrStride, c->stream));
+    c->gf_units = 1;
+    hipLaunchKernelGGL(gf_response_kernel, dim3((unsigned)cdiv(S.w, kGfTile), (unsigned)cdiv(S.h, kGfTile), 1), dim3(kGfTile * kGfTile), 0, c->stream,
+                       (const GfUnit*)c->gf_in.p, K);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, c->gf_eig.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -175,14 +247,16 @@ int velo_get_corner_response(velo_ctx* c, int32_t cam, float* out, int64_t capac
 }
 
 #ifdef VELO_DIAGNOSTICS
-// diagnostics build only (not declared in velo_hip.h): the per-unit header of the last velo_detect_features call, kGfHdr ints per unit
-// (maximum bits, candidates, accepted, corners, selection passes, undecided when the single-workgroup loop began); returns the units
+// diagnostics build only (not declared in velo_hip.h): the per-unit headers of the last detection launch set that the context led (as
+// the only or the first context of the call), kGfHdr ints per unit in `out` (maximum bits, candidates, accepted, corners, selection
+// passes, undecided when the single-workgroup loop began), units in the order the call's jobs first named them; returns the units
 int velo_diag_detect_counters(velo_ctx* c, int* out, int max_units) {
     if (!c || !out) return fail(VELO_ERR_INVALID, "null argument");
     const int n = std::min(c->gf_units, max_units);
     if (n <= 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(out, c->gf_hdr.p, sizeof(int) * kGfHdr * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpy2DAsync(out, sizeof(int) * kGfHdr, c->gf_hdr.p, sizeof(int) * kGfHdrStride, sizeof(int) * kGfHdr, (size_t)n, hipMemcpyDeviceToHost,
+                             c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return n;
 }

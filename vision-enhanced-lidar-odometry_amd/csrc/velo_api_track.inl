@@ -1,7 +1,19 @@
 // velo_api_track.inl -- part of the host side of the C-ABI, included by velo_hip.hip (ONE translation unit; the order of the parts is the order of
-// definition).  C-ABI: resident camera images (velo_set_images, velo_get_image_level) and pyramidal Lucas-Kanade tracking
-// (velo_track_features: trackFeatures, velo.h:28-116); kernels in velo_track_kernels.h.
+// definition).  C-ABI: resident camera images (velo_set_images[_batch], velo_get_image_level) and pyramidal Lucas-Kanade tracking
+// (velo_track_features[_batch]: trackFeatures, velo.h:28-116); kernels in velo_track_kernels.h.
+//
+// Every stage of the visual front end (images and tracking here, detection in velo_api_detect.inl) has ONE implementation, over a list
+// of contexts; the single-context entries hand it a list of one.  Who owns what: the FIRST context of a call (ctxs[0]) lends its
+// stream, its pinned staging and its scratch buffers (lk_raw / lk_in / lk_out, gf_*); every context keeps its own image slots, and the
+// kernels write / read them through per-unit tables that ride in the call's one upload.  Mixed image sizes are served by the SAME
+// launches: a table entry carries its unit's size, grids are sized for the largest unit.
+// Hand-over between the streams: the lending stream first waits for an event recorded on every other named context's stream; the
+// synchronous entries (track, detect) end in a synchronisation of the lending stream, after which nothing of the call is in flight;
+// the asynchronous one (set_images) records an event on the lending stream that every other context's stream then waits for.  With
+// one context there is no other stream: no event is recorded or waited for.
 namespace {
+
+constexpr int kFbMaxCtx = 256;             // contexts per call
 
 int lk_level_count(int w, int h, int win, int max_level) {      // buildOpticalFlowPyramid's deepest level (tests/lk_ref.py level_count)
     for (int lev = 0; lev <= max_level; lev++) {
@@ -29,7 +41,7 @@ void lk_plan(LkPyr* P, int w, int h, long long* cam_pix) {
 
 LkSlot* lk_slot(velo_ctx* c, bool previous) { return &c->lk_slot[previous ? (c->lk_cur ^ 1) : c->lk_cur]; }
 
-// the argument checks of velo_track_features that read no context (shared with velo_track_features_batch)
+// the argument checks of tracking that read no context
 int lk_check_params(int32_t n_jobs, const velo_lk_params* p) {
     if (n_jobs < 0) return fail(VELO_ERR_INVALID, "negative job count %d", n_jobs);
     if (!p) return fail(VELO_ERR_INVALID, "null params");
@@ -56,45 +68,266 @@ int lk_check_jobs(const velo_track_job* jobs, int32_t n_jobs, const float* next_
     return VELO_OK;
 }
 
+// the checks of the context list that read no context
+int fb_check_list(velo_ctx** ctxs, int n_ctx) {
+    if (!ctxs) return fail(VELO_ERR_INVALID, "null context list");
+    if (n_ctx < 1 || n_ctx > kFbMaxCtx) return fail(VELO_ERR_INVALID, "%d contexts; 1..%d", n_ctx, kFbMaxCtx);
+    for (int i = 0; i < n_ctx; i++) {
+        if (!ctxs[i]) return fail(VELO_ERR_INVALID, "context %d is null", i);
+        for (int j = 0; j < i; j++) if (ctxs[j] == ctxs[i]) return fail(VELO_ERR_INVALID, "batch entries %d and %d are the same context", j, i);
+    }
+    return VELO_OK;
+}
+
+int fb_check_devices(velo_ctx** ctxs, int n_ctx) {
+    for (int i = 1; i < n_ctx; i++)
+        if (ctxs[i]->device != ctxs[0]->device)
+            return fail(VELO_ERR_INVALID, "contexts on different devices: entry %d is on device %d, entry 0 on device %d", i, ctxs[i]->device, ctxs[0]->device);
+    return VELO_OK;
+}
+
+// job_ctx of the batch entries; null (the single-context entries pass it): every job runs on context 0
+int fb_check_job_ctx(const int32_t* job_ctx, int n_jobs, int n_ctx) {
+    if (!job_ctx) return VELO_OK;
+    for (int j = 0; j < n_jobs; j++)
+        if (job_ctx[j] < 0 || job_ctx[j] >= n_ctx) return fail(VELO_ERR_INVALID, "job %d: context index %d; 0..%d", j, job_ctx[j], n_ctx - 1);
+    return VELO_OK;
+}
+inline int fb_ctx_of(const int32_t* job_ctx, int j) { return job_ctx ? job_ctx[j] : 0; }
+
+// the lending stream runs after everything already enqueued on the stream of every other context in `used` (null: all)
+int fb_gather(velo_ctx** ctxs, int n_ctx, const std::vector<char>* used) {
+    velo_ctx* c0 = ctxs[0];
+    for (int i = 1; i < n_ctx; i++) {
+        if (used && !(*used)[i]) continue;
+        velo_ctx* c = ctxs[i];
+        if (c->stream == c0->stream) continue;
+        if (!c->fb_here_ev) HIP_TRY(hipEventCreateWithFlags(&c->fb_here_ev, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(c->fb_here_ev, c->stream));
+        HIP_TRY(hipStreamWaitEvent(c0->stream, c->fb_here_ev, 0));
+    }
+    return VELO_OK;
+}
+
+// whatever is enqueued later on any other context's stream runs after what the lending stream holds now
+int fb_release(velo_ctx** ctxs, int n_ctx) {
+    velo_ctx* c0 = ctxs[0];
+    if (n_ctx < 2) return VELO_OK;
+    if (!c0->fb_done_ev) HIP_TRY(hipEventCreateWithFlags(&c0->fb_done_ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c0->fb_done_ev, c0->stream));
+    for (int i = 1; i < n_ctx; i++)
+        if (ctxs[i]->stream != c0->stream) HIP_TRY(hipStreamWaitEvent(ctxs[i]->stream, c0->fb_done_ev, 0));
+    return VELO_OK;
+}
+
+// index of the level table of a w x h image in `pyrs` (appended when new)
+int fb_pyr_index(std::vector<LkPyr>* pyrs, std::vector<long long>* cam_pix, int w, int h) {
+    for (size_t k = 0; k < pyrs->size(); k++) if ((*pyrs)[k].lv[0].w == w && (*pyrs)[k].lv[0].h == h) return (int)k;
+    LkPyr P;
+    long long cp = 0;
+    lk_plan(&P, w, h, &cp);
+    pyrs->push_back(P);
+    cam_pix->push_back(cp);
+    return (int)pyrs->size() - 1;
+}
+
+inline size_t fb_align64(size_t n) { return (n + 63) & ~(size_t)63; }
+
+// velo_set_images[_batch]: imgs[i * n_cams + k] is camera k of context i, sizes[3 i ..] = {width, height, stride} of context i
+int lk_set_images(velo_ctx** ctxs, int n_ctx, const uint8_t* const* imgs, int n_cams, const int32_t* sizes) {
+    // every argument is checked before any context is touched
+    VELO_TRY(fb_check_list(ctxs, n_ctx));
+    if (n_cams < 1 || n_cams > kLkMaxCams) return fail(VELO_ERR_INVALID, "%d cameras; 1..%d", n_cams, kLkMaxCams);
+    if (!imgs) return fail(VELO_ERR_INVALID, "null image list");
+    if (!sizes) return fail(VELO_ERR_INVALID, "null sizes");
+    for (int i = 0; i < n_ctx; i++) {
+        for (int k = 0; k < n_cams; k++) if (!imgs[(size_t)i * n_cams + k]) return fail(VELO_ERR_INVALID, "context %d: image %d is null", i, k);
+        const int w = sizes[3 * i], h = sizes[3 * i + 1], st = sizes[3 * i + 2];
+        if (w < 1 || h < 1 || w > 16384 || h > 16384) return fail(VELO_ERR_INVALID, "context %d: image size %d x %d; 1..16384 each", i, w, h);
+        if (st < w) return fail(VELO_ERR_INVALID, "context %d: row stride %d < width %d", i, st, w);
+    }
+    VELO_TRY(fb_check_devices(ctxs, n_ctx));
+    velo_ctx* c = ctxs[0];
+    HIP_TRY(hipSetDevice(c->device));
+    // the pinned staging buffer may still be read by the previous call's upload
+    if (c->lk_upload_ev) HIP_TRY(hipEventSynchronize(c->lk_upload_ev));
+    else HIP_TRY(hipEventCreateWithFlags(&c->lk_upload_ev, hipEventDisableTiming));
+    std::vector<LkPyr> pyrs;
+    std::vector<long long> cam_pix;
+    std::vector<int> pyr_of(n_ctx);
+    size_t raw_bytes = 0;
+    for (int i = 0; i < n_ctx; i++) {
+        pyr_of[i] = fb_pyr_index(&pyrs, &cam_pix, sizes[3 * i], sizes[3 * i + 1]);
+        raw_bytes += (size_t)n_cams * sizes[3 * i] * sizes[3 * i + 1];
+    }
+    const int n_units = n_ctx * n_cams;
+    const size_t unit_bytes = fb_align64(sizeof(LkBuildUnit) * (size_t)n_units);
+    const size_t pyr_bytes = fb_align64(sizeof(LkPyr) * pyrs.size());
+    const size_t in_bytes = unit_bytes + pyr_bytes + raw_bytes;
+    VELO_TRY(match_pinned((void**)&c->h_lk_raw, &c->h_lk_raw_cap, in_bytes));
+    VELO_TRY(c->lk_raw.reserve(in_bytes));
+    // The slot every context is about to fill is its previous one (current -> previous is a rotation, no copy).  Every allocation comes
+    // first and nothing rotates unless everything was allocated: a failure leaves every context's current and previous images as they
+    // were, except a previous slot whose buffer had to be replaced.
+    for (int i = 0; i < n_ctx; i++) {
+        LkSlot& S = ctxs[i]->lk_slot[ctxs[i]->lk_cur ^ 1];
+        const size_t need = (size_t)cam_pix[pyr_of[i]] * n_cams;
+        if (need > S.pix.cap || need > S.der.cap) S.valid = false;   // growing frees the old buffer: that slot's images are gone either way
+        VELO_TRY(S.pix.reserve(need));
+        VELO_TRY(S.der.reserve(need));
+    }
+    for (int i = 0; i < n_ctx; i++) ctxs[i]->lk_slot[ctxs[i]->lk_cur ^ 1].valid = false;
+    {
+        LkBuildUnit* hu = (LkBuildUnit*)c->h_lk_raw;
+        std::memcpy(c->h_lk_raw + unit_bytes, pyrs.data(), sizeof(LkPyr) * pyrs.size());
+        size_t off = unit_bytes + pyr_bytes;
+        for (int i = 0; i < n_ctx; i++) {
+            const int w = sizes[3 * i], h = sizes[3 * i + 1], st = sizes[3 * i + 2];
+            LkSlot& S = ctxs[i]->lk_slot[ctxs[i]->lk_cur ^ 1];
+            for (int k = 0; k < n_cams; k++) {
+                LkBuildUnit& U = hu[i * n_cams + k];
+                U.raw = c->lk_raw.p + off;
+                U.pix = S.pix.p + (size_t)k * cam_pix[pyr_of[i]];
+                U.der = S.der.p + (size_t)k * cam_pix[pyr_of[i]];
+                U.pyr = pyr_of[i]; U.pad_ = 0;
+                const uint8_t* src = imgs[(size_t)i * n_cams + k];
+                for (int y = 0; y < h; y++) std::memcpy(c->h_lk_raw + off + (size_t)y * w, src + (size_t)y * st, (size_t)w);
+                off += (size_t)w * h;
+            }
+        }
+    }
+    VELO_TRY(fb_gather(ctxs, n_ctx, nullptr));
+    HIP_TRY(hipMemcpyAsync(c->lk_raw.p, c->h_lk_raw, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(c->lk_upload_ev, c->stream));
+    int max_levels = 0;
+    for (const LkPyr& P : pyrs) max_levels = std::max(max_levels, P.n_levels);
+    for (int lev = 0; lev < max_levels; lev++) {
+        int mw = 0, mh = 0;                                   // the largest unit that has this level
+        for (const LkPyr& P : pyrs) if (lev < P.n_levels) { mw = std::max(mw, P.lv[lev].w); mh = std::max(mh, P.lv[lev].h); }
+        const dim3 grid((unsigned)cdiv(mw + 2 * kLkPad, kLkTile), (unsigned)cdiv(mh + 2 * kLkPad, kLkTile), (unsigned)n_units);
+        hipLaunchKernelGGL(lk_build_kernel, grid, dim3(kLkTile * kLkTile), 0, c->stream, (const LkBuildUnit*)c->lk_raw.p,
+                           (const LkPyr*)(c->lk_raw.p + unit_bytes), lev);
+    }
+    HIP_TRY(hipGetLastError());
+    VELO_TRY(fb_release(ctxs, n_ctx));
+    for (int i = 0; i < n_ctx; i++) {
+        velo_ctx* ci = ctxs[i];
+        ci->lk_cur ^= 1;
+        LkSlot& S = ci->lk_slot[ci->lk_cur];
+        S.pyr = pyrs[pyr_of[i]]; S.cam_pix = cam_pix[pyr_of[i]]; S.n_cams = n_cams; S.w = sizes[3 * i]; S.h = sizes[3 * i + 1]; S.valid = true;
+    }
+    return VELO_OK;
+}
+
+// velo_track_features[_batch]: job j runs on ctxs[job_ctx[j]] (job_ctx null: on ctxs[0])
+int lk_track(velo_ctx** ctxs, int n_ctx, const int32_t* job_ctx, const velo_track_job* jobs, int32_t n_jobs, const velo_lk_params* p, float* next_xy,
+             uint8_t* status, uint8_t* kept) {
+    // every argument is checked before any context is touched
+    VELO_TRY(fb_check_list(ctxs, n_ctx));
+    VELO_TRY(lk_check_params(n_jobs, p));
+    if (n_jobs == 0) return VELO_OK;
+    int64_t total = 0;
+    VELO_TRY(lk_check_jobs(jobs, n_jobs, next_xy, status, kept, &total));
+    VELO_TRY(fb_check_job_ctx(job_ctx, n_jobs, n_ctx));
+    VELO_TRY(fb_check_devices(ctxs, n_ctx));
+    std::vector<char> used(n_ctx, 0);
+    for (int j = 0; j < n_jobs; j++) {
+        const int i = fb_ctx_of(job_ctx, j);
+        const LkSlot& Sp = *lk_slot(ctxs[i], true);
+        const LkSlot& Sc = *lk_slot(ctxs[i], false);
+        if (!used[i]) {
+            if (!Sp.valid || !Sc.valid) return fail(VELO_ERR_STATE, "context %d: tracking needs a previous and a current frame: velo_set_images twice", i);
+            if (Sp.w != Sc.w || Sp.h != Sc.h || Sp.cam_pix != Sc.cam_pix)
+                return fail(VELO_ERR_INVALID, "context %d: previous images are %d x %d, current %d x %d", i, Sp.w, Sp.h, Sc.w, Sc.h);
+            used[i] = 1;
+        }
+        if (jobs[j].prev_cam < 0 || jobs[j].prev_cam >= Sp.n_cams || jobs[j].cam < 0 || jobs[j].cam >= Sc.n_cams)
+            return fail(VELO_ERR_INVALID, "job %d: cameras (%d -> %d) outside the %d / %d that context %d uploaded", j, jobs[j].prev_cam, jobs[j].cam, Sp.n_cams,
+                        Sc.n_cams, i);
+    }
+    if (total == 0) return VELO_OK;
+    const int n = (int)total;
+    velo_ctx* c = ctxs[0];
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<LkPyr> pyrs;
+    std::vector<long long> cam_pix;
+    std::vector<int> pyr_of(n_ctx, -1);
+    for (int i = 0; i < n_ctx; i++) if (used[i]) pyr_of[i] = fb_pyr_index(&pyrs, &cam_pix, lk_slot(ctxs[i], false)->w, lk_slot(ctxs[i], false)->h);
+    const size_t job_bytes = fb_align64(sizeof(LkJob) * (size_t)n_jobs);
+    const size_t pyr_bytes = fb_align64(sizeof(LkPyr) * pyrs.size());
+    const size_t in_bytes = job_bytes + pyr_bytes + sizeof(float2) * (size_t)n;
+    const size_t out_bytes = sizeof(float2) * (size_t)n + 2 * (size_t)n;
+    VELO_TRY(match_pinned((void**)&c->h_lk_in, &c->h_lk_in_cap, in_bytes));
+    VELO_TRY(match_pinned((void**)&c->h_lk_out, &c->h_lk_out_cap, out_bytes));
+    VELO_TRY(c->lk_in.reserve(in_bytes));
+    VELO_TRY(c->lk_out.reserve(out_bytes));
+    {
+        LkJob* hj = (LkJob*)c->h_lk_in;
+        std::memcpy(c->h_lk_in + job_bytes, pyrs.data(), sizeof(LkPyr) * pyrs.size());
+        float* hp = (float*)(c->h_lk_in + job_bytes + pyr_bytes);
+        int first = 0;
+        for (int j = 0; j < n_jobs; j++) {
+            const int i = fb_ctx_of(job_ctx, j);
+            const LkSlot& Sp = *lk_slot(ctxs[i], true);
+            const LkSlot& Sc = *lk_slot(ctxs[i], false);
+            hj[j].first = first; hj[j].n = jobs[j].n;
+            hj[j].pyr = pyr_of[i];
+            hj[j].top = std::min(lk_level_count(Sc.w, Sc.h, p->window, p->max_level), Sc.pyr.n_levels - 1);
+            hj[j].prev_pix = Sp.pix.p + (size_t)jobs[j].prev_cam * Sp.cam_pix;
+            hj[j].prev_der = Sp.der.p + (size_t)jobs[j].prev_cam * Sp.cam_pix;
+            hj[j].cur_pix = Sc.pix.p + (size_t)jobs[j].cam * Sc.cam_pix;
+            if (jobs[j].n > 0) std::memcpy(hp + 2 * (size_t)first, jobs[j].prev_xy, sizeof(float) * 2 * (size_t)jobs[j].n);
+            first += jobs[j].n;
+        }
+    }
+    VELO_TRY(fb_gather(ctxs, n_ctx, &used));
+    HIP_TRY(hipMemcpyAsync(c->lk_in.p, c->h_lk_in, in_bytes, hipMemcpyHostToDevice, c->stream));
+    LkParams K;
+    std::memset(&K, 0, sizeof(K));
+    K.win = p->window; K.max_count = p->max_count;
+    K.min_eig = (float)p->min_eig_threshold;
+    K.eps2 = p->epsilon * p->epsilon;
+    K.flow_outlier = p->flow_outlier;
+    const LkJob* djobs = (const LkJob*)c->lk_in.p;
+    const LkPyr* dpyrs = (const LkPyr*)(c->lk_in.p + job_bytes);
+    const float2* dpts = (const float2*)(c->lk_in.p + job_bytes + pyr_bytes);
+    float2* oxy = (float2*)c->lk_out.p;
+    unsigned char* ost = c->lk_out.p + sizeof(float2) * (size_t)n;
+    unsigned char* okp = ost + n;
+    unsigned long long* diag = nullptr;
+#ifdef VELO_DIAGNOSTICS
+    VELO_TRY(c->lk_diag.reserve(2 * kLkLevels));
+    if (!c->lk_diag_init) { HIP_TRY(hipMemsetAsync(c->lk_diag.p, 0, sizeof(unsigned long long) * 2 * kLkLevels, c->stream)); c->lk_diag_init = true; }
+    diag = c->lk_diag.p;
+#endif
+    const dim3 grid((unsigned)cdiv(n, kLkThreads / 64));
+    const int npl = cdiv(p->window * p->window, 64);
+    if (npl <= 4)
+        hipLaunchKernelGGL(lk_track_kernel_4, grid, dim3(kLkThreads), 0, c->stream, djobs, n_jobs, dpyrs, dpts, n, K, oxy, ost, okp, diag);
+    else if (npl <= 8)
+        hipLaunchKernelGGL(lk_track_kernel_8, grid, dim3(kLkThreads), 0, c->stream, djobs, n_jobs, dpyrs, dpts, n, K, oxy, ost, okp, diag);
+    else
+        hipLaunchKernelGGL(lk_track_kernel_16, grid, dim3(kLkThreads), 0, c->stream, djobs, n_jobs, dpyrs, dpts, n, K, oxy, ost, okp, diag);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->h_lk_out, c->lk_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::memcpy(next_xy, c->h_lk_out, sizeof(float2) * (size_t)n);
+    std::memcpy(status, c->h_lk_out + sizeof(float2) * (size_t)n, (size_t)n);
+    std::memcpy(kept, c->h_lk_out + sizeof(float2) * (size_t)n + n, (size_t)n);
+    return VELO_OK;
+}
+
 }  // namespace
 
 extern "C" {   // (continued from the previous part)
 int velo_set_images(velo_ctx* c, const uint8_t* const* imgs, int32_t n_cams, int32_t width, int32_t height, int32_t stride) {
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
-    if (n_cams < 1 || n_cams > kLkMaxCams) return fail(VELO_ERR_INVALID, "%d cameras; 1..%d", n_cams, kLkMaxCams);
-    if (!imgs) return fail(VELO_ERR_INVALID, "null image list");
-    for (int k = 0; k < n_cams; k++) if (!imgs[k]) return fail(VELO_ERR_INVALID, "image %d is null", k);
-    if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail(VELO_ERR_INVALID, "image size %d x %d; 1..16384 each", width, height);
-    if (stride < width) return fail(VELO_ERR_INVALID, "row stride %d < width %d", stride, width);
-    HIP_TRY(hipSetDevice(c->device));
-    // the pinned staging buffer may still be read by the previous call's upload
-    if (c->lk_upload_ev) HIP_TRY(hipEventSynchronize(c->lk_upload_ev));
-    else HIP_TRY(hipEventCreateWithFlags(&c->lk_upload_ev, hipEventDisableTiming));
-    c->lk_cur ^= 1;                                           // current -> previous: a rotation, no copy
-    LkSlot& S = c->lk_slot[c->lk_cur];
-    S.valid = false;
-    LkPyr P;
-    long long cam_pix = 0;
-    lk_plan(&P, width, height, &cam_pix);
-    const size_t raw_bytes = (size_t)n_cams * width * height;
-    VELO_TRY(match_pinned((void**)&c->h_lk_raw, &c->h_lk_raw_cap, raw_bytes));
-    VELO_TRY(c->lk_raw.reserve(raw_bytes));
-    VELO_TRY(S.pix.reserve((size_t)cam_pix * n_cams));
-    VELO_TRY(S.der.reserve((size_t)cam_pix * n_cams));
-    for (int k = 0; k < n_cams; k++)
-        for (int y = 0; y < height; y++)
-            std::memcpy(c->h_lk_raw + ((size_t)k * height + y) * width, imgs[k] + (size_t)y * stride, (size_t)width);
-    HIP_TRY(hipMemcpyAsync(c->lk_raw.p, c->h_lk_raw, raw_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipEventRecord(c->lk_upload_ev, c->stream));
-    for (int lev = 0; lev < P.n_levels; lev++) {
-        const LkLevel& L = P.lv[lev];
-        const dim3 grid((unsigned)cdiv(L.w + 2 * kLkPad, kLkTile), (unsigned)cdiv(L.h + 2 * kLkPad, kLkTile), (unsigned)n_cams);
-        hipLaunchKernelGGL(lk_build_kernel, grid, dim3(kLkTile * kLkTile), 0, c->stream, (const unsigned char*)c->lk_raw.p, S.pix.p, S.der.p,
-                           P, lev, cam_pix);
-    }
-    HIP_TRY(hipGetLastError());
-    S.pyr = P; S.cam_pix = cam_pix; S.n_cams = n_cams; S.w = width; S.h = height; S.valid = true;
-    return VELO_OK;
+    const int32_t sizes[3] = {width, height, stride};
+    return lk_set_images(&c, 1, imgs, n_cams, sizes);
+}
+
+int velo_set_images_batch(velo_ctx** ctxs, int32_t n_ctx, const uint8_t* const* imgs, int32_t n_cams, const int32_t* sizes) {
+    return lk_set_images(ctxs, n_ctx, imgs, n_cams, sizes);
 }
 
 int velo_get_image_level(velo_ctx* c, int32_t cam, int32_t previous, int32_t level, int32_t kind, void* out, int64_t capacity_bytes,
@@ -127,82 +360,19 @@ int velo_get_image_level(velo_ctx* c, int32_t cam, int32_t previous, int32_t lev
 
 int velo_track_features(velo_ctx* c, const velo_track_job* jobs, int32_t n_jobs, const velo_lk_params* p, float* next_xy, uint8_t* status,
                         uint8_t* kept) {
-    // every argument is checked before the context is touched
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
-    VELO_TRY(lk_check_params(n_jobs, p));
-    if (n_jobs == 0) return VELO_OK;
-    int64_t total = 0;
-    VELO_TRY(lk_check_jobs(jobs, n_jobs, next_xy, status, kept, &total));
-    const LkSlot& Sp = *lk_slot(c, true);
-    const LkSlot& Sc = *lk_slot(c, false);
-    if (!Sp.valid || !Sc.valid) return fail(VELO_ERR_STATE, "tracking needs a previous and a current frame: velo_set_images twice");
-    if (Sp.w != Sc.w || Sp.h != Sc.h) return fail(VELO_ERR_INVALID, "previous images are %d x %d, current %d x %d", Sp.w, Sp.h, Sc.w, Sc.h);
-    for (int j = 0; j < n_jobs; j++)
-        if (jobs[j].prev_cam < 0 || jobs[j].prev_cam >= Sp.n_cams || jobs[j].cam < 0 || jobs[j].cam >= Sc.n_cams)
-            return fail(VELO_ERR_INVALID, "job %d: cameras (%d -> %d) outside the uploaded %d / %d", j, jobs[j].prev_cam, jobs[j].cam, Sp.n_cams, Sc.n_cams);
-    if (total == 0) return VELO_OK;
-    const int n = (int)total;
+    return lk_track(&c, 1, nullptr, jobs, n_jobs, p, next_xy, status, kept);
+}
 
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t job_bytes = (sizeof(LkJob) * (size_t)n_jobs + 63) & ~(size_t)63;
-    const size_t in_bytes = job_bytes + sizeof(float2) * (size_t)n;
-    const size_t out_bytes = sizeof(float2) * (size_t)n + 2 * (size_t)n;
-    VELO_TRY(match_pinned((void**)&c->h_lk_in, &c->h_lk_in_cap, in_bytes));
-    VELO_TRY(match_pinned((void**)&c->h_lk_out, &c->h_lk_out_cap, out_bytes));
-    VELO_TRY(c->lk_in.reserve(in_bytes));
-    VELO_TRY(c->lk_out.reserve(out_bytes));
-    {
-        LkJob* hj = (LkJob*)c->h_lk_in;
-        float* hp = (float*)(c->h_lk_in + job_bytes);
-        int first = 0;
-        for (int j = 0; j < n_jobs; j++) {
-            hj[j].prev_cam = jobs[j].prev_cam; hj[j].cam = jobs[j].cam; hj[j].first = first; hj[j].n = jobs[j].n;
-            if (jobs[j].n > 0) std::memcpy(hp + 2 * (size_t)first, jobs[j].prev_xy, sizeof(float) * 2 * (size_t)jobs[j].n);
-            first += jobs[j].n;
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(c->lk_in.p, c->h_lk_in, in_bytes, hipMemcpyHostToDevice, c->stream));
-    LkTrackArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.prev_pix = Sp.pix.p; A.prev_der = Sp.der.p; A.cur_pix = Sc.pix.p; A.cam_pix = Sc.cam_pix;
-    if (Sp.cam_pix != Sc.cam_pix) return fail(VELO_ERR_STATE, "slot layouts differ");
-    A.P = Sc.pyr;
-    A.top = std::min(lk_level_count(Sc.w, Sc.h, p->window, p->max_level), Sc.pyr.n_levels - 1);
-    A.K.win = p->window; A.K.max_count = p->max_count;
-    A.K.min_eig = (float)p->min_eig_threshold;
-    A.K.eps2 = p->epsilon * p->epsilon;
-    A.K.flow_outlier = p->flow_outlier;
-    const LkJob* djobs = (const LkJob*)c->lk_in.p;
-    const float2* dpts = (const float2*)(c->lk_in.p + job_bytes);
-    float2* oxy = (float2*)c->lk_out.p;
-    unsigned char* ost = c->lk_out.p + sizeof(float2) * (size_t)n;
-    unsigned char* okp = ost + n;
-    unsigned long long* diag = nullptr;
-#ifdef VELO_DIAGNOSTICS
-    VELO_TRY(c->lk_diag.reserve(2 * kLkLevels));
-    if (!c->lk_diag_init) { HIP_TRY(hipMemsetAsync(c->lk_diag.p, 0, sizeof(unsigned long long) * 2 * kLkLevels, c->stream)); c->lk_diag_init = true; }
-    diag = c->lk_diag.p;
-#endif
-    const dim3 grid((unsigned)cdiv(n, kLkThreads / 64));
-    const int npl = cdiv(p->window * p->window, 64);
-    if (npl <= 4)
-        hipLaunchKernelGGL(lk_track_kernel_4, grid, dim3(kLkThreads), 0, c->stream, djobs, n_jobs, dpts, n, A, oxy, ost, okp, diag);
-    else if (npl <= 8)
-        hipLaunchKernelGGL(lk_track_kernel_8, grid, dim3(kLkThreads), 0, c->stream, djobs, n_jobs, dpts, n, A, oxy, ost, okp, diag);
-    else
-        hipLaunchKernelGGL(lk_track_kernel_16, grid, dim3(kLkThreads), 0, c->stream, djobs, n_jobs, dpts, n, A, oxy, ost, okp, diag);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_lk_out, c->lk_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    std::memcpy(next_xy, c->h_lk_out, sizeof(float2) * (size_t)n);
-    std::memcpy(status, c->h_lk_out + sizeof(float2) * (size_t)n, (size_t)n);
-    std::memcpy(kept, c->h_lk_out + sizeof(float2) * (size_t)n + n, (size_t)n);
-    return VELO_OK;
+int velo_track_features_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* job_ctx, const velo_track_job* jobs, int32_t n_jobs,
+                              const velo_lk_params* p, float* next_xy, uint8_t* status, uint8_t* kept) {
+    if (!job_ctx && n_jobs > 0) return fail(VELO_ERR_INVALID, "null job_ctx");
+    return lk_track(ctxs, n_ctx, job_ctx, jobs, n_jobs, p, next_xy, status, kept);
 }
 
 #ifdef VELO_DIAGNOSTICS
 // diagnostics build only (not declared in velo_hip.h): out[level] = iterations taken, out[8 + level] = points that entered the iteration
-// loop, summed over every velo_track_features call of the context since the last reset (tools/track_bench.py)
+// loop, summed over every tracking call that the context led (as the only or the first context) since the last reset (tools/track_bench.py)
 int velo_diag_track_counters(velo_ctx* c, unsigned long long* out, int reset) {
     if (!c || !out) return fail(VELO_ERR_INVALID, "null argument");
     std::memset(out, 0, sizeof(unsigned long long) * 2 * kLkLevels);

@@ -23,12 +23,13 @@
 // gf_output_kernel: per job and accepted corner the fresh flag against the job's existing points (LDS chunks, brute force), written in
 //   key order; counts per job.
 //
-// Every kernel body works on ONE unit through a GfUnit (the unit's image plane, size and its share of every scratch buffer) and the
-// call's GfParams.  The single-context kernels derive the GfUnit from their arguments (GfArgs: one slot, one size, unit * plane); the
-// batch kernels (gf_*_batch_kernel, velo_detect_features_batch: units of several contexts and of different image sizes in the same
-// launches) read it from a device table uploaded with the jobs, at an index that is uniform per workgroup -- scalar loads, once.  Grids
-// of the batch kernels are sized for the largest unit; a workgroup outside its unit's image leaves at once.  The selection stays per
-// unit: verdicts depend on that unit's keys and states only, so gf_finish's proof of progress holds for every unit independently.
+// Every kernel works on ONE unit per workgroup through a GfUnit (the unit's image plane, size and its share of every scratch buffer) and
+// the call's GfParams.  The GfUnit comes from a device table uploaded with the jobs, at an index that is uniform per workgroup -- scalar
+// loads, once; the host resolves the camera bases, so units of several contexts and of different image sizes share the same launches
+// (velo_detect_features_batch) and a single-context call (velo_detect_features) is a table of its own cameras: there is no other kernel
+// set.  Grids are sized for the largest unit; a workgroup outside its unit's image leaves at once.  The selection stays per unit:
+// verdicts depend on that unit's keys and states only, so gf_finish's proof of progress holds for every unit independently.  A unit's
+// header is a 128-byte line of its own (kGfHdrStride), so that the per-workgroup atomics of different units do not queue on one line.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,7 +43,6 @@
 namespace velo {
 
 constexpr int kGfTile = 16;                // response kernel: output tile edge (256 threads)
-constexpr int kGfMaxUnits = kLkMaxCams;
 constexpr int kGfStatePad = 64;            // zero border of the state map (>= the largest min_distance)
 constexpr int kGfMaxDist = 64;
 constexpr int kGfRoundLaunches = 4;        // passes by the whole device before the single-workgroup loop
@@ -51,11 +51,12 @@ constexpr int kGfFinishThreads = 1024;
 constexpr int kGfSortLds = 4096;           // keys sorted in LDS (32 KB)
 constexpr int kGfOutBlocks = 16;           // workgroups per job in the output kernel
 constexpr int kGfHdr = 8;                  // ints per unit: max bits, candidates, accepted, corners (capped), passes, undecided at finish
+constexpr int kGfHdrStride = 32;           // ints between the headers of two units: a 128-byte line each
 
 enum { kGfNone = 0, kGfUndecided = 1, kGfAccepted = 2, kGfDropped = 3 };
 
 struct GfJob {
-    int unit;                              // index into GfArgs::cams (batch: into the unit table)
+    int unit;                              // index into the call's unit table
     int first, n;                          // the job's existing points [first, first + n) of the call
     int pad_;
 };
@@ -67,7 +68,7 @@ struct GfUnit {                            // one camera of one context, and its
     unsigned* cand;                        // h x w: candidate pixel indices
     unsigned* und;                         // h x w: undecided at the start of the finish kernel
     unsigned long long* keys;              // a power of two >= h x w
-    int* hdr;                              // kGfHdr
+    int* hdr;                              // kGfHdr ints, kGfHdrStride apart from the next unit's
     int w, h, stride, sstride;             // stride: elements per padded image row
 };
 
@@ -80,39 +81,6 @@ struct GfParams {                          // what every unit of a call shares
     float md2f;                            // (float)(min_distance^2), the reference's md2
     int pad_;
 };
-
-struct GfArgs {
-    const unsigned char* pix;              // current slot
-    long long cam_pix;
-    LkLevel L0;
-    int w, h, n_units;
-    int cams[kGfMaxUnits];
-    float* eig;                            // units x (h x w)
-    unsigned char* state;                  // units x splane, rows sstride apart
-    int sstride;
-    long long splane;
-    unsigned* cand;                        // units x (h x w): candidate pixel indices
-    unsigned* und;                         // units x (h x w): undecided at the start of the finish kernel
-    unsigned long long* keys;              // units x keys_cap (a power of two >= h x w)
-    long long keys_cap;
-    int* hdr;                              // units x kGfHdr
-    GfParams K;
-};
-
-// unit u of a single-context call
-__device__ __forceinline__ GfUnit gf_unit_of(const GfArgs& A, int u) {
-    GfUnit U;
-    const long long plane = (long long)A.w * A.h;
-    U.plane = A.pix + A.cams[u] * A.cam_pix + A.L0.off;
-    U.eig = A.eig + u * plane;
-    U.state = A.state + u * A.splane;
-    U.cand = A.cand + u * plane;
-    U.und = A.und + u * plane;
-    U.keys = A.keys + u * A.keys_cap;
-    U.hdr = A.hdr + u * kGfHdr;
-    U.w = A.w; U.h = A.h; U.stride = A.L0.stride; U.sstride = A.sstride;
-    return U;
-}
 
 struct GfResponseLds {
     int img[kGfTile + 4][kGfTile + 4];
@@ -170,18 +138,8 @@ __device__ __forceinline__ void gf_response_body(const GfUnit& U, const GfParams
     if (threadIdx.x == 0 && smax != 0u) atomicMax((unsigned*)&U.hdr[0], smax);
 }
 
-__global__ void __launch_bounds__(kGfTile * kGfTile) gf_response_kernel(GfArgs A)
-#if VELO_DEF_DETECT
-{
-    __shared__ GfResponseLds S;
-    gf_response_body(gf_unit_of(A, blockIdx.z), A.K, S);
-}
-#else
-;
-#endif
-
 // grid (tiles x, tiles y, units) for the largest unit
-__global__ void __launch_bounds__(kGfTile * kGfTile) gf_response_batch_kernel(const GfUnit* __restrict__ units, GfParams K)
+__global__ void __launch_bounds__(kGfTile * kGfTile) gf_response_kernel(const GfUnit* __restrict__ units, GfParams K)
 #if VELO_DEF_DETECT
 {
     __shared__ GfResponseLds S;
@@ -228,18 +186,8 @@ __device__ __forceinline__ void gf_candidates_body(const GfUnit& U, const GfPara
     if (is) U.cand[s_base + slot] = (unsigned)(y * w + x);
 }
 
-__global__ void __launch_bounds__(256) gf_candidates_kernel(GfArgs A)
-#if VELO_DEF_DETECT
-{
-    __shared__ int s_n, s_base;
-    gf_candidates_body(gf_unit_of(A, blockIdx.z), A.K, s_n, s_base);
-}
-#else
-;
-#endif
-
 // grid (cdiv(w, 64), cdiv(h, 4), units) for the largest unit
-__global__ void __launch_bounds__(256) gf_candidates_batch_kernel(const GfUnit* __restrict__ units, GfParams K)
+__global__ void __launch_bounds__(256) gf_candidates_kernel(const GfUnit* __restrict__ units, GfParams K)
 #if VELO_DEF_DETECT
 {
     __shared__ int s_n, s_base;
@@ -307,16 +255,7 @@ __device__ __forceinline__ void gf_round_body(const GfUnit& U, const GfParams& A
     }
 }
 
-__global__ void __launch_bounds__(256) gf_round_kernel(GfArgs A)
-#if VELO_DEF_DETECT
-{
-    gf_round_body(gf_unit_of(A, blockIdx.y), A.K);
-}
-#else
-;
-#endif
-
-__global__ void __launch_bounds__(256) gf_round_batch_kernel(const GfUnit* __restrict__ units, GfParams K)
+__global__ void __launch_bounds__(256) gf_round_kernel(const GfUnit* __restrict__ units, GfParams K)
 #if VELO_DEF_DETECT
 {
     const GfUnit U = units[blockIdx.y];
@@ -408,17 +347,7 @@ __device__ __forceinline__ void gf_finish_body(const GfUnit& U, const GfParams& 
     }
 }
 
-__global__ void __launch_bounds__(kGfFinishThreads) gf_finish_kernel(GfArgs A)
-#if VELO_DEF_DETECT
-{
-    __shared__ GfFinishLds S;
-    gf_finish_body(gf_unit_of(A, blockIdx.x), A.K, S);
-}
-#else
-;
-#endif
-
-__global__ void __launch_bounds__(kGfFinishThreads) gf_finish_batch_kernel(const GfUnit* __restrict__ units, GfParams K)
+__global__ void __launch_bounds__(kGfFinishThreads) gf_finish_kernel(const GfUnit* __restrict__ units, GfParams K)
 #if VELO_DEF_DETECT
 {
     __shared__ GfFinishLds S;
@@ -482,24 +411,10 @@ __device__ __forceinline__ void gf_output_body(const GfUnit& U, const GfParams& 
     if (threadIdx.x == 0 && s_fresh > 0) atomicAdd(&counts[3 * j + 1], s_fresh);
 }
 
-__global__ void __launch_bounds__(256) gf_output_kernel(GfArgs A, const GfJob* __restrict__ jobs, const float2* __restrict__ existing,
-                                                        int* __restrict__ counts, float2* __restrict__ out_xy, float* __restrict__ out_resp,
+__global__ void __launch_bounds__(256) gf_output_kernel(const GfUnit* __restrict__ units, GfParams K, const GfJob* __restrict__ jobs,
+                                                        const float2* __restrict__ existing, int* __restrict__ counts,
+                                                        float2* __restrict__ out_xy, float* __restrict__ out_resp,
                                                         unsigned char* __restrict__ out_fresh)
-#if VELO_DEF_DETECT
-{
-    __shared__ float2 pts[256];
-    __shared__ int s_fresh;
-    const GfJob J = jobs[blockIdx.y];
-    gf_output_body(gf_unit_of(A, J.unit), A.K, J, existing, counts, out_xy, out_resp, out_fresh, pts, s_fresh);
-}
-#else
-;
-#endif
-
-__global__ void __launch_bounds__(256) gf_output_batch_kernel(const GfUnit* __restrict__ units, GfParams K, const GfJob* __restrict__ jobs,
-                                                              const float2* __restrict__ existing, int* __restrict__ counts,
-                                                              float2* __restrict__ out_xy, float* __restrict__ out_resp,
-                                                              unsigned char* __restrict__ out_fresh)
 #if VELO_DEF_DETECT
 {
     __shared__ float2 pts[256];

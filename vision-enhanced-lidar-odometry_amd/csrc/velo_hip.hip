@@ -64,8 +64,7 @@ extern "C" int velo_launch_lm_solve_ag(int nb_max, int n, void* stream, const vo
 #include "velo_api_pose_comm.inl"   // C-ABI: pose helpers and hand-off, the communicators (RCCL, peer slabs), shards, synchronize
 #include "velo_api_next_rows.inl"   // C-ABI: SURVEY 8(f) rows 3 and 4 -- projection, keypoint depth, batched triangulation
 #include "velo_api_match.inl"   // C-ABI: batched Hamming matching of 64-byte descriptors (matchFeatures, velo.h:499-560)
-#include "velo_api_track.inl"   // C-ABI: resident camera images and pyramidal Lucas-Kanade tracking (trackFeatures, velo.h:28-116)
-#include "velo_api_detect.inl"   // C-ABI: GFTT corner detection on the current images (detectFeatures, velo.h:118-177)
-#include "velo_api_frontend_batch.inl"   // C-ABI: images, tracking and detection of several contexts in one call each (velo_*_batch)
+#include "velo_api_track.inl"   // C-ABI: resident camera images and pyramidal Lucas-Kanade tracking (trackFeatures, velo.h:28-116), of one context or of several in one call
+#include "velo_api_detect.inl"   // C-ABI: GFTT corner detection on the current images (detectFeatures, velo.h:118-177), of one context or of several in one call
 #include "velo_api_landmarks.inl"   // C-ABI: the resident landmark store (main.cpp:614-679, getLandmarksAtFrame) and its batch triangulation (velo_landmarks_*)
 #include "velo_api_frames.inl"   // C-ABI: resident keypoint frames and the assembly of frameToFrame's visual matches from them (velo_frames_*, velo_build_matches*)

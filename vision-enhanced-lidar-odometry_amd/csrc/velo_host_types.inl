@@ -405,11 +405,11 @@ struct velo_ctx {
     // registration reads or writes
     LkSlot lk_slot[2];                   // current = lk_slot[lk_cur], previous = the other (velo_set_images rotates them)
     int lk_cur = 0;
-    DevBuf<unsigned char> lk_raw;        // the frame's raw images, one upload
+    DevBuf<unsigned char> lk_raw;        // unit table | level tables | the frame's raw images, one upload
     unsigned char* h_lk_raw = nullptr;   // pinned staging of lk_raw
     size_t h_lk_raw_cap = 0;
     hipEvent_t lk_upload_ev = nullptr;   // h_lk_raw may be rewritten once this has passed
-    DevBuf<unsigned char> lk_in;         // job table | points
+    DevBuf<unsigned char> lk_in;         // job table | level tables | points
     DevBuf<unsigned char> lk_out;        // next_xy | status | kept
     unsigned char* h_lk_in = nullptr;
     size_t h_lk_in_cap = 0;
@@ -423,19 +423,19 @@ struct velo_ctx {
     DevBuf<unsigned char> gf_state;      // units x padded state map (velo_detect_kernels.h)
     DevBuf<unsigned> gf_cand;            // units x (h x w) candidate indices | units x (h x w) undecided at the finish
     DevBuf<unsigned long long> gf_keys;  // units x keys_cap accepted keys
-    DevBuf<int> gf_hdr;                  // units x kGfHdr
-    DevBuf<unsigned char> gf_in;         // job table | existing points
+    DevBuf<int> gf_hdr;                  // units x kGfHdrStride (a 128-byte line per unit)
+    DevBuf<unsigned char> gf_in;         // unit table | job table | existing points
     DevBuf<unsigned char> gf_out;        // counts | per job xy, response, fresh
     unsigned char* h_gf_in = nullptr;
     size_t h_gf_in_cap = 0;
     unsigned char* h_gf_out = nullptr;
     size_t h_gf_out_cap = 0;
-    int gf_units = 0;                    // units of the last call (velo_diag_detect_counters)
+    int gf_units = 0;                    // units of the last launch set this context led (velo_diag_detect_counters)
     // the resident landmark store (velo_landmarks_*): created by velo_landmarks_reset, buffers of its own, which no registration reads or writes
     std::shared_ptr<LmStore> lm;
     // the resident keypoint frames (velo_frames_*): created by velo_frames_reset; velo_build_matches writes the visual set (vm, n_matches) from them
     std::shared_ptr<FrStore> fr;
-    // front-end batch calls (velo_api_frontend_batch.inl): the FIRST context of a call lends its stream, staging and scratch buffers
+    // front-end calls over several contexts (velo_api_track.inl): the FIRST context of a call lends its stream, staging and scratch buffers
     hipEvent_t fb_here_ev = nullptr;     // "everything enqueued on this context's stream so far": the lending stream waits for it
     hipEvent_t fb_done_ev = nullptr;     // recorded on the lending stream after an asynchronous batch call: the other streams wait for it
 

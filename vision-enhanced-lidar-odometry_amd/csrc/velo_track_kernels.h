@@ -6,10 +6,17 @@
 // the image as uint8 (border reflect-101) and the Scharr derivatives as one 32-bit word per pixel (dx in the low, dy in the high 16 bits;
 // border zero, BORDER_CONSTANT).  A slot holds all cameras of a call, camera-major, `cam_pix` pixels apart.
 //
-// lk_build_kernel: one launch per level for every camera.  A 16 x 16 tile of padded output pixels; the block first evaluates the level's
-// value at the reflect-101 position of every tile pixel and a one-pixel halo into LDS (level 0: the raw upload; level l > 0: pyrDown of
-// the stored level l - 1, 25 integer taps), then writes the padded image (border included) and, inside the image, the derivatives from
-// the LDS tile -- the halo holds the reflected neighbours, so the border rule of calcSharrDeriv falls out of the indexing.
+// Every kernel is table-driven: a call (of one context or of several, possibly of different image sizes) uploads small device tables
+// with its input -- one LkBuildUnit per camera of every context, one LkJob per tracking job with the bases of its cameras resolved on
+// the host, and the distinct LkPyr level tables both index.  The index is uniform per workgroup (build) or made uniform per wave
+// (track: readfirstlane), so the tables are read with scalar loads, once, outside the loops.  The single-context entry points
+// (velo_set_images, velo_track_features) are calls with one context: there is no other kernel set.
+//
+// lk_build_kernel: one launch per level for every camera of every context; the grid is sized for the largest unit, and a unit that has
+// no such level or tile leaves at once.  A 16 x 16 tile of padded output pixels; the block first evaluates the level's value at the
+// reflect-101 position of every tile pixel and a one-pixel halo into LDS (level 0: the raw upload; level l > 0: pyrDown of the stored
+// level l - 1, 25 integer taps), then writes the padded image (border included) and, inside the image, the derivatives from the LDS
+// tile -- the halo holds the reflected neighbours, so the border rule of calcSharrDeriv falls out of the indexing.
 //
 // lk_track_kernel_<N>: ONE WAVE PER POINT, all levels coarse to fine inside the wave.  Lane l owns window pixels l, l + 64, ...: N per
 // lane (N = 4 / 8 / 16 for windows up to 15 / 22 / 31).  At each level the lane keeps its share of the resampled I patch and of
@@ -17,12 +24,6 @@
 // |Ix| <= 4080: a lane's sum stays below 2^31) and the wave adds the 64 partial sums in int64 (butterfly: every lane ends with the same
 // exact total).  The float steps after the sums are computed redundantly by every lane from identical inputs, so control flow is
 // uniform.  Integer sums are exact, hence independent of the reduction order: what lets the result equal the restatement bit for bit.
-//
-// Batch variants (velo_set_images_batch / velo_track_features_batch: several contexts, possibly of different image sizes, in one launch):
-// lk_build_batch_kernel and lk_track_batch_kernel_<N> run the SAME bodies; what the single-context kernels take from their kernel
-// arguments (slot bases, level table) they take from small device tables uploaded with the call -- one LkBuildUnit per camera of every
-// context, one LkBatchJob per job, and the distinct LkPyr level tables both index.  The index is uniform per workgroup (build) or made
-// uniform per wave (track: readfirstlane), so the tables are read with scalar loads, once, outside the loops.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -51,11 +52,6 @@ struct LkPyr {
     LkLevel lv[kLkLevels];
 };
 
-struct LkJob {                             // one velo_track_job as the kernel sees it
-    int prev_cam, cam;
-    int first, n;                          // the job's points [first, first + n) of the call
-};
-
 struct LkParams {                          // what every point of a call shares
     int win;
     int max_count;
@@ -65,24 +61,14 @@ struct LkParams {                          // what every point of a call shares
     double flow_outlier;
 };
 
-struct LkTrackArgs {
-    const unsigned char* prev_pix;         // slot of the previous images
-    const int* prev_der;
-    const unsigned char* cur_pix;          // slot of the current images
-    long long cam_pix;                     // elements per camera in a slot
-    LkPyr P;                               // level sizes (both slots: the same image size)
-    int top;                               // deepest level tracked (buildOpticalFlowPyramid's count for this window, - 1)
-    LkParams K;
-};
-
-struct LkBuildUnit {                       // batch build: one camera of one context
+struct LkBuildUnit {                       // build: one camera of one context
     const unsigned char* raw;              // its w0 x h0 upload
     unsigned char* pix;                    // its share of the context's current slot
     int* der;
     int pyr, pad_;                         // index into the call's table of distinct LkPyr
 };
 
-struct LkBatchJob {                        // batch tracking: one velo_track_job with the bases of its context's cameras resolved
+struct LkJob {                             // tracking: one velo_track_job with the bases of its context's cameras resolved
     int first, n;                          // the job's points [first, first + n) of the call
     int pyr, top;                          // level table of its context's image size; deepest level tracked at that size
     const unsigned char* prev_pix;         // previous image of prev_cam (camera base inside the previous slot)
@@ -149,25 +135,10 @@ __device__ __forceinline__ void lk_build_body(const unsigned char* __restrict__ 
     cder[o] = d;
 }
 
-// one level of every camera: grid (tiles x, tiles y, cameras); raw: cameras x (w0 x h0) bytes
-__global__ void __launch_bounds__(kLkTile * kLkTile)
-lk_build_kernel(const unsigned char* __restrict__ raw, unsigned char* __restrict__ pix, int* __restrict__ der, LkPyr P, int lev,
-                long long cam_pix)
-#if VELO_DEF_TRACK
-{
-    __shared__ int tile[kLkTile + 2][kLkTile + 2];
-    const int cam = blockIdx.z;
-    const int w0 = P.lv[0].w, h0 = P.lv[0].h;
-    lk_build_body(raw + (size_t)cam * w0 * h0, pix + cam * cam_pix, der + cam * cam_pix, P.lv[lev], P.lv[lev > 0 ? lev - 1 : 0], lev, w0, tile);
-}
-#else
-;
-#endif
-
 // one level of every camera of every context: grid (tiles x, tiles y, units), sized for the largest unit; a unit that has no such level
 // or no such tile leaves at once (uniform per workgroup, before any barrier)
 __global__ void __launch_bounds__(kLkTile * kLkTile)
-lk_build_batch_kernel(const LkBuildUnit* __restrict__ units, const LkPyr* __restrict__ pyrs, int lev)
+lk_build_kernel(const LkBuildUnit* __restrict__ units, const LkPyr* __restrict__ pyrs, int lev)
 #if VELO_DEF_TRACK
 {
     __shared__ int tile[kLkTile + 2][kLkTile + 2];
@@ -201,9 +172,8 @@ __device__ __forceinline__ void lk_weights(float a, float b, int* w00, int* w01,
     *w11 = (1 << kLkWBits) - *w00 - *w01 - *w10;
 }
 
-// the job that owns point i: the last job whose first <= i (empty jobs share their first with the next job); Job: LkJob or LkBatchJob
-template <typename Job>
-__device__ __forceinline__ int lk_job_of(const Job* __restrict__ jobs, int n_jobs, int i) {
+// the job that owns point i: the last job whose first <= i (empty jobs share their first with the next job)
+__device__ __forceinline__ int lk_job_of(const LkJob* __restrict__ jobs, int n_jobs, int i) {
     int lo = 0, hi = n_jobs;
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
@@ -335,52 +305,32 @@ __device__ __forceinline__ void lk_track_point(int gi, const unsigned char* __re
 }
 
 template <int N>
-__device__ __forceinline__ void lk_track_body(const LkJob* __restrict__ jobs, int n_jobs, const float2* __restrict__ pts, int total,
-                                              const LkTrackArgs& A, float2* __restrict__ out_xy, unsigned char* __restrict__ out_status,
-                                              unsigned char* __restrict__ out_kept, unsigned long long* __restrict__ diag) {
-    const int gi = (int)blockIdx.x * (kLkThreads / 64) + (int)(threadIdx.x >> 6);
-    if (gi >= total) return;                                   // the whole wave leaves together
-    const LkJob J = jobs[lk_job_of(jobs, n_jobs, gi)];
-    lk_track_point<N>(gi, A.prev_pix + J.prev_cam * A.cam_pix, A.prev_der + J.prev_cam * A.cam_pix, A.cur_pix + J.cam * A.cam_pix, A.P, A.top,
-                      A.K, pts, out_xy, out_status, out_kept, diag);
-}
-
-template <int N>
-__device__ __forceinline__ void lk_track_batch_body(const LkBatchJob* __restrict__ jobs, int n_jobs, const LkPyr* __restrict__ pyrs,
-                                                    const float2* __restrict__ pts, int total, const LkParams& K, float2* __restrict__ out_xy,
-                                                    unsigned char* __restrict__ out_status, unsigned char* __restrict__ out_kept) {
+__device__ __forceinline__ void lk_track_body(const LkJob* __restrict__ jobs, int n_jobs, const LkPyr* __restrict__ pyrs,
+                                              const float2* __restrict__ pts, int total, const LkParams& K, float2* __restrict__ out_xy,
+                                              unsigned char* __restrict__ out_status, unsigned char* __restrict__ out_kept,
+                                              unsigned long long* __restrict__ diag) {
     // a wave is one point: its index is the same in every lane; saying so keeps the search, the job record and the level table in
     // scalar registers and scalar loads
     const int gi = __builtin_amdgcn_readfirstlane((int)blockIdx.x * (kLkThreads / 64) + (int)(threadIdx.x >> 6));
     if (gi >= total) return;                                   // the whole wave leaves together
-    const LkBatchJob J = jobs[lk_job_of(jobs, n_jobs, gi)];
-    lk_track_point<N>(gi, J.prev_pix, J.prev_der, J.cur_pix, pyrs[J.pyr], J.top, K, pts, out_xy, out_status, out_kept, nullptr);
+    const LkJob J = jobs[lk_job_of(jobs, n_jobs, gi)];
+    lk_track_point<N>(gi, J.prev_pix, J.prev_der, J.cur_pix, pyrs[J.pyr], J.top, K, pts, out_xy, out_status, out_kept, diag);
 }
 
 #define VELO_LK_TRACK_KERNEL(NAME, N)                                                                                                   \
     __global__ void __launch_bounds__(kLkThreads)                                                                                       \
-    NAME(const LkJob* __restrict__ jobs, int n_jobs, const float2* __restrict__ pts, int total, LkTrackArgs A, float2* __restrict__ out_xy, \
-         unsigned char* __restrict__ out_status, unsigned char* __restrict__ out_kept, unsigned long long* __restrict__ diag)
-#define VELO_LK_TRACK_BATCH_KERNEL(NAME, N)                                                                                             \
-    __global__ void __launch_bounds__(kLkThreads)                                                                                       \
-    NAME(const LkBatchJob* __restrict__ jobs, int n_jobs, const LkPyr* __restrict__ pyrs, const float2* __restrict__ pts, int total,    \
-         LkParams K, float2* __restrict__ out_xy, unsigned char* __restrict__ out_status, unsigned char* __restrict__ out_kept)
+    NAME(const LkJob* __restrict__ jobs, int n_jobs, const LkPyr* __restrict__ pyrs, const float2* __restrict__ pts, int total,         \
+         LkParams K, float2* __restrict__ out_xy, unsigned char* __restrict__ out_status, unsigned char* __restrict__ out_kept,         \
+         unsigned long long* __restrict__ diag)
 #if VELO_DEF_TRACK
-VELO_LK_TRACK_KERNEL(lk_track_kernel_4, 4) { lk_track_body<4>(jobs, n_jobs, pts, total, A, out_xy, out_status, out_kept, diag); }
-VELO_LK_TRACK_KERNEL(lk_track_kernel_8, 8) { lk_track_body<8>(jobs, n_jobs, pts, total, A, out_xy, out_status, out_kept, diag); }
-VELO_LK_TRACK_KERNEL(lk_track_kernel_16, 16) { lk_track_body<16>(jobs, n_jobs, pts, total, A, out_xy, out_status, out_kept, diag); }
-VELO_LK_TRACK_BATCH_KERNEL(lk_track_batch_kernel_4, 4) { lk_track_batch_body<4>(jobs, n_jobs, pyrs, pts, total, K, out_xy, out_status, out_kept); }
-VELO_LK_TRACK_BATCH_KERNEL(lk_track_batch_kernel_8, 8) { lk_track_batch_body<8>(jobs, n_jobs, pyrs, pts, total, K, out_xy, out_status, out_kept); }
-VELO_LK_TRACK_BATCH_KERNEL(lk_track_batch_kernel_16, 16) { lk_track_batch_body<16>(jobs, n_jobs, pyrs, pts, total, K, out_xy, out_status, out_kept); }
+VELO_LK_TRACK_KERNEL(lk_track_kernel_4, 4) { lk_track_body<4>(jobs, n_jobs, pyrs, pts, total, K, out_xy, out_status, out_kept, diag); }
+VELO_LK_TRACK_KERNEL(lk_track_kernel_8, 8) { lk_track_body<8>(jobs, n_jobs, pyrs, pts, total, K, out_xy, out_status, out_kept, diag); }
+VELO_LK_TRACK_KERNEL(lk_track_kernel_16, 16) { lk_track_body<16>(jobs, n_jobs, pyrs, pts, total, K, out_xy, out_status, out_kept, diag); }
 #else
 VELO_LK_TRACK_KERNEL(lk_track_kernel_4, 4);
 VELO_LK_TRACK_KERNEL(lk_track_kernel_8, 8);
 VELO_LK_TRACK_KERNEL(lk_track_kernel_16, 16);
-VELO_LK_TRACK_BATCH_KERNEL(lk_track_batch_kernel_4, 4);
-VELO_LK_TRACK_BATCH_KERNEL(lk_track_batch_kernel_8, 8);
-VELO_LK_TRACK_BATCH_KERNEL(lk_track_batch_kernel_16, 16);
 #endif
 #undef VELO_LK_TRACK_KERNEL
-#undef VELO_LK_TRACK_BATCH_KERNEL
 
 }  // namespace velo
