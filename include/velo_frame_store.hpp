@@ -9,11 +9,19 @@
 //                 dpose = velo_hip::frameToFrameResident<Eigen::Matrix4d>(ctx, frames, frame, frame - dframe, &pose_inverse,
 //                             scans_M, scans_S, kd_trees, transform, matches, good_matches, residual_type, enable_icp);
 //     frames.dropFrame(frame) when a frame leaves the window.
+//     the loop-closure edge (main.cpp:351-365, ba == 1): once a frame's FREAK descriptors are final,
+//                 frames.putDescriptors(descriptors, frame);
+//     and instead of matchFeatures + getLandmarksAtFrame + frameToFrame for a candidate frame - k:
+//                 dpose = velo_hip::frameToFrameLoop<Eigen::Matrix4d>(ctx, frames, frame, frame - k, &pose_inverse, match_thresh,
+//                             scans_M, scans_S, kd_trees, transform, matches, good_matches, residual_type, enable_icp);
+//     `matches` is matchFeatures' result, for the min_matches gates of main.cpp:366-371.
 //
 // Templated over the container types like the other adaptors (cv::Point2f, pcl::PointCloud<pcl::PointXYZ>::Ptr, Eigen::Matrix4d or
-// stand-ins): a keypoint needs .x / .y, a cloud pointer ->points (a vector of points with .x / .y / .z), a matrix operator()(row, col).
+// stand-ins): a keypoint needs .x / .y, a cloud pointer ->points (a vector of points with .x / .y / .z), a matrix operator()(row, col),
+// a descriptor matrix .rows, .cols (64) and .ptr<unsigned char>(row), as cv::Mat has them.
 #ifndef VELO_FRAME_STORE_HPP_
 #define VELO_FRAME_STORE_HPP_
+#include <cstring>
 #include <utility>
 #include <vector>
 
@@ -60,6 +68,21 @@ public:
         return status_;
     }
 
+    // descriptors[cam][frame]: one 64-byte row per keypoint of the frame as it was put (rows need not be contiguous: a cv::Mat ROI
+    // is gathered); replaces rows put before.  putFrame on the frame drops them: put the descriptors after it.
+    template <class Descriptors>
+    int putDescriptors(const Descriptors& descriptors, int frame) {
+        for (int cam = 0; cam < num_cams_; cam++) {
+            const int n = descriptors[cam][frame].rows > 0 ? descriptors[cam][frame].rows : 0;
+            if (n > 0 && descriptors[cam][frame].cols != 64) return status_ = VELO_ERR_INVALID;
+            std::vector<uint8_t> rows(64 * (size_t)n);
+            for (int i = 0; i < n; i++) std::memcpy(&rows[64 * (size_t)i], descriptors[cam][frame].template ptr<unsigned char>(i), 64);
+            status_ = velo_frames_put_descriptors(ctx_, frame, cam, n ? &rows[0] : 0, n);
+            if (status_ != VELO_OK) return status_;
+        }
+        return status_;
+    }
+
     int dropFrame(int frame) { return status_ = velo_frames_drop(ctx_, frame); }
 
     // keypoints of `frame` over all cameras as the library holds them: no match list of a registration against it is longer
@@ -75,19 +98,15 @@ private:
     int status_;
 };
 
-// frameToFrame (velo.h:598-614) for two frames of `frames`, which lives in `ctx`: the matches (matchUsingId, velo.h:562-590), the
-// landmarks of frame2 (getLandmarksAtFrame with the INVERSE pose handed in; null: no landmarks) and the gather of velo.h:627-654 run
-// on the device, then the registration as in frameToFrame.  `matches` receives matchUsingId's result for the caller's min_matches
-// tests (main.cpp:366-371); good_matches / residual_type as frameToFrame fills them.
-template <typename Mat4, typename CloudPtr, typename KdTrees, typename ResidualT>
-Mat4 frameToFrameResident(Context& ctx, FrameStore& frames, const int frame1, const int frame2, const Mat4* pose2_inverse,
-                          const std::vector<CloudPtr>& scans_M, const std::vector<CloudPtr>& scans_S,
-                          const KdTrees& /*kd_trees: superseded by the device grid*/,
-                          double transform[6],
-                          std::vector<std::vector<std::pair<int, int> > >& matches,
-                          std::vector<std::vector<std::pair<int, int> > >& good_matches,
-                          std::vector<std::vector<ResidualT> >& residual_type,
-                          const bool enable_icp) {
+namespace detail {
+
+// what follows the match list in both branches of main.cpp:351-365: the registration on the visual set the build call left, and
+// matches / good_matches / residual_type in the reference's containers.  build(M or null, per_cam, pairs, cap, &n) is the build call.
+template <typename Mat4, typename CloudPtr, typename ResidualT, typename Build>
+Mat4 register_resident(Context& ctx, FrameStore& frames, const int32_t cap, const Mat4* pose2_inverse, const std::vector<CloudPtr>& scans_M,
+                       const std::vector<CloudPtr>& scans_S, double transform[6], std::vector<std::vector<std::pair<int, int> > >& matches,
+                       std::vector<std::vector<std::pair<int, int> > >& good_matches, std::vector<std::vector<ResidualT> >& residual_type,
+                       const bool enable_icp, Build build) {
     velo_params P = ctx.params();
     P.enable_icp = enable_icp ? 1 : 0;                                            // velo.h:806
     ctx.set_params(P);
@@ -97,10 +116,9 @@ Mat4 frameToFrameResident(Context& ctx, FrameStore& frames, const int frame1, co
     const int num_cams = frames.numCams();
     double M[16];
     if (pose2_inverse) for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) M[4 * r + c] = (*pose2_inverse)(r, c);
-    const int32_t cap = frames.frameSize(frame2);
     std::vector<int32_t> per_cam((size_t)num_cams, 0), pairs(2 * (size_t)(cap > 0 ? cap : 1));
     int32_t n = 0;
-    check(velo_build_matches(ctx.get(), frame1, frame2, pose2_inverse ? M : 0, &per_cam[0], &pairs[0], cap, &n), "velo_build_matches");
+    build(pose2_inverse ? M : 0, &per_cam[0], &pairs[0], cap, &n);
     matches.assign((size_t)num_cams, std::vector<std::pair<int, int> >());
     for (int cam = 0, k = 0; cam < num_cams; cam++)
         for (int32_t i = 0; i < per_cam[(size_t)cam] && k < cap; i++, k++) matches[(size_t)cam].push_back(std::make_pair((int)pairs[2 * (size_t)k], (int)pairs[2 * (size_t)k + 1]));
@@ -122,6 +140,57 @@ Mat4 frameToFrameResident(Context& ctx, FrameStore& frames, const int frame1, co
     Mat4 out;
     for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) out(i, j) = T[i * 4 + j];
     return out;
+}
+
+struct BuildById {
+    velo_ctx* ctx; int frame1, frame2;
+    void operator()(const double* M, int32_t* per_cam, int32_t* pairs, int32_t cap, int32_t* n) const {
+        check(velo_build_matches(ctx, frame1, frame2, M, per_cam, pairs, cap, n), "velo_build_matches");
+    }
+};
+
+struct BuildByDescriptor {
+    velo_ctx* ctx; int frame1, frame2; double match_thresh;
+    void operator()(const double* M, int32_t* per_cam, int32_t* pairs, int32_t cap, int32_t* n) const {
+        check(velo_build_matches_desc(ctx, frame1, frame2, M, match_thresh, per_cam, pairs, cap, n), "velo_build_matches_desc");
+    }
+};
+
+}  // namespace detail
+
+// frameToFrame (velo.h:598-614) for two frames of `frames`, which lives in `ctx`: the matches (matchUsingId, velo.h:562-590), the
+// landmarks of frame2 (getLandmarksAtFrame with the INVERSE pose handed in; null: no landmarks) and the gather of velo.h:627-654 run
+// on the device, then the registration as in frameToFrame.  `matches` receives matchUsingId's result for the caller's min_matches
+// tests (main.cpp:366-371); good_matches / residual_type as frameToFrame fills them.
+template <typename Mat4, typename CloudPtr, typename KdTrees, typename ResidualT>
+Mat4 frameToFrameResident(Context& ctx, FrameStore& frames, const int frame1, const int frame2, const Mat4* pose2_inverse,
+                          const std::vector<CloudPtr>& scans_M, const std::vector<CloudPtr>& scans_S,
+                          const KdTrees& /*kd_trees: superseded by the device grid*/,
+                          double transform[6],
+                          std::vector<std::vector<std::pair<int, int> > >& matches,
+                          std::vector<std::vector<std::pair<int, int> > >& good_matches,
+                          std::vector<std::vector<ResidualT> >& residual_type,
+                          const bool enable_icp) {
+    const detail::BuildById build = {ctx.get(), frame1, frame2};
+    return detail::register_resident<Mat4>(ctx, frames, frames.frameSize(frame2), pose2_inverse, scans_M, scans_S, transform, matches,
+                                           good_matches, residual_type, enable_icp, build);
+}
+
+// The loop-closure edge (main.cpp:351-365 with ba == 1): frameToFrameResident with the matches made by matchFeatures on the two
+// frames' resident descriptor rows (query = frame1, train = frame2, velo.h:499-560) instead of matchUsingId.  `matches` receives
+// matchFeatures' result.
+template <typename Mat4, typename CloudPtr, typename KdTrees, typename ResidualT>
+Mat4 frameToFrameLoop(Context& ctx, FrameStore& frames, const int frame1, const int frame2, const Mat4* pose2_inverse, const double match_thresh,
+                      const std::vector<CloudPtr>& scans_M, const std::vector<CloudPtr>& scans_S,
+                      const KdTrees& /*kd_trees: superseded by the device grid*/,
+                      double transform[6],
+                      std::vector<std::vector<std::pair<int, int> > >& matches,
+                      std::vector<std::vector<std::pair<int, int> > >& good_matches,
+                      std::vector<std::vector<ResidualT> >& residual_type,
+                      const bool enable_icp) {
+    const detail::BuildByDescriptor build = {ctx.get(), frame1, frame2, match_thresh};
+    return detail::register_resident<Mat4>(ctx, frames, frames.frameSize(frame1), pose2_inverse, scans_M, scans_S, transform, matches,
+                                           good_matches, residual_type, enable_icp, build);
 }
 
 }  // namespace velo_hip

@@ -725,6 +725,43 @@ int velo_build_matches(velo_ctx* ctx, int32_t frame1, int32_t frame2, const doub
  * [n_ctx][capacity][2], n_out [n_ctx].  Every context's visual set and outputs are byte-identical to the single entry's. */
 int velo_build_matches_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* frames1, const int32_t* frames2, const double* pose2_inv,
                              int32_t* n_per_cam, int32_t* pairs_out, int32_t capacity, int32_t* n_out);
+
+/* --- the loop-closure edge: the same visual set joined by descriptors (main.cpp:359, velo.h:499-560) ------------------------------
+ * The FREAK rows (n x 64 bytes, contiguous) of an entry velo_frames_put has made, kept on the device next to it in a second arena of
+ * 64-byte rows with the keypoint arena's rules (geometric growth, first-fit free list, host directory; it starts at the byte count
+ * velo_frames_reset was given for the keypoint arena, 1 MiB by default); nothing velo_frames_info reports changes.  A second call for
+ * the same entry replaces the rows.  Refused before anything changes: VELO_ERR_INVALID when n differs from the entry's keypoint
+ * count or rows is NULL with n > 0, VELO_ERR_STATE when the (frame, cam) was never put.  velo_frames_put on an entry DROPS its rows
+ * (the keypoints they belonged to are gone), velo_frames_drop frees them with the frame, velo_frames_reset empties both arenas.
+ * Asynchronous like velo_frames_put: one pinned upload, no synchronisation and no device allocation in the steady state. */
+int velo_frames_put_descriptors(velo_ctx* ctx, int32_t frame, int32_t cam, const uint8_t* rows /* n x 64 */, int32_t n);
+/* info[4] = (frame, cam) entries that hold rows, row-arena bytes (saturating at 2^31 - 1), row-arena reallocations, free row blocks. */
+int velo_frames_desc_info(velo_ctx* ctx, int32_t* info);
+/* velo_build_matches with matchFeatures in place of matchUsingId: per camera, in camera order, every row of frame1 (the query side,
+ * the current frame) gets its nearest row of frame2 (the train side) by Hamming distance, the LOWEST train index on ties; min_dist is
+ * the smallest distance of the camera and a match is dropped iff distance > max(1.5 min_dist, match_thresh), in double
+ * (velo.h:536-549, exactly velo_match_descriptors' rules).  The kept pairs (point1, point2) = (queryIdx, trainIdx), query ascending,
+ * give the records of velo_build_matches (id = frame2's id at point2, the same landmark substitution, every other byte zero); two
+ * queries may keep one train row (two records); an empty side gives no match.  Arguments, outputs and the state the call leaves are
+ * velo_build_matches' (capacity bounds pairs_out only; frame1's keypoint count bounds the matches).  VELO_ERR_STATE, with nothing
+ * changed, also when a (frame, cam) of either frame holds no rows.  One upload of the call's tables, three launches on the resident
+ * rows (int8-MFMA product, filter, record emit), one copy back (per camera min_dist and count, the pairs), one synchronisation: no
+ * descriptor byte crosses the bus.  What this saves over velo_match_descriptors + host assembly + velo_set_visual has not been
+ * measured yet (tools/loop_matches_bench.py is the measurement). */
+int velo_build_matches_desc(velo_ctx* ctx, int32_t frame1, int32_t frame2, const double* pose2_inv16 /* may be NULL */, double match_thresh,
+                            int32_t* n_per_cam, int32_t* pairs_out, int32_t capacity, int32_t* n_out);
+/* The same for (frames1[i], frames2[i]) of ctxs[i] in the SAME three launches (every job carries the base pointers of its rows, so a
+ * call names several contexts' arenas); the rules and the layout of the outputs are velo_build_matches_batch's. */
+int velo_build_matches_desc_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* frames1, const int32_t* frames2, const double* pose2_inv,
+                                  double match_thresh, int32_t* n_per_cam, int32_t* pairs_out, int32_t capacity, int32_t* n_out);
+/* The matches[cam].size() tests of main.cpp:366-371 for every loop-closure candidate of a frame: frame1's rows against those of
+ * frames2[k], k < n_cand, camera by camera, in ONE launch set of n_cand x n_cams jobs on resident rows (frame1's are read in place by
+ * every job).  n_kept / min_dist [n_cand][n_cams]: the pairs velo_build_matches_desc would keep and the camera's smallest distance
+ * (-1: an empty side).  The visual set and everything else of the context stay as they are.  n_cand == 0 is valid (nothing is done).
+ * VELO_ERR_STATE when a (frame, cam) was never put or holds no rows. */
+int velo_match_frames(velo_ctx* ctx, int32_t frame1, const int32_t* frames2, int32_t n_cand, double match_thresh, int32_t* n_kept,
+                      int32_t* min_dist);
+
 /* Read-back of the context's device-side visual set, whoever wrote it (velo_set_visual or velo_build_matches): *n = its records,
  * the first `capacity` are written (out may be NULL). */
 int velo_get_visual(velo_ctx* ctx, velo_match* out, int32_t capacity, int32_t* n);

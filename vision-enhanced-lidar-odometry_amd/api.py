@@ -304,6 +304,12 @@ SIGNATURES = {
     "velo_build_matches_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                            C.c_void_p]),
     "velo_get_visual": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(C.c_int32)]),
+    "velo_frames_put_descriptors": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
+    "velo_frames_desc_info": (C.c_int, [_ctx, C.c_void_p]),
+    "velo_build_matches_desc": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int32, _P(C.c_int32)]),
+    "velo_build_matches_desc_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                                                C.c_int32, C.c_void_p]),
+    "velo_match_frames": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -771,6 +777,41 @@ class Context:
             return per_cam[0, :n_cams[0]].copy(), pairs[0], int(n[0])
         return per_cam[0, :n_cams[0]].copy(), pairs[0, :n[0]].copy()
 
+    def frames_put_descriptors(self, frame: int, cam: int, rows):
+        """The FREAK rows (uint8 (n, 64), one per keypoint) of an entry frames_put has made; a second call replaces them"""
+        r = np.ascontiguousarray(np.asarray(rows, dtype=np.uint8))
+        if r.size == 0:
+            r = r.reshape(0, 64)
+        if r.ndim != 2 or r.shape[1] != 64:
+            raise ValueError(f"descriptors must be uint8 (n, 64), got shape {r.shape}")
+        self._check(self._lib.velo_frames_put_descriptors(self._h, int(frame), int(cam), C.c_void_p(r.ctypes.data) if len(r) else None, len(r)))
+
+    def frames_desc_info(self) -> dict:
+        a = np.zeros(4, dtype=np.int32)
+        self._check(self._lib.velo_frames_desc_info(self._h, C.c_void_p(a.ctypes.data)))
+        return dict(entries=int(a[0]), arena_bytes=int(a[1]), arena_reallocations=int(a[2]), free_blocks=int(a[3]))
+
+    def build_matches_desc(self, frame1: int, frame2: int, pose2_inv=None, match_thresh: float = 29.0, capacity: Optional[int] = None):
+        """build_matches with the frames joined by their resident descriptor rows (matchFeatures, the loop-closure edge) instead of
+        their ids: query = frame1, train = frame2, pairs (point1, point2) = (queryIdx, trainIdx).  Returns what build_matches returns."""
+        per_cam, pairs, n, n_cams = build_matches_desc_batch([self], [frame1], [frame2], None if pose2_inv is None else [pose2_inv],
+                                                             match_thresh, capacity=capacity, raw=True, _with_cams=True)
+        if capacity is not None:
+            return per_cam[0, :n_cams[0]].copy(), pairs[0], int(n[0])
+        return per_cam[0, :n_cams[0]].copy(), pairs[0, :n[0]].copy()
+
+    def match_frames(self, frame1: int, frames2, match_thresh: float = 29.0):
+        """frame1's resident rows against those of every candidate frame of frames2, camera by camera, in one launch set:
+        (n_kept [n_cand, n_cams] i32, min_dist [n_cand, n_cams] i32, -1 where a side is empty).  The visual set is left alone."""
+        f2 = np.ascontiguousarray(np.asarray(frames2, dtype=np.int32).reshape(-1))
+        if getattr(self, "_fr_cams", None) is None:
+            self._fr_cams = self.frames_info()["n_cams"]
+        kept = np.zeros((max(len(f2), 1), self._fr_cams), dtype=np.int32)
+        md = np.full((max(len(f2), 1), self._fr_cams), -1, dtype=np.int32)
+        vp = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+        self._check(self._lib.velo_match_frames(self._h, int(frame1), vp(f2) if len(f2) else None, len(f2), float(match_thresh), vp(kept), vp(md)))
+        return kept[:len(f2)], md[:len(f2)]
+
     def get_visual(self, capacity: Optional[int] = None) -> np.ndarray:
         """The context's device-side visual set (velo_match records), whoever wrote it"""
         n = C.c_int32(0)
@@ -1206,6 +1247,38 @@ def build_matches_batch(ctxs, frames1, frames2, poses2_inv=None, capacity: Optio
     pairs = np.zeros((n_ctx, max(cap, 1), 2), dtype=np.int32)
     _batch_check(lib, lib.velo_build_matches_batch(C.cast(arr, C.c_void_p), n_ctx, vp(f1), vp(f2), vp(M) if M is not None else None,
                                                    vp(per_cam), vp(pairs), cap, vp(n)))
+    n_cams = [len(s[0]) for s in sizes]
+    if _with_cams:
+        return per_cam, pairs[:, :cap], n, n_cams
+    if raw or capacity is not None:
+        return per_cam, pairs[:, :cap], n
+    return [(per_cam[i, :n_cams[i]].copy(), pairs[i, :n[i]].copy()) for i in range(n_ctx)]
+
+
+def build_matches_desc_batch(ctxs, frames1, frames2, poses2_inv=None, match_thresh: float = 29.0, capacity: Optional[int] = None,
+                             raw: bool = False, _with_cams: bool = False):
+    """Context.build_matches_desc for (frames1[i], frames2[i]) of ctxs[i] in ONE call (the same three launches for all); arguments
+    and results as build_matches_batch.  capacity defaults to the keypoints of the largest frame1 (the query side), which bounds every
+    count."""
+    lib, arr = _batch_lib_and_handles(ctxs)
+    n_ctx = len(ctxs)
+    if len(frames1) != n_ctx or len(frames2) != n_ctx:
+        raise ValueError("build_matches_desc_batch: one frame pair per context")
+    f1 = np.ascontiguousarray(np.asarray(frames1, dtype=np.int32).reshape(-1))
+    f2 = np.ascontiguousarray(np.asarray(frames2, dtype=np.int32).reshape(-1))
+    M = None
+    if poses2_inv is not None:
+        M = np.ascontiguousarray(np.asarray(poses2_inv, dtype=np.float64).reshape(-1))
+        if M.size != 16 * n_ctx:
+            raise ValueError("build_matches_desc_batch: one 4 x 4 inverse pose per context")
+    vp = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+    sizes = [c.frames_count(f) for c, f in zip(ctxs, f1)]      # also raises when a context has no frame store
+    cap = max(s[1] for s in sizes) if capacity is None else int(capacity)
+    per_cam = np.zeros((n_ctx, 8), dtype=np.int32)
+    n = np.zeros(n_ctx, dtype=np.int32)
+    pairs = np.zeros((n_ctx, max(cap, 1), 2), dtype=np.int32)
+    _batch_check(lib, lib.velo_build_matches_desc_batch(C.cast(arr, C.c_void_p), n_ctx, vp(f1), vp(f2), vp(M) if M is not None else None,
+                                                        float(match_thresh), vp(per_cam), vp(pairs), cap, vp(n)))
     n_cams = [len(s[0]) for s in sizes]
     if _with_cams:
         return per_cam, pairs[:, :cap], n, n_cams

@@ -1,7 +1,9 @@
 // velo_api_frames.inl -- part of the host side of the C-ABI, included by velo_hip.hip (ONE translation unit; the order of the parts is the order of
 // definition).  C-ABI: resident keypoint frames (velo_frames_*) and the assembly of frameToFrame's visual matches from them
 // (velo_build_matches[_batch], velo_get_visual): matchUsingId (velo.h:562-590), the landmark substitution and the gather of
-// velo.h:627-654 on the device; the kernels are in velo_frame_kernels.h.
+// velo.h:627-654 on the device; the kernels are in velo_frame_kernels.h.  Also the frames' descriptor rows (velo_frames_put_descriptors),
+// the visual set of a loop-closure edge joined by them (velo_build_matches_desc[_batch]: matchFeatures, velo.h:499-560, on the match
+// kernels of velo_match_kernels.h) and the screening of a frame against many candidates (velo_match_frames).
 //
 // Who knows what: the DEVICE holds the arrays of every (frame, camera) in one arena of 4-byte words and one slot table per camera;
 // the HOST keeps the directory (frame, cam) -> block, n, n_with_depth, the largest id of the block (which sizes the slot table
@@ -9,6 +11,8 @@
 // made for the reference's use, a sliding window of frames of similar size (3,000 keypoints per camera, kitti.h) in which a dropped
 // frame's blocks are taken by the next frame's entries of about the same size; a caller that mixes very different sizes pays with
 // arena growth (velo_frames_info shows it), never with wrong results.
+// The descriptor rows of a (frame, camera) live in a second arena of 64-byte rows with a directory and a free list of its own, under
+// the same rules; the keypoint arena does not know of it.
 struct FrStore {
     int n_cams = 0;
     float cam_t[3 * 8] = {};
@@ -23,6 +27,18 @@ struct FrStore {
     struct Entry { size_t off = 0, cap = 0; int n = 0, n_wd = 0, max_id = -1; };
     std::unordered_map<int64_t, Entry> dir;         // frame * 8 + cam
     std::vector<std::pair<size_t, size_t>> free_blocks;   // {offset, words} of dropped and outgrown blocks
+    // the descriptor rows: device arena, then host directory (frame * 8 + cam -> block) and free list, all counted in rows
+    DevBuf<uint4> rows;                             // 4 per row; every block starts on a 64-byte line
+    size_t r_used = 0, r_cap = 0;
+    int r_reallocs = 0;
+    struct RowEntry { size_t off = 0, cap = 0; int n = 0; };
+    std::unordered_map<int64_t, RowEntry> rdir;
+    std::vector<std::pair<size_t, size_t>> r_free;
+    unsigned char* h_rows[2] = {nullptr, nullptr};  // staging of velo_frames_put_descriptors, as h_put below
+    size_t h_rows_cap[2] = {0, 0};
+    hipEvent_t rows_ev[2] = {nullptr, nullptr};
+    int rows_k = 0;
+    DevBuf<unsigned> d_keys;                        // nearest-row keys and min_dist of a descriptor-matched call
     // staging of velo_frames_put: two pinned slots used alternately, so that a put waits only for the upload before the previous one
     unsigned char* h_put[2] = {nullptr, nullptr};
     size_t h_put_cap[2] = {0, 0};
@@ -34,6 +50,7 @@ struct FrStore {
     DevBuf<unsigned char> d_in, d_out;
     ~FrStore() {
         for (int k = 0; k < 2; k++) { if (h_put[k]) (void)hipHostFree(h_put[k]); if (put_ev[k]) (void)hipEventDestroy(put_ev[k]); }
+        for (int k = 0; k < 2; k++) { if (h_rows[k]) (void)hipHostFree(h_rows[k]); if (rows_ev[k]) (void)hipEventDestroy(rows_ev[k]); }
         if (h_in) (void)hipHostFree(h_in);
         if (h_out) (void)hipHostFree(h_out);
     }
@@ -43,6 +60,7 @@ namespace {
 
 constexpr size_t kFrDefaultArena = (1u << 20) / sizeof(int);   // words
 constexpr size_t kFrAlign = 16;                                 // words: every block starts on a 64-byte line
+constexpr size_t kFrDefaultRows = (1u << 20) / 64;              // rows
 
 inline size_t fr_round(size_t words) { return (words + kFrAlign - 1) / kFrAlign * kFrAlign; }
 
@@ -64,6 +82,33 @@ void fr_side(const FrStore& S, const FrStore::Entry& e, FrSide* out) {
     out->xy = reinterpret_cast<const float*>(b + 2 * (size_t)e.n);
     out->cloud = reinterpret_cast<const float*>(b + 4 * (size_t)e.n);
     out->n = e.n; out->pad = 0;
+}
+
+// the state velo_set_visual leaves, for context i of a build call whose records are in vm: per_cam [n_cams] matches, pairs their
+// (point1, point2) in record order; the host copy of the records holds what velo_get_good_matches reads
+void fr_leave_visual(velo_ctx* c, int i, const int* per_cam, const int* pairs, int32_t* n_per_cam, int32_t* pairs_out, int32_t capacity,
+                     int32_t* n_out) {
+    velo_match zero;
+    std::memset(&zero, 0, sizeof(zero));
+    c->h_matches.clear();
+    int total = 0;
+    for (int cam = 0; cam < c->fr->n_cams; cam++) {
+        const int m = per_cam[cam];
+        if (n_per_cam) n_per_cam[(size_t)i * kLmMaxCams + cam] = m;
+        for (int k = 0; k < m; k++) {
+            const int* pr = pairs + 2 * ((size_t)total + (size_t)k);
+            velo_match r = zero;
+            r.cam = cam; r.point1 = pr[0]; r.point2 = pr[1];
+            c->h_matches.push_back(r);
+        }
+        total += m;
+    }
+    c->n_matches = total;
+    c->vflags_valid = false;
+    c->h_vflags.clear();
+    n_out[i] = total;
+    const int w = std::min(total, (int)capacity);
+    if (pairs_out && w > 0) std::memcpy(pairs_out + 2 * (size_t)i * capacity, pairs, sizeof(int32_t) * 2 * (size_t)w);
 }
 
 int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32_t* frames2, const double* pose2_inv, int32_t* n_per_cam,
@@ -186,34 +231,166 @@ int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32
     HIP_TRY(hipStreamSynchronize(st));
     const int* h_counts = (const int*)L->h_out;
     const int* h_pairs = (const int*)(L->h_out + cnt_bytes);
-    velo_match zero;
-    std::memset(&zero, 0, sizeof(zero));
     for (int i = 0; i < n_ctx; i++) {
-        velo_ctx* c = ctxs[i];
-        FrStore& S = *c->fr;
+        FrStore& S = *ctxs[i]->fr;
         S.slots_dirty = false;
-        // the state velo_set_visual leaves; the host copy of the records holds what velo_get_good_matches reads
-        c->h_matches.clear();
-        int total = 0;
+        int per_cam[kLmMaxCams];
         for (int cam = 0; cam < S.n_cams; cam++) {
             const int u = unit0[i] + cam;
-            int m = 0;
-            for (int k = chunk0[(size_t)u]; k < chunk0[(size_t)u + 1]; k++) m += h_counts[k];
-            if (n_per_cam) n_per_cam[(size_t)i * kLmMaxCams + cam] = m;
-            for (int k = 0; k < m; k++) {
-                const int* pr = h_pairs + 2 * (pair0[i] + (size_t)total + (size_t)k);
-                velo_match r = zero;
-                r.cam = cam; r.point1 = pr[0]; r.point2 = pr[1];
-                c->h_matches.push_back(r);
-            }
-            total += m;
+            per_cam[cam] = 0;
+            for (int k = chunk0[(size_t)u]; k < chunk0[(size_t)u + 1]; k++) per_cam[cam] += h_counts[k];
         }
-        c->n_matches = total;
-        c->vflags_valid = false;
-        c->h_vflags.clear();
-        n_out[i] = total;
-        const int w = std::min(total, (int)capacity);
-        if (pairs_out && w > 0) std::memcpy(pairs_out + 2 * (size_t)i * capacity, h_pairs + 2 * pair0[i], sizeof(int32_t) * 2 * (size_t)w);
+        fr_leave_visual(ctxs[i], i, per_cam, h_pairs + 2 * pair0[i], n_per_cam, pairs_out, capacity, n_out);
+    }
+    return VELO_OK;
+}
+
+void fr_free_rows(FrStore& S, int64_t key) {
+    auto it = S.rdir.find(key);
+    if (it == S.rdir.end()) return;
+    if (it->second.cap > 0) S.r_free.push_back(std::make_pair(it->second.off, it->second.cap));
+    S.rdir.erase(it);
+}
+
+// One launch set of descriptor matching on resident rows.  build: context i joins (frames1[i], frames2[i]) camera by camera and its
+// visual set becomes the kept pairs' records (velo_build_matches_desc[_batch]); else the ONE context's frames1[0] is screened against
+// the n_cand frames of frames2, job-major candidate, camera (velo_match_frames: kept / min_d, nothing else changes).
+int fr_desc_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32_t* frames2, int n_cand, bool build, const double* pose2_inv,
+                double match_thresh, int32_t* n_per_cam, int32_t* pairs_out, int32_t capacity, int32_t* n_out, int32_t* kept, int32_t* min_d) {
+    const char* who = build ? "velo_build_matches_desc" : "velo_match_frames";
+    // state first: nothing changes when a frame or its rows are missing
+    for (int i = 0; i < n_ctx; i++) {
+        VELO_TRY(fr_need_store(ctxs[i], who));
+        const FrStore& S = *ctxs[i]->fr;
+        const int n2 = build ? 1 : n_cand;
+        for (int cam = 0; cam < S.n_cams; cam++)
+            for (int k = -1; k < n2; k++) {
+                const int f = k < 0 ? frames1[i] : frames2[build ? i : k];
+                if (!S.dir.count(lm_key(f, cam))) return fail(VELO_ERR_STATE, "context %d: frame %d, camera %d has not been put", i, f, cam);
+                if (!S.rdir.count(lm_key(f, cam))) return fail(VELO_ERR_STATE, "context %d: frame %d, camera %d has no descriptor rows", i, f, cam);
+            }
+    }
+    velo_ctx* c0 = ctxs[0];
+    FrStore* L = c0->fr.get();
+    HIP_TRY(hipSetDevice(c0->device));
+    // the jobs of the call: context-major (or candidate-major), camera-major; a build's job u is its unit u
+    std::vector<MatchResJob> jobs;
+    std::vector<int> unit0(n_ctx + 1, 0);
+    std::vector<size_t> pair0(n_ctx + 1, 0);
+    int64_t blocks = 0, total_q = 0;
+    int max_nq = 0;
+    for (int i = 0; i < n_ctx; i++) {
+        const FrStore& S = *ctxs[i]->fr;
+        for (int k = 0; k < (build ? 1 : n_cand); k++)
+            for (int cam = 0; cam < S.n_cams; cam++) {
+                const FrStore::RowEntry& r1 = S.rdir.at(lm_key(frames1[i], cam));
+                const FrStore::RowEntry& r2 = S.rdir.at(lm_key(frames2[build ? i : k], cam));
+                MatchResJob M;
+                std::memset(&M, 0, sizeof(M));
+                M.q = S.rows.p + 4 * r1.off; M.t = S.rows.p + 4 * r2.off;
+                M.n_query = r1.n; M.n_train = r2.n;
+                M.q_out = (int)total_q;
+                M.blk_start = (int)blocks;
+                M.nqb = cdiv(r1.n, kMatchQ);
+                if (r1.n > 0 && r2.n > 0) blocks += (int64_t)M.nqb * cdiv(r2.n, kMatchT);
+                total_q += r1.n;
+                max_nq = std::max(max_nq, r1.n);
+                jobs.push_back(M);
+            }
+        unit0[i + 1] = (int)jobs.size();
+        pair0[i + 1] = (size_t)total_q;
+    }
+    if (total_q > (int64_t)(INT32_MAX / 4)) return fail(VELO_ERR_INVALID, "%lld queries in one call; at most %d", (long long)total_q, INT32_MAX / 4);
+    if (blocks > (int64_t)INT32_MAX) return fail(VELO_ERR_INVALID, "too many match blocks in one call");
+    const int n_jobs = (int)jobs.size(), nq = (int)total_q;
+    // room: the visual sets, the staging
+    if (build)
+        for (int i = 0; i < n_ctx; i++) {
+            velo_ctx* c = ctxs[i];
+            const size_t n1 = pair0[i + 1] - pair0[i];
+            // records of an earlier velo_register_batch_visual may still be on their way into vm (set_visual_impl without a wait)
+            if (c->pin[3].pending) { HIP_TRY(hipEventSynchronize(c->pin[3].ev)); c->pin[3].pending = false; }
+            if (n1 > 0) {
+                VELO_TRY(c->vm.reserve(n1));
+                VELO_TRY(c->vflags.reserve(3 * n1));
+            }
+        }
+    // device input: jobs | units | contexts; device output: the filter's four arrays | the records' pairs, context after context
+    const size_t job_bytes = fb_align64(sizeof(MatchResJob) * (size_t)n_jobs);
+    const size_t unit_bytes = build ? fb_align64(sizeof(FrDescUnit) * (size_t)n_jobs) : 0;
+    const size_t in_bytes = job_bytes + unit_bytes + (build ? sizeof(FrCtx) * (size_t)n_ctx : 0);
+    const size_t filt_ints = 4 * (size_t)nq + 2 * (size_t)n_jobs;
+    const size_t back_ints = 2 * (size_t)n_jobs + (build ? 2 * (size_t)nq : 0);          // {min_dist, n_kept} per job | pairs: what comes back
+    const size_t out_bytes = sizeof(int) * (filt_ints + (build ? 2 * (size_t)nq : 0));
+    VELO_TRY(match_pinned((void**)&L->h_in, &L->h_in_cap, in_bytes));
+    VELO_TRY(match_pinned((void**)&L->h_out, &L->h_out_cap, sizeof(int) * back_ints));
+    VELO_TRY(L->d_in.reserve(in_bytes));
+    VELO_TRY(L->d_out.reserve(out_bytes));
+    VELO_TRY(L->d_keys.reserve((size_t)nq + (size_t)n_jobs));
+    int* d_filt = (int*)L->d_out.p;
+    int* d_job_out = d_filt + 4 * (size_t)nq;
+    int* d_pairs = d_filt + filt_ints;
+    std::memset(L->h_in, 0, in_bytes);
+    std::memcpy(L->h_in, jobs.data(), sizeof(MatchResJob) * (size_t)n_jobs);
+    if (build) {
+        FrDescUnit* hu = (FrDescUnit*)(L->h_in + job_bytes);
+        FrCtx* hc = (FrCtx*)(L->h_in + job_bytes + unit_bytes);
+        for (int i = 0; i < n_ctx; i++) {
+            velo_ctx* c = ctxs[i];
+            const FrStore& S = *c->fr;
+            for (int cam = 0; cam < S.n_cams; cam++) {
+                FrDescUnit& U = hu[unit0[i] + cam];
+                fr_side(S, S.dir.at(lm_key(frames1[i], cam)), &U.f1);
+                fr_side(S, S.dir.at(lm_key(frames2[i], cam)), &U.f2);
+                U.ctx = i; U.cam = cam;
+                U.ctx_unit0 = unit0[i];
+                U.q_out = jobs[(size_t)(unit0[i] + cam)].q_out;
+                for (int k = 0; k < 3; k++) U.t_cam[k] = S.cam_t[3 * cam + k];
+            }
+            FrCtx& K = hc[i];
+            K.vm = c->vm.p;
+            K.pairs = d_pairs + 2 * pair0[i];
+            if (pose2_inv && c->lm && c->lm->n_ids > 0) {
+                K.lm_pts = c->lm->pts.p; K.lm_added = c->lm->added.p; K.lm_ids = (int)c->lm->n_ids;
+                std::memcpy(K.pose2_inv.m, pose2_inv + 16 * (size_t)i, sizeof(K.pose2_inv.m));
+            }
+        }
+    }
+    VELO_TRY(fb_gather(ctxs, n_ctx, nullptr));
+    hipStream_t st = c0->stream;
+    if (build)
+        for (int i = 0; i < n_ctx; i++) {
+            const size_t n1 = pair0[i + 1] - pair0[i];
+            if (n1 > 0) HIP_TRY(hipMemsetAsync(ctxs[i]->vflags.p, 0, 3 * n1, st));
+        }
+    if (n_jobs > 0) {
+        HIP_TRY(hipMemcpyAsync(L->d_in.p, L->h_in, in_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(L->d_keys.p, 0xFF, sizeof(unsigned) * ((size_t)nq + (size_t)n_jobs), st));   // kMatchNone
+        const MatchResJob* d_jobs = (const MatchResJob*)L->d_in.p;
+        unsigned* keys = L->d_keys.p;
+        unsigned* dmin = L->d_keys.p + nq;
+        if (blocks > 0)
+            hipLaunchKernelGGL(match_mfma_resident_kernel, dim3((unsigned)blocks), dim3(kMatchThreads), 0, st, d_jobs, n_jobs, keys, dmin);
+        hipLaunchKernelGGL(match_filter_resident_kernel, dim3((unsigned)n_jobs), dim3(kMatchThreads), 0, st, d_jobs, (const unsigned*)keys,
+                           (const unsigned*)dmin, match_thresh, nq, d_filt);
+        if (build && max_nq > 0)
+            hipLaunchKernelGGL(fr_emit_desc_kernel, dim3((unsigned)cdiv(max_nq, 256), (unsigned)n_jobs), dim3(256), 0, st,
+                               (const FrDescUnit*)(L->d_in.p + job_bytes), (const FrCtx*)(L->d_in.p + job_bytes + unit_bytes),
+                               (const int*)d_job_out, (const int*)(d_filt + 2 * (size_t)nq));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(L->h_out, d_job_out, sizeof(int) * back_ints, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    const int* h_job = (const int*)L->h_out;
+    if (!build) {
+        for (int j = 0; j < n_jobs; j++) { min_d[j] = h_job[2 * j]; kept[j] = h_job[2 * j + 1]; }
+        return VELO_OK;
+    }
+    const int* h_pairs = h_job + 2 * (size_t)n_jobs;
+    for (int i = 0; i < n_ctx; i++) {
+        int per_cam[kLmMaxCams];
+        for (int cam = 0; cam < ctxs[i]->fr->n_cams; cam++) per_cam[cam] = h_job[2 * (unit0[i] + cam) + 1];
+        fr_leave_visual(ctxs[i], i, per_cam, h_pairs + 2 * pair0[i], n_per_cam, pairs_out, capacity, n_out);
     }
     return VELO_OK;
 }
@@ -236,6 +413,9 @@ int velo_frames_reset(velo_ctx* c, int32_t n_cams, const float* cam_trans, int32
     const size_t want = arena_capacity > 0 ? fr_round(((size_t)arena_capacity + sizeof(int) - 1) / sizeof(int)) : kFrDefaultArena;
     VELO_TRY(S->arena.reserve(want));
     S->cap = want;                                      // the buffer holds a little more; the arena reallocates at what was asked for
+    const size_t want_rows = arena_capacity > 0 ? ((size_t)arena_capacity + 63) / 64 : kFrDefaultRows;   // the row arena starts at the same byte count
+    VELO_TRY(S->rows.reserve(4 * want_rows));
+    S->r_cap = want_rows;
     c->fr = S;
     return VELO_OK;
 }
@@ -305,6 +485,7 @@ int velo_frames_put(velo_ctx* c, int32_t frame, int32_t cam, const int32_t* ids,
         if (old != S.dir.end() && old->second.cap > 0) S.free_blocks.push_back(std::make_pair(old->second.off, old->second.cap));
     }
     S.dir[key] = e;
+    fr_free_rows(S, key);                                            // the keypoints the rows belonged to are gone
     return VELO_OK;
 }
 
@@ -318,7 +499,72 @@ int velo_frames_drop(velo_ctx* c, int32_t frame) {
         if (it == S.dir.end()) continue;
         if (it->second.cap > 0) S.free_blocks.push_back(std::make_pair(it->second.off, it->second.cap));
         S.dir.erase(it);
+        fr_free_rows(S, lm_key(frame, cam));
     }
+    return VELO_OK;
+}
+
+int velo_frames_put_descriptors(velo_ctx* c, int32_t frame, int32_t cam, const uint8_t* rows, int32_t n) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
+    if (cam < 0 || cam >= kLmMaxCams) return fail(VELO_ERR_INVALID, "camera %d; 0..%d", cam, kLmMaxCams - 1);
+    if (n < 0) return fail(VELO_ERR_INVALID, "negative count");
+    if (n > 0 && !rows) return fail(VELO_ERR_INVALID, "null descriptor rows");
+    if (n > kMatchMaxRows) return fail(VELO_ERR_INVALID, "%d descriptor rows; the match key indexes at most %d", n, kMatchMaxRows);
+    VELO_TRY(fr_need_store(c, "velo_frames_put_descriptors"));
+    FrStore& S = *c->fr;
+    const int64_t key = lm_key(frame, cam);
+    auto kp = S.dir.find(key);
+    if (kp == S.dir.end()) return fail(VELO_ERR_STATE, "frame %d, camera %d has not been put", frame, cam);
+    if (n != kp->second.n) return fail(VELO_ERR_INVALID, "%d descriptor rows for the %d keypoints of frame %d, camera %d", n, kp->second.n, frame, cam);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t need = (size_t)n;
+    auto old = S.rdir.find(key);
+    // where the block goes: as in velo_frames_put
+    FrStore::RowEntry e;
+    e.n = n;
+    int from_free = -1;
+    bool in_place = false;
+    if (old != S.rdir.end() && old->second.cap >= need) { e.off = old->second.off; e.cap = old->second.cap; in_place = true; }
+    else if (need == 0) { in_place = true; }                         // an empty entry owns no block
+    else {
+        for (size_t k = 0; k < S.r_free.size() && from_free < 0; k++) if (S.r_free[k].second >= need) from_free = (int)k;
+        if (from_free >= 0) { e.off = S.r_free[(size_t)from_free].first; e.cap = S.r_free[(size_t)from_free].second; }
+        else {
+            if (S.r_used + need > S.r_cap) {
+                const size_t cap = std::max(S.r_used + need, 2 * S.r_cap);
+                VELO_TRY(lm_regrow(c, &S.rows, 4 * S.r_used, 4 * cap, 0));
+                S.r_cap = cap;
+                S.r_reallocs++;
+            }
+            e.off = S.r_used; e.cap = need;
+        }
+    }
+    if (n > 0) {
+        const int k = S.rows_k;
+        VELO_TRY(fr_event_wait(&S.rows_ev[k]));
+        VELO_TRY(match_pinned((void**)&S.h_rows[k], &S.h_rows_cap[k], 64 * need));
+        std::memcpy(S.h_rows[k], rows, 64 * need);
+        HIP_TRY(hipMemcpyAsync(S.rows.p + 4 * e.off, S.h_rows[k], 64 * need, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipEventRecord(S.rows_ev[k], c->stream));
+        S.rows_k = k ^ 1;
+    }
+    // the directory after the last call that can fail
+    if (!in_place) {
+        if (from_free >= 0) S.r_free.erase(S.r_free.begin() + from_free);
+        else S.r_used += need;
+        if (old != S.rdir.end() && old->second.cap > 0) S.r_free.push_back(std::make_pair(old->second.off, old->second.cap));
+    }
+    S.rdir[key] = e;
+    return VELO_OK;
+}
+
+int velo_frames_desc_info(velo_ctx* c, int32_t* info) {
+    if (!c || !info) return fail(VELO_ERR_INVALID, "null argument");
+    VELO_TRY(fr_need_store(c, "velo_frames_desc_info"));
+    const FrStore& S = *c->fr;
+    info[0] = (int32_t)S.rdir.size(); info[1] = (int32_t)std::min<size_t>(S.r_cap * 64, 0x7fffffff); info[2] = S.r_reallocs;
+    info[3] = (int32_t)S.r_free.size();
     return VELO_OK;
 }
 
@@ -372,6 +618,42 @@ int velo_build_matches(velo_ctx* c, int32_t frame1, int32_t frame2, const double
                        int32_t capacity, int32_t* n_out) {
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
     return velo_build_matches_batch(&c, 1, &frame1, &frame2, pose2_inv16, n_per_cam, pairs_out, capacity, n_out);
+}
+
+int velo_build_matches_desc_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* frames1, const int32_t* frames2, const double* pose2_inv,
+                                  double match_thresh, int32_t* n_per_cam, int32_t* pairs_out, int32_t capacity, int32_t* n_out) {
+    // every argument is checked before any context is touched
+    VELO_TRY(fb_check_list(ctxs, n_ctx));
+    if (!frames1 || !frames2) return fail(VELO_ERR_INVALID, "null frames");
+    if (!n_out) return fail(VELO_ERR_INVALID, "null n_out");
+    if (capacity < 0) return fail(VELO_ERR_INVALID, "negative capacity");
+    if (std::isnan(match_thresh)) return fail(VELO_ERR_INVALID, "match_thresh is NaN");
+    for (int i = 0; i < n_ctx; i++)
+        for (int f : {frames1[i], frames2[i]})
+            if (f < 0 || f >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "context %d: frame %d; 0..%d", i, f, kLmMaxFrame - 1);
+    if (pose2_inv)
+        for (int k = 0; k < 16 * n_ctx; k++) if (!std::isfinite(pose2_inv[k])) return fail(VELO_ERR_INVALID, "context %d: pose2_inv[%d] is not finite", k / 16, k % 16);
+    VELO_TRY(fb_check_devices(ctxs, n_ctx));
+    return fr_desc_run(ctxs, n_ctx, frames1, frames2, 0, true, pose2_inv, match_thresh, n_per_cam, pairs_out, capacity, n_out, nullptr, nullptr);
+}
+
+int velo_build_matches_desc(velo_ctx* c, int32_t frame1, int32_t frame2, const double* pose2_inv16, double match_thresh, int32_t* n_per_cam,
+                            int32_t* pairs_out, int32_t capacity, int32_t* n_out) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    return velo_build_matches_desc_batch(&c, 1, &frame1, &frame2, pose2_inv16, match_thresh, n_per_cam, pairs_out, capacity, n_out);
+}
+
+int velo_match_frames(velo_ctx* c, int32_t frame1, const int32_t* frames2, int32_t n_cand, double match_thresh, int32_t* n_kept,
+                      int32_t* min_dist) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (n_cand < 0) return fail(VELO_ERR_INVALID, "negative candidate count %d", n_cand);
+    if (std::isnan(match_thresh)) return fail(VELO_ERR_INVALID, "match_thresh is NaN");
+    if (frame1 < 0 || frame1 >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame1, kLmMaxFrame - 1);
+    if (n_cand == 0) return VELO_OK;
+    if (!frames2 || !n_kept || !min_dist) return fail(VELO_ERR_INVALID, "null frames2 / n_kept / min_dist");
+    for (int k = 0; k < n_cand; k++)
+        if (frames2[k] < 0 || frames2[k] >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "candidate %d: frame %d; 0..%d", k, frames2[k], kLmMaxFrame - 1);
+    return fr_desc_run(&c, 1, &frame1, frames2, n_cand, false, nullptr, match_thresh, nullptr, nullptr, 0, nullptr, n_kept, min_dist);
 }
 
 int velo_get_visual(velo_ctx* c, velo_match* out, int32_t capacity, int32_t* n) {

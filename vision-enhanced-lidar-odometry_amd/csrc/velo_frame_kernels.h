@@ -11,6 +11,11 @@
 //     fr_emit_kernel    a chunk's first record = the matches of the context's chunks before it (cameras in order, ind2 ascending); inside
 //                       the chunk a workgroup scan keeps ind2 order; every match writes its 68-byte record and its (point1, point2) pair
 //     fr_clear_kernel   walks frame1's ids again and sets their slots back to -1: no cost depends on the size of the id space
+//
+// The loop-closure edge (matchFeatures in place of matchUsingId, main.cpp:359) joins the two frames by their descriptor rows instead:
+// the match kernels (velo_match_kernels.h) leave every camera's kept (queryIdx, trainIdx) pairs in query order and their count, and
+//     fr_emit_desc_kernel   one thread per kept pair writes the same record; a record's position is the kept counts of the context's
+//                           earlier cameras plus the pair's rank in its camera, read from the filter's output (no counter, no atomics)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -84,6 +89,47 @@ fr_clear_kernel(const FrUnit* __restrict__ units)
 ;
 #endif
 
+// one camera of one context of a descriptor-matched call; unit u is match job u of the call
+struct FrDescUnit {
+    FrSide f1, f2;                     // f1 = the query side (the current frame), f2 = the train side
+    int ctx, cam;
+    int ctx_unit0;                     // the unit of this context's camera 0
+    int q_out;                         // first entry of this unit's job in the filter's per-query outputs
+    float t_cam[3];
+    int pad;
+};
+
+// the record of the match (ind1, ind2) of one camera (velo.h:630-654) and its pair, written at position pos of the context's visual set
+template <typename Unit>
+__device__ __forceinline__ void fr_write_record(const Unit& U, const FrCtx& C, int ind1, int ind2, int pos) {
+    const FrSide& f1 = U.f1;
+    const FrSide& f2 = U.f2;
+    static_assert(sizeof(VisualMatch) == 13 * sizeof(float) + 3 * sizeof(int) + 4, "no padding between the members: zeroing them zeroes the record");
+    VisualMatch m = {};                                               // every byte that is not written below is zero, pad included
+    const int id = f2.ids[ind2];
+    const int h1 = f1.has_depth[ind1], h2 = f2.has_depth[ind2];
+    bool d2 = h2 != -1;                                               // velo.h:631-632
+    if (C.lm_pts != nullptr && id < C.lm_ids && C.lm_added[id] != 0) {  // velo.h:634-644: landmarks_at_frame.count(id)
+        lm_move_point(C.lm_pts + 3 * (size_t)id, C.pose2_inv.m, m.p3_2);
+        d2 = true;
+    } else if (d2) {                                                  // velo.h:645-648
+        const float* p = f2.cloud + 3 * (size_t)h2;
+        m.p3_2[0] = p[0]; m.p3_2[1] = p[1]; m.p3_2[2] = p[2];
+    }
+    if (h1 != -1) {                                                   // velo.h:649-652
+        const float* p = f1.cloud + 3 * (size_t)h1;
+        m.p3_1[0] = p[0]; m.p3_1[1] = p[1]; m.p3_1[2] = p[2];
+    }
+    m.p2_1[0] = f1.xy[2 * (size_t)ind1]; m.p2_1[1] = f1.xy[2 * (size_t)ind1 + 1];     // velo.h:653-654
+    m.p2_2[0] = f2.xy[2 * (size_t)ind2]; m.p2_2[1] = f2.xy[2 * (size_t)ind2 + 1];
+    m.t_cam[0] = U.t_cam[0]; m.t_cam[1] = U.t_cam[1]; m.t_cam[2] = U.t_cam[2];
+    m.cam = U.cam; m.point1 = ind1; m.point2 = ind2;
+    m.d1 = h1 != -1 ? 1 : 0; m.d2 = d2 ? 1 : 0;
+    C.vm[pos] = m;
+    C.pairs[2 * (size_t)pos] = ind1;
+    C.pairs[2 * (size_t)pos + 1] = ind2;
+}
+
 // the index of frame1 that entry ind2 of frame2 matches, or -1 (velo.h:575-579)
 __device__ __forceinline__ int fr_lookup(const FrUnit& U, int ind2) {
     if (ind2 >= U.f2.n) return -1;
@@ -132,30 +178,27 @@ fr_emit_kernel(const FrUnit* __restrict__ units, const FrCtx* __restrict__ ctxs,
     int total;
     const int pos = base + block_exclusive_scan(ind1 >= 0 ? 1 : 0, &total);
     if (ind1 < 0) return;
-    static_assert(sizeof(VisualMatch) == 13 * sizeof(float) + 3 * sizeof(int) + 4, "no padding between the members: zeroing them zeroes the record");
-    VisualMatch m = {};                                               // every byte that is not written below is zero, pad included
-    const int id = U.f2.ids[ind2];
-    const int h1 = U.f1.has_depth[ind1], h2 = U.f2.has_depth[ind2];
-    bool d2 = h2 != -1;                                               // velo.h:631-632
-    if (C.lm_pts != nullptr && id < C.lm_ids && C.lm_added[id] != 0) {  // velo.h:634-644: landmarks_at_frame.count(id)
-        lm_move_point(C.lm_pts + 3 * (size_t)id, C.pose2_inv.m, m.p3_2);
-        d2 = true;
-    } else if (d2) {                                                  // velo.h:645-648
-        const float* p = U.f2.cloud + 3 * (size_t)h2;
-        m.p3_2[0] = p[0]; m.p3_2[1] = p[1]; m.p3_2[2] = p[2];
-    }
-    if (h1 != -1) {                                                   // velo.h:649-652
-        const float* p = U.f1.cloud + 3 * (size_t)h1;
-        m.p3_1[0] = p[0]; m.p3_1[1] = p[1]; m.p3_1[2] = p[2];
-    }
-    m.p2_1[0] = U.f1.xy[2 * (size_t)ind1]; m.p2_1[1] = U.f1.xy[2 * (size_t)ind1 + 1];     // velo.h:653-654
-    m.p2_2[0] = U.f2.xy[2 * (size_t)ind2]; m.p2_2[1] = U.f2.xy[2 * (size_t)ind2 + 1];
-    m.t_cam[0] = U.t_cam[0]; m.t_cam[1] = U.t_cam[1]; m.t_cam[2] = U.t_cam[2];
-    m.cam = U.cam; m.point1 = ind1; m.point2 = ind2;
-    m.d1 = h1 != -1 ? 1 : 0; m.d2 = d2 ? 1 : 0;
-    C.vm[pos] = m;
-    C.pairs[2 * (size_t)pos] = ind1;
-    C.pairs[2 * (size_t)pos + 1] = ind2;
+    fr_write_record(U, C, ind1, ind2, pos);
+}
+#else
+;
+#endif
+
+// job_out: the filter's per-job {min_dist, n_kept}; pairs: its kept (queryIdx, trainIdx) pairs, job j's from entry q_out
+__global__ void __launch_bounds__(256)
+fr_emit_desc_kernel(const FrDescUnit* __restrict__ units, const FrCtx* __restrict__ ctxs, const int* __restrict__ job_out,
+                    const int* __restrict__ pairs)
+#if VELO_DEF_FRAMES
+{
+    const int u = blockIdx.y;
+    const FrDescUnit& U = units[u];
+    const int kept = job_out[2 * u + 1];
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= kept) return;
+    int base = 0;                                                     // at most 7 earlier cameras, workgroup-uniform
+    for (int v = U.ctx_unit0; v < u; v++) base += job_out[2 * v + 1];
+    const int* pr = pairs + 2 * ((size_t)U.q_out + (size_t)k);
+    fr_write_record(U, ctxs[U.ctx], pr[0], pr[1], base + k);
 }
 #else
 ;

@@ -23,6 +23,10 @@
 // Diagnostics-build variant (match_valu_kernel, VELO_MATCH_VARIANT=0 in libvelo_hip_diag.so only): one query per lane, XOR + popcount
 // over 8 x u64 against train rows staged in LDS.  Same keys, same result bit for bit (tests/test_gpu_match.py).
 //
+// Resident rows (match_mfma_resident_kernel, match_filter_resident_kernel): the same two bodies for jobs whose rows already live on
+// the device, in the row arenas of one or several contexts' frame stores (velo_api_frames.inl) -- a job names each side by its base
+// pointer, nothing is staged.  The product kernel only: the diagnostics variant is not wired to them.
+//
 // match_filter_kernel: one workgroup per job applies velo.h:536-549 -- keep iff distance <= max(1.5 min_dist, match_thresh), in double
 // like the reference -- and writes the kept (queryIdx, trainIdx) pairs in query order with a workgroup exclusive scan.
 #pragma once
@@ -54,8 +58,19 @@ struct MatchJob {        // one (query, train) pair of a call, as the kernels se
     int pad;
 };
 
+struct MatchResJob {     // one (query, train) pair on resident rows: every member but the two pointers means what it means in MatchJob
+    const uint4* q;      // first row of the query / train set (64 bytes each, 64-byte aligned), in whatever arena holds it
+    const uint4* t;
+    int n_query, n_train;
+    int q_out;
+    int blk_start;
+    int nqb;
+    int pad;
+};
+
 // the job that owns block b: the last job whose blk_start <= b (jobs without blocks share their start with the next job)
-__device__ __forceinline__ int match_job_of_block(const MatchJob* __restrict__ jobs, int n_jobs, int b) {
+template <typename Job>
+__device__ __forceinline__ int match_job_of_block(const Job* __restrict__ jobs, int n_jobs, int b) {
     int lo = 0, hi = n_jobs;                 // first job with blk_start > b
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
@@ -92,33 +107,26 @@ __device__ __forceinline__ unsigned match_wave_min(unsigned v) {
 }
 
 // ---- product: int8 MFMA on +-1 bits ----------------------------------------------------------------------------------------------
-// rows: the staged descriptor rows as uint4 (4 per row); keys [sum n_query] and min_dist [n_jobs] start at kMatchNone
-__global__ void __launch_bounds__(kMatchThreads)
-match_mfma_kernel(const uint4* __restrict__ rows, const MatchJob* __restrict__ jobs, int n_jobs, unsigned* __restrict__ keys,
-                  unsigned* __restrict__ min_dist)
-#if VELO_DEF_MATCH
-{
+// One block of job j: 64 queries from q0 against the train rows [t_begin, t_begin + kMatchT).  q_rows / t_rows: the job's first query /
+// train row; key_out: the job's first key.  The arithmetic of both product kernels.
+__device__ __forceinline__ void match_mfma_block(const uint4* __restrict__ q_rows, const uint4* __restrict__ t_rows, int n_query, int n_train,
+                                                 int q0, int t_begin, unsigned* __restrict__ key_out, unsigned* __restrict__ job_min) {
     __shared__ unsigned red[kMatchThreads / 64][kMatchQ];
-    const int j = match_job_of_block(jobs, n_jobs, (int)blockIdx.x);
-    const MatchJob J = jobs[j];
-    const int local = (int)blockIdx.x - J.blk_start;
-    const int q0 = (local % J.nqb) * kMatchQ;
-    const int t_begin = (local / J.nqb) * kMatchT;
-    const int t_end = min(t_begin + kMatchT, J.n_train);
+    const int t_end = min(t_begin + kMatchT, n_train);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, g = lane >> 4;
 
     match_v4i B[4][8];                                      // the block's 64 queries, +-1 bytes (128 VGPRs)
 #pragma unroll
     for (int qt = 0; qt < 4; qt++) {
-        const int q = min(q0 + qt * 16 + r, J.n_query - 1);   // rows past the set repeat the last one; their columns are never stored
-        const uint4 c = rows[((size_t)J.q_row + q) * 4 + g];
+        const int q = min(q0 + qt * 16 + r, n_query - 1);     // rows past the set repeat the last one; their columns are never stored
+        const uint4 c = q_rows[(size_t)q * 4 + g];
 #pragma unroll
         for (int s = 0; s < 8; s++) B[qt][s] = match_expand(c, s);
     }
     unsigned best[4] = {kMatchNone, kMatchNone, kMatchNone, kMatchNone};   // query q0 + 16 qt + (lane & 15): min key over this lane's train rows
     for (int t = t_begin + wave * 16; t < t_end; t += 16 * (kMatchThreads / 64)) {
-        const uint4 c = rows[((size_t)J.t_row + min(t + r, J.n_train - 1)) * 4 + g];
+        const uint4 c = t_rows[(size_t)min(t + r, n_train - 1) * 4 + g];
         match_v4i acc[4];
 #pragma unroll
         for (int qt = 0; qt < 4; qt++) acc[qt] = match_v4i{0, 0, 0, 0};
@@ -152,11 +160,38 @@ match_mfma_kernel(const uint4* __restrict__ rows, const MatchJob* __restrict__ j
 #pragma unroll
         for (int w = 1; w < kMatchThreads / 64; w++) v = min(v, red[w][lane]);
         const int q = q0 + lane;
-        if (q >= J.n_query) v = kMatchNone;
-        if (v != kMatchNone) atomicMin(&keys[J.q_out + q], v);
+        if (q >= n_query) v = kMatchNone;
+        if (v != kMatchNone) atomicMin(&key_out[q], v);
         const unsigned m = match_wave_min(v);
-        if (lane == 0 && m != kMatchNone) atomicMin(&min_dist[j], m >> kMatchIdxBits);
+        if (lane == 0 && m != kMatchNone) atomicMin(job_min, m >> kMatchIdxBits);
     }
+}
+
+// rows: the staged descriptor rows as uint4 (4 per row); keys [sum n_query] and min_dist [n_jobs] start at kMatchNone
+__global__ void __launch_bounds__(kMatchThreads)
+match_mfma_kernel(const uint4* __restrict__ rows, const MatchJob* __restrict__ jobs, int n_jobs, unsigned* __restrict__ keys,
+                  unsigned* __restrict__ min_dist)
+#if VELO_DEF_MATCH
+{
+    const int j = match_job_of_block(jobs, n_jobs, (int)blockIdx.x);
+    const MatchJob J = jobs[j];
+    const int local = (int)blockIdx.x - J.blk_start;
+    match_mfma_block(rows + (size_t)J.q_row * 4, rows + (size_t)J.t_row * 4, J.n_query, J.n_train, (local % J.nqb) * kMatchQ,
+                     (local / J.nqb) * kMatchT, keys + J.q_out, min_dist + j);
+}
+#else
+;
+#endif
+
+// the same on resident rows: every job brings its own two base pointers (a batch names several contexts' arenas)
+__global__ void __launch_bounds__(kMatchThreads)
+match_mfma_resident_kernel(const MatchResJob* __restrict__ jobs, int n_jobs, unsigned* __restrict__ keys, unsigned* __restrict__ min_dist)
+#if VELO_DEF_MATCH
+{
+    const int j = match_job_of_block(jobs, n_jobs, (int)blockIdx.x);
+    const MatchResJob J = jobs[j];
+    const int local = (int)blockIdx.x - J.blk_start;
+    match_mfma_block(J.q, J.t, J.n_query, J.n_train, (local % J.nqb) * kMatchQ, (local / J.nqb) * kMatchT, keys + J.q_out, min_dist + j);
 }
 #else
 ;
@@ -208,37 +243,32 @@ match_valu_kernel(const uint4* __restrict__ rows, const MatchJob* __restrict__ j
 
 // ---- velo.h:536-549: threshold and compaction, one workgroup per job ------------------------------------------------------------
 // out: idx [sum n_query] | dist [sum n_query] | pairs [sum n_query][2] (job j's kept pairs from entry q_out) | per job {min_dist, n_kept}
-__global__ void __launch_bounds__(kMatchThreads)
-match_filter_kernel(const MatchJob* __restrict__ jobs, const unsigned* __restrict__ keys, const unsigned* __restrict__ min_dist,
-                    double match_thresh, int total_q, int* __restrict__ out)
-#if VELO_DEF_MATCH
-{
+__device__ __forceinline__ void match_filter_job(int j, int n_query, int n_train, int q_out, const unsigned* __restrict__ keys,
+                                                 const unsigned* __restrict__ min_dist, double match_thresh, int total_q, int* __restrict__ out) {
     __shared__ int wsum[kMatchThreads / 64];
-    const int j = blockIdx.x;
-    const MatchJob J = jobs[j];
     int* o_idx = out;
     int* o_dist = out + total_q;
     int* o_pairs = out + 2 * (size_t)total_q;
     int* o_job = out + 4 * (size_t)total_q;
-    const bool any = J.n_train > 0 && J.n_query > 0;
+    const bool any = n_train > 0 && n_query > 0;
     const unsigned md = any ? min_dist[j] : 0u;
     const double thr = fmax(1.5 * (double)md, match_thresh);     // std::max(1.5*min_dist, match_thresh), velo.h:546
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int base = 0;
-    for (int c0 = 0; c0 < J.n_query; c0 += kMatchThreads) {
+    for (int c0 = 0; c0 < n_query; c0 += kMatchThreads) {
         const int q = c0 + (int)threadIdx.x;
         bool keep = false;
         int t = -1;
-        if (q < J.n_query) {
+        if (q < n_query) {
             int d = -1;
             if (any) {
-                const unsigned k = keys[J.q_out + q];
+                const unsigned k = keys[q_out + q];
                 t = (int)(k & kMatchIdxMask);
                 d = (int)(k >> kMatchIdxBits);
                 keep = !((double)d > thr);                          // velo.h:546: `continue` when distance > max(...)
             }
-            o_idx[J.q_out + q] = t;
-            o_dist[J.q_out + q] = d;
+            o_idx[q_out + q] = t;
+            o_dist[q_out + q] = d;
         }
         const uint64_t bal = __ballot(keep);
         const int rank = (int)__popcll(bal & ((1ull << lane) - 1ull));
@@ -248,7 +278,7 @@ match_filter_kernel(const MatchJob* __restrict__ jobs, const unsigned* __restric
 #pragma unroll
         for (int w = 0; w < kMatchThreads / 64; w++) { const int s = wsum[w]; if (w < wave) pre += s; tot += s; }
         if (keep) {
-            const size_t e = (size_t)J.q_out + base + pre + rank;
+            const size_t e = (size_t)q_out + base + pre + rank;
             o_pairs[2 * e] = q;
             o_pairs[2 * e + 1] = t;
         }
@@ -259,6 +289,27 @@ match_filter_kernel(const MatchJob* __restrict__ jobs, const unsigned* __restric
         o_job[2 * j] = any ? (int)md : -1;
         o_job[2 * j + 1] = base;
     }
+}
+
+__global__ void __launch_bounds__(kMatchThreads)
+match_filter_kernel(const MatchJob* __restrict__ jobs, const unsigned* __restrict__ keys, const unsigned* __restrict__ min_dist,
+                    double match_thresh, int total_q, int* __restrict__ out)
+#if VELO_DEF_MATCH
+{
+    const MatchJob J = jobs[blockIdx.x];
+    match_filter_job((int)blockIdx.x, J.n_query, J.n_train, J.q_out, keys, min_dist, match_thresh, total_q, out);
+}
+#else
+;
+#endif
+
+__global__ void __launch_bounds__(kMatchThreads)
+match_filter_resident_kernel(const MatchResJob* __restrict__ jobs, const unsigned* __restrict__ keys, const unsigned* __restrict__ min_dist,
+                             double match_thresh, int total_q, int* __restrict__ out)
+#if VELO_DEF_MATCH
+{
+    const MatchResJob& J = jobs[blockIdx.x];
+    match_filter_job((int)blockIdx.x, J.n_query, J.n_train, J.q_out, keys, min_dist, match_thresh, total_q, out);
 }
 #else
 ;
