@@ -186,20 +186,13 @@ int velo_destroy(velo_ctx* c) {
     if (c->h_x) (void)hipHostFree(c->h_x);
     if (c->h_int) (void)hipHostFree(c->h_int);
     c->md_in.release(); c->md_keys.release(); c->md_out.release();
-    if (c->h_md_in) (void)hipHostFree(c->h_md_in);
-    if (c->h_md_out) (void)hipHostFree(c->h_md_out);
     for (auto& sl : c->lk_slot) { sl.pix.release(); sl.der.release(); }
     c->lk_raw.release(); c->lk_in.release(); c->lk_out.release(); c->lk_diag.release();
     if (c->lk_upload_ev) (void)hipEventDestroy(c->lk_upload_ev);
     if (c->fb_here_ev) (void)hipEventDestroy(c->fb_here_ev);
     if (c->fb_done_ev) (void)hipEventDestroy(c->fb_done_ev);
-    if (c->h_lk_raw) (void)hipHostFree(c->h_lk_raw);
-    if (c->h_lk_in) (void)hipHostFree(c->h_lk_in);
-    if (c->h_lk_out) (void)hipHostFree(c->h_lk_out);
     c->gf_eig.release(); c->gf_state.release(); c->gf_cand.release(); c->gf_keys.release(); c->gf_hdr.release();
     c->gf_in.release(); c->gf_out.release();
-    if (c->h_gf_in) (void)hipHostFree(c->h_gf_in);
-    if (c->h_gf_out) (void)hipHostFree(c->h_gf_out);
     for (auto& ps : c->pin) { if (ps.ev) (void)hipEventDestroy(ps.ev); if (ps.p) (void)hipHostFree(ps.p); }
     if (c->src_bbox_ev) (void)hipEventDestroy(c->src_bbox_ev);
     if (c->ev0) (void)hipEventDestroy(c->ev0);

@@ -87,12 +87,12 @@ int gf_run(velo_ctx** ctxs, int n_ctx, const std::vector<GfUnitRef>& units, int 
     const size_t cnt_bytes = fb_align64(sizeof(int) * 3 * (size_t)nj);
     const size_t n_slots = (size_t)nj * cap_d;
     const size_t out_bytes = cnt_bytes + n_slots * (sizeof(float2) + sizeof(float) + 1);
-    VELO_TRY(match_pinned((void**)&c->h_gf_in, &c->h_gf_in_cap, in_bytes));
-    VELO_TRY(match_pinned((void**)&c->h_gf_out, &c->h_gf_out_cap, out_bytes));
+    VELO_TRY(c->h_gf_in.reserve(in_bytes));
+    VELO_TRY(c->h_gf_out.reserve(out_bytes));
     VELO_TRY(c->gf_in.reserve(in_bytes));
     VELO_TRY(c->gf_out.reserve(out_bytes));
     {
-        GfUnit* hu = (GfUnit*)c->h_gf_in;
+        GfUnit* hu = (GfUnit*)c->h_gf_in.p;
         for (int u = 0; u < nu; u++) {
             const LkSlot& S = *lk_slot(ctxs[units[u0 + u].ctx], false);
             GfUnit& U = hu[u];
@@ -105,8 +105,8 @@ int gf_run(velo_ctx** ctxs, int n_ctx, const std::vector<GfUnitRef>& units, int 
             U.hdr = c->gf_hdr.p + (size_t)u * kGfHdrStride;
             U.w = S.w; U.h = S.h; U.stride = S.pyr.lv[0].stride; U.sstride = sstride[u];
         }
-        GfJob* hj = (GfJob*)(c->h_gf_in + unit_bytes);
-        float* hp = (float*)(c->h_gf_in + unit_bytes + job_bytes);
+        GfJob* hj = (GfJob*)(c->h_gf_in.p + unit_bytes);
+        float* hp = (float*)(c->h_gf_in.p + unit_bytes + job_bytes);
         int first = 0;
         for (int k = 0; k < nj; k++) {
             const velo_detect_job& J = jobs[sel[k]];
@@ -118,7 +118,7 @@ int gf_run(velo_ctx** ctxs, int n_ctx, const std::vector<GfUnitRef>& units, int 
     std::vector<char> used(n_ctx, 0);
     for (int u = 0; u < nu; u++) used[units[u0 + u].ctx] = 1;
     VELO_TRY(fb_gather(ctxs, n_ctx, &used));
-    HIP_TRY(hipMemcpyAsync(c->gf_in.p, c->h_gf_in, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->gf_in.p, c->h_gf_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->gf_hdr.p, 0, sizeof(int) * kGfHdrStride * (size_t)nu, c->stream));
     HIP_TRY(hipMemsetAsync(c->gf_state.p, 0, t_state, c->stream));                          // the zero border of the state maps
     HIP_TRY(hipMemsetAsync(c->gf_out.p, 0, cnt_bytes, c->stream));
@@ -136,11 +136,11 @@ int gf_run(velo_ctx** ctxs, int n_ctx, const std::vector<GfUnitRef>& units, int 
     hipLaunchKernelGGL(gf_output_kernel, dim3(kGfOutBlocks, (unsigned)nj), dim3(256), 0, c->stream, d_units, K, (const GfJob*)(c->gf_in.p + unit_bytes),
                        (const float2*)(c->gf_in.p + unit_bytes + job_bytes), d_counts, d_xy, d_resp, d_fresh);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_gf_out, c->gf_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_gf_out.p, c->gf_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->gf_units = nu;
-    const int* h_counts = (const int*)c->h_gf_out;
-    const unsigned char* h_xy = c->h_gf_out + cnt_bytes;
+    const int* h_counts = (const int*)c->h_gf_out.p;
+    const unsigned char* h_xy = c->h_gf_out.p + cnt_bytes;
     const unsigned char* h_resp = h_xy + n_slots * sizeof(float2);
     const unsigned char* h_fresh = h_resp + n_slots * sizeof(float);
     for (int k = 0; k < nj; k++) {
@@ -224,9 +224,9 @@ int velo_get_corner_response(velo_ctx* c, int32_t cam, float* out, int64_t capac
     // a table of one unit whose only live fields are the image, the map and the header (the response kernel reads nothing else)
     VELO_TRY(c->gf_eig.reserve((size_t)S.w * S.h));
     VELO_TRY(c->gf_hdr.reserve(kGfHdrStride));
-    VELO_TRY(match_pinned((void**)&c->h_gf_in, &c->h_gf_in_cap, sizeof(GfUnit)));
+    VELO_TRY(c->h_gf_in.reserve(sizeof(GfUnit)));
     VELO_TRY(c->gf_in.reserve(sizeof(GfUnit)));
-    GfUnit& U = *(GfUnit*)c->h_gf_in;
+    GfUnit& U = *(GfUnit*)c->h_gf_in.p;
     std::memset(&U, 0, sizeof(U));
     U.plane = S.pix.p + (size_t)cam * S.cam_pix + S.pyr.lv[0].off;
     U.eig = c->gf_eig.p;
@@ -235,7 +235,7 @@ int velo_get_corner_response(velo_ctx* c, int32_t cam, float* out, int64_t capac
     GfParams K;
     std::memset(&K, 0, sizeof(K));
     K.scale2 = gf_scale2();
-    HIP_TRY(hipMemcpyAsync(c->gf_in.p, c->h_gf_in, sizeof(GfUnit), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->gf_in.p, c->h_gf_in.p, sizeof(GfUnit), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->gf_hdr.p, 0, sizeof(int) * kGfHdrStride, c->stream));
     c->gf_units = 1;
     hipLaunchKernelGGL(gf_response_kernel, dim3((unsigned)cdiv(S.w, kGfTile), (unsigned)cdiv(S.h, kGfTile), 1), dim3(kGfTile * kGfTile), 0, c->stream,

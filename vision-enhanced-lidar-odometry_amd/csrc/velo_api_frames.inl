@@ -13,47 +13,44 @@
 // arena growth (velo_frames_info shows it), never with wrong results.
 // The descriptor rows of a (frame, camera) live in a second arena of 64-byte rows with a directory and a free list of its own, under
 // the same rules; the keypoint arena does not know of it.
+
+// Both arenas are an FrArena: the device buffer with its bookkeeping (velo_block_list.h), in words (the caller rounds to 16) or rows of four uint4.
+template <typename T, size_t Per>                    // Per elements of T to a unit
+struct FrArena {
+    DevBuf<T> buf;
+    BlockList list;
+    T* at(const Block& b) const { return buf.p + Per * b.off; }
+    // where an entry of `need` units goes (old: the block it holds now, or null); the arena has grown if the plan asked for it, and
+    // nothing else of the bookkeeping has changed: list.commit(plan, old) follows the last call that can fail
+    int place(velo_ctx* c, const Block* old, size_t need, BlockList::Plan* plan) {
+        *plan = list.plan(old, need);
+        if (plan->grow_to > 0) {
+            VELO_TRY(lm_regrow(c, &buf, Per * list.used, Per * plan->grow_to, 0));
+            list.grew(*plan);
+        }
+        return VELO_OK;
+    }
+};
+
 struct FrStore {
     int n_cams = 0;
     float cam_t[3 * 8] = {};
     // device
-    DevBuf<int> arena;
-    size_t used = 0, cap = 0;                       // words handed out from the front / words before the arena reallocates
-    int reallocs = 0;
+    FrArena<int, 1> kp;                             // the keypoint arrays; every block starts on a 64-byte line
     DevBuf<int> slots;                              // n_cams tables of slot_ids entries, all -1 between calls
     size_t slot_ids = 0;
     bool slots_dirty = false;                       // a call failed between the fill and the clear launch: refill before the next one
-    // host
-    struct Entry { size_t off = 0, cap = 0; int n = 0, n_wd = 0, max_id = -1; };
-    std::unordered_map<int64_t, Entry> dir;         // frame * 8 + cam
-    std::vector<std::pair<size_t, size_t>> free_blocks;   // {offset, words} of dropped and outgrown blocks
-    // the descriptor rows: device arena, then host directory (frame * 8 + cam -> block) and free list, all counted in rows
-    DevBuf<uint4> rows;                             // 4 per row; every block starts on a 64-byte line
-    size_t r_used = 0, r_cap = 0;
-    int r_reallocs = 0;
-    struct RowEntry { size_t off = 0, cap = 0; int n = 0; };
-    std::unordered_map<int64_t, RowEntry> rdir;
-    std::vector<std::pair<size_t, size_t>> r_free;
-    unsigned char* h_rows[2] = {nullptr, nullptr};  // staging of velo_frames_put_descriptors, as h_put below
-    size_t h_rows_cap[2] = {0, 0};
-    hipEvent_t rows_ev[2] = {nullptr, nullptr};
-    int rows_k = 0;
+    FrArena<uint4, 4> rows;                         // the descriptor rows, 64 bytes each
     DevBuf<unsigned> d_keys;                        // nearest-row keys and min_dist of a descriptor-matched call
-    // staging of velo_frames_put: two pinned slots used alternately, so that a put waits only for the upload before the previous one
-    unsigned char* h_put[2] = {nullptr, nullptr};
-    size_t h_put_cap[2] = {0, 0};
-    hipEvent_t put_ev[2] = {nullptr, nullptr};
-    int put_k = 0;
+    // host: the directories, frame * 8 + cam -> block
+    struct Entry { Block blk; int n = 0, n_wd = 0, max_id = -1; };
+    std::unordered_map<int64_t, Entry> dir;
+    struct RowEntry { Block blk; int n = 0; };
+    std::unordered_map<int64_t, RowEntry> rdir;
+    PinStage put_stage, rows_stage;                 // staging of velo_frames_put and of velo_frames_put_descriptors
     // staging of velo_build_matches (a batch call uses the first context's); every call ends in a synchronisation, so nothing guards it
-    unsigned char* h_in = nullptr; size_t h_in_cap = 0;
-    unsigned char* h_out = nullptr; size_t h_out_cap = 0;
+    PinBuf<> h_in, h_out;
     DevBuf<unsigned char> d_in, d_out;
-    ~FrStore() {
-        for (int k = 0; k < 2; k++) { if (h_put[k]) (void)hipHostFree(h_put[k]); if (put_ev[k]) (void)hipEventDestroy(put_ev[k]); }
-        for (int k = 0; k < 2; k++) { if (h_rows[k]) (void)hipHostFree(h_rows[k]); if (rows_ev[k]) (void)hipEventDestroy(rows_ev[k]); }
-        if (h_in) (void)hipHostFree(h_in);
-        if (h_out) (void)hipHostFree(h_out);
-    }
 };
 
 namespace {
@@ -69,14 +66,8 @@ int fr_need_store(velo_ctx* c, const char* who) {
     return VELO_OK;
 }
 
-int fr_event_wait(hipEvent_t* ev) {
-    if (*ev) HIP_TRY(hipEventSynchronize(*ev));
-    else HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-    return VELO_OK;
-}
-
 void fr_side(const FrStore& S, const FrStore::Entry& e, FrSide* out) {
-    const int* b = S.arena.p + e.off;
+    const int* b = S.kp.at(e.blk);
     out->ids = b;
     out->has_depth = b + e.n;
     out->xy = reinterpret_cast<const float*>(b + 2 * (size_t)e.n);
@@ -109,6 +100,48 @@ void fr_leave_visual(velo_ctx* c, int i, const int* per_cam, const int* pairs, i
     n_out[i] = total;
     const int w = std::min(total, (int)capacity);
     if (pairs_out && w > 0) std::memcpy(pairs_out + 2 * (size_t)i * capacity, pairs, sizeof(int32_t) * 2 * (size_t)w);
+}
+
+// room for a visual set of n records on context c
+int fr_reserve_visual(velo_ctx* c, size_t n) {
+    // records of an earlier velo_register_batch_visual may still be on their way into vm (set_visual_impl without a wait)
+    if (c->pin[3].pending) { HIP_TRY(hipEventSynchronize(c->pin[3].ev)); c->pin[3].pending = false; }
+    if (n > 0) {
+        VELO_TRY(c->vm.reserve(n));
+        VELO_TRY(c->vflags.reserve(3 * n));
+    }
+    return VELO_OK;
+}
+
+// context i of a call: where its records and their pairs go, and what the landmark substitution reads
+void fr_fill_ctx(const velo_ctx* c, int i, int* d_pairs, const double* pose2_inv, FrCtx* K) {
+    K->vm = c->vm.p;
+    K->pairs = d_pairs;
+    if (pose2_inv && c->lm && c->lm->n_ids > 0) {
+        K->lm_pts = c->lm->pts.p; K->lm_added = c->lm->added.p; K->lm_ids = (int)c->lm->n_ids;
+        std::memcpy(K->pose2_inv.m, pose2_inv + 16 * (size_t)i, sizeof(K->pose2_inv.m));
+    }
+}
+
+int fr_clear_vflags(velo_ctx* c, size_t n, hipStream_t st) {
+    if (n > 0) HIP_TRY(hipMemsetAsync(c->vflags.p, 0, 3 * n, st));
+    return VELO_OK;
+}
+
+// what velo_build_matches_batch and velo_build_matches_desc_batch (match_thresh: its threshold, else null) check before any context is touched
+int fr_check_build_args(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32_t* frames2, const double* pose2_inv,
+                        const double* match_thresh, int32_t capacity, const int32_t* n_out) {
+    VELO_TRY(fb_check_list(ctxs, n_ctx));
+    if (!frames1 || !frames2) return fail(VELO_ERR_INVALID, "null frames");
+    if (!n_out) return fail(VELO_ERR_INVALID, "null n_out");
+    if (capacity < 0) return fail(VELO_ERR_INVALID, "negative capacity");
+    if (match_thresh && std::isnan(*match_thresh)) return fail(VELO_ERR_INVALID, "match_thresh is NaN");
+    for (int i = 0; i < n_ctx; i++)
+        for (int f : {frames1[i], frames2[i]})
+            if (f < 0 || f >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "context %d: frame %d; 0..%d", i, f, kLmMaxFrame - 1);
+    if (pose2_inv)
+        for (int k = 0; k < 16 * n_ctx; k++) if (!std::isfinite(pose2_inv[k])) return fail(VELO_ERR_INVALID, "context %d: pose2_inv[%d] is not finite", k / 16, k % 16);
+    return fb_check_devices(ctxs, n_ctx);
 }
 
 int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32_t* frames2, const double* pose2_inv, int32_t* n_per_cam,
@@ -162,28 +195,22 @@ int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32
             S.slots_dirty = true;                                    // uninitialised until this call's fill is queued and the call ends well
         }
         if (S.slots_dirty) refill[i] = 1;
-        const size_t n2 = pair0[i + 1] - pair0[i];
-        // records of an earlier velo_register_batch_visual may still be on their way into vm (set_visual_impl without a wait)
-        if (c->pin[3].pending) { HIP_TRY(hipEventSynchronize(c->pin[3].ev)); c->pin[3].pending = false; }
-        if (n2 > 0) {
-            VELO_TRY(c->vm.reserve(n2));
-            VELO_TRY(c->vflags.reserve(3 * n2));
-        }
+        VELO_TRY(fr_reserve_visual(c, pair0[i + 1] - pair0[i]));
     }
     const size_t unit_bytes = fb_align64(sizeof(FrUnit) * (size_t)n_units);
     const size_t in_bytes = unit_bytes + sizeof(FrCtx) * (size_t)n_ctx;
     const size_t cnt_bytes = fb_align64(sizeof(int) * (size_t)n_chunks);
     const size_t out_bytes = cnt_bytes + sizeof(int) * 2 * all_n2;
-    VELO_TRY(match_pinned((void**)&L->h_in, &L->h_in_cap, in_bytes));
-    VELO_TRY(match_pinned((void**)&L->h_out, &L->h_out_cap, std::max<size_t>(out_bytes, 64)));
+    VELO_TRY(L->h_in.reserve(in_bytes));
+    VELO_TRY(L->h_out.reserve(std::max<size_t>(out_bytes, 64)));
     VELO_TRY(L->d_in.reserve(in_bytes));
     VELO_TRY(L->d_out.reserve(std::max<size_t>(out_bytes, 64)));
     int* d_counts = (int*)L->d_out.p;
     int* d_pairs = (int*)(L->d_out.p + cnt_bytes);
     {
-        FrUnit* hu = (FrUnit*)L->h_in;
-        FrCtx* hc = (FrCtx*)(L->h_in + unit_bytes);
-        std::memset(L->h_in, 0, in_bytes);
+        FrUnit* hu = (FrUnit*)L->h_in.p;
+        FrCtx* hc = (FrCtx*)(L->h_in.p + unit_bytes);
+        std::memset(L->h_in.p, 0, in_bytes);
         for (int i = 0; i < n_ctx; i++) {
             velo_ctx* c = ctxs[i];
             const FrStore& S = *c->fr;
@@ -198,13 +225,7 @@ int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32
                 U.ctx_chunk0 = chunk0[(size_t)unit0[i]];
                 for (int k = 0; k < 3; k++) U.t_cam[k] = S.cam_t[3 * cam + k];
             }
-            FrCtx& K = hc[i];
-            K.vm = c->vm.p;
-            K.pairs = d_pairs + 2 * pair0[i];
-            if (pose2_inv && c->lm && c->lm->n_ids > 0) {
-                K.lm_pts = c->lm->pts.p; K.lm_added = c->lm->added.p; K.lm_ids = (int)c->lm->n_ids;
-                std::memcpy(K.pose2_inv.m, pose2_inv + 16 * (size_t)i, sizeof(K.pose2_inv.m));
-            }
+            fr_fill_ctx(c, i, d_pairs + 2 * pair0[i], pose2_inv, &hc[i]);
         }
     }
     VELO_TRY(fb_gather(ctxs, n_ctx, nullptr));
@@ -213,10 +234,9 @@ int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32
         FrStore& S = *ctxs[i]->fr;
         if (refill[i] && S.slot_ids > 0) HIP_TRY(hipMemsetAsync(S.slots.p, 0xFF, sizeof(int) * S.slot_ids * (size_t)S.n_cams, st));
         S.slots_dirty = true;                                        // until the clear launch is known to have run
-        const size_t n2 = pair0[i + 1] - pair0[i];
-        if (n2 > 0) HIP_TRY(hipMemsetAsync(ctxs[i]->vflags.p, 0, 3 * n2, st));
+        VELO_TRY(fr_clear_vflags(ctxs[i], pair0[i + 1] - pair0[i], st));
     }
-    HIP_TRY(hipMemcpyAsync(L->d_in.p, L->h_in, in_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(L->d_in.p, L->h_in.p, in_bytes, hipMemcpyHostToDevice, st));
     const FrUnit* d_units = (const FrUnit*)L->d_in.p;
     const FrCtx* d_ctxs = (const FrCtx*)(L->d_in.p + unit_bytes);
     if (n_chunks > 0) {
@@ -226,11 +246,11 @@ int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32
         hipLaunchKernelGGL(fr_emit_kernel, g2, dim3(kFrChunk), 0, st, d_units, d_ctxs, (const int*)d_counts);
         if (max_n1 > 0) hipLaunchKernelGGL(fr_clear_kernel, g1, dim3(256), 0, st, d_units);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(L->h_out, L->d_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(L->h_out.p, L->d_out.p, out_bytes, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
-    const int* h_counts = (const int*)L->h_out;
-    const int* h_pairs = (const int*)(L->h_out + cnt_bytes);
+    const int* h_counts = (const int*)L->h_out.p;
+    const int* h_pairs = (const int*)(L->h_out.p + cnt_bytes);
     for (int i = 0; i < n_ctx; i++) {
         FrStore& S = *ctxs[i]->fr;
         S.slots_dirty = false;
@@ -248,7 +268,7 @@ int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32
 void fr_free_rows(FrStore& S, int64_t key) {
     auto it = S.rdir.find(key);
     if (it == S.rdir.end()) return;
-    if (it->second.cap > 0) S.r_free.push_back(std::make_pair(it->second.off, it->second.cap));
+    S.rows.list.release(it->second.blk);
     S.rdir.erase(it);
 }
 
@@ -287,7 +307,7 @@ int fr_desc_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32_
                 const FrStore::RowEntry& r2 = S.rdir.at(lm_key(frames2[build ? i : k], cam));
                 MatchResJob M;
                 std::memset(&M, 0, sizeof(M));
-                M.q = S.rows.p + 4 * r1.off; M.t = S.rows.p + 4 * r2.off;
+                M.q = S.rows.at(r1.blk); M.t = S.rows.at(r2.blk);
                 M.n_query = r1.n; M.n_train = r2.n;
                 M.q_out = (int)total_q;
                 M.blk_start = (int)blocks;
@@ -305,16 +325,7 @@ int fr_desc_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32_
     const int n_jobs = (int)jobs.size(), nq = (int)total_q;
     // room: the visual sets, the staging
     if (build)
-        for (int i = 0; i < n_ctx; i++) {
-            velo_ctx* c = ctxs[i];
-            const size_t n1 = pair0[i + 1] - pair0[i];
-            // records of an earlier velo_register_batch_visual may still be on their way into vm (set_visual_impl without a wait)
-            if (c->pin[3].pending) { HIP_TRY(hipEventSynchronize(c->pin[3].ev)); c->pin[3].pending = false; }
-            if (n1 > 0) {
-                VELO_TRY(c->vm.reserve(n1));
-                VELO_TRY(c->vflags.reserve(3 * n1));
-            }
-        }
+        for (int i = 0; i < n_ctx; i++) VELO_TRY(fr_reserve_visual(ctxs[i], pair0[i + 1] - pair0[i]));
     // device input: jobs | units | contexts; device output: the filter's four arrays | the records' pairs, context after context
     const size_t job_bytes = fb_align64(sizeof(MatchResJob) * (size_t)n_jobs);
     const size_t unit_bytes = build ? fb_align64(sizeof(FrDescUnit) * (size_t)n_jobs) : 0;
@@ -322,19 +333,19 @@ int fr_desc_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32_
     const size_t filt_ints = 4 * (size_t)nq + 2 * (size_t)n_jobs;
     const size_t back_ints = 2 * (size_t)n_jobs + (build ? 2 * (size_t)nq : 0);          // {min_dist, n_kept} per job | pairs: what comes back
     const size_t out_bytes = sizeof(int) * (filt_ints + (build ? 2 * (size_t)nq : 0));
-    VELO_TRY(match_pinned((void**)&L->h_in, &L->h_in_cap, in_bytes));
-    VELO_TRY(match_pinned((void**)&L->h_out, &L->h_out_cap, sizeof(int) * back_ints));
+    VELO_TRY(L->h_in.reserve(in_bytes));
+    VELO_TRY(L->h_out.reserve(sizeof(int) * back_ints));
     VELO_TRY(L->d_in.reserve(in_bytes));
     VELO_TRY(L->d_out.reserve(out_bytes));
     VELO_TRY(L->d_keys.reserve((size_t)nq + (size_t)n_jobs));
     int* d_filt = (int*)L->d_out.p;
     int* d_job_out = d_filt + 4 * (size_t)nq;
     int* d_pairs = d_filt + filt_ints;
-    std::memset(L->h_in, 0, in_bytes);
-    std::memcpy(L->h_in, jobs.data(), sizeof(MatchResJob) * (size_t)n_jobs);
+    std::memset(L->h_in.p, 0, in_bytes);
+    std::memcpy(L->h_in.p, jobs.data(), sizeof(MatchResJob) * (size_t)n_jobs);
     if (build) {
-        FrDescUnit* hu = (FrDescUnit*)(L->h_in + job_bytes);
-        FrCtx* hc = (FrCtx*)(L->h_in + job_bytes + unit_bytes);
+        FrDescUnit* hu = (FrDescUnit*)(L->h_in.p + job_bytes);
+        FrCtx* hc = (FrCtx*)(L->h_in.p + job_bytes + unit_bytes);
         for (int i = 0; i < n_ctx; i++) {
             velo_ctx* c = ctxs[i];
             const FrStore& S = *c->fr;
@@ -347,24 +358,15 @@ int fr_desc_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32_
                 U.q_out = jobs[(size_t)(unit0[i] + cam)].q_out;
                 for (int k = 0; k < 3; k++) U.t_cam[k] = S.cam_t[3 * cam + k];
             }
-            FrCtx& K = hc[i];
-            K.vm = c->vm.p;
-            K.pairs = d_pairs + 2 * pair0[i];
-            if (pose2_inv && c->lm && c->lm->n_ids > 0) {
-                K.lm_pts = c->lm->pts.p; K.lm_added = c->lm->added.p; K.lm_ids = (int)c->lm->n_ids;
-                std::memcpy(K.pose2_inv.m, pose2_inv + 16 * (size_t)i, sizeof(K.pose2_inv.m));
-            }
+            fr_fill_ctx(c, i, d_pairs + 2 * pair0[i], pose2_inv, &hc[i]);
         }
     }
     VELO_TRY(fb_gather(ctxs, n_ctx, nullptr));
     hipStream_t st = c0->stream;
     if (build)
-        for (int i = 0; i < n_ctx; i++) {
-            const size_t n1 = pair0[i + 1] - pair0[i];
-            if (n1 > 0) HIP_TRY(hipMemsetAsync(ctxs[i]->vflags.p, 0, 3 * n1, st));
-        }
+        for (int i = 0; i < n_ctx; i++) VELO_TRY(fr_clear_vflags(ctxs[i], pair0[i + 1] - pair0[i], st));
     if (n_jobs > 0) {
-        HIP_TRY(hipMemcpyAsync(L->d_in.p, L->h_in, in_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(L->d_in.p, L->h_in.p, in_bytes, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(L->d_keys.p, 0xFF, sizeof(unsigned) * ((size_t)nq + (size_t)n_jobs), st));   // kMatchNone
         const MatchResJob* d_jobs = (const MatchResJob*)L->d_in.p;
         unsigned* keys = L->d_keys.p;
@@ -378,10 +380,10 @@ int fr_desc_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32_
                                (const FrDescUnit*)(L->d_in.p + job_bytes), (const FrCtx*)(L->d_in.p + job_bytes + unit_bytes),
                                (const int*)d_job_out, (const int*)(d_filt + 2 * (size_t)nq));
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(L->h_out, d_job_out, sizeof(int) * back_ints, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(L->h_out.p, d_job_out, sizeof(int) * back_ints, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
-    const int* h_job = (const int*)L->h_out;
+    const int* h_job = (const int*)L->h_out.p;
     if (!build) {
         for (int j = 0; j < n_jobs; j++) { min_d[j] = h_job[2 * j]; kept[j] = h_job[2 * j + 1]; }
         return VELO_OK;
@@ -411,11 +413,11 @@ int velo_frames_reset(velo_ctx* c, int32_t n_cams, const float* cam_trans, int32
     S->n_cams = n_cams;
     std::memcpy(S->cam_t, cam_trans, sizeof(float) * 3 * (size_t)n_cams);
     const size_t want = arena_capacity > 0 ? fr_round(((size_t)arena_capacity + sizeof(int) - 1) / sizeof(int)) : kFrDefaultArena;
-    VELO_TRY(S->arena.reserve(want));
-    S->cap = want;                                      // the buffer holds a little more; the arena reallocates at what was asked for
+    VELO_TRY(S->kp.buf.reserve(want));
+    S->kp.list.cap = want;                              // the buffer holds a little more; the arena reallocates at what was asked for
     const size_t want_rows = arena_capacity > 0 ? ((size_t)arena_capacity + 63) / 64 : kFrDefaultRows;   // the row arena starts at the same byte count
-    VELO_TRY(S->rows.reserve(4 * want_rows));
-    S->r_cap = want_rows;
+    VELO_TRY(S->rows.buf.reserve(4 * want_rows));
+    S->rows.list.cap = want_rows;
     c->fr = S;
     return VELO_OK;
 }
@@ -443,48 +445,26 @@ int velo_frames_put(velo_ctx* c, int32_t frame, int32_t cam, const int32_t* ids,
     const size_t words = 4 * (size_t)n + 3 * (size_t)n_with_depth, need = fr_round(words);
     const int64_t key = lm_key(frame, cam);
     auto old = S.dir.find(key);
+    const Block* old_blk = old != S.dir.end() ? &old->second.blk : nullptr;
     // where the block goes: in place when it fits, else the first free block that is large enough, else the front of the arena
-    FrStore::Entry e;
-    e.n = n; e.n_wd = n_with_depth; e.max_id = max_id;
-    int from_free = -1;
-    bool in_place = false;
-    if (old != S.dir.end() && old->second.cap >= need) { e.off = old->second.off; e.cap = old->second.cap; in_place = true; }
-    else if (need == 0) { in_place = true; }                         // an empty entry owns no block
-    else {
-        for (size_t k = 0; k < S.free_blocks.size() && from_free < 0; k++) if (S.free_blocks[k].second >= need) from_free = (int)k;
-        if (from_free >= 0) { e.off = S.free_blocks[(size_t)from_free].first; e.cap = S.free_blocks[(size_t)from_free].second; }
-        else {
-            if (S.used + need > S.cap) {
-                const size_t cap = std::max(S.used + need, 2 * S.cap);
-                VELO_TRY(lm_regrow(c, &S.arena, S.used, cap, 0));
-                S.cap = cap;
-                S.reallocs++;
-            }
-            e.off = S.used; e.cap = need;
-        }
-    }
+    BlockList::Plan plan;
+    VELO_TRY(S.kp.place(c, old_blk, need, &plan));
     if (words > 0) {
-        const int k = S.put_k;
-        VELO_TRY(fr_event_wait(&S.put_ev[k]));
-        VELO_TRY(match_pinned((void**)&S.h_put[k], &S.h_put_cap[k], sizeof(int) * words));
-        int* h = (int*)S.h_put[k];
+        unsigned char* stage = nullptr;
+        VELO_TRY(S.put_stage.acquire(sizeof(int) * words, &stage));
+        int* h = (int*)stage;
         if (n > 0) {
             std::memcpy(h, ids, sizeof(int) * (size_t)n);
             std::memcpy(h + n, has_depth, sizeof(int) * (size_t)n);
             std::memcpy(h + 2 * (size_t)n, keypoints_xy, sizeof(float) * 2 * (size_t)n);
         }
         if (n_with_depth > 0) std::memcpy(h + 4 * (size_t)n, kp_with_depth_xyz, sizeof(float) * 3 * (size_t)n_with_depth);
-        HIP_TRY(hipMemcpyAsync(S.arena.p + e.off, h, sizeof(int) * words, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipEventRecord(S.put_ev[k], c->stream));
-        S.put_k = k ^ 1;
+        HIP_TRY(hipMemcpyAsync(S.kp.at(plan.block), h, sizeof(int) * words, hipMemcpyHostToDevice, c->stream));
+        VELO_TRY(S.put_stage.sent(c->stream));
     }
     // the directory after the last call that can fail
-    if (!in_place) {
-        if (from_free >= 0) S.free_blocks.erase(S.free_blocks.begin() + from_free);
-        else S.used += need;
-        if (old != S.dir.end() && old->second.cap > 0) S.free_blocks.push_back(std::make_pair(old->second.off, old->second.cap));
-    }
-    S.dir[key] = e;
+    S.kp.list.commit(plan, old_blk);
+    S.dir[key] = FrStore::Entry{plan.block, n, n_with_depth, max_id};
     fr_free_rows(S, key);                                            // the keypoints the rows belonged to are gone
     return VELO_OK;
 }
@@ -497,7 +477,7 @@ int velo_frames_drop(velo_ctx* c, int32_t frame) {
     for (int cam = 0; cam < S.n_cams; cam++) {
         auto it = S.dir.find(lm_key(frame, cam));
         if (it == S.dir.end()) continue;
-        if (it->second.cap > 0) S.free_blocks.push_back(std::make_pair(it->second.off, it->second.cap));
+        S.kp.list.release(it->second.blk);
         S.dir.erase(it);
         fr_free_rows(S, lm_key(frame, cam));
     }
@@ -520,42 +500,19 @@ int velo_frames_put_descriptors(velo_ctx* c, int32_t frame, int32_t cam, const u
     HIP_TRY(hipSetDevice(c->device));
     const size_t need = (size_t)n;
     auto old = S.rdir.find(key);
-    // where the block goes: as in velo_frames_put
-    FrStore::RowEntry e;
-    e.n = n;
-    int from_free = -1;
-    bool in_place = false;
-    if (old != S.rdir.end() && old->second.cap >= need) { e.off = old->second.off; e.cap = old->second.cap; in_place = true; }
-    else if (need == 0) { in_place = true; }                         // an empty entry owns no block
-    else {
-        for (size_t k = 0; k < S.r_free.size() && from_free < 0; k++) if (S.r_free[k].second >= need) from_free = (int)k;
-        if (from_free >= 0) { e.off = S.r_free[(size_t)from_free].first; e.cap = S.r_free[(size_t)from_free].second; }
-        else {
-            if (S.r_used + need > S.r_cap) {
-                const size_t cap = std::max(S.r_used + need, 2 * S.r_cap);
-                VELO_TRY(lm_regrow(c, &S.rows, 4 * S.r_used, 4 * cap, 0));
-                S.r_cap = cap;
-                S.r_reallocs++;
-            }
-            e.off = S.r_used; e.cap = need;
-        }
-    }
+    const Block* old_blk = old != S.rdir.end() ? &old->second.blk : nullptr;
+    BlockList::Plan plan;
+    VELO_TRY(S.rows.place(c, old_blk, need, &plan));
     if (n > 0) {
-        const int k = S.rows_k;
-        VELO_TRY(fr_event_wait(&S.rows_ev[k]));
-        VELO_TRY(match_pinned((void**)&S.h_rows[k], &S.h_rows_cap[k], 64 * need));
-        std::memcpy(S.h_rows[k], rows, 64 * need);
-        HIP_TRY(hipMemcpyAsync(S.rows.p + 4 * e.off, S.h_rows[k], 64 * need, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipEventRecord(S.rows_ev[k], c->stream));
-        S.rows_k = k ^ 1;
+        unsigned char* stage = nullptr;
+        VELO_TRY(S.rows_stage.acquire(64 * need, &stage));
+        std::memcpy(stage, rows, 64 * need);
+        HIP_TRY(hipMemcpyAsync(S.rows.at(plan.block), stage, 64 * need, hipMemcpyHostToDevice, c->stream));
+        VELO_TRY(S.rows_stage.sent(c->stream));
     }
     // the directory after the last call that can fail
-    if (!in_place) {
-        if (from_free >= 0) S.r_free.erase(S.r_free.begin() + from_free);
-        else S.r_used += need;
-        if (old != S.rdir.end() && old->second.cap > 0) S.r_free.push_back(std::make_pair(old->second.off, old->second.cap));
-    }
-    S.rdir[key] = e;
+    S.rows.list.commit(plan, old_blk);
+    S.rdir[key] = FrStore::RowEntry{plan.block, n};
     return VELO_OK;
 }
 
@@ -563,8 +520,8 @@ int velo_frames_desc_info(velo_ctx* c, int32_t* info) {
     if (!c || !info) return fail(VELO_ERR_INVALID, "null argument");
     VELO_TRY(fr_need_store(c, "velo_frames_desc_info"));
     const FrStore& S = *c->fr;
-    info[0] = (int32_t)S.rdir.size(); info[1] = (int32_t)std::min<size_t>(S.r_cap * 64, 0x7fffffff); info[2] = S.r_reallocs;
-    info[3] = (int32_t)S.r_free.size();
+    info[0] = (int32_t)S.rdir.size(); info[1] = (int32_t)std::min<size_t>(S.rows.list.cap * 64, 0x7fffffff); info[2] = S.rows.list.reallocs;
+    info[3] = (int32_t)S.rows.list.free_blocks.size();
     return VELO_OK;
 }
 
@@ -593,24 +550,14 @@ int velo_frames_info(velo_ctx* c, int32_t* info) {
     for (const auto& kv : S.dir) frames.push_back((int)(kv.first / kLmMaxCams));
     std::sort(frames.begin(), frames.end());
     frames.erase(std::unique(frames.begin(), frames.end()), frames.end());
-    info[0] = (int32_t)frames.size(); info[1] = (int32_t)S.dir.size(); info[2] = sat(S.cap * sizeof(int)); info[3] = S.reallocs;
-    info[4] = sat(S.used * sizeof(int)); info[5] = S.n_cams; info[6] = (int32_t)S.slot_ids; info[7] = (int32_t)S.free_blocks.size();
+    info[0] = (int32_t)frames.size(); info[1] = (int32_t)S.dir.size(); info[2] = sat(S.kp.list.cap * sizeof(int)); info[3] = S.kp.list.reallocs;
+    info[4] = sat(S.kp.list.used * sizeof(int)); info[5] = S.n_cams; info[6] = (int32_t)S.slot_ids; info[7] = (int32_t)S.kp.list.free_blocks.size();
     return VELO_OK;
 }
 
 int velo_build_matches_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* frames1, const int32_t* frames2, const double* pose2_inv,
                              int32_t* n_per_cam, int32_t* pairs_out, int32_t capacity, int32_t* n_out) {
-    // every argument is checked before any context is touched
-    VELO_TRY(fb_check_list(ctxs, n_ctx));
-    if (!frames1 || !frames2) return fail(VELO_ERR_INVALID, "null frames");
-    if (!n_out) return fail(VELO_ERR_INVALID, "null n_out");
-    if (capacity < 0) return fail(VELO_ERR_INVALID, "negative capacity");
-    for (int i = 0; i < n_ctx; i++)
-        for (int f : {frames1[i], frames2[i]})
-            if (f < 0 || f >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "context %d: frame %d; 0..%d", i, f, kLmMaxFrame - 1);
-    if (pose2_inv)
-        for (int k = 0; k < 16 * n_ctx; k++) if (!std::isfinite(pose2_inv[k])) return fail(VELO_ERR_INVALID, "context %d: pose2_inv[%d] is not finite", k / 16, k % 16);
-    VELO_TRY(fb_check_devices(ctxs, n_ctx));
+    VELO_TRY(fr_check_build_args(ctxs, n_ctx, frames1, frames2, pose2_inv, nullptr, capacity, n_out));
     return fr_build_run(ctxs, n_ctx, frames1, frames2, pose2_inv, n_per_cam, pairs_out, capacity, n_out);
 }
 
@@ -622,18 +569,7 @@ int velo_build_matches(velo_ctx* c, int32_t frame1, int32_t frame2, const double
 
 int velo_build_matches_desc_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* frames1, const int32_t* frames2, const double* pose2_inv,
                                   double match_thresh, int32_t* n_per_cam, int32_t* pairs_out, int32_t capacity, int32_t* n_out) {
-    // every argument is checked before any context is touched
-    VELO_TRY(fb_check_list(ctxs, n_ctx));
-    if (!frames1 || !frames2) return fail(VELO_ERR_INVALID, "null frames");
-    if (!n_out) return fail(VELO_ERR_INVALID, "null n_out");
-    if (capacity < 0) return fail(VELO_ERR_INVALID, "negative capacity");
-    if (std::isnan(match_thresh)) return fail(VELO_ERR_INVALID, "match_thresh is NaN");
-    for (int i = 0; i < n_ctx; i++)
-        for (int f : {frames1[i], frames2[i]})
-            if (f < 0 || f >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "context %d: frame %d; 0..%d", i, f, kLmMaxFrame - 1);
-    if (pose2_inv)
-        for (int k = 0; k < 16 * n_ctx; k++) if (!std::isfinite(pose2_inv[k])) return fail(VELO_ERR_INVALID, "context %d: pose2_inv[%d] is not finite", k / 16, k % 16);
-    VELO_TRY(fb_check_devices(ctxs, n_ctx));
+    VELO_TRY(fr_check_build_args(ctxs, n_ctx, frames1, frames2, pose2_inv, &match_thresh, capacity, n_out));
     return fr_desc_run(ctxs, n_ctx, frames1, frames2, 0, true, pose2_inv, match_thresh, n_per_cam, pairs_out, capacity, n_out, nullptr, nullptr);
 }
 

@@ -25,17 +25,11 @@ struct LmStore {
     std::vector<int32_t> h_count;
     std::vector<unsigned char> h_added;
     // staging (a batch call uses the first context's)
-    unsigned char* h_in = nullptr; size_t h_in_cap = 0;
-    unsigned char* h_out = nullptr; size_t h_out_cap = 0;
+    PinBuf<> h_in, h_out;
     hipEvent_t in_ev = nullptr;                     // h_in may be rewritten once this has passed
     DevBuf<unsigned char> d_in, d_out;
     DevBuf<velo_tri_obs> d_obs;                     // the gathered observation lists of a call
-    ~LmStore() {
-        if (h_frames) (void)hipHostFree(h_frames);
-        if (h_in) (void)hipHostFree(h_in);
-        if (h_out) (void)hipHostFree(h_out);
-        if (in_ev) (void)hipEventDestroy(in_ev);
-    }
+    ~LmStore() { if (h_frames) (void)hipHostFree(h_frames); if (in_ev) (void)hipEventDestroy(in_ev); }
 };
 
 namespace {
@@ -56,12 +50,6 @@ int lm_regrow(velo_ctx* c, DevBuf<T>* buf, size_t used, size_t want, int fill) {
     HIP_TRY(hipMemsetAsync(nb.p + used, fill, sizeof(T) * (nb.cap - used), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));          // the old buffer is freed by the assignment
     *buf = std::move(nb);
-    return VELO_OK;
-}
-
-int lm_staging_wait(LmStore* S) {
-    if (S->in_ev) HIP_TRY(hipEventSynchronize(S->in_ev));
-    else HIP_TRY(hipEventCreateWithFlags(&S->in_ev, hipEventDisableTiming));
     return VELO_OK;
 }
 
@@ -114,14 +102,14 @@ int lm_triangulate_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, int32_
     const size_t in_bytes = unit_bytes + item_bytes + sizeof(int) * ((size_t)n + 1);
     const size_t res_bytes = fb_align64(sizeof(velo_tri_result) * (size_t)n);
     const size_t out_bytes = res_bytes + sizeof(float) * 3 * (size_t)n;
-    VELO_TRY(lm_staging_wait(L));
-    VELO_TRY(match_pinned((void**)&L->h_in, &L->h_in_cap, in_bytes));
-    VELO_TRY(match_pinned((void**)&L->h_out, &L->h_out_cap, out_bytes));
+    VELO_TRY(event_wait_or_create(&L->in_ev));
+    VELO_TRY(L->h_in.reserve(in_bytes));
+    VELO_TRY(L->h_out.reserve(out_bytes));
     VELO_TRY(L->d_in.reserve(in_bytes));
     VELO_TRY(L->d_out.reserve(out_bytes));
     VELO_TRY(L->d_obs.reserve((size_t)off.back()));
     {
-        LmUnit* hu = (LmUnit*)L->h_in;
+        LmUnit* hu = (LmUnit*)L->h_in.p;
         std::memset(hu, 0, unit_bytes);
         for (int i = 0; i < n_ctx; i++) {
             const velo_ctx* ci = ctxs[i];
@@ -132,11 +120,11 @@ int lm_triangulate_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, int32_
             U.P.lm = lm_params(ci->P);
             U.P.loss_a = ci->P.loss_thresh_3D2D; U.P.loss_w = ci->P.weight_3D2D;    // velo.h:1116-1119
         }
-        std::memcpy(L->h_in + unit_bytes, items.data(), sizeof(LmItem) * (size_t)n);
-        std::memcpy(L->h_in + unit_bytes + item_bytes, off.data(), sizeof(int) * ((size_t)n + 1));
+        std::memcpy(L->h_in.p + unit_bytes, items.data(), sizeof(LmItem) * (size_t)n);
+        std::memcpy(L->h_in.p + unit_bytes + item_bytes, off.data(), sizeof(int) * ((size_t)n + 1));
     }
     VELO_TRY(fb_gather(ctxs, n_ctx, &used));
-    HIP_TRY(hipMemcpyAsync(L->d_in.p, L->h_in, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(L->d_in.p, L->h_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipEventRecord(L->in_ev, c->stream));
     const LmUnit* d_units = (const LmUnit*)L->d_in.p;
     const LmItem* d_items = (const LmItem*)(L->d_in.p + unit_bytes);
@@ -146,10 +134,10 @@ int lm_triangulate_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, int32_
     hipLaunchKernelGGL(lm_gather_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, d_units, d_items, d_off, n, L->d_obs.p);
     hipLaunchKernelGGL(lm_solve_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, d_units, d_items, (const velo_tri_obs*)L->d_obs.p, d_off, n, d_pts, d_res);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(L->h_out, L->d_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(L->h_out.p, L->d_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const velo_tri_result* h_res = (const velo_tri_result*)L->h_out;
-    const float* h_pts = (const float*)(L->h_out + res_bytes);
+    const velo_tri_result* h_res = (const velo_tri_result*)L->h_out.p;
+    const float* h_pts = (const float*)(L->h_out.p + res_bytes);
     for (int i = 0; i < n_ctx; i++) {
         LmStore& S = *ctxs[i]->lm;
         const int b = first[i], m = first[i + 1] - b, w = std::min(m, (int)capacity);
@@ -265,15 +253,15 @@ int velo_landmarks_observe(velo_ctx* c, int32_t frame, int32_t cam, const int32_
     const size_t obs_bytes = fb_align64(sizeof(velo_tri_obs) * (size_t)n);
     const size_t in_bytes = obs_bytes + sizeof(int) * (size_t)n;
     if (n > 0) {
-        VELO_TRY(lm_staging_wait(&S));
-        VELO_TRY(match_pinned((void**)&S.h_in, &S.h_in_cap, in_bytes));
+        VELO_TRY(event_wait_or_create(&S.in_ev));
+        VELO_TRY(S.h_in.reserve(in_bytes));
         VELO_TRY(S.d_in.reserve(in_bytes));
     }
     // the device first, the host's bookkeeping after the last call that can fail: a failed call leaves the store as it was (what a
     // failed launch may have written lies beyond log_len and in id tables whose counts the host does not trust over its own)
     if (n > 0) {
-        velo_tri_obs* ho = (velo_tri_obs*)S.h_in;
-        int* hi = (int*)(S.h_in + obs_bytes);
+        velo_tri_obs* ho = (velo_tri_obs*)S.h_in.p;
+        int* hi = (int*)(S.h_in.p + obs_bytes);
         for (int i = 0; i < n; i++) {
             velo_tri_obs& o = ho[i];
             o.frame = frame; o.cam = cam;
@@ -281,7 +269,7 @@ int velo_landmarks_observe(velo_ctx* c, int32_t frame, int32_t cam, const int32_
             else { const float* p = kp_with_depth_xyz + 3 * (size_t)has_depth[i]; o.kind = VELO_TRI_OBS_3D; o.s[0] = p[0]; o.s[1] = p[1]; o.s[2] = p[2]; }
             hi[i] = ids[i];
         }
-        HIP_TRY(hipMemcpyAsync(S.d_in.p, S.h_in, in_bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(S.d_in.p, S.h_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipEventRecord(S.in_ev, c->stream));
         hipLaunchKernelGGL(lm_append_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, c->stream, (const velo_tri_obs*)S.d_in.p, (const int*)(S.d_in.p + obs_bytes), n,
                            (int)S.log_len, S.log.p, S.prev.p, S.head.p, S.count.p);
@@ -334,21 +322,21 @@ int velo_landmarks_at_frame(velo_ctx* c, int32_t frame, const double* pose_inv16
     if (!xyz_out) return VELO_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t in_bytes = sizeof(int) * (size_t)n, out_bytes = sizeof(float) * 3 * (size_t)n;
-    VELO_TRY(lm_staging_wait(&S));
-    VELO_TRY(match_pinned((void**)&S.h_in, &S.h_in_cap, in_bytes));
-    VELO_TRY(match_pinned((void**)&S.h_out, &S.h_out_cap, out_bytes));
+    VELO_TRY(event_wait_or_create(&S.in_ev));
+    VELO_TRY(S.h_in.reserve(in_bytes));
+    VELO_TRY(S.h_out.reserve(out_bytes));
     VELO_TRY(S.d_in.reserve(in_bytes));
     VELO_TRY(S.d_out.reserve(out_bytes));
-    std::memcpy(S.h_in, ids.data(), in_bytes);
+    std::memcpy(S.h_in.p, ids.data(), in_bytes);
     LmPose M;
     std::memcpy(M.m, pose_inv16, sizeof(M.m));
-    HIP_TRY(hipMemcpyAsync(S.d_in.p, S.h_in, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(S.d_in.p, S.h_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipEventRecord(S.in_ev, c->stream));
     hipLaunchKernelGGL(lm_at_frame_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, c->stream, (const int*)S.d_in.p, n, (const float*)S.pts.p, M, (float*)S.d_out.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(S.h_out, S.d_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(S.h_out.p, S.d_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    std::memcpy(xyz_out, S.h_out, out_bytes);
+    std::memcpy(xyz_out, S.h_out.p, out_bytes);
     return VELO_OK;
 }
 
@@ -364,22 +352,22 @@ int velo_landmarks_get(velo_ctx* c, const int32_t* ids, int32_t n, float* xyz, u
     const size_t in_bytes = sizeof(int) * (size_t)n;
     const size_t xyz_bytes = sizeof(float) * 3 * (size_t)n, cnt_bytes = sizeof(int) * (size_t)n;
     const size_t out_bytes = xyz_bytes + cnt_bytes + (size_t)n;
-    VELO_TRY(lm_staging_wait(&S));
-    VELO_TRY(match_pinned((void**)&S.h_in, &S.h_in_cap, in_bytes));
-    VELO_TRY(match_pinned((void**)&S.h_out, &S.h_out_cap, out_bytes));
+    VELO_TRY(event_wait_or_create(&S.in_ev));
+    VELO_TRY(S.h_in.reserve(in_bytes));
+    VELO_TRY(S.h_out.reserve(out_bytes));
     VELO_TRY(S.d_in.reserve(in_bytes));
     VELO_TRY(S.d_out.reserve(out_bytes));
-    std::memcpy(S.h_in, ids, in_bytes);
-    HIP_TRY(hipMemcpyAsync(S.d_in.p, S.h_in, in_bytes, hipMemcpyHostToDevice, c->stream));
+    std::memcpy(S.h_in.p, ids, in_bytes);
+    HIP_TRY(hipMemcpyAsync(S.d_in.p, S.h_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipEventRecord(S.in_ev, c->stream));
     hipLaunchKernelGGL(lm_get_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, c->stream, (const int*)S.d_in.p, n, (int)S.n_ids, (const float*)S.pts.p,
                        (const unsigned char*)S.added.p, (const int*)S.count.p, (float*)S.d_out.p, (int*)(S.d_out.p + xyz_bytes), S.d_out.p + xyz_bytes + cnt_bytes);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(S.h_out, S.d_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(S.h_out.p, S.d_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (xyz) std::memcpy(xyz, S.h_out, xyz_bytes);
-    if (obs_count) std::memcpy(obs_count, S.h_out + xyz_bytes, cnt_bytes);
-    if (added) std::memcpy(added, S.h_out + xyz_bytes + cnt_bytes, (size_t)n);
+    if (xyz) std::memcpy(xyz, S.h_out.p, xyz_bytes);
+    if (obs_count) std::memcpy(obs_count, S.h_out.p + xyz_bytes, cnt_bytes);
+    if (added) std::memcpy(added, S.h_out.p + xyz_bytes + cnt_bytes, (size_t)n);
     return VELO_OK;
 }
 

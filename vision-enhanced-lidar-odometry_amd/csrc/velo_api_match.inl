@@ -1,18 +1,5 @@
 // velo_api_match.inl -- part of the host side of the C-ABI, included by velo_hip.hip (ONE translation unit; the order of the parts is the order of
 // definition).  C-ABI: batched Hamming matching of 64-byte descriptors -- matchFeatures (velo.h:499-560); kernels in velo_match_kernels.h.
-namespace {
-
-int match_pinned(void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return VELO_OK;
-    if (*p) { (void)hipHostFree(*p); *p = nullptr; *cap = 0; }
-    const size_t want = bytes + bytes / 4 + 4096;
-    HIP_TRY(hipHostMalloc(p, want, hipHostMallocDefault));
-    *cap = want;
-    return VELO_OK;
-}
-
-}  // namespace
-
 extern "C" {   // (continued from the previous part)
 int velo_match_descriptors(velo_ctx* c, const velo_desc_job* jobs, int32_t n_jobs, double match_thresh, int32_t* train_idx, int32_t* distance,
                            int32_t* min_dist, int32_t* n_kept, int32_t* pairs) {
@@ -71,17 +58,17 @@ int velo_match_descriptors(velo_ctx* c, const velo_desc_job* jobs, int32_t n_job
     const size_t job_bytes = (sizeof(MatchJob) * (size_t)n_jobs + 63) & ~(size_t)63;   // the rows start 64-byte aligned
     const size_t in_bytes = job_bytes + 64 * (size_t)n_rows;
     const size_t out_ints = 4 * (size_t)nq + 2 * (size_t)n_jobs;
-    VELO_TRY(match_pinned((void**)&c->h_md_in, &c->h_md_in_cap, in_bytes));
-    VELO_TRY(match_pinned((void**)&c->h_md_out, &c->h_md_out_cap, sizeof(int) * out_ints));
+    VELO_TRY(c->h_md_in.reserve(in_bytes));
+    VELO_TRY(c->h_md_out.reserve(sizeof(int) * out_ints));
     VELO_TRY(c->md_in.reserve(in_bytes));
     VELO_TRY(c->md_keys.reserve((size_t)nq + (size_t)n_jobs));
     VELO_TRY(c->md_out.reserve(out_ints));
-    std::memcpy(c->h_md_in, hj.data(), sizeof(MatchJob) * (size_t)n_jobs);
+    std::memcpy(c->h_md_in.p, hj.data(), sizeof(MatchJob) * (size_t)n_jobs);
     {
-        unsigned char* w = c->h_md_in + job_bytes;
+        unsigned char* w = c->h_md_in.p + job_bytes;
         for (const auto& s : sets) { std::memcpy(w, s.first, 64 * (size_t)s.second); w += 64 * (size_t)s.second; }
     }
-    HIP_TRY(hipMemcpyAsync(c->md_in.p, c->h_md_in, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->md_in.p, c->h_md_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->md_keys.p, 0xFF, sizeof(unsigned) * ((size_t)nq + (size_t)n_jobs), c->stream));   // kMatchNone
     const MatchJob* djobs = (const MatchJob*)c->md_in.p;
     const uint4* drows = (const uint4*)(c->md_in.p + job_bytes);
@@ -96,10 +83,10 @@ int velo_match_descriptors(velo_ctx* c, const velo_desc_job* jobs, int32_t n_job
     hipLaunchKernelGGL(match_filter_kernel, dim3(n_jobs), dim3(kMatchThreads), 0, c->stream, djobs, (const unsigned*)keys, (const unsigned*)dmin,
                        match_thresh, nq, c->md_out.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_md_out, c->md_out.p, sizeof(int) * out_ints, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_md_out.p, c->md_out.p, sizeof(int) * out_ints, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
 
-    const int* o = c->h_md_out;
+    const int* o = c->h_md_out.p;
     if (nq > 0) {
         std::memcpy(train_idx, o, sizeof(int) * (size_t)nq);
         std::memcpy(distance, o + nq, sizeof(int) * (size_t)nq);

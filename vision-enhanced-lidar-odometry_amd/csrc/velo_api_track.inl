@@ -164,7 +164,7 @@ int lk_set_images(velo_ctx** ctxs, int n_ctx, const uint8_t* const* imgs, int n_
     const size_t unit_bytes = fb_align64(sizeof(LkBuildUnit) * (size_t)n_units);
     const size_t pyr_bytes = fb_align64(sizeof(LkPyr) * pyrs.size());
     const size_t in_bytes = unit_bytes + pyr_bytes + raw_bytes;
-    VELO_TRY(match_pinned((void**)&c->h_lk_raw, &c->h_lk_raw_cap, in_bytes));
+    VELO_TRY(c->h_lk_raw.reserve(in_bytes));
     VELO_TRY(c->lk_raw.reserve(in_bytes));
     // The slot every context is about to fill is its previous one (current -> previous is a rotation, no copy).  Every allocation comes
     // first and nothing rotates unless everything was allocated: a failure leaves every context's current and previous images as they
@@ -178,8 +178,8 @@ int lk_set_images(velo_ctx** ctxs, int n_ctx, const uint8_t* const* imgs, int n_
     }
     for (int i = 0; i < n_ctx; i++) ctxs[i]->lk_slot[ctxs[i]->lk_cur ^ 1].valid = false;
     {
-        LkBuildUnit* hu = (LkBuildUnit*)c->h_lk_raw;
-        std::memcpy(c->h_lk_raw + unit_bytes, pyrs.data(), sizeof(LkPyr) * pyrs.size());
+        LkBuildUnit* hu = (LkBuildUnit*)c->h_lk_raw.p;
+        std::memcpy(c->h_lk_raw.p + unit_bytes, pyrs.data(), sizeof(LkPyr) * pyrs.size());
         size_t off = unit_bytes + pyr_bytes;
         for (int i = 0; i < n_ctx; i++) {
             const int w = sizes[3 * i], h = sizes[3 * i + 1], st = sizes[3 * i + 2];
@@ -191,13 +191,13 @@ int lk_set_images(velo_ctx** ctxs, int n_ctx, const uint8_t* const* imgs, int n_
                 U.der = S.der.p + (size_t)k * cam_pix[pyr_of[i]];
                 U.pyr = pyr_of[i]; U.pad_ = 0;
                 const uint8_t* src = imgs[(size_t)i * n_cams + k];
-                for (int y = 0; y < h; y++) std::memcpy(c->h_lk_raw + off + (size_t)y * w, src + (size_t)y * st, (size_t)w);
+                for (int y = 0; y < h; y++) std::memcpy(c->h_lk_raw.p + off + (size_t)y * w, src + (size_t)y * st, (size_t)w);
                 off += (size_t)w * h;
             }
         }
     }
     VELO_TRY(fb_gather(ctxs, n_ctx, nullptr));
-    HIP_TRY(hipMemcpyAsync(c->lk_raw.p, c->h_lk_raw, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->lk_raw.p, c->h_lk_raw.p, in_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipEventRecord(c->lk_upload_ev, c->stream));
     int max_levels = 0;
     for (const LkPyr& P : pyrs) max_levels = std::max(max_levels, P.n_levels);
@@ -257,14 +257,14 @@ int lk_track(velo_ctx** ctxs, int n_ctx, const int32_t* job_ctx, const velo_trac
     const size_t pyr_bytes = fb_align64(sizeof(LkPyr) * pyrs.size());
     const size_t in_bytes = job_bytes + pyr_bytes + sizeof(float2) * (size_t)n;
     const size_t out_bytes = sizeof(float2) * (size_t)n + 2 * (size_t)n;
-    VELO_TRY(match_pinned((void**)&c->h_lk_in, &c->h_lk_in_cap, in_bytes));
-    VELO_TRY(match_pinned((void**)&c->h_lk_out, &c->h_lk_out_cap, out_bytes));
+    VELO_TRY(c->h_lk_in.reserve(in_bytes));
+    VELO_TRY(c->h_lk_out.reserve(out_bytes));
     VELO_TRY(c->lk_in.reserve(in_bytes));
     VELO_TRY(c->lk_out.reserve(out_bytes));
     {
-        LkJob* hj = (LkJob*)c->h_lk_in;
-        std::memcpy(c->h_lk_in + job_bytes, pyrs.data(), sizeof(LkPyr) * pyrs.size());
-        float* hp = (float*)(c->h_lk_in + job_bytes + pyr_bytes);
+        LkJob* hj = (LkJob*)c->h_lk_in.p;
+        std::memcpy(c->h_lk_in.p + job_bytes, pyrs.data(), sizeof(LkPyr) * pyrs.size());
+        float* hp = (float*)(c->h_lk_in.p + job_bytes + pyr_bytes);
         int first = 0;
         for (int j = 0; j < n_jobs; j++) {
             const int i = fb_ctx_of(job_ctx, j);
@@ -281,7 +281,7 @@ int lk_track(velo_ctx** ctxs, int n_ctx, const int32_t* job_ctx, const velo_trac
         }
     }
     VELO_TRY(fb_gather(ctxs, n_ctx, &used));
-    HIP_TRY(hipMemcpyAsync(c->lk_in.p, c->h_lk_in, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->lk_in.p, c->h_lk_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
     LkParams K;
     std::memset(&K, 0, sizeof(K));
     K.win = p->window; K.max_count = p->max_count;
@@ -309,11 +309,11 @@ int lk_track(velo_ctx** ctxs, int n_ctx, const int32_t* job_ctx, const velo_trac
     else
         hipLaunchKernelGGL(lk_track_kernel_16, grid, dim3(kLkThreads), 0, c->stream, djobs, n_jobs, dpyrs, dpts, n, K, oxy, ost, okp, diag);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_lk_out, c->lk_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_lk_out.p, c->lk_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    std::memcpy(next_xy, c->h_lk_out, sizeof(float2) * (size_t)n);
-    std::memcpy(status, c->h_lk_out + sizeof(float2) * (size_t)n, (size_t)n);
-    std::memcpy(kept, c->h_lk_out + sizeof(float2) * (size_t)n + n, (size_t)n);
+    std::memcpy(next_xy, c->h_lk_out.p, sizeof(float2) * (size_t)n);
+    std::memcpy(status, c->h_lk_out.p + sizeof(float2) * (size_t)n, (size_t)n);
+    std::memcpy(kept, c->h_lk_out.p + sizeof(float2) * (size_t)n + n, (size_t)n);
     return VELO_OK;
 }
 

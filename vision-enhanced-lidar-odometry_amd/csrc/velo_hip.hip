@@ -41,6 +41,7 @@
 #include "velo_detect_kernels.h"
 #include "velo_landmark_kernels.h"
 #include "velo_frame_kernels.h"
+#include "velo_block_list.h"
 
 using namespace velo;
 

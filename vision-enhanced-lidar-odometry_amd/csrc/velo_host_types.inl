@@ -84,6 +84,55 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+// page-locked host memory, owned like a device buffer: staging of uploads and landing of read-backs.  Sized in bytes; a buffer that
+// grows is freed first (its contents are not kept), and the owner sees to it that no copy is in flight when it asks for more.
+template <typename T = unsigned char>
+struct PinBuf {
+    T* p = nullptr;
+    size_t cap = 0;                      // bytes
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    PinBuf(PinBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    PinBuf& operator=(PinBuf&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~PinBuf() { release(); }
+    int reserve(size_t bytes) {
+        if (bytes <= cap) return VELO_OK;
+        release();
+        const size_t want = bytes + bytes / 4 + 4096;
+        HIP_TRY(hipHostMalloc((void**)&p, want, hipHostMallocDefault));
+        cap = want;
+        return VELO_OK;
+    }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+};
+
+// the host may write a staging buffer again once the event recorded behind its last upload has passed; the first use creates the event
+int event_wait_or_create(hipEvent_t* ev) {
+    if (*ev) HIP_TRY(hipEventSynchronize(*ev));
+    else HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    return VELO_OK;
+}
+
+// double-buffered upload staging: two pinned slots used alternately, so that an upload waits only for the one before the previous one
+struct PinStage {
+    PinBuf<> buf[2];
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int k = 0;
+    ~PinStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    int acquire(size_t bytes, unsigned char** p) {
+        VELO_TRY(event_wait_or_create(&ev[k]));
+        VELO_TRY(buf[k].reserve(bytes));
+        *p = buf[k].p;
+        return VELO_OK;
+    }
+    int sent(hipStream_t stream) {       // behind the copy out of the slot acquire() gave
+        HIP_TRY(hipEventRecord(ev[k], stream));
+        k ^= 1;
+        return VELO_OK;
+    }
+};
+
 struct Grid {
     GridDesc d{};
     double gate = 0.0;          // squared-distance gate the cell size was derived from
@@ -395,10 +444,8 @@ struct velo_ctx {
     DevBuf<unsigned char> md_in;         // one staged upload: job table | the distinct descriptor rows (64 bytes each)
     DevBuf<unsigned> md_keys;            // [sum n_query] nearest-row keys | [n_jobs] min_dist
     DevBuf<int> md_out;                  // train_idx | distance | pairs (per job from its first query) | {min_dist, n_kept} per job
-    unsigned char* h_md_in = nullptr;    // pinned staging of md_in
-    size_t h_md_in_cap = 0;
-    int* h_md_out = nullptr;             // pinned landing of md_out
-    size_t h_md_out_cap = 0;
+    PinBuf<> h_md_in;                    // pinned staging of md_in
+    PinBuf<int> h_md_out;                // pinned landing of md_out
     int match_variant = 1;               // 1 = int8 MFMA (product), 0 = XOR + popcount (VELO_MATCH_VARIANT, diagnostics build only)
 
     // resident camera images and Lucas-Kanade tracking (velo_set_images / velo_track_features): buffers of their own, which no
@@ -406,15 +453,12 @@ struct velo_ctx {
     LkSlot lk_slot[2];                   // current = lk_slot[lk_cur], previous = the other (velo_set_images rotates them)
     int lk_cur = 0;
     DevBuf<unsigned char> lk_raw;        // unit table | level tables | the frame's raw images, one upload
-    unsigned char* h_lk_raw = nullptr;   // pinned staging of lk_raw
-    size_t h_lk_raw_cap = 0;
+    PinBuf<> h_lk_raw;                   // pinned staging of lk_raw
     hipEvent_t lk_upload_ev = nullptr;   // h_lk_raw may be rewritten once this has passed
     DevBuf<unsigned char> lk_in;         // job table | level tables | points
     DevBuf<unsigned char> lk_out;        // next_xy | status | kept
-    unsigned char* h_lk_in = nullptr;
-    size_t h_lk_in_cap = 0;
-    unsigned char* h_lk_out = nullptr;
-    size_t h_lk_out_cap = 0;
+    PinBuf<> h_lk_in;
+    PinBuf<> h_lk_out;
     DevBuf<unsigned long long> lk_diag;  // diagnostics build: iterations / entries per level (velo_diag_track_counters)
     bool lk_diag_init = false;
 
@@ -426,10 +470,8 @@ struct velo_ctx {
     DevBuf<int> gf_hdr;                  // units x kGfHdrStride (a 128-byte line per unit)
     DevBuf<unsigned char> gf_in;         // unit table | job table | existing points
     DevBuf<unsigned char> gf_out;        // counts | per job xy, response, fresh
-    unsigned char* h_gf_in = nullptr;
-    size_t h_gf_in_cap = 0;
-    unsigned char* h_gf_out = nullptr;
-    size_t h_gf_out_cap = 0;
+    PinBuf<> h_gf_in;
+    PinBuf<> h_gf_out;
     int gf_units = 0;                    // units of the last launch set this context led (velo_diag_detect_counters)
     // the resident landmark store (velo_landmarks_*): created by velo_landmarks_reset, buffers of its own, which no registration reads or writes
     std::shared_ptr<LmStore> lm;
