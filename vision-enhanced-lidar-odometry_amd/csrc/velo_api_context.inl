@@ -75,6 +75,7 @@ int velo_create(velo_ctx** out, int device) {
         if (const char* e = getenv("VELO_CHAIN_MARGIN")) { c->chain_margin = std::max(atoi(e), 0); c->chain_margin_fixed = true; }
         if (const char* e = dev_env("VELO_ASSOC_LDS_PAD")) { c->assoc_lds_pad = std::max(atoi(e), 0); c->assoc_lds_pad_fixed = true; }
         if (const char* e = dev_env("VELO_LM_LEAN")) c->lm_lean = atoi(e);
+        if (const char* e = dev_env("VELO_LM_SLIM")) c->lm_slim = atoi(e);
         if (const char* e = dev_env("VELO_LM_PERSIST")) c->lm_persist = atoi(e);
         if (const char* e = dev_env("VELO_LM_PERSIST_WGS")) c->lm_persist_wgs = std::max(atoi(e), 0);
         if (const char* e = dev_env("VELO_ASKER_ROWS")) c->asker_rows = atoi(e);

@@ -138,11 +138,14 @@ int attach_askers(velo_ctx* c, AssocOut* out, bool enable) {
 // A round may use the lane kernel when it starts from seeds (a round of this source against this target has run) on the regular
 // grid (gate radius of the first iteration <= 5 cells; the density-shrunk grid of a 2M-point map keeps the tube kernel and its
 // query-by-query second phase), with the default variant and no diagnostics / placement table / partial records.
+// the target's grid had to be density-shrunk (a 2M-point map: the gate radius of the first iteration spans more than 5 cells)
+bool shrunk_grid(const velo_ctx* c, const Grid* G) {
+    return (int)std::ceil(std::sqrt(std::max(gate_of_iter(c->P, 1), 0.0)) / (G->h * 0.999)) > 5;
+}
 bool lane_round(const velo_ctx* c, const Grid* G, bool partial) {
     if (!c->assoc_lane || !c->warm_start || c->assoc_variant >= 0 || c->debug_skip || c->tube_map >= 0 || partial) return false;
     if (!c->prev_ready || c->seed_rounds < 1) return false;
-    const int reach_cells = (int)std::ceil(std::sqrt(std::max(gate_of_iter(c->P, 1), 0.0)) / (G->h * 0.999));
-    return reach_cells <= 5;
+    return !shrunk_grid(c, G);
 }
 
 // Sparse rounds (the reference's icp_skip = 200: 640 queries, metres apart) search one wave per query (assoc_direct_kernel).

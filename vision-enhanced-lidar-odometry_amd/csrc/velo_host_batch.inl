@@ -541,6 +541,10 @@ static int f2f_batch_lockstep(velo_ctx** ctxs, int n, double* x, double* T, velo
                     for (int i = 0; i < n; i++) packv.item[i] = items_r[i];
                     c0->lm_kernel_name = lean ? "eval_step_batch_lean_v_kernel" : "eval_step_batch_v_kernel";
                 }
+                // scan-to-map groups: the lean launch that keeps 126 VGPRs (its rows one by one), see eval_step_batch_lean_v_slim_kernel
+                const Grid* g_first = grid_for_iter(c0, 1);
+                const bool slim = by_value && lean && (c0->lm_slim >= 0 ? c0->lm_slim != 0 : (g_first && shrunk_grid(c0, g_first)));
+                if (slim) c0->lm_kernel_name = "eval_step_batch_lean_v_slim_kernel";
                 for (int k = 0; k < K; k++) {
                     if (by_value_vis) {
                         int nb_all = 0;
@@ -550,7 +554,8 @@ static int f2f_batch_lockstep(velo_ctx** ctxs, int n, double* x, double* T, velo
                         continue;
                     }
                     if (by_value) {
-                        if (lean) VELO_LAUNCH_T(c0, c0->lm_kernel_name, 0, eval_step_batch_lean_v_kernel, dim3(nb_max, n), dim3(kEvalThreads), 0, bs, Q, packv, c0->batch_tickets.p, k == 0 ? 1 : 0);
+                        if (slim) VELO_LAUNCH_T(c0, c0->lm_kernel_name, 0, eval_step_batch_lean_v_slim_kernel, dim3(nb_max, n), dim3(kEvalThreads), 0, bs, Q, packv, c0->batch_tickets.p, k == 0 ? 1 : 0);
+                        else if (lean) VELO_LAUNCH_T(c0, c0->lm_kernel_name, 0, eval_step_batch_lean_v_kernel, dim3(nb_max, n), dim3(kEvalThreads), 0, bs, Q, packv, c0->batch_tickets.p, k == 0 ? 1 : 0);
                         else VELO_LAUNCH_T(c0, c0->lm_kernel_name, 0, eval_step_batch_v_kernel, dim3(nb_max, n), dim3(kEvalThreads), 0, bs, Q, packv, c0->batch_tickets.p, k == 0 ? 1 : 0);
                         continue;
                     }

@@ -280,6 +280,7 @@ struct velo_ctx {
     int lm_persist_wgs = 0;              // workgroups per context of that launch (0 = one per virtual block); VELO_LM_PERSIST_WGS (diagnostics build)
     DevBuf<SolveCtl> solve_ctl;          // its per-context control blocks (owned by the first context of a group; zero between launches)
     DevBuf<AgCtl> ag_ctl;                // all-gather solve (lm_solve_ag_batch_kernel, lm_persist == 2): epoch, abort word and flags per context of a group
+    int lm_slim = -1;                    // the lean launch's 126-VGPR form (rows one by one): -1 = for groups on a density-shrunk grid; VELO_LM_SLIM (diagnostics build) forces 0 / 1
     int lm_lean = -1;                    // lean fused LM kernel in lock-step groups: -1 = when several groups share the chip; VELO_LM_LEAN (diagnostics build) forces 0 / 1
     // chain mode: a whole frame_to_frame as ONE chain of launches (pose scalars of the next round and the solve summaries stay on the device)
     int patch_order = 1;                 // query list in patch order (VELO_PATCH_ORDER=0: the reference's ring order)

@@ -3139,7 +3139,8 @@ __device__ __forceinline__ void eval_point_column(const double x[6], int done, i
 }
 
 // R1 cost3DPD (costfunctions.h:39-54) through the matrices of the eval point: r = N . (R p + t - v0), dr/dw_j = N . (dR/dw_j p)
-__device__ __forceinline__ void res_3dpd_mat(const double (*M)[9], const double t[3], const double p[3], const double n[3], const double v0[3],
+template <class MatPtr>      // const double (*)[9], generic or (the lean sweeps) LDS address space
+__device__ __forceinline__ void res_3dpd_mat(const MatPtr M, const double t[3], const double p[3], const double n[3], const double v0[3],
                                              double* r, double J[6]) {
     double m[3];
 #pragma unroll
@@ -3463,11 +3464,16 @@ __device__ __forceinline__ void sweep_row(const EvalArgs& A, const LMEvalPoint& 
     // the 56 accumulator registers and the prefetched rows the kernel would need scratch memory, and a kernel that touches scratch
     // at all costs ~11 us more per launch on this system.  The pointer is made opaque so that the loads are not hoisted out of the
     // loop again.  The one-launch iteration (one wave per SIMD, registers to spare) keeps them in registers: 3.2 vs 4.7 us of rows.
-    const double (*M)[9] = M_FROM_LDS ? s_pt.M : Mreg;
-    if (M_FROM_LDS) asm volatile("" : "+v"(M));
+    // The opaque pointer keeps its LDS address space: through a generic one the reads are FLAT loads, which count as global loads too,
+    // and every one of them waited for all the row loads still in flight.
     const double pd[3] = {p.x, p.y, p.z}, nd[3] = {n.x, n.y, n.z}, vd[3] = {v.x, v.y, v.z};
     double r, J[6];
-    res_3dpd_mat(M, t, pd, nd, vd, &r, J);
+    if (M_FROM_LDS) {                                            // (every M_FROM_LDS caller hands in a __shared__ LMEvalPoint: the cast relies on it)
+        typedef const __attribute__((address_space(3))) double (*LdsMat)[9];
+        LdsMat M = (LdsMat)s_pt.M;
+        asm volatile("" : "+v"(M));
+        res_3dpd_mat(M, t, pd, nd, vd, &r, J);
+    } else res_3dpd_mat(Mreg, t, pd, nd, vd, &r, J);
     double rho0, rho1;
     loss_cauchy(A.loss_a_3dpd, A.w_3dpd, r * r, &rho0, &rho1);
     acc[27] += 0.5 * rho0;
@@ -3480,9 +3486,32 @@ __device__ __forceinline__ void sweep_row(const EvalArgs& A, const LMEvalPoint& 
         for (int k = 0; k < 6; k++) A.rows_J[(size_t)row * 6 + k] = J[k] * sr;
     }
 }
+// The rows behind the prefetched ones, kRowChunk at a time.  request: the chunk's loads, whole records, addresses clamped like
+// prefetch_rows' (no load depends on a row's validity or on the thread's row count: those predicate the arithmetic only).  arrive:
+// every value of the chunk is named by an opaque use, so the loads stay where they were requested -- together, ahead of the first
+// use of any of them -- instead of being sunk one by one behind the validity test of their row (three dependent round trips per row).
+constexpr int kRowChunk = 3;
+struct RowChunk { float4 p[kRowChunk], n[kRowChunk], v[kRowChunk]; };
+__device__ __forceinline__ void row_chunk_request(const EvalArgs& A, const int i0, const int nthreads, RowChunk& g) {
+#pragma unroll
+    for (int k = 0; k < kRowChunk; k++) {
+        const int i = min(i0 + k * nthreads, A.q_end - 1);
+        g.p[k] = A.cp[i]; g.n[k] = A.cn[i]; g.v[k] = A.cv0[i];
+    }
+}
+__device__ __forceinline__ void row_chunk_arrive(RowChunk& g) {
+#pragma unroll
+    for (int k = 0; k < kRowChunk; k++)
+        asm volatile("" : "+v"(g.p[k].x), "+v"(g.p[k].y), "+v"(g.p[k].z), "+v"(g.p[k].w), "+v"(g.n[k].x), "+v"(g.n[k].y), "+v"(g.n[k].z),
+                          "+v"(g.v[k].x), "+v"(g.v[k].y), "+v"(g.v[k].z));
+}
 // this workgroup's rows at the eval point in LDS -> the 28 accumulators of every thread (the prefetched rows first, with
-// compile-time indices, then whatever is left)
-template <bool M_FROM_LDS, int PRE = kPre>
+// compile-time indices, then whatever is left, in chunks).  AHEAD (the lean kernels: one prefetched row, so nearly every thread has
+// rows behind it): the first chunk is requested before the prefetched rows are evaluated and has their arithmetic to arrive in.
+// TOGETHER = false: the rows behind the prefetched ones one by one, each loaded where it is used -- 126 VGPRs in the lean kernels
+// instead of 150 (four waves per SIMD instead of three), for groups whose LM launches run under long association launches
+// (eval_step_batch_lean_v_slim_kernel).  Same rows, same order: the partial rows do not depend on the form.
+template <bool M_FROM_LDS, int PRE = kPre, bool AHEAD = (PRE < kPre), bool TOGETHER = true>
 __device__ __forceinline__ void sweep_rows(const EvalArgs& A, const RowPrefetchT<PRE>& f, const LMEvalPoint& s_pt, const int bx, const int nbx, double acc[kNumAcc], const int tid_in = -1) {
     const int tid = bx * blockDim.x + (tid_in < 0 ? (int)threadIdx.x : tid_in), nthreads = nbx * blockDim.x;
     double Mreg[4][9];
@@ -3498,12 +3527,29 @@ __device__ __forceinline__ void sweep_rows(const EvalArgs& A, const RowPrefetchT
     for (int k = 0; k < 3; k++) t[k] = s_pt.t[k];
 #pragma unroll
     for (int k = 0; k < kNumAcc; k++) acc[k] = 0.0;
+    int i0 = A.q_begin + tid + PRE * nthreads;
+    RowChunk g;
+    if (AHEAD && TOGETHER) row_chunk_request(A, i0, nthreads, g);
 #pragma unroll
     for (int k = 0; k < PRE; k++) {
         const int i = A.q_begin + tid + k * nthreads;
         if (i < A.q_end) sweep_row<M_FROM_LDS>(A, s_pt, Mreg, t, f.p[k], f.n[k], f.v[k], i, acc);
     }
-    for (int i = A.q_begin + tid + PRE * nthreads; i < A.q_end; i += nthreads) sweep_row<M_FROM_LDS>(A, s_pt, Mreg, t, A.cp[i], A.cn[i], A.cv0[i], i, acc);
+    if (!TOGETHER) {
+        for (int i = i0; i < A.q_end; i += nthreads) sweep_row<M_FROM_LDS>(A, s_pt, Mreg, t, A.cp[i], A.cn[i], A.cv0[i], i, acc);
+        return;
+    }
+    // (requested: the first trip of an AHEAD sweep finds its chunk in flight -- also in a thread that has no row behind the prefetched
+    // ones: the addresses are clamped and the rows predicated)
+    for (bool requested = AHEAD; requested || i0 < A.q_end; requested = false, i0 += kRowChunk * nthreads) {
+        if (!requested) row_chunk_request(A, i0, nthreads, g);
+        row_chunk_arrive(g);
+#pragma unroll
+        for (int k = 0; k < kRowChunk; k++) {
+            const int i = i0 + k * nthreads;
+            if (i < A.q_end) sweep_row<M_FROM_LDS>(A, s_pt, Mreg, t, g.p[k], g.n[k], g.v[k], i, acc);
+        }
+    }
 }
 
 __device__ __forceinline__ void eval_icp_body(const EvalArgs& A, const int bx, const int nbx) {
@@ -4426,7 +4472,7 @@ lm_step_batch_kernel(LMParams Q, const LMBatchItem* __restrict__ items)
 // VIS: the contexts' visual blocks ride in the same launch -- workgroups nb_icp .. nb_icp + nb_vis - 1 of a context run the visual sweep
 // (visual_sweep_acc, the arithmetic of eval_visual_kernel) into the partial rows behind the point-to-plane ones and draw tickets like
 // the others, instead of a launch of their own ahead of every iteration (21.7 us each, 48 per call).
-template <bool M_LDS, int PRE, int CHUNK, bool VIS = false>
+template <bool M_LDS, int PRE, int CHUNK, bool VIS = false, bool ROWS_TOGETHER = true>
 __device__ __forceinline__ void eval_step_batch_body(const LMParams& Q, const LMBatchItem& it, int* __restrict__ tickets, const int first) {
     const int bx = blockIdx.x, nbx = it.nb_icp, nb_all = VIS ? it.nb_icp + it.nb_vis : it.nb_icp;
     if (bx >= nb_all) return;
@@ -4456,7 +4502,7 @@ __device__ __forceinline__ void eval_step_batch_body(const LMParams& Q, const LM
         else visual_sweep_acc(A, s_pt, bx - nbx, it.nb_vis, acc);
         block_reduce_store<true>(acc, A.partials + (size_t)(A.vis_row0 + bx - nbx) * kNumAcc, s_scratch);
     } else {
-        sweep_rows<M_LDS, PRE>(A, f, s_pt, bx, nbx, acc);
+        sweep_rows<M_LDS, PRE, (PRE < kPre), ROWS_TOGETHER>(A, f, s_pt, bx, nbx, acc);
         block_reduce_store<true>(acc, A.partials + (size_t)bx * kNumAcc, s_scratch);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // this thread's row entries have been written through
@@ -4532,6 +4578,17 @@ eval_step_batch_lean_v_kernel(LMParams Q, LMBatchPackV P, int* __restrict__ tick
 #if VELO_DEF_LMB
 {
     eval_step_batch_body<true, VELO_LEAN_PRE, 64>(Q, P.item[blockIdx.y], tickets, first);
+}
+#else
+;
+#endif
+// the same launch for groups that register against a density-shrunk grid (scan-to-map): their LM launches spend nearly all of their time
+// under 330 us association launches, where the launch with 150 VGPRs takes 48 us and the one with 126 takes 41 (C4: 1,770 against 1,815 pairs/s)
+__global__ void __launch_bounds__(kEvalThreads) __attribute__((amdgpu_num_vgpr(152)))
+eval_step_batch_lean_v_slim_kernel(LMParams Q, LMBatchPackV P, int* __restrict__ tickets, int first)
+#if VELO_DEF_LMB
+{
+    eval_step_batch_body<true, VELO_LEAN_PRE, 64, false, false>(Q, P.item[blockIdx.y], tickets, first);
 }
 #else
 ;
@@ -4632,7 +4689,7 @@ __device__ __forceinline__ int persist_sweep(const EvalArgs& A, SolveCtl* __rest
     __syncthreads();
     double acc[kNumAcc];
 #ifndef VELO_T2
-    sweep_rows<true, PRE>(A, f, *s_pt, bx, nb, acc);
+    sweep_rows<true, PRE, false>(A, f, *s_pt, bx, nb, acc);
 #else
     for (int q = 0; q < kNumAcc; q++) acc[q] = f.p[0].x;
 #endif

@@ -88,7 +88,7 @@ __device__ __forceinline__ void lm_solve_ag_body(const LMParams& Q, const LMBatc
         asm volatile("" : "+v"(tt));                                      // opaque per iteration: see block_reduce_store
         const EvalArgs& A = it.A;
         double acc[kNumAcc];
-        sweep_rows<M_LDS, PRE>(A, f, s_pt, bx, nb, acc, tt);
+        sweep_rows<M_LDS, PRE, false>(A, f, s_pt, bx, nb, acc, tt);
         block_reduce_store<true>(acc, A.partials + (size_t)(k & 1) * half + (size_t)bx * kNumAcc, s_scratch, tt);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // this thread's row entries have been written through
         __syncthreads();
