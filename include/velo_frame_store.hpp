@@ -8,6 +8,12 @@
 //     instead of matchUsingId + getLandmarksAtFrame + frameToFrame (main.cpp:366-405):
 //                 dpose = velo_hip::frameToFrameResident<Eigen::Matrix4d>(ctx, frames, frame, frame - dframe, &pose_inverse,
 //                             scans_M, scans_S, kd_trees, transform, matches, good_matches, residual_type, enable_icp);
+//     directly after the dframe == 1 registration, instead of removeSlightlyLessTerribleFeatures (main.cpp:504-514):
+//                 frames.pruneFrame(ctx, keypoints, keypoints_p, kp_with_depth, keypoint_ids, descriptors, has_depth, frame);
+//     the resident frame and the caller's containers are then what the reference's function leaves, and the frame serves the further
+//     diagonal edges, its loop-closure edges and the next frame's edges as it is; good_matches keeps the old indices.  The result of
+//     a filter that stays on the host (removeTerribleFeatures) goes in as an index list:
+//                 frames.keepFrame(cam, frame, indices, keypoints, keypoints_p, kp_with_depth, keypoint_ids, descriptors, has_depth);
 //     frames.dropFrame(frame) when a frame leaves the window.
 //     the loop-closure edge (main.cpp:351-365, ba == 1): once a frame's FREAK descriptors are final,
 //                 frames.putDescriptors(descriptors, frame);
@@ -18,7 +24,8 @@
 //
 // Templated over the container types like the other adaptors (cv::Point2f, pcl::PointCloud<pcl::PointXYZ>::Ptr, Eigen::Matrix4d or
 // stand-ins): a keypoint needs .x / .y, a cloud pointer ->points (a vector of points with .x / .y / .z), a matrix operator()(row, col),
-// a descriptor matrix .rows, .cols (64) and .ptr<unsigned char>(row), as cv::Mat has them.
+// a descriptor matrix .rows, .cols (64) and .ptr<unsigned char>(row), as cv::Mat has them; pruneFrame / keepFrame also use its
+// resize(rows) and the cloud pointer's element_type, push_back and default constructor.
 #ifndef VELO_FRAME_STORE_HPP_
 #define VELO_FRAME_STORE_HPP_
 #include <cstring>
@@ -28,6 +35,42 @@
 #include "velo_frame_to_frame.hpp"
 
 namespace velo_hip {
+
+namespace detail {
+
+// velo.h:302-325 on the containers of one camera of one frame, with the ascending list of kept indices the device wrote in place of
+// the std::set: every item moves towards the front, so the containers are compacted in place and cut; the cloud is made anew
+template <class Points, class CloudPtr, class IdVec, class Mat, class DepthVec>
+void apply_kept(const int32_t* kept, const int m, Points& keypoints, Points& keypoints_p, CloudPtr& kp_with_depth, IdVec& keypoint_ids,
+                Mat& descriptors, DepthVec& has_depth) {
+    typedef typename CloudPtr::element_type Cloud;
+    CloudPtr tmp_kp_with_depth(new Cloud);
+    const bool with_p = keypoints_p.size() == keypoints.size(), with_rows = descriptors.rows > 0;
+    int jd = 0;
+    for (int j = 0; j < m; j++) {
+        const size_t i = (size_t)kept[j];
+        keypoints[(size_t)j] = keypoints[i];
+        if (with_p) keypoints_p[(size_t)j] = keypoints_p[i];
+        keypoint_ids[(size_t)j] = keypoint_ids[i];
+        if (with_rows && i != (size_t)j)
+            std::memmove(descriptors.template ptr<unsigned char>(j), descriptors.template ptr<unsigned char>((int)i), (size_t)descriptors.cols);
+        const int d = has_depth[i];
+        if (d != -1) {
+            tmp_kp_with_depth->push_back(kp_with_depth->points[(size_t)d]);
+            has_depth[(size_t)j] = jd++;
+        } else {
+            has_depth[(size_t)j] = -1;
+        }
+    }
+    keypoints.resize((size_t)m);
+    if (with_p) keypoints_p.resize((size_t)m);
+    keypoint_ids.resize((size_t)m);
+    has_depth.resize((size_t)m);
+    if (with_rows) descriptors.resize((size_t)m);
+    kp_with_depth = tmp_kp_with_depth;
+}
+
+}  // namespace detail
 
 class FrameStore {
 public:
@@ -84,6 +127,45 @@ public:
     }
 
     int dropFrame(int frame) { return status_ = velo_frames_drop(ctx_, frame); }
+
+    // removeSlightlyLessTerribleFeatures(keypoints, ..., frame, good_matches) (velo.h:272-327) with good_matches read on the device:
+    // `ctx` holds the visual set frameToFrameResident / frameToFrameLoop built with `frame` as frame1 and the flags of that
+    // registration.  The resident frame is pruned on the device (velo_frames_prune); the kept indices come back and cut the caller's
+    // containers of every camera to what the reference's function leaves.  Nothing changes when the library refuses the prune.
+    template <class Keypoints, class Clouds, class Ids, class Descriptors, class HasDepth>
+    int pruneFrame(Context& ctx, Keypoints& keypoints, Keypoints& keypoints_p, Clouds& kp_with_depth, Ids& keypoint_ids, Descriptors& descriptors,
+                   HasDepth& has_depth, int frame) {
+        if (ctx.get() != ctx_) return status_ = VELO_ERR_INVALID;      // the store lives in another context
+        const int32_t cap = frameSize(frame);
+        if (status_ != VELO_OK) return status_;
+        std::vector<int32_t> n_kept(8, 0), n_wd(8, 0), kept((size_t)(cap > 0 ? cap : 1));
+        int32_t total = 0;
+        status_ = velo_frames_prune(ctx_, frame, &n_kept[0], &n_wd[0], &kept[0], cap, &total);
+        if (status_ != VELO_OK) return status_;
+        size_t first = 0;
+        for (int cam = 0; cam < num_cams_; cam++) {
+            detail::apply_kept(&kept[first], n_kept[(size_t)cam], keypoints[cam][frame], keypoints_p[cam][frame], kp_with_depth[cam][frame],
+                               keypoint_ids[cam][frame], descriptors[cam][frame], has_depth[cam][frame]);
+            first += (size_t)n_kept[(size_t)cam];
+        }
+        return status_;
+    }
+
+    // The same for ONE camera and an index list (any order, duplicates allowed) made on the host: velo_frames_keep, then the
+    // containers of that camera.
+    template <class Indices, class Keypoints, class Clouds, class Ids, class Descriptors, class HasDepth>
+    int keepFrame(int cam, int frame, const Indices& indices, Keypoints& keypoints, Keypoints& keypoints_p, Clouds& kp_with_depth,
+                  Ids& keypoint_ids, Descriptors& descriptors, HasDepth& has_depth) {
+        const size_t n = keypoints[cam][frame].size();
+        std::vector<int32_t> idx(indices.begin(), indices.end()), kept(n > 0 ? n : 1);
+        int32_t n_kept = 0, n_wd = 0;
+        status_ = velo_frames_keep(ctx_, frame, cam, idx.empty() ? 0 : &idx[0], (int32_t)idx.size(), &kept[0], (int32_t)n, &n_kept, &n_wd);
+        if (status_ != VELO_OK) return status_;
+        if ((size_t)n_kept > n) return status_ = VELO_ERR_STATE;       // the containers are not the frame that was put
+        detail::apply_kept(&kept[0], n_kept, keypoints[cam][frame], keypoints_p[cam][frame], kp_with_depth[cam][frame], keypoint_ids[cam][frame],
+                           descriptors[cam][frame], has_depth[cam][frame]);
+        return status_;
+    }
 
     // keypoints of `frame` over all cameras as the library holds them: no match list of a registration against it is longer
     int32_t frameSize(int frame) {

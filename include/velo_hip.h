@@ -762,6 +762,47 @@ int velo_build_matches_desc_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t*
 int velo_match_frames(velo_ctx* ctx, int32_t frame1, const int32_t* frames2, int32_t n_cand, double match_thresh, int32_t* n_kept,
                       int32_t* min_dist);
 
+/* --- pruning a resident frame to a registration's good matches (removeSlightlyLessTerribleFeatures, velo.h:272-327, main.cpp:504-514) ---
+ * Read-back of one entry as the store holds it: *n / *n_with_depth its counts, *has_rows 1 when it holds descriptor rows; the first
+ * `capacity` items of ids, keypoints_xy, has_depth and rows (64 bytes each) and the first `capacity_with_depth` depth points are
+ * written; every array and every count may be NULL.  Synchronises.  VELO_ERR_STATE: no velo_frames_reset, or an entry never put. */
+int velo_frames_get(velo_ctx* ctx, int32_t frame, int32_t cam, int32_t* ids, float* keypoints_xy /* n x 2 */, int32_t* has_depth,
+                    float* kp_with_depth_xyz /* n_with_depth x 3 */, uint8_t* rows /* n x 64 */, int32_t capacity, int32_t capacity_with_depth,
+                    int32_t* n, int32_t* n_with_depth, int32_t* has_rows);
+/* Cuts ONE entry down to the SET of indices in keep_idx (any order, duplicates allowed: the std::set of velo.h:287-290), on the device,
+ * exactly as velo.h:302-325 does: the kept keypoints stay in ascending old index; ids, keypoints and the descriptor rows (when the
+ * entry holds rows) are gathered; has_depth[j] becomes the rank of j among the kept keypoints with depth, else -1; the new cloud is
+ * old_cloud[old has_depth] in KEYPOINT order -- two keypoints that shared a depth point get a copy each, so the cloud can grow.  The
+ * landmark store is untouched.  kept_out (may be NULL): the first `capacity` kept old indices, ascending; *n_kept / *n_with_depth (may
+ * be NULL) the entry's new counts, which velo_frames_count reports from now on (the directory's largest id stays an upper bound).
+ * n_keep == 0 empties the entry, which still counts as put.  This is how the result of a filter that stays on the host
+ * (removeTerribleFeatures, velo.h:232-270) reaches the store: 4 bytes per kept keypoint instead of a second put of frame and rows.
+ * Refused before anything changes: VELO_ERR_INVALID for an index outside [0, n) or a NULL list with n_keep > 0, VELO_ERR_STATE for an
+ * entry never put.  One upload (the call's tables and the list), three launches (mark, count, move into scratch), one copy back (the
+ * chunk counts and the kept indices), one synchronisation, then device-to-device copies of the result over the entry's block, queued
+ * on the context's stream: no keypoint, depth point or descriptor byte crosses the bus, and no device allocation in the steady state. */
+int velo_frames_keep(velo_ctx* ctx, int32_t frame, int32_t cam, const int32_t* keep_idx, int32_t n_keep, int32_t* kept_out, int32_t capacity,
+                     int32_t* n_kept, int32_t* n_with_depth);
+/* removeSlightlyLessTerribleFeatures(..., frame, good_matches) for every camera of `frame`, the keep set read on the device from the
+ * context's visual set: keypoint i of camera cam stays iff some record with that cam and point1 == i has a non-zero gate flag in any
+ * of its three slots -- exactly the point1 values velo_get_good_matches reports.  The result per camera is velo_frames_keep's.
+ * n_kept / n_with_depth [n_cams] (may be NULL); kept_out [capacity] (may be NULL) the kept old indices, camera-major and ascending,
+ * with which the caller compacts keypoints_p and whatever else it keeps; *n_out (may be NULL) their total.  The visual set and
+ * velo_get_good_matches keep the OLD indices, as good_matches does in the reference.
+ * The library must know that the visual set indexes these entries: velo_build_matches[_desc][_batch] record frame1 and a stamp of
+ * each of its entries; velo_set_visual, a velo_frames_put / _keep / _prune / _drop of that frame and velo_frames_reset invalidate
+ * them.  VELO_ERR_STATE, with nothing changed: no frame store; a camera of `frame` never put; `frame` is not the recorded frame1; a
+ * stale stamp (so a second prune on one visual set); no registration or velo_build_visual since the build (the flags are not valid);
+ * a sharded context (velo_set_query_shard / a communicator with world > 1), whose sweep covers a slice of the visual set only. */
+int velo_frames_prune(velo_ctx* ctx, int32_t frame, int32_t* n_kept /* [n_cams] */, int32_t* n_with_depth /* [n_cams] */, int32_t* kept_out,
+                      int32_t capacity, int32_t* n_out);
+/* The same for (ctxs[i], frames[i]), i < n_ctx, in the SAME launches, under the rules of the other batch entries (distinct contexts on
+ * one device, the first lends its stream, staging and scratch and waits for the others' streams, n_ctx == 1 IS the single entry,
+ * camera counts may differ); n_kept / n_with_depth [n_ctx][8], kept_out [n_ctx][capacity], n_out [n_ctx].  No context changes when
+ * one is refused.  Every context's entries and outputs are byte-identical to the single entry's. */
+int velo_frames_prune_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* frames, int32_t* n_kept, int32_t* n_with_depth, int32_t* kept_out,
+                            int32_t capacity, int32_t* n_out);
+
 /* Read-back of the context's device-side visual set, whoever wrote it (velo_set_visual or velo_build_matches): *n = its records,
  * the first `capacity` are written (out may be NULL). */
 int velo_get_visual(velo_ctx* ctx, velo_match* out, int32_t capacity, int32_t* n);

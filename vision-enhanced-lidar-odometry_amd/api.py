@@ -304,6 +304,11 @@ SIGNATURES = {
     "velo_build_matches_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                            C.c_void_p]),
     "velo_get_visual": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(C.c_int32)]),
+    "velo_frames_get": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                  _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
+    "velo_frames_keep": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
+    "velo_frames_prune": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _P(C.c_int32)]),
+    "velo_frames_prune_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "velo_frames_put_descriptors": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
     "velo_frames_desc_info": (C.c_int, [_ctx, C.c_void_p]),
     "velo_build_matches_desc": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int32, _P(C.c_int32)]),
@@ -812,6 +817,38 @@ class Context:
         self._check(self._lib.velo_match_frames(self._h, int(frame1), vp(f2) if len(f2) else None, len(f2), float(match_thresh), vp(kept), vp(md)))
         return kept[:len(f2)], md[:len(f2)]
 
+    # -- pruning a resident frame (removeSlightlyLessTerribleFeatures, velo.h:272-327) ---------------------------------------
+    def frames_get(self, frame: int, cam: int):
+        """One entry as the store holds it: (ids [n] i32, keypoints [n, 2] f32, has_depth [n] i32, kp_with_depth [m, 3] f32,
+        rows uint8 [n, 64] or None when the entry holds no descriptor rows)"""
+        n, m, hr = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.velo_frames_get(self._h, int(frame), int(cam), None, None, None, None, None, 0, 0, C.byref(n), C.byref(m), C.byref(hr)))
+        ids, has = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32)
+        xy, cloud = np.zeros((n.value, 2), np.float32), np.zeros((m.value, 3), np.float32)
+        rows = np.zeros((n.value, 64), np.uint8) if hr.value else None
+        vp = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None   # noqa: E731
+        self._check(self._lib.velo_frames_get(self._h, int(frame), int(cam), vp(ids), vp(xy), vp(has), vp(cloud), vp(rows), n.value, m.value,
+                                              C.byref(n), C.byref(m), C.byref(hr)))
+        return ids, xy, has, cloud, rows
+
+    def frames_keep(self, frame: int, cam: int, keep_idx):
+        """Cuts the entry (frame, cam) down to the SET of indices in keep_idx (any order, duplicates allowed) on the device, as
+        velo.h:302-325 does; returns (kept old indices, ascending, i32; the entry's new n_with_depth)"""
+        k = np.ascontiguousarray(np.asarray(keep_idx, dtype=np.int32).reshape(-1))
+        cap = max(int(self.frames_count(frame)[0][cam]), 0) if 0 <= cam < self.frames_info()["n_cams"] else 0
+        kept = np.zeros(max(cap, 1), dtype=np.int32)
+        n, m = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.velo_frames_keep(self._h, int(frame), int(cam), C.c_void_p(k.ctypes.data) if len(k) else None, len(k),
+                                               C.c_void_p(kept.ctypes.data), cap, C.byref(n), C.byref(m)))
+        return kept[:n.value].copy(), m.value
+
+    def frames_prune(self, frame: int):
+        """removeSlightlyLessTerribleFeatures on the device for every camera of `frame`, the keep set read from the visual set
+        build_matches[_desc] made with `frame` as frame1 and the flags of the registration since: per camera the kept old indices
+        (ascending, i32), and n_with_depth [n_cams] i32"""
+        kept, n_wd = frames_prune_batch([self], [frame])[0]
+        return kept, n_wd
+
     def get_visual(self, capacity: Optional[int] = None) -> np.ndarray:
         """The context's device-side visual set (velo_match records), whoever wrote it"""
         n = C.c_int32(0)
@@ -1285,6 +1322,32 @@ def build_matches_desc_batch(ctxs, frames1, frames2, poses2_inv=None, match_thre
     if raw or capacity is not None:
         return per_cam, pairs[:, :cap], n
     return [(per_cam[i, :n_cams[i]].copy(), pairs[i, :n[i]].copy()) for i in range(n_ctx)]
+
+
+def frames_prune_batch(ctxs, frames, raw: bool = False):
+    """Context.frames_prune for (ctxs[i], frames[i]) in ONE call (the same launches for all): per context (list of the kept old
+    indices per camera, n_with_depth [n_cams]).  raw: the call's arrays as they are -- n_kept [n_ctx, 8], n_with_depth [n_ctx, 8],
+    kept_out [n_ctx, capacity], n_out [n_ctx]."""
+    lib, arr = _batch_lib_and_handles(ctxs)
+    n_ctx = len(ctxs)
+    if len(frames) != n_ctx:
+        raise ValueError("frames_prune_batch: one frame per context")
+    f = np.ascontiguousarray(np.asarray(frames, dtype=np.int32).reshape(-1))
+    sizes = [c.frames_count(fr) for c, fr in zip(ctxs, f)]     # also raises when a context has no frame store
+    cap = max(s[1] for s in sizes)
+    n_kept, n_wd = np.zeros((n_ctx, 8), dtype=np.int32), np.zeros((n_ctx, 8), dtype=np.int32)
+    kept = np.zeros((n_ctx, max(cap, 1)), dtype=np.int32)
+    n = np.zeros(n_ctx, dtype=np.int32)
+    vp = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+    _batch_check(lib, lib.velo_frames_prune_batch(C.cast(arr, C.c_void_p), n_ctx, vp(f), vp(n_kept), vp(n_wd), vp(kept), cap, vp(n)))
+    if raw:
+        return n_kept, n_wd, kept[:, :cap], n
+    out = []
+    for i in range(n_ctx):
+        n_cams = len(sizes[i][0])
+        cuts = np.r_[0, np.cumsum(n_kept[i, :n_cams])]
+        out.append(([kept[i, cuts[c]:cuts[c + 1]].copy() for c in range(n_cams)], n_wd[i, :n_cams].copy()))
+    return out
 
 
 SCAN_ON_DEVICE, SCAN_SHARED, SCAN_PROMOTE = 1, 2, 4

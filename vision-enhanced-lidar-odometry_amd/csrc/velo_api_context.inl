@@ -627,6 +627,7 @@ static int set_visual_impl(velo_ctx* c, const velo_match* m, int32_t n, bool wai
     c->n_matches = n;
     c->h_matches.assign(m, m + n);
     c->vflags_valid = false;
+    c->vis_frame1 = -1;                                               // these records index the caller's arrays, not a resident frame
     c->h_vflags.clear();
     lap("host copy of the records");
     if (n > 0) {

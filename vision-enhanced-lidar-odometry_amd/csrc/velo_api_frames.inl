@@ -43,7 +43,7 @@ struct FrStore {
     FrArena<uint4, 4> rows;                         // the descriptor rows, 64 bytes each
     DevBuf<unsigned> d_keys;                        // nearest-row keys and min_dist of a descriptor-matched call
     // host: the directories, frame * 8 + cam -> block
-    struct Entry { Block blk; int n = 0, n_wd = 0, max_id = -1; };
+    struct Entry { Block blk; int n = 0, n_wd = 0, max_id = -1; uint64_t gen = 0; };   // gen: a stamp no two versions of any entry share
     std::unordered_map<int64_t, Entry> dir;
     struct RowEntry { Block blk; int n = 0; };
     std::unordered_map<int64_t, RowEntry> rdir;
@@ -51,6 +51,8 @@ struct FrStore {
     // staging of velo_build_matches (a batch call uses the first context's); every call ends in a synchronisation, so nothing guards it
     PinBuf<> h_in, h_out;
     DevBuf<unsigned char> d_in, d_out;
+    DevBuf<unsigned char> d_prune;                  // scratch of a prune call: the keep maps | the gathered blocks | the gathered rows
+    uint64_t next_gen = 1;
 };
 
 namespace {
@@ -73,6 +75,14 @@ void fr_side(const FrStore& S, const FrStore::Entry& e, FrSide* out) {
     out->xy = reinterpret_cast<const float*>(b + 2 * (size_t)e.n);
     out->cloud = reinterpret_cast<const float*>(b + 4 * (size_t)e.n);
     out->n = e.n; out->pad = 0;
+}
+
+// The context's visual set indexes the entries of frame1 as they are now (velo_frames_prune asks): whatever replaces, prunes or
+// drops an entry gives it a new stamp, velo_set_visual and velo_frames_reset forget the frame.
+void fr_stamp_visual(velo_ctx* c, int frame1) {
+    const FrStore& S = *c->fr;
+    c->vis_frame1 = frame1;
+    for (int cam = 0; cam < S.n_cams; cam++) c->vis_gen[cam] = S.dir.at(lm_key(frame1, cam)).gen;
 }
 
 // the state velo_set_visual leaves, for context i of a build call whose records are in vm: per_cam [n_cams] matches, pairs their
@@ -261,6 +271,7 @@ int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32
             for (int k = chunk0[(size_t)u]; k < chunk0[(size_t)u + 1]; k++) per_cam[cam] += h_counts[k];
         }
         fr_leave_visual(ctxs[i], i, per_cam, h_pairs + 2 * pair0[i], n_per_cam, pairs_out, capacity, n_out);
+        fr_stamp_visual(ctxs[i], frames1[i]);
     }
     return VELO_OK;
 }
@@ -393,8 +404,169 @@ int fr_desc_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32_
         int per_cam[kLmMaxCams];
         for (int cam = 0; cam < ctxs[i]->fr->n_cams; cam++) per_cam[cam] = h_job[2 * (unit0[i] + cam) + 1];
         fr_leave_visual(ctxs[i], i, per_cam, h_pairs + 2 * pair0[i], n_per_cam, pairs_out, capacity, n_out);
+        fr_stamp_visual(ctxs[i], frames1[i]);
     }
     return VELO_OK;
+}
+
+// One launch set that cuts entries down to a keep set (velo.h:282-326 per entry).  keep_cam < 0: every camera of frames[i] of ctxs[i],
+// the keep set read from the context's visual set and its gate flags (velo_frames_prune[_batch]; outputs [n_ctx][8], [n_ctx][capacity],
+// [n_ctx]); else the ONE entry (frames[0], keep_cam) of the one context and the n_keep indices of keep_idx (velo_frames_keep; outputs
+// of one entry).  The callers have checked the arguments; the state is checked here, before anything changes.
+int fr_prune_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, int keep_cam, const int32_t* keep_idx, int32_t n_keep, int32_t* n_kept,
+                 int32_t* n_with_depth, int32_t* kept_out, int32_t capacity, int32_t* n_out) {
+    const bool by_list = keep_cam >= 0;
+    const char* who = by_list ? "velo_frames_keep" : "velo_frames_prune";
+    for (int i = 0; i < n_ctx; i++) {
+        velo_ctx* c = ctxs[i];
+        VELO_TRY(fr_need_store(c, who));
+        const FrStore& S = *c->fr;
+        if (by_list) {
+            auto it = S.dir.find(lm_key(frames[i], keep_cam));
+            if (it == S.dir.end()) return fail(VELO_ERR_STATE, "frame %d, camera %d has not been put", frames[i], keep_cam);
+            for (int k = 0; k < n_keep; k++)
+                if (keep_idx[k] < 0 || keep_idx[k] >= it->second.n)
+                    return fail(VELO_ERR_INVALID, "keep_idx[%d] = %d; the entry has %d keypoints", k, keep_idx[k], it->second.n);
+            continue;
+        }
+        for (int cam = 0; cam < S.n_cams; cam++)
+            if (!S.dir.count(lm_key(frames[i], cam))) return fail(VELO_ERR_STATE, "context %d: frame %d, camera %d has not been put", i, frames[i], cam);
+        if (c->vis_frame1 != frames[i])
+            return fail(VELO_ERR_STATE, "context %d: the visual set was not built with frame %d as frame1 (velo_build_matches[_desc])", i, frames[i]);
+        for (int cam = 0; cam < S.n_cams; cam++)
+            if (c->vis_gen[cam] != S.dir.at(lm_key(frames[i], cam)).gen)
+                return fail(VELO_ERR_STATE, "context %d: frame %d, camera %d has changed since the visual set was built from it", i, frames[i], cam);
+        if (!c->vflags_valid) return fail(VELO_ERR_STATE, "context %d: no registration or velo_build_visual since the visual set was built", i);
+        if (c->shard_world > 1) return fail(VELO_ERR_STATE, "context %d: rank %d of %d sweeps a slice of the visual set only", i, c->shard_rank, c->shard_world);
+    }
+    velo_ctx* c0 = ctxs[0];
+    FrStore* L = c0->fr.get();
+    HIP_TRY(hipSetDevice(c0->device));
+    // the units of the call, context-major and camera-major, and where each one's share of the scratch and of the outputs lies
+    struct Span { size_t map, out, rows, kept; };
+    std::vector<FrStore::Entry*> ent;
+    std::vector<FrStore::RowEntry*> rent;
+    std::vector<Span> span;
+    std::vector<int> unit0(n_ctx + 1, 0), chunk0;
+    size_t map_bytes = 0, out_words = 0, row_count = 0, all_n = 0;
+    int n_chunks = 0, max_chunks = 0, max_src = by_list ? (int)n_keep : 0;
+    for (int i = 0; i < n_ctx; i++) {
+        FrStore& S = *ctxs[i]->fr;
+        for (int cam = by_list ? keep_cam : 0; cam < (by_list ? keep_cam + 1 : S.n_cams); cam++) {
+            FrStore::Entry& e = S.dir.at(lm_key(frames[i], cam));
+            auto r = S.rdir.find(lm_key(frames[i], cam));
+            ent.push_back(&e);
+            rent.push_back(r != S.rdir.end() ? &r->second : nullptr);
+            span.push_back(Span{map_bytes, out_words, row_count, all_n});
+            chunk0.push_back(n_chunks);
+            const int ch = cdiv(e.n, kFrChunk);
+            n_chunks += ch;
+            max_chunks = std::max(max_chunks, ch);
+            map_bytes += fb_align64((size_t)e.n);
+            out_words += fr_round(7 * (size_t)e.n);                  // at most n kept, every one with a depth point of its own
+            if (r != S.rdir.end()) row_count += (size_t)e.n;
+            all_n += (size_t)e.n;
+        }
+        unit0[i + 1] = (int)ent.size();
+        if (!by_list) max_src = std::max(max_src, ctxs[i]->n_matches);
+    }
+    chunk0.push_back(n_chunks);
+    const int n_units = (int)ent.size();
+    // device input: units | sources | the keep list; device output, copied back in one piece: the chunk counts | the kept indices
+    const size_t unit_bytes = fb_align64(sizeof(FrPruneUnit) * (size_t)n_units), src_bytes = fb_align64(sizeof(FrPruneSrc) * (size_t)n_ctx);
+    const size_t in_bytes = unit_bytes + src_bytes + sizeof(int) * (size_t)(by_list ? n_keep : 0);
+    const size_t cnt_bytes = fb_align64(sizeof(int) * (size_t)n_chunks);
+    const size_t back_bytes = cnt_bytes + sizeof(int) * all_n;
+    const size_t scratch = map_bytes + sizeof(int) * out_words + 64 * row_count;
+    VELO_TRY(L->h_in.reserve(in_bytes));
+    VELO_TRY(L->h_out.reserve(std::max<size_t>(back_bytes, 64)));
+    VELO_TRY(L->d_in.reserve(in_bytes));
+    VELO_TRY(L->d_out.reserve(std::max<size_t>(back_bytes, 64)));
+    if (scratch > L->d_prune.cap) {                                     // geometric, and kept
+        HIP_TRY(hipStreamSynchronize(c0->stream));                       // the copies of the call before may still read the old scratch
+        VELO_TRY(L->d_prune.reserve(std::max(scratch, 2 * L->d_prune.cap)));
+    }
+    unsigned char* d_map = L->d_prune.p;
+    int* d_blocks = (int*)(L->d_prune.p + map_bytes);
+    uint4* d_rows = (uint4*)(L->d_prune.p + map_bytes + sizeof(int) * out_words);
+    int* d_counts = (int*)L->d_out.p;
+    int* d_kept = (int*)(L->d_out.p + cnt_bytes);
+    {
+        FrPruneUnit* hu = (FrPruneUnit*)L->h_in.p;
+        FrPruneSrc* hs = (FrPruneSrc*)(L->h_in.p + unit_bytes);
+        std::memset(L->h_in.p, 0, in_bytes);
+        for (int i = 0; i < n_ctx; i++) {
+            velo_ctx* c = ctxs[i];
+            const FrStore& S = *c->fr;
+            for (int u = unit0[i]; u < unit0[i + 1]; u++) {
+                FrPruneUnit& U = hu[u];
+                fr_side(S, *ent[u], &U.f);
+                U.rows = rent[u] ? S.rows.at(rent[u]->blk) : nullptr;
+                U.map = d_map + span[u].map;
+                U.out = d_blocks + span[u].out;
+                U.rows_out = d_rows + 4 * span[u].rows;
+                U.kept = d_kept + span[u].kept;
+                U.chunk0 = chunk0[(size_t)u]; U.n_chunks = chunk0[(size_t)u + 1] - chunk0[(size_t)u];
+            }
+            FrPruneSrc& R = hs[i];
+            R.unit0 = unit0[i]; R.n_cams = unit0[i + 1] - unit0[i];
+            if (by_list) {
+                R.keep = (const int*)(L->d_in.p + unit_bytes + src_bytes); R.n = n_keep;
+                if (n_keep > 0) std::memcpy(L->h_in.p + unit_bytes + src_bytes, keep_idx, sizeof(int) * (size_t)n_keep);
+            } else { R.vm = c->vm.p; R.vflags = c->vflags.p; R.n = c->n_matches; }
+        }
+    }
+    VELO_TRY(fb_gather(ctxs, n_ctx, nullptr));
+    hipStream_t st = c0->stream;
+    if (n_chunks > 0) {
+        HIP_TRY(hipMemcpyAsync(L->d_in.p, L->h_in.p, in_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_map, 0, map_bytes, st));
+        const FrPruneUnit* d_units = (const FrPruneUnit*)L->d_in.p;
+        const dim3 g((unsigned)max_chunks, (unsigned)n_units);
+        if (max_src > 0)
+            hipLaunchKernelGGL(fr_mark_kernel, dim3((unsigned)cdiv(max_src, 256), (unsigned)n_ctx), dim3(256), 0, st, d_units,
+                               (const FrPruneSrc*)(L->d_in.p + unit_bytes));
+        hipLaunchKernelGGL(fr_prune_count_kernel, g, dim3(kFrChunk), 0, st, d_units, d_counts);
+        hipLaunchKernelGGL(fr_prune_move_kernel, g, dim3(kFrChunk), 0, st, d_units, (const int*)d_counts);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(L->h_out.p, L->d_out.p, back_bytes, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    // The host now knows every unit's new size: it places the block (in place unless shared depth points made the cloud longer than the
+    // block holds) and queues the copies out of the scratch behind the launches -- the only writes into an arena.  A unit's directory
+    // entry changes after the last call of that unit that can fail.
+    const int* h_counts = (const int*)L->h_out.p;
+    const int* h_kept = (const int*)(L->h_out.p + cnt_bytes);
+    for (int i = 0; i < n_ctx; i++) {
+        velo_ctx* c = ctxs[i];
+        FrStore& S = *c->fr;
+        int total = 0;
+        for (int u = unit0[i]; u < unit0[i + 1]; u++) {
+            int m = 0, m_wd = 0;
+            for (int k = chunk0[(size_t)u]; k < chunk0[(size_t)u + 1]; k++) { m += h_counts[k] & 0xffff; m_wd += h_counts[k] >> 16; }
+            FrStore::Entry& e = *ent[u];
+            const size_t words = 4 * (size_t)m + 3 * (size_t)m_wd;
+            BlockList::Plan plan;
+            // an arena that has to grow is copied on its context's stream: not before the copies this call has queued into it have landed
+            if (S.kp.list.plan(&e.blk, fr_round(words)).grow_to > 0) HIP_TRY(hipStreamSynchronize(st));
+            VELO_TRY(S.kp.place(c, &e.blk, fr_round(words), &plan));
+            if (words > 0)
+                HIP_TRY(hipMemcpyAsync(S.kp.at(plan.block), d_blocks + span[u].out, sizeof(int) * words, hipMemcpyDeviceToDevice, st));
+            if (rent[u] && m > 0)                                      // m <= n rows: always in place
+                HIP_TRY(hipMemcpyAsync(S.rows.at(rent[u]->blk), d_rows + 4 * span[u].rows, 64 * (size_t)m, hipMemcpyDeviceToDevice, st));
+            S.kp.list.commit(plan, &e.blk);
+            e.blk = plan.block; e.n = m; e.n_wd = m_wd; e.gen = S.next_gen++;      // max_id stays an upper bound: it only sizes the slot table
+            if (rent[u]) rent[u]->n = m;
+            const int slot = by_list ? 0 : i * kLmMaxCams + (u - unit0[i]);
+            if (n_kept) n_kept[slot] = m;
+            if (n_with_depth) n_with_depth[slot] = m_wd;
+            if (kept_out)
+                for (int k = 0; k < m && total + k < capacity; k++) kept_out[(size_t)i * capacity + (size_t)(total + k)] = h_kept[span[u].kept + (size_t)k];
+            total += m;
+        }
+        if (n_out) n_out[i] = total;
+    }
+    return fb_release(ctxs, n_ctx);
 }
 
 }  // namespace
@@ -409,6 +581,7 @@ int velo_frames_reset(velo_ctx* c, int32_t n_cams, const float* cam_trans, int32
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));           // nothing of the old store is in flight when it goes
     c->fr.reset();
+    c->vis_frame1 = -1;                                 // whatever the visual set was built from is gone
     std::shared_ptr<FrStore> S = std::make_shared<FrStore>();
     S->n_cams = n_cams;
     std::memcpy(S->cam_t, cam_trans, sizeof(float) * 3 * (size_t)n_cams);
@@ -464,7 +637,7 @@ int velo_frames_put(velo_ctx* c, int32_t frame, int32_t cam, const int32_t* ids,
     }
     // the directory after the last call that can fail
     S.kp.list.commit(plan, old_blk);
-    S.dir[key] = FrStore::Entry{plan.block, n, n_with_depth, max_id};
+    S.dir[key] = FrStore::Entry{plan.block, n, n_with_depth, max_id, S.next_gen++};
     fr_free_rows(S, key);                                            // the keypoints the rows belonged to are gone
     return VELO_OK;
 }
@@ -590,6 +763,59 @@ int velo_match_frames(velo_ctx* c, int32_t frame1, const int32_t* frames2, int32
     for (int k = 0; k < n_cand; k++)
         if (frames2[k] < 0 || frames2[k] >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "candidate %d: frame %d; 0..%d", k, frames2[k], kLmMaxFrame - 1);
     return fr_desc_run(&c, 1, &frame1, frames2, n_cand, false, nullptr, match_thresh, nullptr, nullptr, 0, nullptr, n_kept, min_dist);
+}
+
+int velo_frames_get(velo_ctx* c, int32_t frame, int32_t cam, int32_t* ids, float* keypoints_xy, int32_t* has_depth, float* kp_with_depth_xyz,
+                    uint8_t* rows, int32_t capacity, int32_t capacity_with_depth, int32_t* n, int32_t* n_with_depth, int32_t* has_rows) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
+    if (cam < 0 || cam >= kLmMaxCams) return fail(VELO_ERR_INVALID, "camera %d; 0..%d", cam, kLmMaxCams - 1);
+    if (capacity < 0 || capacity_with_depth < 0) return fail(VELO_ERR_INVALID, "negative capacity");
+    VELO_TRY(fr_need_store(c, "velo_frames_get"));
+    const FrStore& S = *c->fr;
+    auto it = S.dir.find(lm_key(frame, cam));
+    if (it == S.dir.end()) return fail(VELO_ERR_STATE, "frame %d, camera %d has not been put", frame, cam);
+    const FrStore::Entry& e = it->second;
+    auto r = S.rdir.find(lm_key(frame, cam));
+    if (n) *n = e.n;
+    if (n_with_depth) *n_with_depth = e.n_wd;
+    if (has_rows) *has_rows = r != S.rdir.end() ? 1 : 0;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));           // the uploads and the copies of a prune are queued there
+    const size_t w = (size_t)std::min(e.n, (int)capacity), wd = (size_t)std::min(e.n_wd, (int)capacity_with_depth);
+    const int* b = S.kp.at(e.blk);
+    if (ids && w > 0) HIP_TRY(hipMemcpy(ids, b, sizeof(int) * w, hipMemcpyDeviceToHost));
+    if (has_depth && w > 0) HIP_TRY(hipMemcpy(has_depth, b + e.n, sizeof(int) * w, hipMemcpyDeviceToHost));
+    if (keypoints_xy && w > 0) HIP_TRY(hipMemcpy(keypoints_xy, b + 2 * (size_t)e.n, sizeof(float) * 2 * w, hipMemcpyDeviceToHost));
+    if (kp_with_depth_xyz && wd > 0) HIP_TRY(hipMemcpy(kp_with_depth_xyz, b + 4 * (size_t)e.n, sizeof(float) * 3 * wd, hipMemcpyDeviceToHost));
+    if (rows && r != S.rdir.end() && w > 0) HIP_TRY(hipMemcpy(rows, S.rows.at(r->second.blk), 64 * w, hipMemcpyDeviceToHost));
+    return VELO_OK;
+}
+
+int velo_frames_keep(velo_ctx* c, int32_t frame, int32_t cam, const int32_t* keep_idx, int32_t n_keep, int32_t* kept_out, int32_t capacity,
+                     int32_t* n_kept, int32_t* n_with_depth) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
+    if (cam < 0 || cam >= kLmMaxCams) return fail(VELO_ERR_INVALID, "camera %d; 0..%d", cam, kLmMaxCams - 1);
+    if (n_keep < 0 || capacity < 0) return fail(VELO_ERR_INVALID, "negative count");
+    if (n_keep > 0 && !keep_idx) return fail(VELO_ERR_INVALID, "a keep list of %d indices and a null pointer", n_keep);
+    return fr_prune_run(&c, 1, &frame, cam, keep_idx, n_keep, n_kept, n_with_depth, kept_out, capacity, nullptr);
+}
+
+int velo_frames_prune_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* frames, int32_t* n_kept, int32_t* n_with_depth, int32_t* kept_out,
+                            int32_t capacity, int32_t* n_out) {
+    VELO_TRY(fb_check_list(ctxs, n_ctx));
+    if (!frames) return fail(VELO_ERR_INVALID, "null frames");
+    if (capacity < 0) return fail(VELO_ERR_INVALID, "negative capacity");
+    for (int i = 0; i < n_ctx; i++)
+        if (frames[i] < 0 || frames[i] >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "context %d: frame %d; 0..%d", i, frames[i], kLmMaxFrame - 1);
+    VELO_TRY(fb_check_devices(ctxs, n_ctx));
+    return fr_prune_run(ctxs, n_ctx, frames, -1, nullptr, 0, n_kept, n_with_depth, kept_out, capacity, n_out);
+}
+
+int velo_frames_prune(velo_ctx* c, int32_t frame, int32_t* n_kept, int32_t* n_with_depth, int32_t* kept_out, int32_t capacity, int32_t* n_out) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    return velo_frames_prune_batch(&c, 1, &frame, n_kept, n_with_depth, kept_out, capacity, n_out);
 }
 
 int velo_get_visual(velo_ctx* c, velo_match* out, int32_t capacity, int32_t* n) {

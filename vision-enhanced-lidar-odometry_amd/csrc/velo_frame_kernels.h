@@ -16,6 +16,18 @@
 // the match kernels (velo_match_kernels.h) leave every camera's kept (queryIdx, trainIdx) pairs in query order and their count, and
 //     fr_emit_desc_kernel   one thread per kept pair writes the same record; a record's position is the kept counts of the context's
 //                           earlier cameras plus the pair's rank in its camera, read from the filter's output (no counter, no atomics)
+//
+// A registration's good matches prune the current frame (removeSlightlyLessTerribleFeatures, velo.h:272-327): every (frame, camera)
+// block is cut down to the keypoints that occur as point1 of a record the gate flagged -- a mark, a scan and a scatter, no arithmetic:
+//     fr_mark_kernel          one thread per record of a context's visual set (or per entry of a keep list): map[point1] = 1, a plain
+//                             byte store of the same value whoever wins; the map is cleared on the stream before the launch
+//     fr_prune_count_kernel   per chunk of kFrChunk keypoints: kept keypoints | kept keypoints with depth << 16 (one packed scan)
+//     fr_prune_move_kernel    a chunk's first kept keypoint = the kept ones of the unit's earlier chunks, inside the chunk the packed scan
+//                             keeps index order (no counter: the order is fixed); writes the block in the layout of the NEW n, the kept
+//                             old indices and the kept descriptor rows
+// The new layout overlaps the old one (has_depth starts at word m, inside the old ids) while other workgroups still read the old block,
+// so the move kernel never writes an arena: it gathers into scratch that nothing else of the launch reads, and the host copies a unit's
+// result over its block in stream order (velo_api_frames.inl), after the whole launch.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -199,6 +211,127 @@ fr_emit_desc_kernel(const FrDescUnit* __restrict__ units, const FrCtx* __restric
     for (int v = U.ctx_unit0; v < u; v++) base += job_out[2 * v + 1];
     const int* pr = pairs + 2 * ((size_t)U.q_out + (size_t)k);
     fr_write_record(U, ctxs[U.ctx], pr[0], pr[1], base + k);
+}
+#else
+;
+#endif
+
+// one camera of one context of a prune call (or the one entry of velo_frames_keep)
+struct FrPruneUnit {
+    FrSide f;                          // the entry as it is: read only
+    const uint4* rows;                 // its descriptor rows, four uint4 each, or null
+    unsigned char* map;                // f.n bytes, 1 = the keypoint stays
+    int* out;                          // scratch, 64-byte aligned: ids[m] | has_depth[m] | xy[m][2] | cloud[m_with_depth][3] for the new m
+    uint4* rows_out;                   // scratch: the kept rows
+    int* kept;                         // the kept old indices, ascending
+    int chunk0, n_chunks;              // this unit's chunks in the call's count array
+};
+
+// what marks: the visual set of one context (its units are unit0 + cam), or a keep list for unit0
+struct FrPruneSrc {
+    const VisualMatch* vm;
+    const unsigned char* vflags;       // three slots per record; a record counts when any is non-zero
+    const int* keep;                   // non-null: n indices instead of records
+    int n, unit0, n_cams, pad;
+};
+
+__global__ void __launch_bounds__(256)
+fr_mark_kernel(const FrPruneUnit* __restrict__ units, const FrPruneSrc* __restrict__ srcs)
+#if VELO_DEF_FRAMES
+{
+    const FrPruneSrc& S = srcs[blockIdx.y];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= S.n) return;
+    int u = S.unit0, idx;
+    if (S.keep != nullptr) idx = S.keep[i];
+    else {
+        const unsigned char* f = S.vflags + 3 * (size_t)i;
+        if ((f[0] | f[1] | f[2]) == 0) return;                        // velo_get_good_matches reports a record once per non-zero slot
+        const int cam = S.vm[i].cam;
+        if (cam < 0 || cam >= S.n_cams) return;
+        u += cam;
+        idx = S.vm[i].point1;
+    }
+    const FrPruneUnit& U = units[u];
+    if (idx >= 0 && idx < U.f.n) U.map[idx] = 1;                      // the std::set of velo.h:287-290: idempotent, no atomics
+}
+#else
+;
+#endif
+
+// kept | kept-with-depth << 16 of keypoint i of U: both at most kFrChunk per chunk, so the packed sums never carry
+__device__ __forceinline__ int fr_prune_flag(const FrPruneUnit& U, int i, int* has_depth) {
+    *has_depth = -1;
+    if (i >= U.f.n || U.map[i] == 0) return 0;
+    *has_depth = U.f.has_depth[i];
+    return *has_depth != -1 ? 0x10001 : 1;
+}
+
+__global__ void __launch_bounds__(kFrChunk)
+fr_prune_count_kernel(const FrPruneUnit* __restrict__ units, int* __restrict__ counts)
+#if VELO_DEF_FRAMES
+{
+    const FrPruneUnit& U = units[blockIdx.y];
+    const int first = blockIdx.x * kFrChunk;
+    if (first >= U.f.n) return;                                       // workgroup-uniform
+    int d, total;
+    (void)block_exclusive_scan(fr_prune_flag(U, first + (int)threadIdx.x, &d), &total);
+    if (threadIdx.x == 0) counts[U.chunk0 + blockIdx.x] = total;
+}
+#else
+;
+#endif
+
+__global__ void __launch_bounds__(kFrChunk)
+fr_prune_move_kernel(const FrPruneUnit* __restrict__ units, const int* __restrict__ counts)
+#if VELO_DEF_FRAMES
+{
+    __shared__ int part[3][kFrChunk / kWave];
+    __shared__ int src[kFrChunk];
+    const FrPruneUnit& U = units[blockIdx.y];
+    const int first = blockIdx.x * kFrChunk;
+    if (first >= U.f.n) return;                                       // workgroup-uniform
+    // the unit's kept keypoints (the new n) and what its chunks before this one keep, with and without depth
+    int all = 0, bk = 0, bd = 0;
+    for (int k = (int)threadIdx.x; k < U.n_chunks; k += kFrChunk) {
+        const int c = counts[U.chunk0 + k];
+        all += c & 0xffff;
+        if (k < (int)blockIdx.x) { bk += c & 0xffff; bd += c >> 16; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { all += __shfl_xor(all, off); bk += __shfl_xor(bk, off); bd += __shfl_xor(bd, off); }
+    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = all; part[1][threadIdx.x >> 6] = bk; part[2][threadIdx.x >> 6] = bd; }
+    __syncthreads();
+    int m = 0, base = 0, base_d = 0;
+#pragma unroll
+    for (int w = 0; w < kFrChunk / kWave; w++) { m += part[0][w]; base += part[1][w]; base_d += part[2][w]; }
+    const int i = first + (int)threadIdx.x;
+    int d, total;
+    const int flag = fr_prune_flag(U, i, &d);
+    const int ex = block_exclusive_scan(flag, &total);
+    if (flag != 0) {                                                  // velo.h:303-317, j and jd from the scan
+        const int j = base + (ex & 0xffff);
+        int* o = U.out;
+        o[j] = U.f.ids[i];
+        reinterpret_cast<float2*>(o + 2 * (size_t)m)[j] = reinterpret_cast<const float2*>(U.f.xy)[i];
+        if (d != -1) {
+            const int jd = base_d + (ex >> 16);
+            const float* p = U.f.cloud + 3 * (size_t)d;               // a depth point two keypoints share is copied for each
+            float* q = reinterpret_cast<float*>(o + 4 * (size_t)m) + 3 * (size_t)jd;
+            q[0] = p[0]; q[1] = p[1]; q[2] = p[2];
+            o[(size_t)m + j] = jd;
+        } else o[(size_t)m + j] = -1;
+        U.kept[j] = i;
+        src[ex & 0xffff] = (int)threadIdx.x;
+    }
+    if (U.rows == nullptr) return;                                    // workgroup-uniform
+    __syncthreads();
+    // the chunk's kept rows, 16 bytes per lane and four lanes to a row: a wave writes 1 KB of consecutive memory
+    const int n_kept = total & 0xffff;
+    for (int t = (int)threadIdx.x; t < 4 * n_kept; t += kFrChunk) {
+        const int r = t >> 2, q = t & 3;
+        U.rows_out[4 * (size_t)(base + r) + q] = U.rows[4 * (size_t)(first + src[r]) + q];
+    }
 }
 #else
 ;

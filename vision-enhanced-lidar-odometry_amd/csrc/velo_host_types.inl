@@ -393,6 +393,8 @@ struct velo_ctx {
     std::vector<velo_match> h_matches;
     std::vector<unsigned char> h_vflags;
     bool vflags_valid = false;
+    int vis_frame1 = -1;                 // velo_build_matches[_desc] made the visual set from this frame of the frame store (-1: somebody else did) ...
+    uint64_t vis_gen[8] = {};            // ... when its cameras' entries had these stamps (velo_frames_prune asks)
 
     // LM
     DevBuf<LMState> state;
