@@ -28,104 +28,100 @@ int velo_create(velo_ctx** out, int device) {
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(VELO_ERR_NODEVICE, "device %d is %s; this library carries gfx950 code objects only", device, prop.gcnArchName);
-    velo_ctx* c = new velo_ctx();
+    // owned from here on: every return below releases what was created so far (stream, pinned buffers, events, device buffers), and the
+    // error text stays the first failure's (no destructor reports one)
+    std::unique_ptr<velo_ctx> owner(new velo_ctx());
+    velo_ctx* c = owner.get();
     c->device = device;
-    // everything that can fail after the allocation runs inside init, so that a failure releases what was already created
-    // (stream, pinned buffers, events, device buffers) instead of leaking it behind a NULL *out
-    auto init = [&]() -> int {
-        default_params(&c->P);
-        for (int k = 0; k < VELO_MAX_SOLVES; k++) { c->pred_evals[k] = (k == 0) ? 12 : 5; c->eval_hist_n[k] = 0; }
-        if (const char* e = dev_env("VELO_ASSOC_VARIANT")) c->assoc_variant = atoi(e);
-        if (const char* e = dev_env("VELO_CLUSTER_W")) { c->cluster_w = std::max(atoi(e), 0); c->cluster_w_set = true; }
-        if (const char* e = dev_env("VELO_TRI_VARIANT")) c->tri_variant = atoi(e);
-        if (const char* e = dev_env("VELO_MATCH_VARIANT")) c->match_variant = atoi(e);
+    default_params(&c->P);
+    for (int k = 0; k < VELO_MAX_SOLVES; k++) { c->pred_evals[k] = (k == 0) ? 12 : 5; c->eval_hist_n[k] = 0; }
+    if (const char* e = dev_env("VELO_ASSOC_VARIANT")) c->assoc_variant = atoi(e);
+    if (const char* e = dev_env("VELO_CLUSTER_W")) { c->cluster_w = std::max(atoi(e), 0); c->cluster_w_set = true; }
+    if (const char* e = dev_env("VELO_TRI_VARIANT")) c->tri_variant = atoi(e);
+    if (const char* e = dev_env("VELO_MATCH_VARIANT")) c->match_variant = atoi(e);
 #ifdef VELO_DIAGNOSTICS
-        if (dev_env("VELO_LM_TRACE") && atoi(dev_env("VELO_LM_TRACE"))) {
-            c->lm_trace_on = true;
-            VELO_TRY(c->lm_trace.reserve((size_t)kTraceMaxEvals * kTraceStages * kTraceWgs));
-        }
-        // the diagnostic instantiations (cycle stamps, counters, sections switched off -- some bits give WRONG results on purpose) exist
-        // only in the tools' build of this file (build.py: libvelo_hip_diag.so); the product library ignores the variable
-        if (const char* e = dev_env("VELO_DEBUG_SKIP")) c->debug_skip = atoi(e);
+    if (dev_env("VELO_LM_TRACE") && atoi(dev_env("VELO_LM_TRACE"))) {
+        c->lm_trace_on = true;
+        VELO_TRY(c->lm_trace.reserve((size_t)kTraceMaxEvals * kTraceStages * kTraceWgs));
+    }
+    // the diagnostic instantiations (cycle stamps, counters, sections switched off -- some bits give WRONG results on purpose) exist
+    // only in the tools' build of this file (build.py: libvelo_hip_diag.so); the product library ignores the variable
+    if (const char* e = dev_env("VELO_DEBUG_SKIP")) c->debug_skip = atoi(e);
 #endif
-        if (const char* e = dev_env("VELO_GRAPHS")) c->use_graphs = atoi(e) != 0;
-        if (const char* e = dev_env("VELO_XCD_MAP")) c->xcd_map = atoi(e);
-        if (const char* e = dev_env("VELO_TUBE_MAP")) c->tube_map = atoi(e);
-        if (const char* e = dev_env("VELO_WARM_START")) c->warm_start = atoi(e);
-        if (const char* e = dev_env("VELO_DIMG_SEEDS")) c->dimg_seeds = atoi(e);
-        if (const char* e = dev_env("VELO_XCD_CHUNKS")) c->xcd_chunks = atoi(e);
-        if (const char* e = dev_env("VELO_CU_MASK")) c->cu_mask_mode = atoi(e);
-        if (const char* e = dev_env("VELO_SMALL_SOLVE")) c->small_solve = atoi(e);
-        if (const char* e = dev_env("VELO_LM_MERGED")) c->lm_merged = atoi(e);
-        if (const char* e = dev_env("VELO_LM_FUSED")) c->lm_fused = atoi(e);
-        if (const char* e = dev_env("VELO_LM_ITER")) c->lm_iter = atoi(e);
-        if (const char* e = dev_env("VELO_LM_VIS_MERGED")) c->lm_vis_merged = atoi(e);
-        if (const char* e = dev_env("VELO_ASSOC_LANE")) c->assoc_lane = atoi(e);
-        if (const char* e = dev_env("VELO_LM_MERGED_VIS")) c->lm_trace_vis_off = atoi(e) == 0;
-        if (const char* e = dev_env("VELO_ASKER_QUEUE")) c->asker_queue = atoi(e);
-        if (const char* e = dev_env("VELO_DENSE_ROWS")) c->dense_rows = std::min(std::max(atoi(e), 0), 0xfffff);
-        if (const char* e = dev_env("VELO_ASK_MAP")) c->ask_map = atoi(e) != 0 ? 1 : 0;
-        if (const char* e = dev_env("VELO_DENSE_FAR")) c->dense_far = std::min(std::max(atoi(e), 0), 64);
-        if (const char* e = dev_env("VELO_DENSE_BATCH")) c->dense_batch = atoi(e);
-        if (const char* e = dev_env("VELO_ASSOC_DIRECT_MAX")) c->direct_max = std::max(atoi(e), 0);
-        if (const char* e = dev_env("VELO_PATCH_ORDER")) c->patch_order = atoi(e);
-        if (const char* e = dev_env("VELO_PATCH_SHAPE")) { int a = 0, b = 0; if (sscanf(e, "%d,%d", &a, &b) == 2 && a >= 1 && b >= 1) { c->patch_rings = a; c->patch_len = b; } }
-        if (const char* e = dev_env("VELO_ASSOC_DIRECT_SKIP")) c->direct_skip = std::max(atoi(e), 1);
-        if (const char* e = getenv("VELO_CHAIN")) c->chain = atoi(e);
-        if (const char* e = getenv("VELO_CHAIN_MARGIN")) { c->chain_margin = std::max(atoi(e), 0); c->chain_margin_fixed = true; }
-        if (const char* e = dev_env("VELO_ASSOC_LDS_PAD")) { c->assoc_lds_pad = std::max(atoi(e), 0); c->assoc_lds_pad_fixed = true; }
-        if (const char* e = dev_env("VELO_LM_LEAN")) c->lm_lean = atoi(e);
-        if (const char* e = dev_env("VELO_LM_SLIM")) c->lm_slim = atoi(e);
-        if (const char* e = dev_env("VELO_LM_PERSIST")) c->lm_persist = atoi(e);
-        if (const char* e = dev_env("VELO_LM_PERSIST_WGS")) c->lm_persist_wgs = std::max(atoi(e), 0);
-        if (const char* e = dev_env("VELO_ASKER_ROWS")) c->asker_rows = atoi(e);
-        if (const char* e = dev_env("VELO_PERSISTENT_WGS")) c->persistent_wgs = std::max(atoi(e), 1);
-        if (const char* e = getenv("VELO_BATCH_LOCKSTEP")) c->batch_lockstep = atoi(e);
-        if (c->cu_mask_mode > 0) {
-            static std::atomic<int> seq{0};
-            const int q = (seq.fetch_add(1) / 2) % 4;
-            uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int i = 0; i < 256; i++) {
-                const bool mine = c->cu_mask_mode == 1 ? (i / 64 == q) : ((i % 8) / 2 == q);
-                if (mine) mask[i / 32] |= 1u << (i % 32);
-            }
-            HIP_TRY(hipExtStreamCreateWithCUMask(&c->stream, 8, mask));
-        } else
-        HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        HIP_TRY(hipHostMalloc((void**)&c->h_status, sizeof(HostStatus), hipHostMallocDefault));
-        HIP_TRY(hipHostMalloc((void**)&c->h_x, sizeof(double) * 64, hipHostMallocDefault));
-        HIP_TRY(hipHostMalloc((void**)&c->h_int, sizeof(int) * 32, hipHostMallocDefault));   // [0] counters, [8..13] target box keys, [16..21] source box keys
-        VELO_TRY(c->state.reserve(2));                       // [1]: the other half of the one-launch iteration's double buffer
-        VELO_TRY(c->eval_pt.reserve(1));
-        VELO_TRY(c->pose_rec.reserve(1)); VELO_TRY(c->solve_log.reserve(VELO_MAX_SOLVES)); VELO_TRY(c->chain_fail.reserve(1));
-        HIP_TRY(hipMemsetAsync(c->chain_fail.p, 0, sizeof(int), c->stream));
-        HIP_TRY(hipMemsetAsync(c->pose_rec.p, 0, sizeof(PoseRecord), c->stream));
-        HIP_TRY(hipHostMalloc((void**)&c->h_log, sizeof(SolveLog) * VELO_MAX_SOLVES + 64, hipHostMallocDefault));
-        VELO_TRY(c->partials.reserve((size_t)2 * (kMaxEvalBlocks + kMaxVisBlocks) * kNumAcc));   // two halves, same reason
-        VELO_TRY(c->reduced.reserve(2 * kNumAcc));
-        VELO_TRY(c->xdev.reserve(8));
-        VELO_TRY(c->ticket.reserve(1));
-        HIP_TRY(hipMemsetAsync(c->ticket.p, 0, sizeof(int), c->stream));
-        VELO_TRY(c->bbox_keys.reserve(6));
-        VELO_TRY(c->n_valid.reserve(2));
-        VELO_TRY(c->dbg.reserve(8));
-        HIP_TRY(hipMemsetAsync(c->dbg.p, 0, 64, c->stream));
-        HIP_TRY(hipMemsetAsync(c->state.p, 0, 2 * sizeof(LMState), c->stream));
-        HIP_TRY(hipEventCreate(&c->ev0));
-        HIP_TRY(hipEventCreate(&c->ev1));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return VELO_OK;
-    };
-    const int st = init();
-    if (st != VELO_OK) { const std::string keep = g_err; velo_destroy(c); g_err = keep; return st; }
-    *out = c;
+    if (const char* e = dev_env("VELO_GRAPHS")) c->use_graphs = atoi(e) != 0;
+    if (const char* e = dev_env("VELO_XCD_MAP")) c->xcd_map = atoi(e);
+    if (const char* e = dev_env("VELO_TUBE_MAP")) c->tube_map = atoi(e);
+    if (const char* e = dev_env("VELO_WARM_START")) c->warm_start = atoi(e);
+    if (const char* e = dev_env("VELO_DIMG_SEEDS")) c->dimg_seeds = atoi(e);
+    if (const char* e = dev_env("VELO_XCD_CHUNKS")) c->xcd_chunks = atoi(e);
+    if (const char* e = dev_env("VELO_CU_MASK")) c->cu_mask_mode = atoi(e);
+    if (const char* e = dev_env("VELO_SMALL_SOLVE")) c->small_solve = atoi(e);
+    if (const char* e = dev_env("VELO_LM_MERGED")) c->lm_merged = atoi(e);
+    if (const char* e = dev_env("VELO_LM_FUSED")) c->lm_fused = atoi(e);
+    if (const char* e = dev_env("VELO_LM_ITER")) c->lm_iter = atoi(e);
+    if (const char* e = dev_env("VELO_LM_VIS_MERGED")) c->lm_vis_merged = atoi(e);
+    if (const char* e = dev_env("VELO_ASSOC_LANE")) c->assoc_lane = atoi(e);
+    if (const char* e = dev_env("VELO_LM_MERGED_VIS")) c->lm_trace_vis_off = atoi(e) == 0;
+    if (const char* e = dev_env("VELO_ASKER_QUEUE")) c->asker_queue = atoi(e);
+    if (const char* e = dev_env("VELO_DENSE_ROWS")) c->dense_rows = std::min(std::max(atoi(e), 0), 0xfffff);
+    if (const char* e = dev_env("VELO_ASK_MAP")) c->ask_map = atoi(e) != 0 ? 1 : 0;
+    if (const char* e = dev_env("VELO_DENSE_FAR")) c->dense_far = std::min(std::max(atoi(e), 0), 64);
+    if (const char* e = dev_env("VELO_DENSE_BATCH")) c->dense_batch = atoi(e);
+    if (const char* e = dev_env("VELO_ASSOC_DIRECT_MAX")) c->direct_max = std::max(atoi(e), 0);
+    if (const char* e = dev_env("VELO_PATCH_ORDER")) c->patch_order = atoi(e);
+    if (const char* e = dev_env("VELO_PATCH_SHAPE")) { int a = 0, b = 0; if (sscanf(e, "%d,%d", &a, &b) == 2 && a >= 1 && b >= 1) { c->patch_rings = a; c->patch_len = b; } }
+    if (const char* e = dev_env("VELO_ASSOC_DIRECT_SKIP")) c->direct_skip = std::max(atoi(e), 1);
+    if (const char* e = getenv("VELO_CHAIN")) c->chain = atoi(e);
+    if (const char* e = getenv("VELO_CHAIN_MARGIN")) { c->chain_margin = std::max(atoi(e), 0); c->chain_margin_fixed = true; }
+    if (const char* e = dev_env("VELO_ASSOC_LDS_PAD")) { c->assoc_lds_pad = std::max(atoi(e), 0); c->assoc_lds_pad_fixed = true; }
+    if (const char* e = dev_env("VELO_LM_LEAN")) c->lm_lean = atoi(e);
+    if (const char* e = dev_env("VELO_LM_SLIM")) c->lm_slim = atoi(e);
+    if (const char* e = dev_env("VELO_LM_PERSIST")) c->lm_persist = atoi(e);
+    if (const char* e = dev_env("VELO_LM_PERSIST_WGS")) c->lm_persist_wgs = std::max(atoi(e), 0);
+    if (const char* e = dev_env("VELO_ASKER_ROWS")) c->asker_rows = atoi(e);
+    if (const char* e = dev_env("VELO_PERSISTENT_WGS")) c->persistent_wgs = std::max(atoi(e), 1);
+    if (const char* e = getenv("VELO_BATCH_LOCKSTEP")) c->batch_lockstep = atoi(e);
+    if (c->cu_mask_mode > 0) {
+        static std::atomic<int> seq{0};
+        const int q = (seq.fetch_add(1) / 2) % 4;
+        uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int i = 0; i < 256; i++) {
+            const bool mine = c->cu_mask_mode == 1 ? (i / 64 == q) : ((i % 8) / 2 == q);
+            if (mine) mask[i / 32] |= 1u << (i % 32);
+        }
+        HIP_TRY(hipExtStreamCreateWithCUMask(c->own_stream.put(), 8, mask));
+    } else
+    HIP_TRY(hipStreamCreateWithFlags(c->own_stream.put(), hipStreamNonBlocking));
+    c->stream = c->own_stream;
+    VELO_TRY(c->h_status.reserve(sizeof(HostStatus)));
+    VELO_TRY(c->h_x.reserve(sizeof(double) * 64));
+    VELO_TRY(c->h_int.reserve(sizeof(int) * 32));
+    VELO_TRY(c->state.reserve(2));                       // [1]: the other half of the one-launch iteration's double buffer
+    VELO_TRY(c->eval_pt.reserve(1));
+    VELO_TRY(c->pose_rec.reserve(1)); VELO_TRY(c->solve_log.reserve(VELO_MAX_SOLVES)); VELO_TRY(c->chain_fail.reserve(1));
+    HIP_TRY(hipMemsetAsync(c->chain_fail.p, 0, sizeof(int), c->stream));
+    HIP_TRY(hipMemsetAsync(c->pose_rec.p, 0, sizeof(PoseRecord), c->stream));
+    VELO_TRY(c->h_log.reserve(sizeof(SolveLog) * VELO_MAX_SOLVES + 64));
+    VELO_TRY(c->partials.reserve((size_t)2 * (kMaxEvalBlocks + kMaxVisBlocks) * kNumAcc));   // two halves, same reason
+    VELO_TRY(c->reduced.reserve(2 * kNumAcc));
+    VELO_TRY(c->xdev.reserve(8));
+    VELO_TRY(c->ticket.reserve(1));
+    HIP_TRY(hipMemsetAsync(c->ticket.p, 0, sizeof(int), c->stream));
+    VELO_TRY(c->bbox_keys.reserve(6));
+    VELO_TRY(c->n_valid.reserve(2));
+    VELO_TRY(c->dbg.reserve(8));
+    HIP_TRY(hipMemsetAsync(c->dbg.p, 0, 64, c->stream));
+    HIP_TRY(hipMemsetAsync(c->state.p, 0, 2 * sizeof(LMState), c->stream));
+    VELO_TRY(c->ev0.ensure(hipEventDefault));
+    VELO_TRY(c->ev1.ensure(hipEventDefault));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *out = owner.release();
     return VELO_OK;
 }
 
-int velo_destroy(velo_ctx* c) {
-    if (!c) return VELO_OK;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
+#ifdef VELO_DIAGNOSTICS
+// what a VELO_DEBUG_SKIP run collected on the device, printed when its context goes (debug_skip is zero in the product build)
+static void debug_skip_dump(velo_ctx* c) {
     if ((c->debug_skip & 32) && c->wg_times.p && c->wg_times_n > 0) {
         std::vector<unsigned long long> h((size_t)16 * c->wg_times_n);
         if (hipMemcpy(h.data(), c->wg_times.p, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
@@ -155,52 +151,19 @@ int velo_destroy(velo_ctx* c) {
             fprintf(stderr, "[velo dbg] wave-0 cycles: setup %llu cluster %llu runlist %llu stage %llu sweep %llu sweepbar %llu merge %llu finish %llu\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
         }
     }
-    if (c->comm) { (void)ncclCommDestroy(c->comm); c->comm = nullptr; }
-    for (int r = 0; r < kMaxPeers; r++) if (c->peer_mapped[r]) { (void)hipIpcCloseMemHandle(c->peer_mapped[r]); c->peer_mapped[r] = nullptr; }
-    for (int r = 0; r < kMaxPeers; r++) if (c->peer_area_mapped[r]) { (void)hipIpcCloseMemHandle(c->peer_area_mapped[r]); c->peer_area_mapped[r] = nullptr; }
-    if (c->peer_slab) { (void)hipFree(c->peer_slab); c->peer_slab = nullptr; }
-    for (void* p : c->peer_retired) (void)hipFree(p);
-    c->peer_retired.clear();
-    if (c->h_agree) { (void)hipHostFree(c->h_agree); c->h_agree = nullptr; }
-    if (c->peer_area) { (void)hipFree(c->peer_area); c->peer_area = nullptr; }
-    c->T.reset();                                            // the target goes with its last holder
-    c->vis_counts.release(); c->lb_status.release(); c->scan_tiles.release(); c->cursor.release(); c->scan_total.release(); c->bbox_keys.release();
-    c->src.release(); c->src_off.release(); c->q_off.release(); c->q_src.release(); c->staging.release();
-    c->seg_flag.release(); c->seg_excl.release(); c->seg_ring.release(); c->seg_off.release();
-    c->cp.release(); c->cn.release(); c->cv0.release(); c->aux0.release(); c->aux1.release(); c->n_valid.release(); c->dbg.release(); c->wg_times.release(); c->items.release(); c->item_counters.release(); c->qpos.release(); c->partials_rec.release(); c->partials_all.release();
-    c->vm.release(); c->vflags.release();
-    for (int k = 0; k < 2; k++) if (c->chunk_graph[k]) (void)hipGraphExecDestroy(c->chunk_graph[k]);
-    c->state.release(); c->partials.release(); c->reduced.release(); c->xdev.release(); c->ticket.release();
-    c->row_off_vis.release(); c->row_off_icp.release(); c->rows_r.release(); c->rows_J.release();
-    if (c->h_batch) (void)hipHostFree(c->h_batch);
-    c->batch_items.release(); c->batch_states.release(); c->batch_x.release();
-    c->ask_count.release(); c->ask_list.release(); c->ask_keys.release(); c->ask_rings.release();
-    c->solve_ctl.release(); c->ag_ctl.release();
-    c->pf.land[0].release(); c->pf.land[1].release(); c->nf.undo_cloud.release();
-    for (int k = 0; k < 2; k++) if (c->pf.pin[k]) { (void)hipHostFree(c->pf.pin[k]); c->pf.pin[k] = nullptr; c->pf.pin_cap[k] = 0; }
-    if (c->nf.call_done) { (void)hipEventDestroy(c->nf.call_done); c->nf.call_done = nullptr; }
-    if (c->pf.stream) { (void)hipStreamSynchronize(c->pf.stream); (void)hipStreamDestroy(c->pf.stream); c->pf.stream = nullptr; }
-    if (c->pf.ev) { (void)hipEventDestroy(c->pf.ev); c->pf.ev = nullptr; }
-    c->batch_tickets.release(); c->batch_pose.release(); c->batch_logs.release(); c->batch_fail.release(); c->pose_rec.release(); c->solve_log.release(); c->chain_fail.release();
-    if (c->h_log) (void)hipHostFree(c->h_log);
-    if (c->h_status) (void)hipHostFree(c->h_status);
-    if (c->h_x) (void)hipHostFree(c->h_x);
-    if (c->h_int) (void)hipHostFree(c->h_int);
-    c->md_in.release(); c->md_keys.release(); c->md_out.release();
-    for (auto& sl : c->lk_slot) { sl.pix.release(); sl.der.release(); }
-    c->lk_raw.release(); c->lk_in.release(); c->lk_out.release(); c->lk_diag.release();
-    if (c->lk_upload_ev) (void)hipEventDestroy(c->lk_upload_ev);
-    if (c->fb_here_ev) (void)hipEventDestroy(c->fb_here_ev);
-    if (c->fb_done_ev) (void)hipEventDestroy(c->fb_done_ev);
-    c->gf_eig.release(); c->gf_state.release(); c->gf_cand.release(); c->gf_keys.release(); c->gf_hdr.release();
-    c->gf_in.release(); c->gf_out.release();
-    for (auto& ps : c->pin) { if (ps.ev) (void)hipEventDestroy(ps.ev); if (ps.p) (void)hipHostFree(ps.p); }
-    if (c->src_bbox_ev) (void)hipEventDestroy(c->src_bbox_ev);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    for (auto& e : c->assoc_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    for (auto& e : c->klog) { if (e.a) (void)hipEventDestroy(e.a); if (e.b) (void)hipEventDestroy(e.b); }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+}
+#endif
+
+// Everything a context holds is owned by a member and goes with `delete c` (velo_host_types.inl); only what has an order is spelled out here.
+int velo_destroy(velo_ctx* c) {
+    if (!c) return VELO_OK;
+    (void)hipSetDevice(c->device);
+    if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
+    if (c->pf.stream) (void)hipStreamSynchronize(c->pf.stream);
+#ifdef VELO_DIAGNOSTICS
+    debug_skip_dump(c);
+#endif
+    if (c->comm) { (void)ncclCommDestroy(c->comm); c->comm = nullptr; }   // while the stream it worked on is alive
     delete c;
     return VELO_OK;
 }
@@ -286,7 +249,7 @@ static int set_source_begin(velo_ctx* c, const float* xyz, int64_t stride, const
         const size_t bytes = (size_t)(n - 1) * (size_t)stride + 12;
         if (c->pf.ready && c->pf.host == (const void*)xyz && c->pf.bytes == bytes) {
             // this cloud was announced one call ago (velo_hint_next_source) and is on the device already: the ingest waits for its copy's event
-            if (c->pf.in_pin) dsrc = c->pf.pin[c->pf.buf];                // (page-locked host memory: the ingest launch reads it over the bus)
+            if (c->pf.in_pin) dsrc = c->pf.pin[c->pf.buf].p;               // (page-locked host memory: the ingest launch reads it over the bus)
             else { HIP_TRY(hipStreamWaitEvent(c->stream, c->pf.ev, 0)); dsrc = c->pf.land[c->pf.buf].p; }
         } else {
             VELO_TRY(c->staging.reserve(bytes));
@@ -344,9 +307,9 @@ int velo_set_scan_velodyne(velo_ctx* c, int32_t as_target, const float* xyzr, in
         for (int k = 0; k < 12; k++) M.m[k] = velo_to_cam[k];       // rows 0..2 of the row-major 4x4
         hipLaunchKernelGGL(ring_reorder_kernel, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, rec, stride, n, (const int*)c->seg_ring.p, (const int*)c->seg_off.p, M, dst.p);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(c->h_int, c->scan_total.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_int.p, c->scan_total.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        n_rings = c->h_int[0];
+        n_rings = c->h_int.p[0];
         h_off.resize((size_t)n_rings + 1);
         HIP_TRY(hipMemcpy(h_off.data(), c->seg_off.p, sizeof(int) * ((size_t)n_rings + 1), hipMemcpyDeviceToHost));
     }
@@ -398,7 +361,7 @@ static int promote_begin(velo_ctx* c) {
     unsigned keys[6];
     if (box_known) {
         HIP_TRY(hipEventSynchronize(c->src_bbox_ev));                  // passed long ago unless the loading call ended on an error before its synchronisation
-        std::memcpy(keys, c->h_int + 16, sizeof(keys));
+        std::memcpy(keys, c->h_int.p + 16, sizeof(keys));
     }
     c->src_bbox_valid = false;
     VELO_TRY(target_ingest(c, reinterpret_cast<const float*>(c->T->tgt.p), (int64_t)sizeof(float4), 1));

@@ -18,7 +18,7 @@ struct LmStore {
     size_t log_len = 0, log_cap = 0, n_ids = 0, id_cap = 0, frame_cap = 0;
     int log_reallocs = 0;
     // host
-    TriFrame* h_frames = nullptr;                   // pinned mirror of the frame table: a pose travels from its own slot
+    PinBuf<TriFrame> h_frames;                      // pinned mirror of the frame table: a pose travels from its own slot
     std::vector<unsigned char> pose_set, frame_seen;
     int n_missing = 0;                              // frames that hold an observation and no pose
     std::unordered_map<int64_t, std::vector<int32_t>> lists;   // frame * 8 + cam -> ids[cam][frame]
@@ -26,10 +26,9 @@ struct LmStore {
     std::vector<unsigned char> h_added;
     // staging (a batch call uses the first context's)
     PinBuf<> h_in, h_out;
-    hipEvent_t in_ev = nullptr;                     // h_in may be rewritten once this has passed
+    Event in_ev;                                    // h_in may be rewritten once this has passed
     DevBuf<unsigned char> d_in, d_out;
     DevBuf<velo_tri_obs> d_obs;                     // the gathered observation lists of a call
-    ~LmStore() { if (h_frames) (void)hipHostFree(h_frames); if (in_ev) (void)hipEventDestroy(in_ev); }
 };
 
 namespace {
@@ -102,7 +101,7 @@ int lm_triangulate_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, int32_
     const size_t in_bytes = unit_bytes + item_bytes + sizeof(int) * ((size_t)n + 1);
     const size_t res_bytes = fb_align64(sizeof(velo_tri_result) * (size_t)n);
     const size_t out_bytes = res_bytes + sizeof(float) * 3 * (size_t)n;
-    VELO_TRY(event_wait_or_create(&L->in_ev));
+    VELO_TRY(L->in_ev.wait_or_create());
     VELO_TRY(L->h_in.reserve(in_bytes));
     VELO_TRY(L->h_out.reserve(out_bytes));
     VELO_TRY(L->d_in.reserve(in_bytes));
@@ -186,22 +185,22 @@ int velo_landmarks_set_pose(velo_ctx* c, int32_t frame, const double* pose6) {
     if ((size_t)frame >= S.frame_cap) {
         // the table grows geometrically: a new pinned mirror and a new device table, filled from the mirror
         const size_t cap = std::max<size_t>({(size_t)frame + 1, 2 * S.frame_cap, 256});
-        TriFrame* nh = nullptr;
-        HIP_TRY(hipHostMalloc((void**)&nh, sizeof(TriFrame) * cap, hipHostMallocDefault));
-        std::memset(nh, 0, sizeof(TriFrame) * cap);
+        PinBuf<TriFrame> nh;
+        VELO_TRY(nh.reserve(sizeof(TriFrame) * cap));
+        std::memset(nh.p, 0, sizeof(TriFrame) * cap);
         HIP_TRY(hipStreamSynchronize(c->stream));      // copies out of the old mirror have landed
-        if (S.h_frames) { std::memcpy(nh, S.h_frames, sizeof(TriFrame) * S.frame_cap); (void)hipHostFree(S.h_frames); }
-        S.h_frames = nh;
+        if (S.h_frames.p) std::memcpy(nh.p, S.h_frames.p, sizeof(TriFrame) * S.frame_cap);
+        S.h_frames = std::move(nh);
         DevBuf<TriFrame> nd;
         VELO_TRY(nd.reserve(cap));
         S.frames = std::move(nd);
-        HIP_TRY(hipMemcpyAsync(S.frames.p, S.h_frames, sizeof(TriFrame) * cap, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(S.frames.p, S.h_frames.p, sizeof(TriFrame) * cap, hipMemcpyHostToDevice, c->stream));
         S.frame_cap = cap;
         S.pose_set.resize(std::max(cap, S.pose_set.size()), 0);
         S.frame_seen.resize(std::max(cap, S.frame_seen.size()), 0);
     }
-    tri_frame_from_pose(pose6, &S.h_frames[frame]);
-    HIP_TRY(hipMemcpyAsync(S.frames.p + frame, S.h_frames + frame, sizeof(TriFrame), hipMemcpyHostToDevice, c->stream));
+    tri_frame_from_pose(pose6, &S.h_frames.p[frame]);
+    HIP_TRY(hipMemcpyAsync(S.frames.p + frame, S.h_frames.p + frame, sizeof(TriFrame), hipMemcpyHostToDevice, c->stream));
     if (!S.pose_set[(size_t)frame]) { S.pose_set[(size_t)frame] = 1; if (S.frame_seen[(size_t)frame]) S.n_missing--; }
     return VELO_OK;
 }
@@ -253,7 +252,7 @@ int velo_landmarks_observe(velo_ctx* c, int32_t frame, int32_t cam, const int32_
     const size_t obs_bytes = fb_align64(sizeof(velo_tri_obs) * (size_t)n);
     const size_t in_bytes = obs_bytes + sizeof(int) * (size_t)n;
     if (n > 0) {
-        VELO_TRY(event_wait_or_create(&S.in_ev));
+        VELO_TRY(S.in_ev.wait_or_create());
         VELO_TRY(S.h_in.reserve(in_bytes));
         VELO_TRY(S.d_in.reserve(in_bytes));
     }
@@ -322,7 +321,7 @@ int velo_landmarks_at_frame(velo_ctx* c, int32_t frame, const double* pose_inv16
     if (!xyz_out) return VELO_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t in_bytes = sizeof(int) * (size_t)n, out_bytes = sizeof(float) * 3 * (size_t)n;
-    VELO_TRY(event_wait_or_create(&S.in_ev));
+    VELO_TRY(S.in_ev.wait_or_create());
     VELO_TRY(S.h_in.reserve(in_bytes));
     VELO_TRY(S.h_out.reserve(out_bytes));
     VELO_TRY(S.d_in.reserve(in_bytes));
@@ -352,7 +351,7 @@ int velo_landmarks_get(velo_ctx* c, const int32_t* ids, int32_t n, float* xyz, u
     const size_t in_bytes = sizeof(int) * (size_t)n;
     const size_t xyz_bytes = sizeof(float) * 3 * (size_t)n, cnt_bytes = sizeof(int) * (size_t)n;
     const size_t out_bytes = xyz_bytes + cnt_bytes + (size_t)n;
-    VELO_TRY(event_wait_or_create(&S.in_ev));
+    VELO_TRY(S.in_ev.wait_or_create());
     VELO_TRY(S.h_in.reserve(in_bytes));
     VELO_TRY(S.h_out.reserve(out_bytes));
     VELO_TRY(S.d_in.reserve(in_bytes));

@@ -119,9 +119,9 @@ int velo_depth_association(velo_ctx* c, const float* keypoints_xy, int32_t n, do
                        (const float4*)c->kp_point.p, n, c->kp_has.p, c->kp_out.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(has_depth, c->kp_has.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_int, c->scan_total.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_int.p, c->scan_total.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const int nd = c->h_int[0];
+    const int nd = c->h_int.p[0];
     if (n_with_depth) *n_with_depth = nd;
     if (kp_with_depth_xyz && capacity_points > 0 && nd > 0) {
         std::vector<float4> h((size_t)nd);

@@ -128,15 +128,20 @@ int velo_comm_init(velo_ctx* c, const char id[128], int32_t rank, int32_t world)
 }
 
 static void peer_release(velo_ctx* c) {
-    for (int r = 0; r < kMaxPeers; r++) {
-        if (c->peer_mapped[r]) { (void)hipIpcCloseMemHandle(c->peer_mapped[r]); c->peer_mapped[r] = nullptr; }
-    }
-    for (int r = 0; r < kMaxPeers; r++) {
-        if (c->peer_area_mapped[r]) { (void)hipIpcCloseMemHandle(c->peer_area_mapped[r]); c->peer_area_mapped[r] = nullptr; }
-    }
+    for (IpcMap& m : c->peer_mapped) m.reset();
+    for (IpcMap& m : c->peer_area_mapped) m.reset();
     c->peer_on = false; c->peer_recs_on = false;
     std::memset(&c->peer, 0, sizeof(c->peer));
     std::memset(&c->peer_recs, 0, sizeof(c->peer_recs));
+}
+
+// fine-grained device memory: stores of a peer on another GPU become visible while the kernels run
+static int slab_alloc(void** slab, size_t bytes) {
+    if (hipExtMallocWithFlags(slab, bytes, hipDeviceMallocFinegrained) != hipSuccess) {
+        (void)hipGetLastError();
+        HIP_TRY(hipMalloc(slab, bytes));
+    }
+    return VELO_OK;
 }
 
 int velo_comm_peer_export(velo_ctx* c, char handle[64]) {
@@ -147,19 +152,11 @@ int velo_comm_peer_export(velo_ctx* c, char handle[64]) {
     // slow peer's timed-out call may still be storing old-epoch blocks while a fast rank is already here; with sequence numbers
     // restarting at attach, such a block written into a re-used slab could be taken for a new one.  The old slab is therefore
     // retired, not cleared and re-used: stale stores land in memory nobody reads any more (4.5 KB per recovery, freed with the context).
-    if (c->peer_slab) { c->peer_retired.push_back(c->peer_slab); c->peer_slab = nullptr; }
+    if (c->peer_slab) c->peer_retired.push_back(std::move(c->peer_slab));
     // ... but not for ever: a context that exports per leg or per recovery would grow by an allocation granule each time.  Only a call that
     // timed out (5 s bound) before the LAST TWO exports could still be storing into an older slab; those are freed here.
-    while (c->peer_retired.size() > 2) { (void)hipFree(c->peer_retired.front()); c->peer_retired.erase(c->peer_retired.begin()); }
-    {
-        // fine-grained device memory: stores of a peer on another GPU become visible while the kernels run
-        void* p = nullptr;
-        if (hipExtMallocWithFlags(&p, sizeof(PeerSlab), hipDeviceMallocFinegrained) != hipSuccess) {
-            (void)hipGetLastError();
-            HIP_TRY(hipMalloc(&p, sizeof(PeerSlab)));
-        }
-        c->peer_slab = (PeerSlab*)p;
-    }
+    while (c->peer_retired.size() > 2) c->peer_retired.erase(c->peer_retired.begin());
+    VELO_TRY(slab_alloc((void**)c->peer_slab.put(), sizeof(PeerSlab)));
     // The slab is cleared HERE, before its handle leaves this call, and never again: a peer may store into it as soon as it has attached,
     // and nothing orders that against this rank's own attach.  (Every rank exports before any rank can attach -- the host program's
     // exchange of the handles is that barrier -- so no store of the new epoch can precede this clear.)
@@ -180,7 +177,7 @@ int velo_comm_peer_attach(velo_ctx* c, const char* handles, int32_t rank, int32_
     HIP_TRY(hipStreamSynchronize(c->stream));
     peer_release(c);
     VELO_TRY(c->peer_seq.reserve(1)); VELO_TRY(c->peer_err.reserve(1)); VELO_TRY(c->peer_kseq.reserve(1));
-    if (!c->h_agree) HIP_TRY(hipHostMalloc((void**)&c->h_agree, sizeof(int) * 64, hipHostMallocDefault));
+    VELO_TRY(c->h_agree.reserve(sizeof(int) * 64));
     HIP_TRY(hipMemset(c->peer_seq.p, 0, sizeof(unsigned long long)));
     HIP_TRY(hipMemset(c->peer_kseq.p, 0, sizeof(unsigned long long)));
     HIP_TRY(hipMemset(c->peer_err.p, 0, sizeof(int)));
@@ -193,10 +190,8 @@ int velo_comm_peer_attach(velo_ctx* c, const char* handles, int32_t rank, int32_
         if (r == rank) { c->peer.slab[r] = c->peer_slab; continue; }
         hipIpcMemHandle_t h;
         std::memcpy(&h, handles + (size_t)r * 64, 64);
-        void* p = nullptr;
-        HIP_TRY(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess));
-        c->peer_mapped[r] = p;
-        c->peer.slab[r] = (PeerSlab*)p;
+        HIP_TRY(hipIpcOpenMemHandle(c->peer_mapped[r].put(), h, hipIpcMemLazyEnablePeerAccess));
+        c->peer.slab[r] = (PeerSlab*)c->peer_mapped[r].get();
     }
     c->peer.seq = c->peer_seq.p; c->peer.kseq = c->peer_kseq.p; c->peer.error = c->peer_err.p; c->peer.rank = rank; c->peer.world = world;
     c->peer_on = true;
@@ -211,12 +206,7 @@ int velo_comm_peer_export_records(velo_ctx* c, int32_t max_queries, char handle[
     if (c->peer_area && c->peer_area_queries != max_queries) return fail(VELO_ERR_STATE, "the record area exists already, sized for %d queries", c->peer_area_queries);
     if (!c->peer_area) {
         const size_t recs = 2 * ((size_t)max_queries + 8 * kMaxPeers);
-        void* p = nullptr;
-        if (hipExtMallocWithFlags(&p, recs * sizeof(PartialRec), hipDeviceMallocFinegrained) != hipSuccess) {
-            (void)hipGetLastError();
-            HIP_TRY(hipMalloc(&p, recs * sizeof(PartialRec)));
-        }
-        c->peer_area = (PartialRec*)p;
+        VELO_TRY(slab_alloc((void**)c->peer_area.put(), recs * sizeof(PartialRec)));
         c->peer_area_queries = max_queries;
     }
     hipIpcMemHandle_t h;
@@ -236,10 +226,8 @@ int velo_comm_peer_attach_records(velo_ctx* c, const char* handles, int32_t max_
         if (r == rank) { c->peer_recs.area[r] = c->peer_area; continue; }
         hipIpcMemHandle_t h;
         std::memcpy(&h, handles + (size_t)r * 64, 64);
-        void* p = nullptr;
-        HIP_TRY(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess));
-        c->peer_area_mapped[r] = p;
-        c->peer_recs.area[r] = (PartialRec*)p;
+        HIP_TRY(hipIpcOpenMemHandle(c->peer_area_mapped[r].put(), h, hipIpcMemLazyEnablePeerAccess));
+        c->peer_recs.area[r] = (PartialRec*)c->peer_area_mapped[r].get();
     }
     c->peer_recs.rank = rank; c->peer_recs.world = W; c->peer_recs.max_share = 0;
     c->peer_recs.parity_stride = (size_t)max_queries + 8 * kMaxPeers;

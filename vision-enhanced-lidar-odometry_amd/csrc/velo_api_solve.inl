@@ -6,9 +6,9 @@ int velo_associate(velo_ctx* c, const double x[6], int32_t iter, int32_t* n_vali
     HIP_TRY(hipSetDevice(c->device));
     if ((c->comm || c->peer_on) && c->target_sharded) {
         VELO_TRY(associate_target_sharded(c, x, iter, true));
-        HIP_TRY(hipMemcpyAsync(c->h_int, c->n_valid.p + c->nv_idx, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_int.p, c->n_valid.p + c->nv_idx, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        c->last_n_valid = c->h_int[0];
+        c->last_n_valid = c->h_int.p[0];
         if (n_valid) *n_valid = c->last_n_valid;
         return peer_check(c);                                  // a timed-out record exchange merged stale areas
     }
@@ -103,9 +103,9 @@ int velo_merge_partials(velo_ctx* c, const velo_partial* const* tables, int32_t 
         if (qe > qb) HIP_TRY(hipMemcpyAsync(c->partials_all.p + (size_t)w * share, tables[w] + qb, sizeof(velo_partial) * (size_t)(qe - qb), hipMemcpyHostToDevice, c->stream));
     }
     VELO_TRY(launch_merge(c, c->partials_all.p, world, share, c->last_partial_iter, true));
-    HIP_TRY(hipMemcpyAsync(c->h_int, c->n_valid.p + c->nv_idx, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_int.p, c->n_valid.p + c->nv_idx, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->last_n_valid = c->h_int[0];
+    c->last_n_valid = c->h_int.p[0];
     if (n_valid) *n_valid = c->last_n_valid;
     return VELO_OK;
 }
@@ -177,8 +177,8 @@ int velo_get_good_matches(velo_ctx* c, velo_good_match* out, int32_t capacity, i
 int velo_evaluate(velo_ctx* c, const double x[6], double* cost, double JtJ[36], double Jtr[6]) {
     if (!c || !x) return fail(VELO_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
-    std::memcpy(c->h_x, x, sizeof(double) * 6);
-    HIP_TRY(hipMemcpyAsync(c->xdev.p, c->h_x, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
+    std::memcpy(c->h_x.p, x, sizeof(double) * 6);
+    HIP_TRY(hipMemcpyAsync(c->xdev.p, c->h_x.p, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
     const EvalArgs A = eval_args(c, c->xdev.p);
     const EvalPlan plan = eval_plan(A);
     const int nblocks = plan.total();
@@ -194,10 +194,10 @@ int velo_evaluate(velo_ctx* c, const double x[6], double* cost, double JtJ[36], 
         NCCL_TRY(ncclAllReduce(c->reduced.p, c->reduced.p + kNumAcc, kNumAcc, ncclDouble, ncclSum, c->comm, c->stream));
         res = c->reduced.p + kNumAcc;
     }
-    HIP_TRY(hipMemcpyAsync(c->h_x + 8, res, sizeof(double) * kNumAcc, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_x.p + 8, res, sizeof(double) * kNumAcc, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     VELO_TRY(peer_check(c));                                   // a timed-out all-reduce summed stale slab contents
-    const double* E = c->h_x + 8;
+    const double* E = c->h_x.p + 8;
     if (cost) *cost = E[27];
     if (JtJ) {
         int k = 0;
@@ -252,8 +252,8 @@ int velo_evaluate_rows(velo_ctx* c, const double x[6], double* residuals, double
     VELO_TRY(c->rows_J.reserve((size_t)rows * 6));
     if (!h_vis.empty()) HIP_TRY(hipMemcpy(c->row_off_vis.p, h_vis.data(), sizeof(int) * h_vis.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->row_off_icp.p, h_icp.data(), sizeof(int) * h_icp.size(), hipMemcpyHostToDevice));
-    std::memcpy(c->h_x, x, sizeof(double) * 6);
-    HIP_TRY(hipMemcpyAsync(c->xdev.p, c->h_x, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
+    std::memcpy(c->h_x.p, x, sizeof(double) * 6);
+    HIP_TRY(hipMemcpyAsync(c->xdev.p, c->h_x.p, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
     EvalArgs A = eval_args(c, c->xdev.p);
     A.rows_r = c->rows_r.p; A.rows_J = c->rows_J.p; A.row_offset_vis = c->row_off_vis.p; A.row_offset_icp = c->row_off_icp.p;
     launch_eval(c, A, eval_plan(A));
@@ -273,8 +273,8 @@ int velo_evaluate_functors(velo_ctx* c, const velo_functor* f, int32_t n, const 
     VELO_TRY(c->fn_in.reserve((size_t)n));
     VELO_TRY(c->rows_r.reserve((size_t)n * 3));
     if (jacobians) VELO_TRY(c->rows_J.reserve((size_t)n * 18));
-    std::memcpy(c->h_x, x, sizeof(double) * 6);
-    HIP_TRY(hipMemcpyAsync(c->xdev.p, c->h_x, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
+    std::memcpy(c->h_x.p, x, sizeof(double) * 6);
+    HIP_TRY(hipMemcpyAsync(c->xdev.p, c->h_x.p, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->fn_in.p, f, sizeof(velo_functor) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(functor_batch_kernel, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const FunctorRec*)c->fn_in.p, n, (const double*)c->xdev.p,
                        c->rows_r.p, jacobians ? c->rows_J.p : nullptr);
@@ -290,8 +290,8 @@ int velo_residual_stats_at(velo_ctx* c, const double x[6], velo_residual_stats* 
     HIP_TRY(hipSetDevice(c->device));
     std::memset(out, 0, sizeof(*out));
     if (!c->vflags_valid) VELO_TRY(do_build_visual(c, x, false, 1, nullptr));
-    std::memcpy(c->h_x, x, sizeof(double) * 6);
-    HIP_TRY(hipMemcpyAsync(c->xdev.p, c->h_x, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
+    std::memcpy(c->h_x.p, x, sizeof(double) * 6);
+    HIP_TRY(hipMemcpyAsync(c->xdev.p, c->h_x.p, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
     EvalArgs A = eval_args(c, c->xdev.p);
     const int n = 3 * A.n_matches + (A.q_end - A.q_begin);
     int blocks = 0, residuals = 0;

@@ -102,7 +102,7 @@ int fb_gather(velo_ctx** ctxs, int n_ctx, const std::vector<char>* used) {
         if (used && !(*used)[i]) continue;
         velo_ctx* c = ctxs[i];
         if (c->stream == c0->stream) continue;
-        if (!c->fb_here_ev) HIP_TRY(hipEventCreateWithFlags(&c->fb_here_ev, hipEventDisableTiming));
+        VELO_TRY(c->fb_here_ev.ensure());
         HIP_TRY(hipEventRecord(c->fb_here_ev, c->stream));
         HIP_TRY(hipStreamWaitEvent(c0->stream, c->fb_here_ev, 0));
     }
@@ -113,7 +113,7 @@ int fb_gather(velo_ctx** ctxs, int n_ctx, const std::vector<char>* used) {
 int fb_release(velo_ctx** ctxs, int n_ctx) {
     velo_ctx* c0 = ctxs[0];
     if (n_ctx < 2) return VELO_OK;
-    if (!c0->fb_done_ev) HIP_TRY(hipEventCreateWithFlags(&c0->fb_done_ev, hipEventDisableTiming));
+    VELO_TRY(c0->fb_done_ev.ensure());
     HIP_TRY(hipEventRecord(c0->fb_done_ev, c0->stream));
     for (int i = 1; i < n_ctx; i++)
         if (ctxs[i]->stream != c0->stream) HIP_TRY(hipStreamWaitEvent(ctxs[i]->stream, c0->fb_done_ev, 0));
@@ -150,8 +150,7 @@ int lk_set_images(velo_ctx** ctxs, int n_ctx, const uint8_t* const* imgs, int n_
     velo_ctx* c = ctxs[0];
     HIP_TRY(hipSetDevice(c->device));
     // the pinned staging buffer may still be read by the previous call's upload
-    if (c->lk_upload_ev) HIP_TRY(hipEventSynchronize(c->lk_upload_ev));
-    else HIP_TRY(hipEventCreateWithFlags(&c->lk_upload_ev, hipEventDisableTiming));
+    VELO_TRY(c->lk_upload_ev.wait_or_create());
     std::vector<LkPyr> pyrs;
     std::vector<long long> cam_pix;
     std::vector<int> pyr_of(n_ctx);

@@ -188,26 +188,16 @@ int do_associate(velo_ctx* c, const double x[6], int iter, bool want_aux, bool w
             VELO_LAUNCH_T(c, "seed_kernel", 132ull * (uint64_t)(qe - qb), seed_kernel, dim3(cdiv(qe - qb, 256)), dim3(256), 0, c->stream, SA);
         }
         if (c->debug_skip & 32) { VELO_TRY(c->wg_times.reserve((size_t)16 * cdiv(qe - qb, 64) + 2)); HIP_TRY(hipMemsetAsync(c->wg_times.p, 0, sizeof(unsigned long long) * ((size_t)16 * cdiv(qe - qb, 64) + 2), c->stream)); out.wg_times = c->wg_times.p; c->wg_times_n = cdiv(qe - qb, 64); }
-        std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+        EventPair* ev = nullptr;
         const char* assoc_name = direct ? "assoc_direct_kernel" : "assoc_search_v5_kernel";
         const uint64_t assoc_b = 12ull * (uint64_t)(qe - qb) + 12ull * (uint64_t)c->T->n_tgt + 28ull * (uint64_t)(qe - qb);
-        if (assoc_bracket(c, assoc_name, assoc_b)) {
-            if (c->assoc_events_used >= 256) c->assoc_events_used = 0;      // standalone velo_associate calls: recycle
-            if (c->assoc_events_used >= (int)c->assoc_events.size()) {
-                hipEvent_t a, b;
-                HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
-                c->assoc_events.emplace_back(a, b);
-                c->assoc_event_info.emplace_back(nullptr, 0);
-            }
-            c->assoc_event_info[(size_t)c->assoc_events_used] = {assoc_name, assoc_b};
-            ev = &c->assoc_events[c->assoc_events_used++];
-        }
+        if (assoc_bracket(c, assoc_name, assoc_b) && !(ev = assoc_event_pair(c, assoc_name, assoc_b))) return VELO_ERR_HIP;
         // The tube kernel is launched with hipExtLaunchKernelGGL, which stamps the two events with the KERNEL's own start and
         // stop (what a rocprofv3 kernel trace reports); events recorded around a launch would also count the time the launch waits
         // for the chip while other streams' kernels run.  The A/B variants keep the record-around bracket.
         const int variant_timed = c->assoc_variant >= 0 ? c->assoc_variant : 5;
         const bool ext_timed = direct || lane || variant_timed == 5 || (variant_timed >= 52 && variant_timed <= 59);
-        if (ev && !ext_timed) HIP_TRY(hipEventRecord(ev->first, c->stream));
+        if (ev && !ext_timed) HIP_TRY(hipEventRecord(ev->a.get(), c->stream));
         const int aux = want_aux ? 1 : 0;
         const int groups = cdiv(qe - qb, 64);
         const double gate = gate_of_iter(c->P, iter);
@@ -264,7 +254,7 @@ int do_associate(velo_ctx* c, const double x[6], int iter, bool want_aux, bool w
             case 7: {   // sparse round: one wave per query
                 out.n_valid_next = c->n_valid.p + (c->nv_idx ^ 1);
                 c->nv_clean[c->nv_idx ^ 1] = true;
-                hipExtLaunchKernelGGL(assoc_direct_kernel, dim3(qe - qb), dim3(64), 0, c->stream, ev ? ev->first : nullptr, ev ? ev->second : nullptr, 0,
+                hipExtLaunchKernelGGL(assoc_direct_kernel, dim3(qe - qb), dim3(64), 0, c->stream, ev ? ev->a.get() : nullptr, ev ? ev->b.get() : nullptr, 0,
                                       S, P_dev, P_dev ? c->chain_fail.p : (int*)nullptr, V, c->qpts, qb, qe, (const float4*)c->T->tgt_pad.p, (const int*)c->T->tgt_off.p,
                                       gbits, c->P.icp_norm_condition, h_safe, out, aux);
                 break;
@@ -273,7 +263,7 @@ int do_associate(velo_ctx* c, const double x[6], int iter, bool want_aux, bool w
             case 6: {   // lane kernel: one lane owns one query (rounds that start from seeds)
                 out.n_valid_next = c->n_valid.p + (c->nv_idx ^ 1);
                 c->nv_clean[c->nv_idx ^ 1] = true;
-                hipExtLaunchKernelGGL(assoc_lane_kernel, dim3(cdiv(groups, 4)), dim3(256), 0, c->stream, ev ? ev->first : nullptr, ev ? ev->second : nullptr, 0,
+                hipExtLaunchKernelGGL(assoc_lane_kernel, dim3(cdiv(groups, 4)), dim3(256), 0, c->stream, ev ? ev->a.get() : nullptr, ev ? ev->b.get() : nullptr, 0,
                                       S, P_dev, P_dev ? c->chain_fail.p : (int*)nullptr, V, c->qpts, qb, qe, (const float4*)c->T->tgt_pad.p, (const int*)c->T->tgt_off.p,
                                       gbits, c->P.icp_norm_condition, out, aux);
                 break;
@@ -297,11 +287,11 @@ int do_associate(velo_ctx* c, const double x[6], int iter, bool want_aux, bool w
                 // own ~40 us) -- hence the cold round only.
                 const bool queue = asker_rows < (1 << 30) && variant == 5 && !c->debug_skip && c->seed_rounds == 0;
                 VELO_TRY(attach_askers(c, &out, queue));
-                hipEvent_t ev_stop = ev ? ev->second : nullptr;
+                hipEvent_t ev_stop = ev ? ev->b.get() : nullptr;
                 if (out.ask_list && ev) ev_stop = nullptr;              // the bracket closes behind the asker launch
 #define VELO_LAUNCH_V5(NW, MINW, DBG, PPT, ASKER)                                                                                         \
                 hipExtLaunchKernelGGL((assoc_search_v5_kernel<NW, MINW, DBG, PPT, ASKER>), dim3(grid_groups), dim3(NW * 64), c->assoc_lds_pad, c->stream,                    \
-                                      ev ? ev->first : nullptr, ev_stop, 0, S, P_dev, P_dev ? c->chain_fail.p : (int*)nullptr, V, c->qpts, qb, qe,                      \
+                                      ev ? ev->a.get() : nullptr, ev_stop, 0, S, P_dev, P_dev ? c->chain_fail.p : (int*)nullptr, V, c->qpts, qb, qe,                      \
                                    (const float4*)c->T->tgt_pad.p, (const int*)c->T->tgt_off.p, gbits, c->P.icp_norm_condition, cw, h_safe, out, aux, perm, c->debug_skip ? c->debug_skip : (asker_rows < (1 << 30) ? (c->dense_rows | (c->dense_far << 20)) : 0), asker_rows)
                 // default: 5 waves/SIMD (96 VGPRs, no spills, no scratch traffic), 2 candidate pairs per trip.  Measured on C2:
                 // 62 us; 6 waves + 2 pairs (5 spilled VGPRs) 65; 7 waves + 2 pairs 64; 5 waves + 4 pairs 66; 6 waves + 4 pairs 71
@@ -327,8 +317,8 @@ int do_associate(velo_ctx* c, const double x[6], int iter, bool want_aux, bool w
                     a.tgt_pad = c->T->tgt_pad.p; a.tgt_off = c->T->tgt_off.p; a.gate_bits = gbits; a.norm_cond = c->P.icp_norm_condition; a.cluster_w = cw;
                     a.h_safe = h_safe; a.out = out; a.want_aux = aux; a.group_perm = perm; a.dbg = c->dense_rows | (c->dense_far << 20); a.asker_rows = asker_rows;
                     hipExtLaunchKernelGGL((assoc_search_v5_batch_kernel<4, 5, false, 2, 2>), dim3(grid_groups, 1), dim3(256), c->assoc_lds_pad, c->stream,
-                                          ev ? ev->first : nullptr, ev_stop, 0, B1);
-                    hipExtLaunchKernelGGL(assoc_asker_kernel, dim3(cdiv(qe - qb, kAskChunk) + 8), dim3(64), 0, c->stream, nullptr, ev ? ev->second : nullptr, 0,
+                                          ev ? ev->a.get() : nullptr, ev_stop, 0, B1);
+                    hipExtLaunchKernelGGL(assoc_asker_kernel, dim3(cdiv(qe - qb, kAskChunk) + 8), dim3(64), 0, c->stream, nullptr, ev ? ev->b.get() : nullptr, 0,
                                           S, P_dev, (const int*)(P_dev ? c->chain_fail.p : nullptr), V, c->qpts, (const float4*)c->T->tgt_pad.p, (const int*)c->T->tgt_off.p,
                                           gbits, c->P.icp_norm_condition, h_safe, out, aux);
                 }
@@ -353,7 +343,7 @@ int do_associate(velo_ctx* c, const double x[6], int iter, bool want_aux, bool w
 #undef VELO_LAUNCH_V3
         HIP_TRY(hipGetLastError());
         if (out.prev_a && (variant == 7 || variant == 6 || variant == 5 || (variant >= 52 && variant <= 59))) c->seed_rounds++;   // these kernels leave seeds behind
-        if (ev && !ext_timed) HIP_TRY(hipEventRecord(ev->second, c->stream));
+        if (ev && !ext_timed) HIP_TRY(hipEventRecord(ev->b.get(), c->stream));
 #ifdef VELO_DIAGNOSTICS
         if ((c->debug_skip & 24) && dev_env("VELO_DEBUG_EACH")) {       // per-launch read-out (default: totals when the context goes)
             unsigned long long h[8];
@@ -367,9 +357,9 @@ int do_associate(velo_ctx* c, const double x[6], int iter, bool want_aux, bool w
     if (partial) { c->have_partials = true; c->last_partial_iter = iter; if (wait) HIP_TRY(hipStreamSynchronize(c->stream)); return VELO_OK; }
     c->have_corr = true;
     if (wait) {
-        HIP_TRY(hipMemcpyAsync(c->h_int, c->n_valid.p + c->nv_idx, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_int.p, c->n_valid.p + c->nv_idx, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        c->last_n_valid = c->h_int[0];
+        c->last_n_valid = c->h_int.p[0];
         if (n_valid) *n_valid = c->last_n_valid;
     }
     return VELO_OK;

@@ -124,22 +124,12 @@ static int do_associate_group(velo_ctx** ctxs, int n, const std::vector<std::arr
         if (k == 0) continue;
         if (ctxs[first]->xcd_chunks) gmax = ctxs[first]->xcd_chunks == 2 ? 64 * cdiv(gmax, 64) : 8 * cdiv(gmax, 8);
         velo_ctx* c = ctxs[first];
-        std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+        EventPair* ev = nullptr;
         uint64_t bytes = 0;                                           // B_assoc of every context this launch serves
         for (int j = 0; j < k; j++) bytes += 40ull * (uint64_t)(B.item[j].q_end - B.item[j].q_begin);
         for (int i = b; i < b + m; i++) { int q0, q1; q_range(ctxs[i], &q0, &q1); if (q1 > q0) bytes += 12ull * (uint64_t)ctxs[i]->T->n_tgt; }
         const char* assoc_name = all_direct ? "assoc_direct_batch_kernel" : "assoc_search_v5_batch_kernel";
-        if (assoc_bracket(c, assoc_name, bytes)) {
-            if (c->assoc_events_used >= 256) c->assoc_events_used = 0;
-            if (c->assoc_events_used >= (int)c->assoc_events.size()) {
-                hipEvent_t e0, e1;
-                HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-                c->assoc_events.emplace_back(e0, e1);
-                c->assoc_event_info.emplace_back(nullptr, 0);
-            }
-            c->assoc_event_info[(size_t)c->assoc_events_used] = {assoc_name, bytes};
-            ev = &c->assoc_events[c->assoc_events_used++];
-        }
+        if (assoc_bracket(c, assoc_name, bytes) && !(ev = assoc_event_pair(c, assoc_name, bytes))) return VELO_ERR_HIP;
         launched[(size_t)first] = 1;
         if (n_seeded > 0) {                                          // this round's seeds for the contexts that take them from their target's direction image
             int nq_seed = 0;
@@ -156,18 +146,18 @@ static int do_associate_group(velo_ctx** ctxs, int n, const std::vector<std::arr
             }
             for (int i = b; i < b + m; i++) ctxs[i]->ask_clean[0] = ctxs[i]->ask_clean[1] = false;   // no launch clears a counter this round
         }
-        if (all_direct) hipExtLaunchKernelGGL(assoc_direct_batch_kernel, dim3(nq_max, k), dim3(64), 0, c->stream, ev ? ev->first : nullptr, ev ? ev->second : nullptr, 0, B);
+        if (all_direct) hipExtLaunchKernelGGL(assoc_direct_batch_kernel, dim3(nq_max, k), dim3(64), 0, c->stream, ev ? ev->a.get() : nullptr, ev ? ev->b.get() : nullptr, 0, B);
 #ifdef VELO_DIAGNOSTICS
-        else if (all_lane) hipExtLaunchKernelGGL(assoc_lane_batch_kernel, dim3(cdiv(gmax, 4), k), dim3(256), 0, c->stream, ev ? ev->first : nullptr, ev ? ev->second : nullptr, 0, B);
+        else if (all_lane) hipExtLaunchKernelGGL(assoc_lane_batch_kernel, dim3(cdiv(gmax, 4), k), dim3(256), 0, c->stream, ev ? ev->a.get() : nullptr, ev ? ev->b.get() : nullptr, 0, B);
 #endif
         else if (any_asker && all_queue) {
-            hipExtLaunchKernelGGL((assoc_search_v5_batch_kernel<4, 5, false, 2, 2>), dim3(gmax, k), dim3(256), c->assoc_lds_pad, c->stream, ev ? ev->first : nullptr, nullptr, 0, B);
-            hipExtLaunchKernelGGL(assoc_asker_batch_kernel, dim3(cdiv(gmax * 64, kAskChunk) + 8, k), dim3(64), 0, c->stream, nullptr, ev ? ev->second : nullptr, 0, B);
+            hipExtLaunchKernelGGL((assoc_search_v5_batch_kernel<4, 5, false, 2, 2>), dim3(gmax, k), dim3(256), c->assoc_lds_pad, c->stream, ev ? ev->a.get() : nullptr, nullptr, 0, B);
+            hipExtLaunchKernelGGL(assoc_asker_batch_kernel, dim3(cdiv(gmax * 64, kAskChunk) + 8, k), dim3(64), 0, c->stream, nullptr, ev ? ev->b.get() : nullptr, 0, B);
         }
         else if (any_asker) hipExtLaunchKernelGGL((assoc_search_v5_batch_kernel<4, 5, false, 2, true>), dim3(gmax, k), dim3(256), c->assoc_lds_pad, c->stream,
-                                             ev ? ev->first : nullptr, ev ? ev->second : nullptr, 0, B);
+                                             ev ? ev->a.get() : nullptr, ev ? ev->b.get() : nullptr, 0, B);
         else hipExtLaunchKernelGGL((assoc_search_v5_batch_kernel<4, 5, false, 2, false>), dim3(gmax, k), dim3(256), c->assoc_lds_pad, c->stream,
-                                   ev ? ev->first : nullptr, ev ? ev->second : nullptr, 0, B);
+                                   ev ? ev->a.get() : nullptr, ev ? ev->b.get() : nullptr, 0, B);
         HIP_TRY(hipGetLastError());
     }
     return VELO_OK;
@@ -245,7 +235,7 @@ static int advance_launch(velo_ctx** ctxs, int n, const AdvJob* jobs, const std:
         for (int k = 0; k < m; k++) {                                  // the boxes ride back on the stream (a LATER call, the next promotion, reads them)
             velo_ctx* c = owner[k];
             // (advance_scatter_kernel wrote the keys into the page-locked words itself)
-            if (!c->src_bbox_ev) HIP_TRY(hipEventCreateWithFlags(&c->src_bbox_ev, hipEventDisableTiming));
+            VELO_TRY(c->src_bbox_ev.ensure());
             HIP_TRY(hipEventRecord(c->src_bbox_ev, bs));
         }
     }
@@ -334,15 +324,8 @@ static int f2f_batch_lockstep(velo_ctx** ctxs, int n, double* x, double* T, velo
     size_t vis_bytes = 0;                                            // chain mode with visual blocks: flags and block counts come back through page-locked memory too
     for (int i = 0; i < n; i++) vis_bytes += (((size_t)3 * (size_t)std::max(ctxs[i]->n_matches, 0) + 15) & ~(size_t)15) + sizeof(int) * 2 * VELO_MAX_STATS;
     const size_t need = n_item_slots * sizeof(LMBatchItem) + (size_t)n * (sizeof(LMState) + 8 * sizeof(double) + sizeof(SolveLog) * VELO_MAX_SOLVES + 8) + 16 + vis_bytes;
-    if (c0->h_batch_bytes < need) {
-        static const bool alloc_trace = dev_env("VELO_ALLOC_TRACE") != nullptr;
-        if (alloc_trace) fprintf(stderr, "[velo alloc] pinned batch block: %zu -> %zu bytes\n", c0->h_batch_bytes, need);
-        if (c0->h_batch) (void)hipHostFree(c0->h_batch);
-        c0->h_batch = nullptr; c0->h_batch_bytes = 0;
-        HIP_TRY(hipHostMalloc(&c0->h_batch, need, hipHostMallocDefault));
-        c0->h_batch_bytes = need;
-    }
-    LMBatchItem* h_items = (LMBatchItem*)c0->h_batch;
+    VELO_TRY(c0->h_batch.reserve(need));
+    LMBatchItem* h_items = (LMBatchItem*)c0->h_batch.p;
     LMState* h_states = (LMState*)(h_items + n_item_slots);
     double* h_x = (double*)(h_states + n);
     SolveLog* h_logs = (SolveLog*)(h_x + 8 * (size_t)n);
@@ -627,14 +610,14 @@ static int f2f_batch_lockstep(velo_ctx** ctxs, int n, double* x, double* T, velo
         bool hinted = false;
         for (int i = 0; i < n; i++) { nq_call[(size_t)i] = ctxs[i]->n_q; nt_call[(size_t)i] = ctxs[i]->T->n_tgt; hinted = hinted || ctxs[i]->nf.hint_valid; }
         if (hinted) {
-            if (!c0->nf.call_done) HIP_TRY(hipEventCreateWithFlags(&c0->nf.call_done, hipEventDisableTiming));
+            VELO_TRY(c0->nf.call_done.ensure());
             HIP_TRY(hipEventRecord(c0->nf.call_done, bs));
         }
         for (int i = 0; i < n; i++) VELO_TRY(prefetch_issue(ctxs[i]));   // the next frames' uploads run under this chain (velo_hint_next_source)
         bool preloaded = false;
         static const bool ahead_trace = dev_env("VELO_AHEAD_TRACE") != nullptr;   // dev aid: how long the loads enqueued behind the chain take on the stream
-        static thread_local hipEvent_t tr0 = nullptr, tr1 = nullptr;
-        if (ahead_trace && hinted) { if (!tr0) { HIP_TRY(hipEventCreate(&tr0)); HIP_TRY(hipEventCreate(&tr1)); } HIP_TRY(hipEventRecord(tr0, bs)); }
+        static thread_local Event tr0, tr1;
+        if (ahead_trace && hinted) { VELO_TRY(tr0.ensure(hipEventDefault)); VELO_TRY(tr1.ensure(hipEventDefault)); HIP_TRY(hipEventRecord(tr0, bs)); }
         if (hinted) VELO_TRY(preload_group(ctxs, n, bs, &preloaded));    // velo_hint_next_frame: the next frame's promotion, ingest and index build behind this chain
         if (ahead_trace && hinted) HIP_TRY(hipEventRecord(tr1, bs));
         static const bool enq_trace = dev_env("VELO_ENQ_TRACE") != nullptr;         // dev aid: how long the host needs to ENQUEUE a group's chain, and how long it then waits

@@ -62,8 +62,8 @@ static int frame_to_frame_chain(velo_ctx* c, double xc[6], velo_summary* S, bool
     const LMParams Q = lm_params(c->P);
     const size_t half = (size_t)(kMaxEvalBlocks + kMaxVisBlocks) * kNumAcc;
     const int max_launches = c->P.max_num_iterations + 2;
-    std::memcpy(c->h_x, xc, sizeof(double) * 6);
-    HIP_TRY(hipMemcpyAsync(c->xdev.p, c->h_x, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
+    std::memcpy(c->h_x.p, xc, sizeof(double) * 6);
+    HIP_TRY(hipMemcpyAsync(c->xdev.p, c->h_x.p, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
     // Visual blocks: the residual-type choice + outlier gate of every f2f iteration (velo.h:622-792) runs on the device at the pose
     // the device holds (iteration 1: the initial guess, later: the state's x); block / residual counts per iteration and the
     // last iteration's flags come back with everything else at the end.  The solves then take sweep + visual sweep + step launches.
@@ -90,11 +90,11 @@ static int frame_to_frame_chain(velo_ctx* c, double xc[6], velo_summary* S, bool
         AgreeCounts mine;
         std::memset(&mine, 0, sizeof(mine));
         for (int k = 0; k < VELO_MAX_SOLVES; k++) mine.v[k] = std::min(std::max(c->pred_evals[k], 1) + margin_for(c, k), max_launches);
-        hipLaunchKernelGGL(peer_agree_kernel, dim3(1), dim3(64), 0, c->stream, c->peer, mine, (int)VELO_MAX_SOLVES, c->h_agree);
+        hipLaunchKernelGGL(peer_agree_kernel, dim3(1), dim3(64), 0, c->stream, c->peer, mine, (int)VELO_MAX_SOLVES, c->h_agree.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(c->stream));
         VELO_TRY(peer_check(c));
-        for (int k = 0; k < VELO_MAX_SOLVES; k++) k_agreed[k] = std::min(std::max(c->h_agree[k], 1), max_launches);
+        for (int k = 0; k < VELO_MAX_SOLVES; k++) k_agreed[k] = std::min(std::max(c->h_agree.p[k], 1), max_launches);
     }
     for (int iter = 1; iter <= c->P.f2f_iterations; iter++) {
         if (visual) {
@@ -156,10 +156,10 @@ static int frame_to_frame_chain(velo_ctx* c, double xc[6], velo_summary* S, bool
         }
     }
     // the last solve has no association behind it that would notice an unfinished solve: the final state says so itself
-    int* h_fail = reinterpret_cast<int*>(c->h_log + VELO_MAX_SOLVES);
-    HIP_TRY(hipMemcpyAsync(c->h_log, c->solve_log.p, sizeof(SolveLog) * (size_t)std::min(rounds, VELO_MAX_SOLVES), hipMemcpyDeviceToHost, c->stream));
+    int* h_fail = reinterpret_cast<int*>(c->h_log.p + VELO_MAX_SOLVES);
+    HIP_TRY(hipMemcpyAsync(c->h_log.p, c->solve_log.p, sizeof(SolveLog) * (size_t)std::min(rounds, VELO_MAX_SOLVES), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(h_fail, c->chain_fail.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&c->h_status->s, c->state.p + (j & 1), sizeof(LMState), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&c->h_status.p->s, c->state.p + (j & 1), sizeof(LMState), hipMemcpyDeviceToHost, c->stream));
     int* h_vis_counts = h_fail + 1;                                  // 2 x VELO_MAX_STATS ints behind the failure flag (the pinned block has 64 spare bytes)
     int* pin_flags = nullptr;
     if (visual) {                                                    // (through page-locked memory: a pageable destination makes the copy a staged, host-blocking one)
@@ -171,7 +171,7 @@ static int frame_to_frame_chain(velo_ctx* c, double xc[6], velo_summary* S, bool
     const int nq_call = c->n_q, nt_call = c->T->n_tgt;
     const bool ahead = c->nf.hint_valid && !c->peer_on && !c->comm;   // (sharded registrations load their slices together: nothing ahead)
     if (ahead) {
-        if (!c->nf.call_done) HIP_TRY(hipEventCreateWithFlags(&c->nf.call_done, hipEventDisableTiming));
+        VELO_TRY(c->nf.call_done.ensure());
         HIP_TRY(hipEventRecord(c->nf.call_done, c->stream));
     }
     VELO_TRY(prefetch_issue(c));                                     // the next frame's upload runs under this chain (velo_hint_next_source)
@@ -181,7 +181,7 @@ static int frame_to_frame_chain(velo_ctx* c, double xc[6], velo_summary* S, bool
     else HIP_TRY(hipStreamSynchronize(c->stream));
     if (visual) { const unsigned char* pf = reinterpret_cast<const unsigned char*>(pin_flags); c->h_vflags.assign(pf, pf + (size_t)3 * c->n_matches); }
     VELO_TRY(peer_check(c));
-    if (*h_fail || !c->h_status->s.done) {
+    if (*h_fail || !c->h_status.p->s.done) {
         if (preloaded) { HIP_TRY(hipStreamSynchronize(c->stream)); VELO_TRY(undo_preload(c)); }     // the repeat runs on the pair this call registered
         HIP_TRY(hipMemsetAsync(c->chain_fail.p, 0, sizeof(int), c->stream));
         note_miss(c);
@@ -193,7 +193,7 @@ static int frame_to_frame_chain(velo_ctx* c, double xc[6], velo_summary* S, bool
     }
     const uint64_t nq = (uint64_t)nq_call;
     for (int k = 0; k < rounds; k++) {
-        const SolveLog& L = c->h_log[std::min(k, VELO_MAX_SOLVES - 1)];
+        const SolveLog& L = c->h_log.p[std::min(k, VELO_MAX_SOLVES - 1)];
         S->n_assoc_rounds++;
         S->n_queries = nq_call;
         const uint64_t b_assoc = 12ull * nq + 12ull * (uint64_t)nt_call + 28ull * nq;
@@ -214,8 +214,8 @@ static int frame_to_frame_chain(velo_ctx* c, double xc[6], velo_summary* S, bool
         if (S->n_solves < VELO_MAX_SOLVES) S->solves[S->n_solves] = ss;
         S->n_solves++;
     }
-    c->last_n_valid = c->h_status->s.n_valid;
-    for (int k = 0; k < 6; k++) xc[k] = c->h_status->s.x[k];
+    c->last_n_valid = c->h_status.p->s.n_valid;
+    for (int k = 0; k < 6; k++) xc[k] = c->h_status.p->s.x[k];
     *completed = true;
     return VELO_OK;
 }

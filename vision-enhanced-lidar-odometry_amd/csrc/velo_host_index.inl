@@ -22,6 +22,16 @@ bool assoc_bracket(velo_ctx* c, const char* name, uint64_t bytes) {
     a->launches++; a->bytes += bytes;
     return c->timing >= 3 || (a->launches - 1) % c->timing_every == 0;
 }
+// the pair of an association launch that is bracketed (recycled from the first one after 256: standalone velo_associate calls), with what
+// read_assoc_timing reports about the launch; null (the error set) when no events are to be had
+EventPair* assoc_event_pair(velo_ctx* c, const char* name, uint64_t bytes) {
+    if (c->assoc_events_used >= 256) c->assoc_events_used = 0;
+    EventPair* ev = next_event_pair(c->assoc_events, &c->assoc_events_used);
+    if (!ev) return nullptr;
+    c->assoc_event_info.resize(c->assoc_events.size());
+    c->assoc_event_info[(size_t)c->assoc_events_used - 1] = {name, bytes};
+    return ev;
+}
 // An event pair for the launch that follows, or null.  Every launch of the kernel is COUNTED (with its bytes); every timing_every-th
 // one is bracketed -- a bracket makes the runtime put two more packets into the queue, ~5 us of a chain whose launches take 20 us --
 // and velo_get_kernel_times scales the bracketed time up by launches / sampled.
@@ -33,12 +43,8 @@ velo_ctx::TimedLaunch* klog_slot(velo_ctx* c, const char* name, uint64_t bytes) 
     //  times more sparsely from then on: the brackets of every 8th launch cost the C2 headline 2.4 %, 3,905 against 3,995 pairs/s)
     const int every = c->timing >= 3 ? 1 : c->timing_every * (a->launches > 128 ? 4 : 1);
     if ((a->launches - 1) % every != 0 || c->klog_used >= 1024) return nullptr;
-    if (c->klog_used >= (int)c->klog.size()) {
-        velo_ctx::TimedLaunch t;
-        if (hipEventCreate(&t.a) != hipSuccess || hipEventCreate(&t.b) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        c->klog.push_back(t);
-    }
-    velo_ctx::TimedLaunch* t = &c->klog[(size_t)c->klog_used++];
+    velo_ctx::TimedLaunch* t = next_event_pair(c->klog, &c->klog_used);
+    if (!t) { (void)hipGetLastError(); return nullptr; }              // no events to be had: the launch goes untimed
     t->name = name; t->bytes = bytes;
     return t;
 }
@@ -46,7 +52,7 @@ velo_ctx::TimedLaunch* klog_slot(velo_ctx* c, const char* name, uint64_t bytes) 
 #define VELO_LAUNCH_T(c, name, bytes, kernel, grid, block, lds, stream, ...)                                                        \
     do {                                                                                                                            \
         velo_ctx::TimedLaunch* tl__ = klog_slot(c, name, bytes);                                                                    \
-        hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, tl__ ? tl__->a : nullptr, tl__ ? tl__->b : nullptr, 0, __VA_ARGS__); \
+        hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, tl__ ? tl__->a.get() : nullptr, tl__ ? tl__->b.get() : nullptr, 0, __VA_ARGS__); \
     } while (0)
 
 // a context about to load a NEW target: a TargetData other contexts still hold is left to them
@@ -98,22 +104,17 @@ int prefetch_issue(velo_ctx* c) {
     // by the ingest enqueued right behind this call's chain, the other one by the ingest of one step ago, which has long run.
     static const bool pageable = dev_env("VELO_PF_PAGEABLE") != nullptr;
     if (!pageable) {
-        if (c->pf.pin_cap[nb] < c->pf.bytes) {
-            if (c->pf.pin[nb]) { (void)hipHostFree(c->pf.pin[nb]); c->pf.pin[nb] = nullptr; c->pf.pin_cap[nb] = 0; }
-            const size_t want = c->pf.bytes + c->pf.bytes / 8 + 4096;
-            HIP_TRY(hipHostMalloc((void**)&c->pf.pin[nb], want, hipHostMallocDefault));
-            c->pf.pin_cap[nb] = want;
-        }
+        VELO_TRY(c->pf.pin[nb].reserve(c->pf.bytes));
         static const bool slow_trace_p = dev_env("VELO_SLOW_TRACE") != nullptr;
         const auto tm0 = std::chrono::steady_clock::now();
-        std::memcpy(c->pf.pin[nb], c->pf.host, c->pf.bytes);
+        std::memcpy(c->pf.pin[nb].p, c->pf.host, c->pf.bytes);
         if (slow_trace_p) fprintf(stderr, "[velo slow] prefetch_issue: memcpy of %zu bytes into the page-locked buffer %.0f us\n", c->pf.bytes,
                                   std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tm0).count());
         c->pf.buf = nb; c->pf.ready = true; c->pf.hinted = false; c->pf.in_pin = true;
         return VELO_OK;
     }
-    if (!c->pf.stream) HIP_TRY(hipStreamCreateWithFlags(&c->pf.stream, hipStreamNonBlocking));
-    if (!c->pf.ev) HIP_TRY(hipEventCreateWithFlags(&c->pf.ev, hipEventDisableTiming));
+    if (!c->pf.stream) HIP_TRY(hipStreamCreateWithFlags(c->pf.stream.put(), hipStreamNonBlocking));
+    VELO_TRY(c->pf.ev.ensure());
     VELO_TRY(c->pf.land[nb].reserve(c->pf.bytes));
     static const bool slow_trace = dev_env("VELO_SLOW_TRACE") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
@@ -288,15 +289,9 @@ bool query_list_stale(const velo_ctx* c) {
 int pin_acquire(velo_ctx* c, int k, size_t n, int** out) {
     velo_ctx::PinSlot& s = c->pin[k];
     if (s.pending) { HIP_TRY(hipEventSynchronize(s.ev)); s.pending = false; }
-    if (s.cap < n) {
-        static const bool alloc_trace = dev_env("VELO_ALLOC_TRACE") != nullptr;
-        if (alloc_trace) fprintf(stderr, "[velo alloc] pinned slot %d: %zu -> %zu ints\n", k, s.cap, n + 64);
-        if (s.p) { (void)hipHostFree(s.p); s.p = nullptr; s.cap = 0; }
-        HIP_TRY(hipHostMalloc((void**)&s.p, (n + 64) * sizeof(int)));
-        s.cap = n + 64;
-    }
-    if (!s.ev) HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-    *out = s.p;
+    VELO_TRY(s.buf.reserve(n * sizeof(int)));
+    VELO_TRY(s.ev.ensure());
+    *out = s.buf.p;
     return VELO_OK;
 }
 int pin_release(velo_ctx* c, int k) {

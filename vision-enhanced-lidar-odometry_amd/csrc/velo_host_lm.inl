@@ -5,8 +5,8 @@ namespace {   // (continued from the previous part)
 // numbers are out of step from then on: the communicator must be attached again (velo_comm_peer_export + _attach on every rank).
 int peer_check(velo_ctx* c) {
     if (!c->peer_on) return VELO_OK;
-    HIP_TRY(hipMemcpy(c->h_int, c->peer_err.p, sizeof(int), hipMemcpyDeviceToHost));
-    if (c->h_int[0]) return fail(VELO_ERR_COMM, "peer exchange timed out: a rank of the communicator did not arrive (attach the communicator again)");
+    HIP_TRY(hipMemcpy(c->h_int.p, c->peer_err.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (c->h_int.p[0]) return fail(VELO_ERR_COMM, "peer exchange timed out: a rank of the communicator did not arrive (attach the communicator again)");
     return VELO_OK;
 }
 
@@ -15,7 +15,7 @@ int read_assoc_timing(velo_ctx* c, velo_summary* S) {
     double ms = 0.0;
     for (int k = 0; k < c->assoc_events_used; k++) {
         float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, c->assoc_events[k].first, c->assoc_events[k].second));
+        HIP_TRY(hipEventElapsedTime(&t, c->assoc_events[k].a, c->assoc_events[k].b));
         ms += t;
         if (c->timing >= 2 && k < (int)c->assoc_event_info.size()) kacc_add(c, c->assoc_event_info[(size_t)k].first, t, 0, 1, 0);   // (counted when enqueued)
     }
@@ -41,8 +41,8 @@ int do_build_visual(velo_ctx* c, const double* x_host, bool x_on_state, int iter
     const double* xd = nullptr;
     if (x_on_state) xd = c->state.p->x;
     else {
-        std::memcpy(c->h_x, x_host, sizeof(double) * 6);
-        HIP_TRY(hipMemcpyAsync(c->xdev.p, c->h_x, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
+        std::memcpy(c->h_x.p, x_host, sizeof(double) * 6);
+        HIP_TRY(hipMemcpyAsync(c->xdev.p, c->h_x.p, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
         xd = c->xdev.p;
     }
     hipLaunchKernelGGL(visual_gate_kernel, dim3(cdiv(n, 128)), dim3(128), 0, c->stream, xd, visual_params(c->P), c->vm.p, n, iter, c->vflags.p, (int*)nullptr);
@@ -93,7 +93,7 @@ int launch_chunk(velo_ctx* c, const EvalArgs& A, const EvalPlan& E, const LMPara
     const bool graphable = c->use_graphs && !c->comm && !c->peer_on;
     if (!graphable) {
         for (int k = 0; k < iters; k++) VELO_TRY(enqueue_lm_iteration(c, A, E, Q));
-        HIP_TRY(hipMemcpyAsync(&c->h_status->s, c->state.p, sizeof(LMState), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(&c->h_status.p->s, c->state.p, sizeof(LMState), hipMemcpyDeviceToHost, c->stream));
         return VELO_OK;
     }
     // signature of everything the captured nodes bake in; a mismatch re-captures that slot
@@ -103,7 +103,7 @@ int launch_chunk(velo_ctx* c, const EvalArgs& A, const EvalPlan& E, const LMPara
         std::memcpy(w, &A, sizeof(EvalArgs)); w += sizeof(EvalArgs);
         std::memcpy(w, &Q, sizeof(LMParams)); w += sizeof(LMParams);
         std::memcpy(w, &E, sizeof(EvalPlan)); w += sizeof(EvalPlan);
-        const void* ptrs[3] = {c->state.p, c->eval_pt.p, c->h_status};
+        const void* ptrs[3] = {c->state.p, c->eval_pt.p, c->h_status.p};
         std::memcpy(w, ptrs, sizeof(ptrs)); w += sizeof(ptrs);
         const int zero = 0;
         std::memcpy(w, &zero, sizeof(int));
@@ -112,18 +112,18 @@ int launch_chunk(velo_ctx* c, const EvalArgs& A, const EvalPlan& E, const LMPara
     for (int k = 0; k < 2; k++) if (c->chunk_graph[k] && c->chunk_graph_iters[k] == iters && c->chunk_graph_sig[k] == sig) slot = k;
     if (slot < 0) {
         slot = (c->chunk_graph[0] && c->chunk_graph_iters[0] != iters) ? 1 : 0;   // slot 0: first-solve chunk size seen first, slot 1: the other
-        if (c->chunk_graph[slot]) { (void)hipGraphExecDestroy(c->chunk_graph[slot]); c->chunk_graph[slot] = nullptr; }
+        c->chunk_graph[slot].reset();
         hipGraph_t g = nullptr;
         HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         int st = VELO_OK;
         for (int k = 0; k < iters && st == VELO_OK; k++) st = enqueue_lm_iteration(c, A, E, Q);
-        hipError_t e1 = hipMemcpyAsync(&c->h_status->s, c->state.p, sizeof(LMState), hipMemcpyDeviceToHost, c->stream);
+        hipError_t e1 = hipMemcpyAsync(&c->h_status.p->s, c->state.p, sizeof(LMState), hipMemcpyDeviceToHost, c->stream);
         hipError_t e2 = hipStreamEndCapture(c->stream, &g);
         if (st != VELO_OK) { if (g) (void)hipGraphDestroy(g); return st; }
         if (e1 != hipSuccess || e2 != hipSuccess || !g) { if (g) (void)hipGraphDestroy(g); return fail(VELO_ERR_HIP, "graph capture of the LM chunk failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2)); }
-        hipError_t e3 = hipGraphInstantiate(&c->chunk_graph[slot], g, nullptr, nullptr, 0);
+        hipError_t e3 = hipGraphInstantiate(c->chunk_graph[slot].put(), g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
-        if (e3 != hipSuccess) { c->chunk_graph[slot] = nullptr; return fail(VELO_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e3)); }
+        if (e3 != hipSuccess) { c->chunk_graph[slot].h = nullptr; return fail(VELO_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e3)); }
         c->chunk_graph_iters[slot] = iters;
         c->chunk_graph_sig[slot] = sig;
     }
@@ -138,8 +138,8 @@ int do_solve(velo_ctx* c, const double* x_in, double x_out[6], velo_solve_summar
     const EvalPlan E = eval_plan(A);
     const double* xd = nullptr;
     if (x_in) {
-        std::memcpy(c->h_x, x_in, sizeof(double) * 6);
-        HIP_TRY(hipMemcpyAsync(c->xdev.p, c->h_x, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
+        std::memcpy(c->h_x.p, x_in, sizeof(double) * 6);
+        HIP_TRY(hipMemcpyAsync(c->xdev.p, c->h_x.p, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream));
         xd = c->xdev.p;
     }
     const int max_iters_all = c->P.max_num_iterations + 1;
@@ -155,9 +155,9 @@ int do_solve(velo_ctx* c, const double* x_in, double x_out[6], velo_solve_summar
                            (const int*)(c->have_corr ? c->n_valid.p + c->nv_idx : nullptr), E.nb_icp, E.nb_vis, max_iters_all + 2,
                            (PoseRecord*)nullptr, (SolveLog*)nullptr);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&c->h_status->s, c->state.p, sizeof(LMState), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(&c->h_status.p->s, c->state.p, sizeof(LMState), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (!c->h_status->s.done) return fail(VELO_ERR_STATE, "LM did not terminate after %d sweeps", max_iters_all + 2);
+        if (!c->h_status.p->s.done) return fail(VELO_ERR_STATE, "LM did not terminate after %d sweeps", max_iters_all + 2);
     } else if (!c->comm && !c->peer_on && !c->use_graphs && c->lm_merged && x_in && E.nb_icp > 0 && !c->lm_trace_vis_off) {
         // one launch per LM iteration: every sweep workgroup consumes the previous sweep's partial rows itself (lm_iter_kernel).
         // Launch k reads state / partial rows [k & 1] and writes [(k + 1) & 1]; launch 0 starts the solve.  A solve of n
@@ -179,9 +179,9 @@ int do_solve(velo_ctx* c, const double* x_in, double x_out[6], velo_solve_summar
                                    (const double*)(c->partials.p + (size_t)(k & 1) * half), E.nb_icp, c->partials.p + (size_t)((k + 1) & 1) * half, k == 0 ? 1 : 0, xd, nvp, (PoseRecord*)nullptr, (SolveLog*)nullptr);
             }
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&c->h_status->s, c->state.p + (k & 1), sizeof(LMState), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(&c->h_status.p->s, c->state.p + (k & 1), sizeof(LMState), hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
-            if (c->h_status->s.done) break;
+            if (c->h_status.p->s.done) break;
             if (k > max_launches + 16) return fail(VELO_ERR_STATE, "LM did not terminate after %d launches", k);
             chunk = 3;
         }
@@ -195,13 +195,13 @@ int do_solve(velo_ctx* c, const double* x_in, double x_out[6], velo_solve_summar
         VELO_TRY(launch_chunk(c, A, E, Q, chunk));
         launched += chunk;
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->h_status->s.done) break;
+        if (c->h_status.p->s.done) break;
         if (launched > max_iters + 16) return fail(VELO_ERR_STATE, "LM did not terminate after %d sweeps", launched);
         chunk = 3;
     }
     }
     VELO_TRY(peer_check(c));
-    const LMState& s = c->h_status->s;
+    const LMState& s = c->h_status.p->s;
 #ifdef VELO_DIAGNOSTICS
     if (c->lm_trace_on) {
         std::vector<unsigned long long> tr((size_t)kTraceMaxEvals * kTraceStages * kTraceWgs);

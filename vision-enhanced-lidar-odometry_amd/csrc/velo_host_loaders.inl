@@ -33,8 +33,8 @@ int target_finalize_begin(velo_ctx* c) {
     // bbox of the finite points -> host (the only sync of set_target; the grid dimensions are sized from it)
     unsigned init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
     if (n == 0) {                                                     // (with points the ring_of launch initialises the keys)
-        std::memcpy(c->h_int, init, sizeof(init));
-        HIP_TRY(hipMemcpyAsync(c->bbox_keys.p, c->h_int, sizeof(init), hipMemcpyHostToDevice, c->stream));
+        std::memcpy(c->h_int.p, init, sizeof(init));
+        HIP_TRY(hipMemcpyAsync(c->bbox_keys.p, c->h_int.p, sizeof(init), hipMemcpyHostToDevice, c->stream));
     }
     if (n > 0) {
         VELO_LAUNCH_T(c, "ring_of_kernel", 4ull * (uint64_t)n, ring_of_kernel, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, c->T->tgt_off.p, n_rings, n, c->T->tgt_first_ring, c->T->tgt_ring_of.p, c->bbox_keys.p);
@@ -43,7 +43,7 @@ int target_finalize_begin(velo_ctx* c) {
         VELO_LAUNCH_T(c, "bbox_kernel", 16ull * (uint64_t)n, bbox_kernel, dim3(std::min(cdiv(n, 256 * 8), 256)), dim3(256), 0, c->stream, c->T->tgt.p, n, c->bbox_keys.p);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipMemcpyAsync(c->h_int + 8, c->bbox_keys.p, sizeof(init), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_int.p + 8, c->bbox_keys.p, sizeof(init), hipMemcpyDeviceToHost, c->stream));
     VELO_TRY(build_direction_image(c));
     return VELO_OK;
 }
@@ -91,7 +91,7 @@ int target_ingest(velo_ctx* c, const float* xyz, int64_t stride, int on_device) 
         HIP_TRY(hipGetLastError());
         c->lb_zeroed = kLbWordsCleared;
     }
-    HIP_TRY(hipMemcpyAsync(c->h_int + 8, keys, sizeof(unsigned) * 6, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_int.p + 8, keys, sizeof(unsigned) * 6, hipMemcpyDeviceToHost, c->stream));
     VELO_TRY(build_direction_image(c));
     return VELO_OK;
 }
@@ -99,7 +99,7 @@ int target_finalize_end(velo_ctx* c) {
     if (c->target_early) { c->target_early = false; return VELO_OK; }     // promote_begin knew the box: everything is enqueued already
     HIP_TRY(hipStreamSynchronize(c->stream));
     unsigned keys[6];
-    std::memcpy(keys, c->h_int + 8, sizeof(keys));
+    std::memcpy(keys, c->h_int.p + 8, sizeof(keys));
     if (keys[0] == 0xffffffffu) {   // no finite point at all
         for (int k = 0; k < 6; k++) c->T->bbox[k] = 0.f;
     } else {
@@ -145,7 +145,7 @@ int source_ingest(velo_ctx* c) {
         J.raw = c->src_raw.dsrc; J.stride = c->src_raw.stride; J.src = c->src.p; J.src_off_dev = c->src_off.p; J.q_src = c->q_src.p;
         J.qpts = own_list ? c->qpts_buf.p : (float4*)nullptr;
         J.keys = c->nf.keys.p + 8 * c->nf.parity; J.keys_next = c->nf.keys.p + 8 * (c->nf.parity ^ 1);
-        J.h_keys = reinterpret_cast<unsigned*>(c->h_int + 16);
+        J.h_keys = reinterpret_cast<unsigned*>(c->h_int.p + 16);
         c->nf.parity ^= 1;
         J.n_s = c->n_src; J.n_rings_s = R; J.nb_pack = cdiv(c->n_src, 256); J.nb_q = 0;   // (the pack workgroups emit the queries themselves)
         J.skip = skip; J.nq = c->n_q; J.patch = patch ? 1 : 0; J.patch_rings = c->patch_rings; J.patch_len = c->patch_len;
@@ -180,8 +180,8 @@ int source_ingest(velo_ctx* c) {
                   patch ? 1 : 0, c->patch_rings, c->patch_len, c->q_src.p, own_list ? c->qpts_buf.p : (float4*)nullptr, reinterpret_cast<unsigned*>(c->src_off.p + 2 * (R + 1)));
     HIP_TRY(hipGetLastError());
     // the box keys ride back on the stream; every way out of a call synchronises it, so a LATER call (a promotion) may read them
-    HIP_TRY(hipMemcpyAsync(c->h_int + 16, c->src_off.p + 2 * (R + 1), sizeof(unsigned) * 6, hipMemcpyDeviceToHost, c->stream));
-    if (!c->src_bbox_ev) HIP_TRY(hipEventCreateWithFlags(&c->src_bbox_ev, hipEventDisableTiming));
+    HIP_TRY(hipMemcpyAsync(c->h_int.p + 16, c->src_off.p + 2 * (R + 1), sizeof(unsigned) * 6, hipMemcpyDeviceToHost, c->stream));
+    VELO_TRY(c->src_bbox_ev.ensure());
     HIP_TRY(hipEventRecord(c->src_bbox_ev, c->stream));
     c->src_bbox_valid = true;
     c->src_raw.on = false;

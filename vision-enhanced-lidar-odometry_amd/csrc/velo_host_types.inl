@@ -58,7 +58,7 @@ struct DevBuf {
     DevBuf& operator=(const DevBuf&) = delete;
     DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
     DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
-    ~DevBuf() { release(); }             // every buffer a context owns goes with it (velo_destroy -> delete)
+    ~DevBuf() { release(); }             // every buffer a context owns goes with it: velo_destroy is `delete c` and lists none of them
     int reserve(size_t n) {
         if (n <= cap) return VELO_OK;
         const size_t cap_before = cap; (void)cap_before;
@@ -98,8 +98,12 @@ struct PinBuf {
     ~PinBuf() { release(); }
     int reserve(size_t bytes) {
         if (bytes <= cap) return VELO_OK;
-        release();
         const size_t want = bytes + bytes / 4 + 4096;
+#ifdef VELO_DIAGNOSTICS
+        static const bool alloc_trace = getenv("VELO_ALLOC_TRACE") != nullptr;   // dev aid, as in DevBuf::reserve: which pinned buffers still grow in a warm loop?
+        if (alloc_trace) fprintf(stderr, "[velo alloc] pinned buffer: %zu -> %zu bytes\n", cap, want);
+#endif
+        release();
         HIP_TRY(hipHostMalloc((void**)&p, want, hipHostMallocDefault));
         cap = want;
         return VELO_OK;
@@ -107,21 +111,58 @@ struct PinBuf {
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 };
 
-// the host may write a staging buffer again once the event recorded behind its last upload has passed; the first use creates the event
-int event_wait_or_create(hipEvent_t* ev) {
-    if (*ev) HIP_TRY(hipEventSynchronize(*ev));
-    else HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-    return VELO_OK;
+// One owner for every runtime handle that is not memory with a size: move-only, null by default, destroyed with its holder.  It converts to
+// the raw handle, so launch, record and wait sites read as they would with a bare one; put() is where a create call writes a fresh handle.
+template <typename H, auto Destroy>
+struct Owned {
+    H h = nullptr;
+    Owned() = default;
+    explicit Owned(H x) : h(x) {}
+    Owned(const Owned&) = delete;
+    Owned& operator=(const Owned&) = delete;
+    Owned(Owned&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Owned& operator=(Owned&& o) noexcept { if (this != &o) { reset(o.h); o.h = nullptr; } return *this; }
+    ~Owned() { reset(); }
+    void reset(H x = nullptr) { if (h) (void)Destroy(h); h = x; }
+    H* put() { reset(); return &h; }
+    H get() const { return h; }
+    operator H() const { return h; }
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using GraphExec = Owned<hipGraphExec_t, hipGraphExecDestroy>;
+using IpcMap = Owned<void*, hipIpcCloseMemHandle>;                      // a peer's allocation mapped into this process
+template <typename T> using DevRaw = Owned<T*, hipFree>;                // a device allocation DevBuf does not make (the fine-grained slabs)
+struct Event : Owned<hipEvent_t, hipEventDestroy> {
+    int ensure(unsigned flags = hipEventDisableTiming) {                // created on first use; one compare from then on
+        if (!h) HIP_TRY(hipEventCreateWithFlags(&h, flags));
+        return VELO_OK;
+    }
+    // the host may write a staging buffer again once the event recorded behind its last upload has passed; the first use creates the event
+    int wait_or_create() {
+        if (h) HIP_TRY(hipEventSynchronize(h));
+        else HIP_TRY(hipEventCreateWithFlags(&h, hipEventDisableTiming));
+        return VELO_OK;
+    }
+};
+// start / stop events of a timed launch, from a pool that grows by one pair when all are in use (pairs, once made, are reused)
+struct EventPair { Event a, b; };
+template <typename P>
+P* next_event_pair(std::vector<P>& pool, int* used) {
+    if (*used >= (int)pool.size()) {
+        P p;
+        if (p.a.ensure(hipEventDefault) != VELO_OK || p.b.ensure(hipEventDefault) != VELO_OK) return nullptr;
+        pool.push_back(std::move(p));
+    }
+    return &pool[(size_t)(*used)++];
 }
 
 // double-buffered upload staging: two pinned slots used alternately, so that an upload waits only for the one before the previous one
 struct PinStage {
     PinBuf<> buf[2];
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Event ev[2];
     int k = 0;
-    ~PinStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
     int acquire(size_t bytes, unsigned char** p) {
-        VELO_TRY(event_wait_or_create(&ev[k]));
+        VELO_TRY(ev[k].wait_or_create());
         VELO_TRY(buf[k].reserve(bytes));
         *p = buf[k].p;
         return VELO_OK;
@@ -226,7 +267,10 @@ struct FrStore;   // the resident keypoint frames (velo_api_frames.inl)
 
 struct velo_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
+    // Members go in reverse order of declaration: the context's own stream is declared before every other handle and buffer, so it is
+    // the last of them to be destroyed -- whatever is freed before it is freed while the stream it was used on still exists.
+    Stream own_stream;
+    hipStream_t stream = nullptr;        // where this context's work is enqueued: own_stream, except while the leader of a lock-step group lends its own
     velo_params P;
     int timing = 0;                      // 0 off, 1 association launches (velo_summary::assoc_kernel_ms), 2 every instrumented launch by kernel name
     int assoc_variant = -1;              // VELO_ASSOC_VARIANT: -1 = default (tube kernel 5); 0 = per-lane reference kernel; 1/2/4/8 = waves per group
@@ -247,7 +291,7 @@ struct velo_ctx {
     DevBuf<int> scan_tiles, cursor, scan_total;   // scratch of an index build / of the segmenter's scans
     struct { const char* dsrc = nullptr; int64_t stride = 0; bool on = false; } src_raw;   // set_source: the records the fused ingest launch still has to read (source_finalize)
     bool src_bbox_valid = false;         // h_int[16..21] hold the bounding-box keys of the source cloud (source_ingest; on the host once src_bbox_ev has passed)
-    hipEvent_t src_bbox_ev = nullptr;    // recorded behind the keys' copy: a promotion waits on it (a no-op after any completed call) before it trusts them
+    Event src_bbox_ev;                   // recorded behind the keys' copy: a promotion waits on it (a no-op after any completed call) before it trusts them
     bool target_early = false;           // promote_begin already sized and enqueued the index (box known): target_finalize_end has nothing to wait for
     int lb_zeroed = 0;                            // status words of the one-pass scan that target_ingest_kernel cleared for the next build (0: build_grid clears them)
     bool batch_load = false;                      // set while velo_register_batch loads this context's scans for a batch of two or more (see build_grid)
@@ -327,7 +371,7 @@ struct velo_ctx {
     DevBuf<PoseRecord> pose_rec;
     DevBuf<SolveLog> solve_log;
     DevBuf<int> chain_fail;
-    SolveLog* h_log = nullptr;           // pinned: VELO_MAX_SOLVES logs + the failure flag behind them
+    PinBuf<SolveLog> h_log;              // pinned: VELO_MAX_SOLVES logs + the failure flag behind them
     int lm_fused = 1;                    // VELO_LM_FUSED=0: the lock-step batch driver launches sweep and LM step separately (A/B, identical results)
     int lm_vis_merged = 1;               // chained batch solves with visual blocks run them INSIDE the fused sweep + step launch (extra workgroups, eval_step_batch_(lean_)vis_kernel);
                                          // VELO_LM_VIS_MERGED=0: a launch of their own ahead of it (A/B, identical results)
@@ -347,8 +391,8 @@ struct velo_ctx {
     // (main.cpp:216 loads a scan per frame): two landing buffers, so the upload for frame k + 2 never touches what frame k + 1's ingest reads
     struct Prefetch {
         const void* host = nullptr; size_t bytes = 0; bool hinted = false, ready = false; int buf = 0;
-        DevBuf<char> land[2]; hipStream_t stream = nullptr; hipEvent_t ev = nullptr;
-        char* pin[2] = {nullptr, nullptr}; size_t pin_cap[2] = {0, 0}; bool in_pin = false;   // the announced cloud in page-locked memory of the library's own (see prefetch_issue)
+        DevBuf<char> land[2]; Stream stream; Event ev;
+        PinBuf<char> pin[2]; bool in_pin = false;   // the announced cloud in page-locked memory of the library's own (see prefetch_issue)
     } pf;
     // velo_hint_next_frame: the NEXT frame of a drive -- promote the scan held as source, load the announced scan as the new source, build the
     // index -- is enqueued BEHIND the current registration's chain of launches, before the calling thread waits for it: the loads of frame
@@ -362,7 +406,7 @@ struct velo_ctx {
         velo_scan_ref hint{};               //  the caller announces frame k + 1 before the job of frame k, loaded ahead one call ago, has been handed over)
         DevBuf<float4> undo_cloud; std::vector<int> undo_off; int undo_n = 0, undo_rings = 0;   // the old target's cloud: its BUFFER, rotated out (no copy)
         DevBuf<unsigned> keys; int parity = 0;   // group-batched loads (AdvJob): the source's bounding-box keys in two slots, used alternately
-        hipEvent_t call_done = nullptr;     // behind the call's last read-back copy: what the calling thread waits for when more has been enqueued behind it
+        Event call_done;                    // behind the call's last read-back copy: what the calling thread waits for when more has been enqueued behind it
     } nf;
     double last_chain_us = 0.0;          // the previous chained lock-step call this context led: enqueue -> results in (sizes the stagger of the groups' starts)
     AdvJob* adv = nullptr;               // set while a group's loads are being COLLECTED (preload_group): target_ingest / build_grid / source_ingest fill it instead of launching
@@ -406,7 +450,7 @@ struct velo_ctx {
     bool lm_trace_on = false;
     int lm_trace_idx = 0;                 // launches of the current solve so far
     // captured LM chunks (single GPU): key = iterations per chunk; rebuilt when anything baked into the nodes changes
-    hipGraphExec_t chunk_graph[2] = {nullptr, nullptr};
+    GraphExec chunk_graph[2];
     int chunk_graph_iters[2] = {0, 0};
     std::vector<unsigned char> chunk_graph_sig[2];   // bytes of everything baked into the nodes
     bool use_graphs = false;             // LM chunks as hipGraphs (VELO_GRAPHS=1): measured no gain, replay overhead ~ launches saved
@@ -414,12 +458,12 @@ struct velo_ctx {
     int eval_hist[VELO_MAX_SOLVES][4];   // ... and of the last four calls: how far a solve's count moves decides the chain's margin
     int eval_hist_n[VELO_MAX_SOLVES];
     bool chain_margin_fixed = false;     // VELO_CHAIN_MARGIN given: that margin, always
-    HostStatus* h_status = nullptr;      // pinned
-    double* h_x = nullptr;               // pinned, 8 doubles
-    int* h_int = nullptr;                // pinned scratch
+    PinBuf<HostStatus> h_status;         // pinned
+    PinBuf<double> h_x;                  // pinned, 64 doubles
+    PinBuf<int> h_int;                   // pinned scratch: [0] counters, [8..13] target box keys, [16..21] source box keys
     // pinned staging for the small host tables a load sends to the device (source ring offsets, query offsets): the copy is asynchronous
     // and the slot's event says when the host may write the slot again -- no stream synchronisation at the end of a load
-    struct PinSlot { int* p = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool pending = false; };
+    struct PinSlot { PinBuf<int> buf; Event ev; bool pending = false; };
     PinSlot pin[4];                               // 0: source ring offsets (+ query offsets), 1: query offsets, 2: target ring offsets + bounding-box keys,
                                                   // 3: the visual matches on their way to the device (set_visual_impl without a wait)
     DevBuf<int> row_off_vis, row_off_icp;
@@ -457,7 +501,7 @@ struct velo_ctx {
     int lk_cur = 0;
     DevBuf<unsigned char> lk_raw;        // unit table | level tables | the frame's raw images, one upload
     PinBuf<> h_lk_raw;                   // pinned staging of lk_raw
-    hipEvent_t lk_upload_ev = nullptr;   // h_lk_raw may be rewritten once this has passed
+    Event lk_upload_ev;                  // h_lk_raw may be rewritten once this has passed
     DevBuf<unsigned char> lk_in;         // job table | level tables | points
     DevBuf<unsigned char> lk_out;        // next_xy | status | kept
     PinBuf<> h_lk_in;
@@ -481,8 +525,8 @@ struct velo_ctx {
     // the resident keypoint frames (velo_frames_*): created by velo_frames_reset; velo_build_matches writes the visual set (vm, n_matches) from them
     std::shared_ptr<FrStore> fr;
     // front-end calls over several contexts (velo_api_track.inl): the FIRST context of a call lends its stream, staging and scratch buffers
-    hipEvent_t fb_here_ev = nullptr;     // "everything enqueued on this context's stream so far": the lending stream waits for it
-    hipEvent_t fb_done_ev = nullptr;     // recorded on the lending stream after an asynchronous batch call: the other streams wait for it
+    Event fb_here_ev;                    // "everything enqueued on this context's stream so far": the lending stream waits for it
+    Event fb_done_ev;                    // recorded on the lending stream after an asynchronous batch call: the other streams wait for it
 
     // lock-step batch driver (velo_frame_to_frame_batch): scratch owned by the FIRST context of a batch
     DevBuf<LMBatchItem> batch_items;
@@ -491,37 +535,36 @@ struct velo_ctx {
     DevBuf<int> batch_fail;
     DevBuf<LMState> batch_states;
     DevBuf<double> batch_x;
-    void* h_batch = nullptr;             // pinned: items, x, states
-    size_t h_batch_bytes = 0;
+    PinBuf<> h_batch;                    // pinned: items, x, states
     int batch_lockstep = 1;              // VELO_BATCH_LOCKSTEP=0: one host thread per context instead (A/B)
 
     // sharding / comm
     int shard_rank = 0, shard_world = 1;
     ncclComm_t comm = nullptr;
     // peer-slab all-reduce (velo_comm_peer_export / _attach): my slab, the peers' mappings, my sequence counter and error word
-    PeerSlab* peer_slab = nullptr;
+    DevRaw<PeerSlab> peer_slab;
     bool peer_on = false;
     PeerComm peer{};
-    void* peer_mapped[kMaxPeers] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    IpcMap peer_mapped[kMaxPeers];
     DevBuf<unsigned long long> peer_seq;
     DevBuf<unsigned long long> peer_kseq;           // counter of the launch-count agreements (peer_agree_kernel)
-    int* h_agree = nullptr;                         // pinned: the agreed launch counts of a chained peer call
-    std::vector<void*> peer_retired;                // slabs of earlier exports: a peer's timed-out call may still store into them; freed with the context
+    PinBuf<int> h_agree;                            // pinned: the agreed launch counts of a chained peer call
+    std::vector<DevRaw<PeerSlab>> peer_retired;     // slabs of earlier exports: a peer's timed-out call may still store into them; freed with the context
     DevBuf<int> peer_err;
-    PartialRec* peer_area = nullptr;     // my receive area of the record exchange (fine-grained, exported)
+    DevRaw<PartialRec> peer_area;        // my receive area of the record exchange (fine-grained, exported)
     int peer_area_queries = 0;           // max_queries it was sized for
-    void* peer_area_mapped[kMaxPeers] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    IpcMap peer_area_mapped[kMaxPeers];
     PeerRecs peer_recs{};
     bool peer_recs_on = false;
     unsigned long long peer_xseq = 0;    // exchanges so far (all ranks count alike)
 
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> assoc_events;   // reused pool
+    Event ev0, ev1;
+    std::vector<EventPair> assoc_events;   // reused pool
     std::vector<std::pair<const char*, uint64_t>> assoc_event_info;  // kernel name + algorithmic bytes of the launch behind each pair
     int assoc_events_used = 0;
     // velo_set_timing(ctx, 2): every instrumented launch (association, LM, index build) is bracketed by the start / stop events of
     // hipExtLaunchKernelGGL; a call's brackets are read after its final synchronisation and added up per kernel name (velo_get_kernel_times)
-    struct TimedLaunch { hipEvent_t a = nullptr, b = nullptr; const char* name = nullptr; uint64_t bytes = 0; };
+    struct TimedLaunch : EventPair { const char* name = nullptr; uint64_t bytes = 0; };
     std::vector<TimedLaunch> klog;
     int klog_used = 0;
     struct KernelAcc { const char* name; double ms; int64_t launches, sampled; uint64_t bytes; };   // ms: of the `sampled` bracketed launches
