@@ -5,6 +5,9 @@
 //     velo_hip::FrameStore frames(ctx.get(), num_cams, &cam_trans[0][0]);
 //     per frame, once its keypoints, ids and depth are final for a registration (again when they change):
 //                 frames.putFrame(keypoints, keypoint_ids, has_depth, keypoints_with_depth, frame);
+//     or, instead of projectLidarToCamera + featureDepthAssociation per camera (main.cpp:254-265) and the putFrame / putDescriptors /
+//     LandmarkStore::observeFrame that would follow them, with has_depth and keypoints_with_depth made and kept on the device:
+//                 frames.putFrameWithDepth(frame, keypoints, keypoint_ids, &descriptors, &bounds[0][0], depth_assoc_thresh, observe);
 //     instead of matchUsingId + getLandmarksAtFrame + frameToFrame (main.cpp:366-405):
 //                 dpose = velo_hip::frameToFrameResident<Eigen::Matrix4d>(ctx, frames, frame, frame - dframe, &pose_inverse,
 //                             scans_M, scans_S, kd_trees, transform, matches, good_matches, residual_type, enable_icp);
@@ -70,6 +73,45 @@ void apply_kept(const int32_t* kept, const int m, Points& keypoints, Points& key
     kp_with_depth = tmp_kp_with_depth;
 }
 
+// one frame of one store as velo_frames_put_frame reads it: the staging vectors live as long as the table that points into them
+struct PackedFrame {
+    std::vector<std::vector<int32_t> > ids;
+    std::vector<std::vector<float> > xy;
+    std::vector<std::vector<uint8_t> > rows;
+    velo_frame_cam cams[8];
+    // descriptors: null = no rows; else one 64-byte row per keypoint (a camera without keypoints still holds a row set, an empty one)
+    template <class Keypoints, class Ids, class Descriptors>
+    int pack(int num_cams, int frame, const Keypoints& keypoints, const Ids& keypoint_ids, const Descriptors* descriptors, const double* bounds) {
+        ids.assign((size_t)num_cams, std::vector<int32_t>());
+        xy.assign((size_t)num_cams, std::vector<float>());
+        rows.assign((size_t)num_cams, std::vector<uint8_t>());
+        std::memset(cams, 0, sizeof(cams));
+        for (int cam = 0; cam < num_cams; cam++) {
+            const size_t n = keypoints[cam][frame].size();
+            std::vector<int32_t>& i = ids[(size_t)cam];
+            std::vector<float>& k = xy[(size_t)cam];
+            i.resize(n + 1);                                            // never empty: &v[0] is an address even for n == 0
+            k.resize(2 * n + 2);
+            for (size_t j = 0; j < n; j++) {
+                i[j] = keypoint_ids[cam][frame][j];
+                k[2 * j] = keypoints[cam][frame][j].x;
+                k[2 * j + 1] = keypoints[cam][frame][j].y;
+            }
+            velo_frame_cam& K = cams[cam];
+            K.ids = &i[0]; K.keypoints_xy = &k[0]; K.n = (int32_t)n;
+            for (int b = 0; b < 4; b++) K.bounds[b] = bounds[4 * cam + b];
+            if (!descriptors) continue;
+            const int nr = (*descriptors)[cam][frame].rows > 0 ? (*descriptors)[cam][frame].rows : 0;
+            if ((size_t)nr != n || (nr > 0 && (*descriptors)[cam][frame].cols != 64)) return VELO_ERR_INVALID;
+            std::vector<uint8_t>& r = rows[(size_t)cam];
+            r.resize(64 * n + 64);
+            for (int j = 0; j < nr; j++) std::memcpy(&r[64 * (size_t)j], (*descriptors)[cam][frame].template ptr<unsigned char>(j), 64);
+            K.rows = &r[0];
+        }
+        return VELO_OK;
+    }
+};
+
 }  // namespace detail
 
 class FrameStore {
@@ -124,6 +166,49 @@ public:
             if (status_ != VELO_OK) return status_;
         }
         return status_;
+    }
+
+    // projectLidarToCamera + featureDepthAssociation + putFrame (+ putDescriptors when `descriptors` is not null, + Landmarks::observeFrame
+    // with observe) for every camera of `frame` in ONE call, has_depth and keypoints_with_depth made and kept on the device
+    // (velo_frames_put_frame): keypoints[cam][frame][i] canonical, keypoint_ids[cam][frame][i], (*descriptors)[cam][frame] one row per
+    // keypoint, bounds [num_cams][4] = min_x, max_x, min_y, max_y of every camera.  The scan is the context's source (of_target: its
+    // target).  n_with_depth (may be null): the depth points of every camera.  The caller's has_depth / keypoints_with_depth
+    // containers are not filled: nothing on the host reads them any more (velo_frames_get does when something must).
+    template <class Keypoints, class Ids, class Descriptors>
+    int putFrameWithDepth(int frame, const Keypoints& keypoints, const Ids& keypoint_ids, const Descriptors* descriptors, const double* bounds,
+                          double thresh, bool observe, bool of_target = false, std::vector<int32_t>* n_with_depth = 0) {
+        detail::PackedFrame P;
+        if ((status_ = P.pack(num_cams_, frame, keypoints, keypoint_ids, descriptors, bounds)) != VELO_OK) return status_;
+        int32_t n_wd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        status_ = velo_frames_put_frame(ctx_, frame, of_target ? 1 : 0, P.cams, thresh, observe ? VELO_PUT_OBSERVE : 0, n_wd);
+        if (status_ == VELO_OK && n_with_depth) n_with_depth->assign(n_wd, n_wd + num_cams_);
+        return status_;
+    }
+
+    // The same for frames[i] of stores[i] (distinct contexts on one device), i < n, in ONE call (velo_frames_put_frame_batch): the
+    // containers, bounds and of_target flags of store i are keypoints[i], keypoint_ids[i], descriptors[i] (the array or an entry may be
+    // null), bounds[i], of_target[i] (null: the source everywhere).  Every store's status becomes the call's.
+    template <class Keypoints, class Ids, class Descriptors>
+    static int putFramesWithDepth(FrameStore* const* stores, int n, const int* frames, const Keypoints* const* keypoints, const Ids* const* keypoint_ids,
+                                  const Descriptors* const* descriptors, const double* const* bounds, double thresh, bool observe,
+                                  const bool* of_target = 0) {
+        if (n < 1 || !stores || !frames || !keypoints || !keypoint_ids || !bounds) return VELO_ERR_INVALID;
+        std::vector<detail::PackedFrame> P((size_t)n);
+        std::vector<velo_ctx*> ctxs((size_t)n);
+        std::vector<int32_t> fr((size_t)n), side((size_t)n, 0), n_wd(8 * (size_t)n, 0);
+        std::vector<velo_frame_cam> cams(8 * (size_t)n);
+        int status = VELO_OK;
+        for (int i = 0; i < n && status == VELO_OK; i++) {
+            status = P[(size_t)i].pack(stores[i]->num_cams_, frames[i], *keypoints[i], *keypoint_ids[i], descriptors ? descriptors[i] : 0, bounds[i]);
+            std::memcpy(&cams[8 * (size_t)i], P[(size_t)i].cams, sizeof(P[(size_t)i].cams));
+            ctxs[(size_t)i] = stores[i]->ctx_;
+            fr[(size_t)i] = frames[i];
+            side[(size_t)i] = of_target && of_target[i] ? 1 : 0;
+        }
+        if (status == VELO_OK)
+            status = velo_frames_put_frame_batch(&ctxs[0], n, &fr[0], &side[0], &cams[0], thresh, observe ? VELO_PUT_OBSERVE : 0, &n_wd[0]);
+        for (int i = 0; i < n; i++) stores[i]->status_ = status;
+        return status;
     }
 
     int dropFrame(int frame) { return status_ = velo_frames_drop(ctx_, frame); }

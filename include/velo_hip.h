@@ -803,6 +803,48 @@ int velo_frames_prune(velo_ctx* ctx, int32_t frame, int32_t* n_kept /* [n_cams] 
 int velo_frames_prune_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* frames, int32_t* n_kept, int32_t* n_with_depth, int32_t* kept_out,
                             int32_t capacity, int32_t* n_out);
 
+/* --- a frame put with its keypoint depth computed on the device (velo.h:329-497 in front of the stores above) --------------------
+ * One camera of a frame as the caller's extractor leaves it: ids and canonical keypoints, optionally the FREAK rows, and the camera's
+ * window (velo_project_lidar's bounds). */
+typedef struct velo_frame_cam {
+    const int32_t* ids;          /* n */
+    const float*   keypoints_xy; /* n x 2, canonical */
+    const uint8_t* rows;         /* n x 64 FREAK rows, or NULL: the entry gets no rows */
+    int32_t        n;
+    double         bounds[4];    /* min_x, max_x, min_y, max_y of this camera: velo_project_lidar's */
+} velo_frame_cam;
+
+#define VELO_PUT_OBSERVE 1       /* also do velo_landmarks_observe for every camera, from the entry */
+
+/* For every camera cam of the frame store (cams holds the store's n_cams entries) the end state of
+ *     velo_project_lidar(ctx, of_target, the store's cam_trans[cam], bounds); velo_depth_association(keypoints, depth_assoc_thresh);
+ *     velo_frames_put(frame, cam, ids, keypoints, has_depth, cloud); velo_frames_put_descriptors(frame, cam, rows, n) when rows is given;
+ *     velo_landmarks_observe(frame, cam, the same arrays) with VELO_PUT_OBSERVE
+ * byte for byte in velo_frames_get, velo_frames_info, velo_frames_desc_info (every block is placed at its exact size, in camera order)
+ * and in the landmark store -- and has_depth and the depth cloud never exist on the host: the device projects the context's scan for
+ * every camera into stacks of the frame store's own, associates depth, writes has_depth and the cloud (in keypoint order, from a scan:
+ * no counter) into the entry and, on request, appends the landmark log from it.  The context's velo_project_lidar state
+ * (velo_get_projection, velo_depth_association), the registration state, the visual set and the good matches are untouched; a recorded
+ * frame1 stamp of `frame` is invalidated as by velo_frames_put.  n_with_depth [n_cams] (may be NULL): every camera's depth points.
+ * Refused with nothing changed: VELO_ERR_INVALID for what velo_frames_put refuses (a negative id, an id >= 2^26, frame >= 2^22, a NULL
+ * array with n > 0), for rows with n above the match key's row limit, for unknown flags and, with VELO_PUT_OBSERVE, for what
+ * velo_landmarks_observe refuses (an id twice in one camera, a (frame, cam) observed before); VELO_ERR_STATE without a frame store,
+ * without a cloud on the named side and, with VELO_PUT_OBSERVE, without a landmark store of the same camera count.
+ * One upload (the call's tables, ids, keypoints and rows), four launches for all cameras (projection, depth search, chunk counts,
+ * write; with VELO_PUT_OBSERVE one more that builds the log records, and the unchanged append per camera), one copy back (the chunk
+ * counts), one synchronisation, then one device-to-device copy per block and row set: no keypoint or descriptor byte crosses the bus
+ * twice, no has_depth or depth point crosses it at all, and no device allocation in the steady state.  What this saves over the four
+ * calls per camera is measured by tools/frame_depth_bench.py. */
+int velo_frames_put_frame(velo_ctx* ctx, int32_t frame, int32_t of_target, const velo_frame_cam* cams /* the store's n_cams */,
+                          double depth_assoc_thresh, int32_t flags, int32_t* n_with_depth /* [n_cams], may be NULL */);
+/* The same for (ctxs[i], frames[i], of_target[i]) in the SAME launches, under the rules of the other batch entries (distinct contexts
+ * on one device, the first lends its stream, staging and scratch and waits for the others' streams, n_ctx == 1 IS the single entry);
+ * contexts may differ in camera count, ring count and cloud size.  Every argument is checked before any context is touched, and no
+ * context changes when one is refused.  Every context's stores are byte-identical to the single entry's. */
+int velo_frames_put_frame_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* frames, const int32_t* of_target,
+                                const velo_frame_cam* cams /* [n_ctx][8], a context's first n_cams used */,
+                                double depth_assoc_thresh, int32_t flags, int32_t* n_with_depth /* [n_ctx][8] */);
+
 /* Read-back of the context's device-side visual set, whoever wrote it (velo_set_visual or velo_build_matches): *n = its records,
  * the first `capacity` are written (out may be NULL). */
 int velo_get_visual(velo_ctx* ctx, velo_match* out, int32_t capacity, int32_t* n);

@@ -100,6 +100,41 @@ def gftt_params(max_corners: int = 3000, quality_level: float = 0.001, min_dista
     return VeloGfttParams(int(max_corners), int(block_size), float(quality_level), float(min_distance))
 
 
+class VeloFrameCam(C.Structure):
+    """velo_frame_cam: one camera of a frame for velo_frames_put_frame -- ids, canonical keypoints, optional FREAK rows, the window"""
+    _fields_ = [("ids", C.c_void_p), ("keypoints_xy", C.c_void_p), ("rows", C.c_void_p), ("n", C.c_int32), ("bounds", C.c_double * 4)]
+
+
+VELO_PUT_OBSERVE = 1
+
+
+class FrameCam:
+    """One camera of a frame as frames_put_frame takes it: ids [n], keypoints_xy [n, 2] (canonical), window (min_x, max_x, min_y,
+    max_y: project_lidar's) and optionally the FREAK rows, uint8 [n, 64].  Holds contiguous copies for the duration of the call."""
+
+    def __init__(self, ids, keypoints_xy, window, rows=None):
+        self.ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+        self.keypoints_xy = np.ascontiguousarray(np.asarray(keypoints_xy, dtype=np.float32).reshape(-1, 2))
+        if len(self.ids) != len(self.keypoints_xy):
+            raise ValueError("FrameCam: one keypoint per id")
+        self.window = _dvec(window, 4)
+        self.rows = None
+        if rows is not None:
+            r = np.ascontiguousarray(np.asarray(rows, dtype=np.uint8))
+            r = r.reshape(0, 64) if r.size == 0 else r
+            if r.ndim != 2 or r.shape[1] != 64 or len(r) != len(self.ids):
+                raise ValueError(f"FrameCam: descriptors must be uint8 (n, 64) with one row per id, got shape {r.shape}")
+            self.rows = r
+
+    def as_struct(self) -> VeloFrameCam:
+        n = len(self.ids)
+        rows = None
+        if self.rows is not None:                     # an empty row set is still "rows given": any non-null address says so
+            rows = self.rows.ctypes.data if n else self.window.ctypes.data
+        return VeloFrameCam(self.ids.ctypes.data if n else None, self.keypoints_xy.ctypes.data if n else None, rows, n,
+                            (C.c_double * 4)(*self.window))
+
+
 class VeloResidualStat(C.Structure):
     _fields_ = [("median", C.c_double), ("mean", C.c_double), ("count", C.c_int64)]
 
@@ -315,6 +350,8 @@ SIGNATURES = {
     "velo_build_matches_desc_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
                                                 C.c_int32, C.c_void_p]),
     "velo_match_frames": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
+    "velo_frames_put_frame": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_void_p]),
+    "velo_frames_put_frame_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p]),
 }
 
 _lib = None
@@ -849,6 +886,13 @@ class Context:
         kept, n_wd = frames_prune_batch([self], [frame])[0]
         return kept, n_wd
 
+    # -- a frame put with its keypoint depth computed on the device (velo.h:329-497 in front of the stores) ------------------
+    def frames_put_frame(self, frame: int, cams, thresh: float = 0.015, of_target: bool = False, observe: bool = False) -> np.ndarray:
+        """project_lidar + depth_association + frames_put (+ frames_put_descriptors where a FrameCam has rows, + landmarks_observe
+        with observe=True) for every camera of the frame store in one call, has_depth and the depth cloud never leaving the device.
+        cams: one FrameCam per camera of the store.  Returns n_with_depth [n_cams] i32."""
+        return frames_put_frame_batch([self], [frame], [cams], thresh, [of_target], observe)[0]
+
     def get_visual(self, capacity: Optional[int] = None) -> np.ndarray:
         """The context's device-side visual set (velo_match records), whoever wrote it"""
         n = C.c_int32(0)
@@ -1348,6 +1392,32 @@ def frames_prune_batch(ctxs, frames, raw: bool = False):
         cuts = np.r_[0, np.cumsum(n_kept[i, :n_cams])]
         out.append(([kept[i, cuts[c]:cuts[c + 1]].copy() for c in range(n_cams)], n_wd[i, :n_cams].copy()))
     return out
+
+
+def frames_put_frame_batch(ctxs, frames, cams_per_ctx, thresh: float = 0.015, of_target=None, observe: bool = False, raw: bool = False):
+    """Context.frames_put_frame for (ctxs[i], frames[i], cams_per_ctx[i]) in ONE call (the same launches for all); of_target: one
+    flag per context (None: the source everywhere).  Per context n_with_depth [n_cams] i32; raw: the call's [n_ctx, 8] array."""
+    lib, arr = _batch_lib_and_handles(ctxs)
+    n_ctx = len(ctxs)
+    if len(frames) != n_ctx or len(cams_per_ctx) != n_ctx:
+        raise ValueError("frames_put_frame_batch: one frame and one camera list per context")
+    f = np.ascontiguousarray(np.asarray(frames, dtype=np.int32).reshape(-1))
+    t = np.ascontiguousarray(np.asarray([0] * n_ctx if of_target is None else [int(bool(v)) for v in of_target], dtype=np.int32).reshape(-1))
+    if len(t) != n_ctx:
+        raise ValueError("frames_put_frame_batch: one of_target flag per context")
+    table = (VeloFrameCam * (8 * n_ctx))()
+    for i, cams in enumerate(cams_per_ctx):
+        if len(cams) > 8:
+            raise ValueError("frames_put_frame_batch: at most 8 cameras")
+        for k, cam in enumerate(cams):
+            table[8 * i + k] = cam.as_struct()
+    n_wd = np.zeros((n_ctx, 8), dtype=np.int32)
+    vp = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+    _batch_check(lib, lib.velo_frames_put_frame_batch(C.cast(arr, C.c_void_p), n_ctx, vp(f), vp(t), C.cast(table, C.c_void_p), float(thresh),
+                                                      VELO_PUT_OBSERVE if observe else 0, vp(n_wd)))
+    if raw:
+        return n_wd
+    return [n_wd[i, :len(cams)].copy() for i, cams in enumerate(cams_per_ctx)]
 
 
 SCAN_ON_DEVICE, SCAN_SHARED, SCAN_PROMOTE = 1, 2, 4

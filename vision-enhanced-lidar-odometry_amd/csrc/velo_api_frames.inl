@@ -3,7 +3,9 @@
 // (velo_build_matches[_batch], velo_get_visual): matchUsingId (velo.h:562-590), the landmark substitution and the gather of
 // velo.h:627-654 on the device; the kernels are in velo_frame_kernels.h.  Also the frames' descriptor rows (velo_frames_put_descriptors),
 // the visual set of a loop-closure edge joined by them (velo_build_matches_desc[_batch]: matchFeatures, velo.h:499-560, on the match
-// kernels of velo_match_kernels.h) and the screening of a frame against many candidates (velo_match_frames).
+// kernels of velo_match_kernels.h) and the screening of a frame against many candidates (velo_match_frames).  Also the prune of a frame
+// to a registration's good matches (velo_frames_prune / _keep) and the put of a frame whose keypoint depth the device computes
+// (velo_frames_put_frame[_batch]: velo.h:329-497 on the device functions of velo_depth_kernels.h, in front of this store and the landmark store).
 //
 // Who knows what: the DEVICE holds the arrays of every (frame, camera) in one arena of 4-byte words and one slot table per camera;
 // the HOST keeps the directory (frame, cam) -> block, n, n_with_depth, the largest id of the block (which sizes the slot table
@@ -22,11 +24,13 @@ struct FrArena {
     T* at(const Block& b) const { return buf.p + Per * b.off; }
     // where an entry of `need` units goes (old: the block it holds now, or null); the arena has grown if the plan asked for it, and
     // nothing else of the bookkeeping has changed: list.commit(plan, old) follows the last call that can fail
-    int place(velo_ctx* c, const Block* old, size_t need, BlockList::Plan* plan) {
-        *plan = list.plan(old, need);
+    int place(velo_ctx* c, const Block* old, size_t need, BlockList::Plan* plan) { return place(c, &list, old, need, plan); }
+    // the same on a copy of the bookkeeping: a call that places several entries and fails on a later one hands no list back
+    int place(velo_ctx* c, BlockList* l, const Block* old, size_t need, BlockList::Plan* plan) {
+        *plan = l->plan(old, need);
         if (plan->grow_to > 0) {
-            VELO_TRY(lm_regrow(c, &buf, Per * list.used, Per * plan->grow_to, 0));
-            list.grew(*plan);
+            VELO_TRY(lm_regrow(c, &buf, Per * l->used, Per * plan->grow_to, 0));
+            l->grew(*plan);
         }
         return VELO_OK;
     }
@@ -52,6 +56,8 @@ struct FrStore {
     PinBuf<> h_in, h_out;
     DevBuf<unsigned char> d_in, d_out;
     DevBuf<unsigned char> d_prune;                  // scratch of a prune call: the keep maps | the gathered blocks | the gathered rows
+    // scratch of a frame put with its depth: the call's upload (tables | ring offsets | block images | rows) | every unit's stacks, points, flags, records
+    DevBuf<unsigned char> d_depth;
     uint64_t next_gen = 1;
 };
 
@@ -569,6 +575,283 @@ int fr_prune_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, int keep_cam
     return fb_release(ctxs, n_ctx);
 }
 
+// One launch set that puts frames[i] of ctxs[i] with the depth of its keypoints computed on the device (velo_frames_put_frame[_batch];
+// cams [n_ctx][8], n_with_depth [n_ctx][8] or null).  The callers have checked the list; everything else is checked here, before
+// anything changes.  What the call leaves per camera is what velo_project_lidar, velo_depth_association, velo_frames_put,
+// velo_frames_put_descriptors and (VELO_PUT_OBSERVE) velo_landmarks_observe leave, the arenas' and the log's bookkeeping included.
+int fr_put_frame_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, const int32_t* of_target, const velo_frame_cam* cams, double thresh,
+                     int32_t flags, int32_t* n_with_depth) {
+    const bool observe = (flags & VELO_PUT_OBSERVE) != 0;
+    struct Span {
+        const velo_frame_cam* K;
+        size_t img, rows;                                            // bytes into the upload
+        size_t pstack, vstack, ring_cnt, kp_point, flag, obs, obs_ids;   // bytes into the scratch behind it
+        int max_id;
+    };
+    std::vector<Span> span;
+    std::vector<int> unit0(n_ctx + 1, 0);
+    for (int i = 0; i < n_ctx; i++) {
+        velo_ctx* c = ctxs[i];
+        VELO_TRY(fr_need_store(c, "velo_frames_put_frame"));
+        const FrStore& S = *c->fr;
+        for (int cam = 0; cam < S.n_cams; cam++) {
+            const velo_frame_cam& K = cams[(size_t)i * kLmMaxCams + cam];
+            if (K.n < 0) return fail(VELO_ERR_INVALID, "context %d, camera %d: negative count", i, cam);
+            if (K.n > 0 && (!K.ids || !K.keypoints_xy)) return fail(VELO_ERR_INVALID, "context %d, camera %d: null ids / keypoints", i, cam);
+            if (K.rows && K.n > kMatchMaxRows)
+                return fail(VELO_ERR_INVALID, "context %d, camera %d: %d descriptor rows; the match key indexes at most %d", i, cam, K.n, kMatchMaxRows);
+            int32_t max_id = -1;
+            for (int k = 0; k < K.n; k++) {
+                if (K.ids[k] < 0) return fail(VELO_ERR_INVALID, "context %d, camera %d, entry %d: negative id %d", i, cam, k, K.ids[k]);
+                if (K.ids[k] >= kLmMaxId) return fail(VELO_ERR_INVALID, "context %d, camera %d, entry %d: id %d; below %d", i, cam, k, K.ids[k], kLmMaxId);
+                max_id = std::max(max_id, K.ids[k]);
+            }
+            if (observe && K.n > 1) {   // an id twice in one camera: found in a sorted copy, as velo_landmarks_observe finds it
+                std::vector<int32_t> sorted(K.ids, K.ids + K.n);
+                std::sort(sorted.begin(), sorted.end());
+                for (int k = 1; k < K.n; k++)
+                    if (sorted[(size_t)k] == sorted[(size_t)k - 1])
+                        return fail(VELO_ERR_INVALID, "context %d, camera %d: id %d appears twice", i, cam, sorted[(size_t)k]);
+            }
+            Span sp;
+            std::memset(&sp, 0, sizeof(sp));
+            sp.K = &K; sp.max_id = max_id;
+            span.push_back(sp);
+        }
+        unit0[i + 1] = (int)span.size();
+    }
+    for (int i = 0; i < n_ctx; i++) {
+        velo_ctx* c = ctxs[i];
+        if (of_target[i] ? !c->have_target : !c->have_source)
+            return fail(VELO_ERR_STATE, "context %d: no %s cloud loaded", i, of_target[i] ? "target" : "source");
+        if (!observe) continue;
+        VELO_TRY(lm_need_store(c, "velo_frames_put_frame (VELO_PUT_OBSERVE)"));
+        if (c->lm->n_cams != c->fr->n_cams)
+            return fail(VELO_ERR_STATE, "context %d: the landmark store has %d cameras, the frame store %d", i, c->lm->n_cams, c->fr->n_cams);
+        for (int cam = 0; cam < c->fr->n_cams; cam++)
+            if (c->lm->lists.count(lm_key(frames[i], cam)))
+                return fail(VELO_ERR_INVALID, "context %d: frame %d, camera %d has been observed already", i, frames[i], cam);
+    }
+    velo_ctx* c0 = ctxs[0];
+    FrStore* L = c0->fr.get();
+    HIP_TRY(hipSetDevice(c0->device));
+    // where everything lies: the upload (units | every context's ring offsets | every unit's block image | its rows) and, behind it in
+    // the same device buffer, every unit's share of the scratch.  A unit without keypoints projects nothing and owns no scratch.
+    const int n_units = (int)span.size();
+    std::vector<int> chunk0, n_rings(n_ctx, 0), n_pts(n_ctx, 0);
+    std::vector<size_t> off_at(n_ctx, 0);
+    size_t cur = 0;
+    auto take = [&cur](size_t bytes) { const size_t at = cur; cur = fb_align64(cur + bytes); return at; };
+    (void)take(sizeof(FrDepthUnit) * (size_t)n_units);
+    for (int i = 0; i < n_ctx; i++) {
+        const velo_ctx* c = ctxs[i];
+        n_rings[i] = std::max((int)(of_target[i] ? c->T->h_tgt_off : c->h_src_off).size() - 1, 0);
+        n_pts[i] = of_target[i] ? c->T->n_tgt : c->n_src;
+        off_at[i] = take(sizeof(int) * ((size_t)n_rings[i] + 1));
+    }
+    for (Span& sp : span) sp.img = take(sizeof(int) * fr_round(7 * (size_t)sp.K->n));          // at most n depth points
+    for (Span& sp : span) if (sp.K->rows && sp.K->n > 0) sp.rows = take(64 * (size_t)sp.K->n);
+    const size_t in_bytes = cur;
+    int n_chunks = 0, max_chunks = 0, max_n = 0, max_rings = 0;
+    for (int i = 0; i < n_ctx; i++)
+        for (int u = unit0[i]; u < unit0[i + 1]; u++) {
+            Span& sp = span[(size_t)u];
+            const size_t n = (size_t)sp.K->n;
+            const int ch = cdiv(sp.K->n, kFrChunk);
+            chunk0.push_back(n_chunks);
+            n_chunks += ch;
+            max_chunks = std::max(max_chunks, ch);
+            max_n = std::max(max_n, sp.K->n);
+            if (n == 0) continue;
+            max_rings = std::max(max_rings, n_rings[i]);
+            sp.pstack = take(sizeof(float4) * (size_t)std::max(n_pts[i], 1));
+            sp.vstack = take(sizeof(float4) * (size_t)std::max(n_pts[i], 1));
+            sp.ring_cnt = take(sizeof(int) * (size_t)std::max(n_rings[i], 1));
+            sp.kp_point = take(sizeof(float4) * n);
+            sp.flag = take(sizeof(int) * n);
+            if (observe) { sp.obs = take(sizeof(velo_tri_obs) * n); sp.obs_ids = take(sizeof(int) * n); }
+        }
+    chunk0.push_back(n_chunks);
+    const size_t all_bytes = cur;
+    const size_t cnt_bytes = std::max<size_t>(sizeof(int) * (size_t)n_chunks, 64);
+    VELO_TRY(L->h_in.reserve(in_bytes));
+    VELO_TRY(L->h_out.reserve(cnt_bytes));
+    VELO_TRY(L->d_out.reserve(cnt_bytes));
+    if (all_bytes > L->d_depth.cap) {                                   // geometric, and kept
+        HIP_TRY(hipStreamSynchronize(c0->stream));                       // the copies of the call before may still read the old scratch
+        VELO_TRY(L->d_depth.reserve(std::max(all_bytes, 2 * L->d_depth.cap)));
+    }
+    // room in the landmark stores: the id tables and the log, which grows as the calls per camera would have grown it (velo_landmarks_info
+    // shows capacity and reallocations) -- in one step, and the store's own numbers change with the rest of its bookkeeping
+    struct LogPlan { size_t need_ids = 0, log_cap = 0; int reallocs = 0; };
+    std::vector<LogPlan> lp(n_ctx);
+    for (int i = 0; observe && i < n_ctx; i++) {
+        velo_ctx* c = ctxs[i];
+        LmStore& M = *c->lm;
+        int max_id = -1;
+        size_t len = M.log_len, cap = M.log_cap;
+        for (int u = unit0[i]; u < unit0[i + 1]; u++) {
+            const size_t n = (size_t)span[(size_t)u].K->n;
+            max_id = std::max(max_id, span[(size_t)u].max_id);
+            if (len + n > cap) { cap = std::max(len + n, 2 * cap); lp[i].reallocs++; }
+            len += n;
+        }
+        lp[i].need_ids = std::max(M.n_ids, (size_t)(max_id + 1));
+        lp[i].log_cap = cap;
+        if (lp[i].need_ids > M.id_cap) {
+            const size_t ids = std::max<size_t>({lp[i].need_ids, 2 * M.id_cap, 4096});
+            VELO_TRY(lm_regrow(c, &M.head, M.n_ids, ids, 0xFF));       // -1: no observation yet
+            VELO_TRY(lm_regrow(c, &M.count, M.n_ids, ids, 0));
+            VELO_TRY(lm_regrow(c, &M.pts, 3 * M.n_ids, 3 * ids, 0));
+            VELO_TRY(lm_regrow(c, &M.added, M.n_ids, ids, 0));
+            M.id_cap = std::min(std::min(M.head.cap, M.count.cap), std::min(M.pts.cap / 3, M.added.cap));
+        }
+        if (cap > M.log_cap && (M.log.cap < cap || M.prev.cap < cap)) {
+            VELO_TRY(lm_regrow(c, &M.log, M.log_len, cap, 0));
+            VELO_TRY(lm_regrow(c, &M.prev, M.log_len, cap, 0xFF));
+        }
+    }
+    unsigned char* dev = L->d_depth.p;
+    {
+        FrDepthUnit* hu = (FrDepthUnit*)L->h_in.p;
+        std::memset(hu, 0, sizeof(FrDepthUnit) * (size_t)n_units);
+        for (int i = 0; i < n_ctx; i++) {
+            const velo_ctx* c = ctxs[i];
+            const FrStore& S = *c->fr;
+            const std::vector<int>& h_off = of_target[i] ? c->T->h_tgt_off : c->h_src_off;
+            int* ho = (int*)(L->h_in.p + off_at[i]);
+            ho[0] = 0;
+            if (n_rings[i] > 0) std::memcpy(ho, h_off.data(), sizeof(int) * ((size_t)n_rings[i] + 1));
+            for (int u = unit0[i]; u < unit0[i + 1]; u++) {
+                const Span& sp = span[(size_t)u];
+                const velo_frame_cam& K = *sp.K;
+                const int cam = u - unit0[i];
+                const size_t n = (size_t)K.n;
+                FrDepthUnit& U = hu[u];
+                U.n = K.n; U.frame = frames[i]; U.cam = cam;
+                U.chunk0 = chunk0[(size_t)u]; U.n_chunks = chunk0[(size_t)u + 1] - chunk0[(size_t)u];
+                U.image = (int*)(dev + sp.img);
+                if (n == 0) continue;
+                U.pts = (const float4*)(of_target[i] ? c->T->tgt.p : c->src.p);
+                U.off = (const int*)(dev + off_at[i]);
+                U.n_rings = n_rings[i];
+                U.W.tx = S.cam_t[3 * cam]; U.W.ty = S.cam_t[3 * cam + 1]; U.W.tz = S.cam_t[3 * cam + 2];
+                U.W.min_x = K.bounds[0]; U.W.max_x = K.bounds[1]; U.W.min_y = K.bounds[2]; U.W.max_y = K.bounds[3];
+                U.pstack = (float4*)(dev + sp.pstack); U.vstack = (float4*)(dev + sp.vstack); U.ring_cnt = (int*)(dev + sp.ring_cnt);
+                U.kp_point = (float4*)(dev + sp.kp_point); U.flag = (int*)(dev + sp.flag);
+                if (observe) { U.obs = (velo_tri_obs*)(dev + sp.obs); U.obs_ids = (int*)(dev + sp.obs_ids); }
+                int* img = (int*)(L->h_in.p + sp.img);               // has_depth and the cloud are the device's to write
+                std::memcpy(img, K.ids, sizeof(int) * n);
+                std::memcpy(img + 2 * n, K.keypoints_xy, sizeof(float) * 2 * n);
+                if (K.rows) std::memcpy(L->h_in.p + sp.rows, K.rows, 64 * n);
+            }
+        }
+    }
+    VELO_TRY(fb_gather(ctxs, n_ctx, nullptr));
+    hipStream_t st = c0->stream;
+    int* d_counts = (int*)L->d_out.p;
+    if (n_chunks > 0) {
+        HIP_TRY(hipMemcpyAsync(dev, L->h_in.p, in_bytes, hipMemcpyHostToDevice, st));
+        const FrDepthUnit* d_units = (const FrDepthUnit*)dev;
+        const dim3 g((unsigned)max_chunks, (unsigned)n_units);
+        if (max_rings > 0) hipLaunchKernelGGL(fr_depth_project_kernel, dim3((unsigned)max_rings, (unsigned)n_units), dim3(256), 0, st, d_units);
+        hipLaunchKernelGGL(fr_depth_assoc_kernel, dim3((unsigned)cdiv(max_n, 4), (unsigned)n_units), dim3(256), 0, st, d_units, thresh);
+        hipLaunchKernelGGL(fr_depth_count_kernel, g, dim3(kFrChunk), 0, st, d_units, d_counts);
+        hipLaunchKernelGGL(fr_depth_write_kernel, g, dim3(kFrChunk), 0, st, d_units, (const int*)d_counts);
+        if (observe) {
+            hipLaunchKernelGGL(fr_depth_obs_kernel, g, dim3(256), 0, st, d_units);
+            // the append runs unchanged, a camera at a time: two cameras of a context may hold the same id
+            for (int i = 0; i < n_ctx; i++) {
+                LmStore& M = *ctxs[i]->lm;
+                size_t base = M.log_len;
+                for (int u = unit0[i]; u < unit0[i + 1]; u++) {
+                    const Span& sp = span[(size_t)u];
+                    const int n = sp.K->n;
+                    if (n > 0)
+                        hipLaunchKernelGGL(lm_append_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, (const velo_tri_obs*)(dev + sp.obs),
+                                           (const int*)(dev + sp.obs_ids), n, (int)base, M.log.p, M.prev.p, M.head.p, M.count.p);
+                    base += (size_t)n;
+                }
+            }
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(L->h_out.p, L->d_out.p, sizeof(int) * (size_t)n_chunks, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    // The host now knows every block's size: it places the blocks in camera order -- the keypoint block as velo_frames_put would, the row
+    // block as velo_frames_put_descriptors after it -- on COPIES of the arenas' lists, queues the copies out of the scratch behind the
+    // launches, and hands lists and directories back after the last call that can fail.
+    const int* h_counts = (const int*)L->h_out.p;
+    struct Change { int64_t key; FrStore::Entry e; bool has_rows; FrStore::RowEntry r; };
+    struct Pending { BlockList kl, rl; std::vector<Change> ch; };
+    std::vector<Pending> pend(n_ctx);
+    for (int i = 0; i < n_ctx; i++) {
+        velo_ctx* c = ctxs[i];
+        FrStore& S = *c->fr;
+        Pending& P = pend[(size_t)i];
+        P.kl = S.kp.list; P.rl = S.rows.list;
+        for (int u = unit0[i]; u < unit0[i + 1]; u++) {
+            const Span& sp = span[(size_t)u];
+            const int n = sp.K->n;
+            int n_wd = 0;
+            for (int k = chunk0[(size_t)u]; k < chunk0[(size_t)u + 1]; k++) n_wd += h_counts[k];
+            const size_t words = 4 * (size_t)n + 3 * (size_t)n_wd;
+            Change C;
+            C.key = lm_key(frames[i], u - unit0[i]);
+            auto old = S.dir.find(C.key);
+            const Block* old_blk = old != S.dir.end() ? &old->second.blk : nullptr;
+            BlockList::Plan plan;
+            // an arena that has to grow is copied on its context's stream: not before the copies this call has queued into it have landed
+            if (P.kl.plan(old_blk, fr_round(words)).grow_to > 0) HIP_TRY(hipStreamSynchronize(st));
+            VELO_TRY(S.kp.place(c, &P.kl, old_blk, fr_round(words), &plan));
+            if (words > 0) HIP_TRY(hipMemcpyAsync(S.kp.at(plan.block), dev + sp.img, sizeof(int) * words, hipMemcpyDeviceToDevice, st));
+            P.kl.commit(plan, old_blk);
+            C.e = FrStore::Entry{plan.block, n, n_wd, sp.max_id, 0};
+            // the rows the entry held go with its keypoints; new ones take a block of their own
+            auto old_rows = S.rdir.find(C.key);
+            if (old_rows != S.rdir.end()) P.rl.release(old_rows->second.blk);
+            C.has_rows = sp.K->rows != nullptr;
+            if (C.has_rows) {
+                if (P.rl.plan(nullptr, (size_t)n).grow_to > 0) HIP_TRY(hipStreamSynchronize(st));
+                VELO_TRY(S.rows.place(c, &P.rl, nullptr, (size_t)n, &plan));
+                if (n > 0) HIP_TRY(hipMemcpyAsync(S.rows.at(plan.block), dev + sp.rows, 64 * (size_t)n, hipMemcpyDeviceToDevice, st));
+                P.rl.commit(plan, nullptr);
+                C.r = FrStore::RowEntry{plan.block, n};
+            }
+            P.ch.push_back(C);
+            if (n_with_depth) n_with_depth[(size_t)i * kLmMaxCams + (size_t)(u - unit0[i])] = n_wd;
+        }
+    }
+    VELO_TRY(fb_release(ctxs, n_ctx));
+    for (int i = 0; i < n_ctx; i++) {
+        velo_ctx* c = ctxs[i];
+        FrStore& S = *c->fr;
+        Pending& P = pend[(size_t)i];
+        S.kp.list = std::move(P.kl); S.rows.list = std::move(P.rl);
+        for (Change& C : P.ch) {
+            C.e.gen = S.next_gen++;
+            S.dir[C.key] = C.e;
+            if (C.has_rows) S.rdir[C.key] = C.r; else S.rdir.erase(C.key);
+        }
+        if (!observe) continue;
+        // velo_landmarks_observe's bookkeeping, camera after camera
+        LmStore& M = *c->lm;
+        const int frame = frames[i];
+        M.log_cap = lp[i].log_cap; M.log_reallocs += lp[i].reallocs;
+        if ((size_t)frame >= M.frame_seen.size()) { M.frame_seen.resize((size_t)frame + 1, 0); M.pose_set.resize((size_t)frame + 1, 0); }
+        M.n_ids = lp[i].need_ids;
+        if (M.h_count.size() < M.n_ids) { M.h_count.resize(M.n_ids, 0); M.h_added.resize(M.n_ids, 0); }
+        for (int u = unit0[i]; u < unit0[i + 1]; u++) {
+            const velo_frame_cam& K = *span[(size_t)u].K;
+            if (!M.frame_seen[(size_t)frame] && K.n > 0) { M.frame_seen[(size_t)frame] = 1; if (!M.pose_set[(size_t)frame]) M.n_missing++; }
+            M.lists[lm_key(frame, u - unit0[i])].assign(K.ids, K.ids + K.n);
+            for (int k = 0; k < K.n; k++) M.h_count[(size_t)K.ids[k]]++;
+            M.log_len += (size_t)K.n;
+        }
+    }
+    return VELO_OK;
+}
+
 }  // namespace
 
 extern "C" {   // (continued from the previous part)
@@ -816,6 +1099,24 @@ int velo_frames_prune_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* frame
 int velo_frames_prune(velo_ctx* c, int32_t frame, int32_t* n_kept, int32_t* n_with_depth, int32_t* kept_out, int32_t capacity, int32_t* n_out) {
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
     return velo_frames_prune_batch(&c, 1, &frame, n_kept, n_with_depth, kept_out, capacity, n_out);
+}
+
+int velo_frames_put_frame_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* frames, const int32_t* of_target, const velo_frame_cam* cams,
+                                double depth_assoc_thresh, int32_t flags, int32_t* n_with_depth) {
+    VELO_TRY(fb_check_list(ctxs, n_ctx));
+    if (!frames || !of_target) return fail(VELO_ERR_INVALID, "null frames / of_target");
+    if (!cams) return fail(VELO_ERR_INVALID, "null cams");
+    if (flags & ~VELO_PUT_OBSERVE) return fail(VELO_ERR_INVALID, "unknown flags 0x%x", (unsigned)flags);
+    for (int i = 0; i < n_ctx; i++)
+        if (frames[i] < 0 || frames[i] >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "context %d: frame %d; 0..%d", i, frames[i], kLmMaxFrame - 1);
+    VELO_TRY(fb_check_devices(ctxs, n_ctx));
+    return fr_put_frame_run(ctxs, n_ctx, frames, of_target, cams, depth_assoc_thresh, flags, n_with_depth);
+}
+
+int velo_frames_put_frame(velo_ctx* c, int32_t frame, int32_t of_target, const velo_frame_cam* cams, double depth_assoc_thresh, int32_t flags,
+                          int32_t* n_with_depth) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    return velo_frames_put_frame_batch(&c, 1, &frame, &of_target, cams, depth_assoc_thresh, flags, n_with_depth);
 }
 
 int velo_get_visual(velo_ctx* c, velo_match* out, int32_t capacity, int32_t* n) {

@@ -19,16 +19,14 @@ struct CamWindow { float tx, ty, tz; double min_x, max_x, min_y, max_y; };
 // a time.  A run whose x never decreases (and does not start left of the stack top) can neither pop nor be dropped
 // (velo.h:351-365 both require c.x < top.x), so it is pushed by 64 lanes at once; only runs that contain a descent -- depth
 // discontinuities seen with parallax -- are replayed entry by entry by lane 0.
+// The pass is a __device__ function: project_ring_kernel runs it on the context's stacks, fr_depth_project_kernel (velo_frame_kernels.h)
+// on those of every camera of a frame put -- one text of the occlusion-stack rule.
 constexpr int kProjChunk = 1024;
-__global__ void __launch_bounds__(256)
-project_ring_kernel(const float4* __restrict__ pts, const int* __restrict__ off, int n_rings, CamWindow W,
-                    float4* __restrict__ pstack, float4* __restrict__ vstack, int* __restrict__ cnt)
-#if VELO_DEF_LOAD
-{
+__device__ __forceinline__ void
+project_ring(const float4* __restrict__ pts, const int* __restrict__ off, int ring, const CamWindow& W,
+             float4* __restrict__ pstack, float4* __restrict__ vstack, int* __restrict__ cnt) {
     __shared__ float4 s_e[kProjChunk];                               // {c.x, c.y, shifted z, bits(index inside the ring)}
     __shared__ float4 s_p[kProjChunk];                               // un-shifted point
-    const int ring = blockIdx.x;
-    if (ring >= n_rings) return;
     const int tid = threadIdx.x, lane = tid & 63;
     const int base = off[ring], n = off[ring + 1] - base;
     int top = 0;                    // stack height (wave 0, uniform)
@@ -86,6 +84,16 @@ project_ring_kernel(const float4* __restrict__ pts, const int* __restrict__ off,
     }
     if (tid == 0) cnt[ring] = top;
 }
+
+__global__ void __launch_bounds__(256)
+project_ring_kernel(const float4* __restrict__ pts, const int* __restrict__ off, int n_rings, CamWindow W,
+                    float4* __restrict__ pstack, float4* __restrict__ vstack, int* __restrict__ cnt)
+#if VELO_DEF_LOAD
+{
+    const int ring = blockIdx.x;
+    if (ring >= n_rings) return;
+    project_ring(pts, off, ring, W, pstack, vstack, cnt);
+}
 #else
 ;
 #endif
@@ -108,15 +116,12 @@ __device__ __forceinline__ void lerp_p(const float p1[3], const float p2[3], flo
 // `last_interp` (velo.h:394-491); that state is just "ring s-1 bracketed the keypoint, at segment mid" -- a pure function
 // of ring s-1 -- so every lane runs the reference's bisection on its own ring, lane s reads lane s-1's result, and the
 // first lane whose test passes is the ring at which the reference stops.
-__global__ void __launch_bounds__(256)
-depth_assoc_kernel(const float2* __restrict__ kps, int n_kp, const float4* __restrict__ pstack, const float4* __restrict__ vstack,
-                   const int* __restrict__ off, const int* __restrict__ cnt, int n_rings, double thresh,
-                   float4* __restrict__ kp_point, int* __restrict__ flag)
-#if VELO_DEF_LOAD
-{
-    const int lane = threadIdx.x & 63;
-    const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (k >= n_kp) return;
+// The search of keypoint k by one wave is a __device__ function: depth_assoc_kernel runs it on the context's projection,
+// fr_depth_assoc_kernel (velo_frame_kernels.h) on that of every camera of a frame put.
+__device__ __forceinline__ void
+depth_assoc_keypoint(const float2* __restrict__ kps, int k, int lane, const float4* __restrict__ pstack, const float4* __restrict__ vstack,
+                     const int* __restrict__ off, const int* __restrict__ cnt, int n_rings, double thresh,
+                     float4* __restrict__ kp_point, int* __restrict__ flag) {
     const float2 kp = kps[k];
     int carry_found = 0, carry_mid = 0;
     int hit = 0;
@@ -166,6 +171,18 @@ depth_assoc_kernel(const float2* __restrict__ kps, int n_kp, const float4* __res
         carry_found = __shfl(found, 63); carry_mid = __shfl(mid, 63);
     }
     if (lane == 0) flag[k] = hit;
+}
+
+__global__ void __launch_bounds__(256)
+depth_assoc_kernel(const float2* __restrict__ kps, int n_kp, const float4* __restrict__ pstack, const float4* __restrict__ vstack,
+                   const int* __restrict__ off, const int* __restrict__ cnt, int n_rings, double thresh,
+                   float4* __restrict__ kp_point, int* __restrict__ flag)
+#if VELO_DEF_LOAD
+{
+    const int lane = threadIdx.x & 63;
+    const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (k >= n_kp) return;
+    depth_assoc_keypoint(kps, k, lane, pstack, vstack, off, cnt, n_rings, thresh, kp_point, flag);
 }
 #else
 ;

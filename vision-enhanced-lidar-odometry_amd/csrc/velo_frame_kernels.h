@@ -28,11 +28,23 @@
 // The new layout overlaps the old one (has_depth starts at word m, inside the old ids) while other workgroups still read the old block,
 // so the move kernel never writes an arena: it gathers into scratch that nothing else of the launch reads, and the host copies a unit's
 // result over its block in stream order (velo_api_frames.inl), after the whole launch.
+//
+// A frame put with its keypoint depth (velo_frames_put_frame[_batch]: projectLidarToCamera + featureDepthAssociation, velo.h:329-497,
+// in front of the store): the bodies are velo_depth_kernels.h's device functions, run per UNIT on stacks of the frame store's own,
+//     fr_depth_project_kernel   grid (rings, units): project_ring on the unit's cloud, window and stacks
+//     fr_depth_assoc_kernel     one wave per keypoint of every unit: depth_assoc_keypoint -> the keypoint's point and flag
+//     fr_depth_count_kernel     per chunk of kFrChunk keypoints: how many have depth
+//     fr_depth_write_kernel     a chunk's first depth point = those of the unit's earlier chunks, inside the chunk the scan keeps
+//                               keypoint order (no counter: velo.h:481-483's append order); writes has_depth and the cloud into the
+//                               unit's block image, whose ids and keypoints came with the call's upload
+//     fr_depth_obs_kernel       (VELO_PUT_OBSERVE) one thread per keypoint: the image's entry as lm_append_kernel's record and id
+// The image is sized for n depth points and lies in scratch: the host learns the count, places the block at its exact size and copies.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/velo_hip.h"
 #include "velo_kernels.h"
+#include "velo_depth_kernels.h"
 #include "velo_landmark_kernels.h"
 
 #ifndef VELO_DEF_FRAMES
@@ -332,6 +344,127 @@ fr_prune_move_kernel(const FrPruneUnit* __restrict__ units, const int* __restric
         const int r = t >> 2, q = t & 3;
         U.rows_out[4 * (size_t)(base + r) + q] = U.rows[4 * (size_t)(first + src[r]) + q];
     }
+}
+#else
+;
+#endif
+
+// one camera of one context of a frame put with its depth
+struct FrDepthUnit {
+    const float4* pts;                 // the context's cloud on the named side, ring-major
+    const int* off;                    // its ring offsets, n_rings + 1 entries
+    CamWindow W;                       // the store's translation of this camera and the caller's window
+    float4* pstack;                    // scratch: this unit's occlusion stacks, parallel to the cloud (velo_depth_kernels.h) ...
+    float4* vstack;
+    int* ring_cnt;                     // ... and their heights
+    float4* kp_point;                  // scratch, per keypoint: the interpolated point ...
+    int* flag;                         // ... and whether there is one
+    int* image;                        // 64-byte aligned: ids[n] | has_depth[n] | xy[n][2] | cloud[n_with_depth][3], room for n depth points
+    velo_tri_obs* obs;                 // VELO_PUT_OBSERVE: the n records and ids lm_append_kernel reads, else null
+    int* obs_ids;
+    int n_rings, n;                    // n_rings == 0 for a unit without keypoints: nothing is projected for it
+    int chunk0, n_chunks;              // this unit's chunks in the call's count array
+    int frame, cam;
+};
+
+__global__ void __launch_bounds__(256)
+fr_depth_project_kernel(const FrDepthUnit* __restrict__ units)
+#if VELO_DEF_FRAMES
+{
+    const FrDepthUnit& U = units[blockIdx.y];
+    const int ring = blockIdx.x;
+    if (ring >= U.n_rings) return;                                    // workgroup-uniform
+    project_ring(U.pts, U.off, ring, U.W, U.pstack, U.vstack, U.ring_cnt);
+}
+#else
+;
+#endif
+
+__global__ void __launch_bounds__(256)
+fr_depth_assoc_kernel(const FrDepthUnit* __restrict__ units, double thresh)
+#if VELO_DEF_FRAMES
+{
+    const FrDepthUnit& U = units[blockIdx.y];
+    const int lane = threadIdx.x & 63;
+    const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (k >= U.n) return;                                             // wave-uniform
+    depth_assoc_keypoint(reinterpret_cast<const float2*>(U.image + 2 * (size_t)U.n), k, lane, U.pstack, U.vstack, U.off, U.ring_cnt, U.n_rings,
+                         thresh, U.kp_point, U.flag);
+}
+#else
+;
+#endif
+
+__global__ void __launch_bounds__(kFrChunk)
+fr_depth_count_kernel(const FrDepthUnit* __restrict__ units, int* __restrict__ counts)
+#if VELO_DEF_FRAMES
+{
+    const FrDepthUnit& U = units[blockIdx.y];
+    const int first = blockIdx.x * kFrChunk;
+    if (first >= U.n) return;                                         // workgroup-uniform
+    const int i = first + (int)threadIdx.x;
+    int total;
+    (void)block_exclusive_scan(i < U.n ? U.flag[i] : 0, &total);
+    if (threadIdx.x == 0) counts[U.chunk0 + blockIdx.x] = total;
+}
+#else
+;
+#endif
+
+__global__ void __launch_bounds__(kFrChunk)
+fr_depth_write_kernel(const FrDepthUnit* __restrict__ units, const int* __restrict__ counts)
+#if VELO_DEF_FRAMES
+{
+    __shared__ int part[kFrChunk / kWave];
+    const FrDepthUnit& U = units[blockIdx.y];
+    const int first = blockIdx.x * kFrChunk;
+    if (first >= U.n) return;                                         // workgroup-uniform
+    int before = 0;                                                   // depth points of the unit's chunks before this one
+    for (int k = (int)threadIdx.x; k < (int)blockIdx.x; k += kFrChunk) before += counts[U.chunk0 + k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = before;
+    __syncthreads();
+    int base = 0;
+#pragma unroll
+    for (int w = 0; w < kFrChunk / kWave; w++) base += part[w];
+    const int i = first + (int)threadIdx.x;
+    const int f = i < U.n ? U.flag[i] : 0;
+    int total;
+    const int j = base + block_exclusive_scan(f, &total);
+    if (i >= U.n) return;
+    int* has_depth = U.image + (size_t)U.n;
+    if (f != 0) {                                                     // velo.h:481-483: appended in keypoint order
+        const float4 p = U.kp_point[i];
+        float* q = reinterpret_cast<float*>(U.image + 4 * (size_t)U.n) + 3 * (size_t)j;
+        q[0] = p.x; q[1] = p.y; q[2] = p.z;
+        has_depth[i] = j;
+    } else has_depth[i] = -1;
+}
+#else
+;
+#endif
+
+// main.cpp:622-645's choice for entry i of the unit's image: the depth point when it has one (3-D), else the keypoint (2-D)
+__global__ void __launch_bounds__(256)
+fr_depth_obs_kernel(const FrDepthUnit* __restrict__ units)
+#if VELO_DEF_FRAMES
+{
+    const FrDepthUnit& U = units[blockIdx.y];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= U.n || U.obs == nullptr) return;
+    const int h = U.image[(size_t)U.n + i];
+    velo_tri_obs o;
+    o.frame = U.frame; o.cam = U.cam;
+    if (h == -1) {
+        const float* xy = reinterpret_cast<const float*>(U.image + 2 * (size_t)U.n) + 2 * (size_t)i;
+        o.kind = VELO_TRI_OBS_2D; o.s[0] = xy[0]; o.s[1] = xy[1]; o.s[2] = 0.0f;
+    } else {
+        const float* p = reinterpret_cast<const float*>(U.image + 4 * (size_t)U.n) + 3 * (size_t)h;
+        o.kind = VELO_TRI_OBS_3D; o.s[0] = p[0]; o.s[1] = p[1]; o.s[2] = p[2];
+    }
+    U.obs[i] = o;
+    U.obs_ids[i] = U.image[i];
 }
 #else
 ;
