@@ -849,6 +849,60 @@ int velo_frames_put_frame_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* f
  * the first `capacity` are written (out may be NULL). */
 int velo_get_visual(velo_ctx* ctx, velo_match* out, int32_t capacity, int32_t* n);
 
+/* --- the sliding-window scan map of scan-to-map odometry, resident on the device ---------------------------------------------------
+ * Scan-to-map (BASELINE configs 4-5) registers every scan against the last scans of the drive, all moved into one frame.  A map keeps
+ * that window in HBM: every scan AS IT WAS REGISTERED, in its own sensor frame -- ring-major points, its ring offsets, a pose (row-major
+ * 4 x 4, double) -- and writes the target cloud on demand in whatever reference frame the caller names.  So a map point is rounded to
+ * float exactly once however long the drive runs, "everything in the newest pose's frame" is one streaming launch, and a pose can be
+ * corrected afterwards (a loop closure) with no point traffic at all.  A map is owned like a scan cache: a handle of its own, bound to
+ * one device, used with any context on that device, one call at a time.  It has no stream: insert and load run on the named context's
+ * stream; a load on another stream waits (on the device) for the last insert, and an insert that may take a block a load still reads
+ * waits for the last load.
+ * create:   at most max_scans scans and max_points points (1 .. 2^30); VELO_ERR_NODEVICE without a device, as velo_cache_create.
+ * insert:   the context's source cloud (of_target = 0) or whole-scan target cloud (1) enters under `frame`, device to device, with its
+ *           ring offsets and pose16.  Empty rings of a source are not stored as rings (a target ring may not be empty).  Before the scan
+ *           is stored the OLDEST scans go while the map holds max_scans scans or points + n > max_points; *n_evicted (may be NULL) says
+ *           how many.  Refused with nothing changed and nothing evicted: VELO_ERR_STATE for what velo_cache_store refuses (no scan on
+ *           that side, a target shard) and for a frame that is present (drop it first); VELO_ERR_INVALID for a context on another
+ *           device, a scan with no point, a scan of more than max_points points, a pose that is not finite.  Storage is one arena of
+ *           points with a first-fit free list (blocks are neither split nor merged: made for a window of scans of similar size); it
+ *           starts at 4 KB and grows geometrically, and growth is the only wait: in the steady state an insert is one asynchronous
+ *           copy, no device allocation, no synchronisation.
+ * set_pose: replaces a scan's pose.  drop / clear: the blocks return to the free list.  All three are host bookkeeping;
+ *           VELO_ERR_STATE for a frame that is not in the map.
+ * frames:   oldest first; returns the count (0 for NULL).
+ * info:     int64[8] = scans, points, rings, max_scans, max_points, evictions so far, arena capacity in points, arena growths.
+ * get_scan: one stored scan back (tests): *n_points / *n_rings always; the first capacity_points points (n x 3), the first
+ *           capacity_rings entries of its n_rings + 1 ring offsets, its pose; any output may be NULL.
+ * load:     the map becomes the context's target in the frame ref_inv16 -- the caller supplies the INVERSE of the reference pose, as
+ *           for velo_landmarks_at_frame.  Scans oldest first, rings in scan order, ring offsets concatenated.  Per scan the host forms
+ *           M = ref_inv * pose in double, every entry of rows 0..2 as ((a_i0 b_0j + a_i1 b_1j) + a_i2 b_2j) + a_i3 b_3j; per point the
+ *           device computes q_i = ((M_i0 x + M_i1 y) + M_i2 z) + M_i3 with the floats widened to double, summed left to right without
+ *           contraction, and rounds to float.  No division by a fourth row; no shortcut for an identity (-0.0f comes out +0.0f).  The
+ *           end state is the one velo_set_target leaves when handed that cloud and those offsets, byte for byte: cloud, ring ids, padded
+ *           rings, bounding box and index; correspondences, partials and warm-start seeds invalidated; the target owned by the context
+ *           (velo_share_target from it works).  One table upload and ONE materialise launch for the whole window, then the ingest launch
+ *           of velo_set_target on the materialised cloud in place, then the index build.  VELO_ERR_STATE for an empty map, with the
+ *           context untouched.
+ * load_batch: entry i makes maps[i] the target of ctxs[i] in the frame ref_inv[16 i ..]: distinct contexts on one device (the rules of
+ *           the other batch entries: the first lends its stream and waits for the others' streams; n == 1 IS the single entry); two
+ *           entries may name one map with different frames.  One table upload and one materialise launch for every scan of every entry,
+ *           then every context's ingest and bounding-box request are enqueued before any is waited for.  Every argument and every map
+ *           is checked before any context is touched.  Every context's end state is byte-identical to the single entry's. */
+typedef struct velo_map velo_map;
+int velo_map_create(velo_map** out, int32_t device, int32_t max_scans, int64_t max_points);
+int velo_map_destroy(velo_map* map);                      /* NULL is fine */
+int velo_map_insert(velo_map* map, velo_ctx* ctx, int32_t of_target, int32_t frame, const double pose16[16], int32_t* n_evicted);
+int velo_map_set_pose(velo_map* map, int32_t frame, const double pose16[16]);
+int velo_map_drop(velo_map* map, int32_t frame);
+int velo_map_clear(velo_map* map);
+int velo_map_frames(const velo_map* map, int32_t* frames_out, int32_t capacity);
+int velo_map_info(const velo_map* map, int64_t* info /* [8] */);
+int velo_map_get_scan(velo_map* map, int32_t frame, float* xyz /* n x 3 */, int32_t capacity_points, int32_t* n_points,
+                      int32_t* ring_offsets, int32_t capacity_rings, int32_t* n_rings, double pose16[16]);
+int velo_map_load(velo_map* map, velo_ctx* ctx, const double ref_inv16[16]);
+int velo_map_load_batch(velo_map** maps, velo_ctx** ctxs, int32_t n, const double* ref_inv /* n x 16 */);
+
 #ifdef __cplusplus
 }
 #endif

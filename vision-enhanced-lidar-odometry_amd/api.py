@@ -352,6 +352,17 @@ SIGNATURES = {
     "velo_match_frames": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
     "velo_frames_put_frame": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_void_p]),
     "velo_frames_put_frame_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p]),
+    "velo_map_create": (C.c_int, [_P(C.c_void_p), C.c_int32, C.c_int32, C.c_int64]),
+    "velo_map_destroy": (C.c_int, [C.c_void_p]),
+    "velo_map_insert": (C.c_int, [C.c_void_p, _ctx, C.c_int32, C.c_int32, _dp, _P(C.c_int32)]),
+    "velo_map_set_pose": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "velo_map_drop": (C.c_int, [C.c_void_p, C.c_int32]),
+    "velo_map_clear": (C.c_int, [C.c_void_p]),
+    "velo_map_frames": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int32]),
+    "velo_map_info": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
+    "velo_map_get_scan": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(C.c_int32), C.c_void_p, C.c_int32, _P(C.c_int32), _dp]),
+    "velo_map_load": (C.c_int, [C.c_void_p, _ctx, _dp]),
+    "velo_map_load_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _dp]),
 }
 
 _lib = None
@@ -1150,6 +1161,101 @@ class ScanCache:
         out = (C.c_int32 * max(n, 1))()
         n = self._lib.velo_cache_frames(self._h, out, n)
         return [int(out[i]) for i in range(n)]
+
+
+MAP_INFO_FIELDS = ("scans", "points", "rings", "max_scans", "max_points", "evictions", "arena_points", "arena_growths")
+
+
+class ScanMap:
+    """Device-resident sliding-window scan map (velo_map_*): every scan as it was registered, in its own sensor frame, with a pose;
+    load() writes the window into a context as its target in the frame the caller names (ref_inv: the INVERSE of the reference pose)."""
+
+    def __init__(self, device: int = 0, max_scans: int = 17, max_points: int = 1 << 22, lib: Optional[C.CDLL] = None):
+        self._lib = lib if lib is not None else load_library()
+        self._h = C.c_void_p()
+        status = self._lib.velo_map_create(C.byref(self._h), int(device), int(max_scans), int(max_points))
+        if status != 0:
+            msg = self._lib.velo_last_error()
+            raise VeloError(f"velo status {status}: {msg.decode() if msg else ''}")
+
+    def _check(self, status: int):
+        if status != 0:
+            msg = self._lib.velo_last_error()
+            raise VeloError(f"velo status {status}: {msg.decode() if msg else ''}")
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h:
+            self._lib.velo_map_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def insert(self, ctx: "Context", of_target: bool, frame: int, pose) -> int:
+        """the scan `ctx` holds enters under `frame` with its pose (4 x 4); returns how many of the oldest scans went for it"""
+        p = _dvec(pose, 16)
+        gone = C.c_int32(0)
+        self._check(self._lib.velo_map_insert(self._h, ctx.handle, int(bool(of_target)), int(frame), _ptr(p), C.byref(gone)))
+        return gone.value
+
+    def set_pose(self, frame: int, pose):
+        p = _dvec(pose, 16)
+        self._check(self._lib.velo_map_set_pose(self._h, int(frame), _ptr(p)))
+
+    def drop(self, frame: int):
+        self._check(self._lib.velo_map_drop(self._h, int(frame)))
+
+    def clear(self):
+        self._check(self._lib.velo_map_clear(self._h))
+
+    def frames(self):
+        """frame numbers, oldest first"""
+        n = self._lib.velo_map_frames(self._h, None, 0)
+        out = (C.c_int32 * max(n, 1))()
+        n = self._lib.velo_map_frames(self._h, out, n)
+        return [int(out[i]) for i in range(n)]
+
+    def info(self) -> dict:
+        v = (C.c_int64 * 8)()
+        self._check(self._lib.velo_map_info(self._h, v))
+        return dict(zip(MAP_INFO_FIELDS, (int(x) for x in v)))
+
+    def get_scan(self, frame: int):
+        """(xyz [n, 3] float32, ring offsets int32, pose [4, 4]) of one stored scan"""
+        n, r = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.velo_map_get_scan(self._h, int(frame), None, 0, C.byref(n), None, 0, C.byref(r), None))
+        xyz = np.zeros((max(n.value, 1), 3), dtype=np.float32)
+        off = np.zeros(r.value + 1, dtype=np.int32)
+        pose = np.zeros(16)
+        self._check(self._lib.velo_map_get_scan(self._h, int(frame), xyz.ctypes.data_as(C.c_void_p), n.value, C.byref(n),
+                                                off.ctypes.data_as(C.c_void_p), r.value + 1, C.byref(r), _ptr(pose)))
+        return xyz[:n.value], off, pose.reshape(4, 4)
+
+    def load(self, ctx: "Context", ref_inv):
+        p = _dvec(ref_inv, 16)
+        self._check(self._lib.velo_map_load(self._h, ctx.handle, _ptr(p)))
+
+
+def map_load_batch(maps, ctxs, ref_invs):
+    """ScanMap.load for every (maps[i], ctxs[i], ref_invs[i]) in ONE call: one table upload and one materialise launch for all of them."""
+    if len(maps) != len(ctxs) or not len(ctxs):
+        raise ValueError("map_load_batch: one map per context, at least one")
+    lib = ctxs[0]._lib                                          # the build the contexts were created on
+    n = len(ctxs)
+    ms = (C.c_void_p * n)(*[m.handle for m in maps])
+    cs = (_ctx * n)(*[c.handle for c in ctxs])
+    r = _dvec(np.asarray(ref_invs, dtype=np.float64), 16 * n)
+    st = lib.velo_map_load_batch(ms, cs, n, _ptr(r))
+    if st != 0:
+        msg = lib.velo_last_error()
+        raise VeloError(f"velo status {st}: {msg.decode() if msg else ''}")
 
 
 def comm_unique_id() -> bytes:
