@@ -672,6 +672,68 @@ int velo_landmarks_frame_count(velo_ctx* ctx, int32_t frame, int32_t* n_seen, in
  * pairs observed, 0. */
 int velo_landmarks_info(velo_ctx* ctx, int32_t* info);
 
+/* --- bundle adjustment of a window of frames over the landmark store (main.cpp:673-725, bundle2D / bundle3D costfunctions.h:222-286) ---
+ * A joint refinement of poses and landmarks over the observations the store holds; nothing is uploaded but the frame list and the ids
+ * the window's frames observed.
+ *   frames    n_frames frame numbers, ascending and distinct, each with a pose set (VELO_ERR_STATE otherwise).  The first n_fixed
+ *             (>= 1) are constants and fix the gauge; the other n_free = n_frames - n_fixed (1 .. 10) are unknowns, the 6 doubles of
+ *             their ceres_poses_vec entry (angle-axis, centre).  n_frames x n_cams <= 64.
+ *   landmarks take part if they are added, have at least 2 observations in window frames and at least one of them in a free frame;
+ *             their point, widened from the stored float, is an unknown of 3 doubles.  Every other landmark keeps its bytes.
+ *   residuals per landmark its window observations in the store's block order (3-D first, then 2-D, each camera-major and frame-
+ *             ascending): bundle3D with weight = params->weight_3d and TrivialLoss; bundle2D with cam_trans[cam] and
+ *             ScaledLoss(CauchyLoss(loss_thresh_3D2D), weight_3D2D) -- the losses velo_landmarks_triangulate uses, from velo_params.
+ *   solver    Ceres' trust-region Levenberg-Marquardt over all unknowns with the settings of the context's
+ *             velo_params; the linear step is the Schur complement on the landmark blocks.
+ *   result    poses_out [n_frames][6]: the fixed frames as they were, the free frames refined.  The points are stored back as float and
+ *             the store's frame table is refreshed as velo_landmarks_set_pose does it.  Parameters move on accepted steps only; two
+ *             identical calls on identical state give identical bytes.
+ * Refused before anything changes: VELO_ERR_INVALID for a NULL argument, frames that are not ascending, n_fixed < 1, n_free outside
+ * 1 .. 10, n_frames x n_cams > 64, a weight that is not positive and finite; VELO_ERR_STATE without a store or for a frame without a
+ * pose.  Not offered for several contexts in one call: their LM chains have different lengths. */
+#define VELO_BA_MAX_FREE 10
+#define VELO_BA_MAX_TRACE 50
+#define VELO_BA_ACCEPTED 0      /* velo_ba_iteration.status */
+#define VELO_BA_REJECTED 1
+#define VELO_BA_INVALID 2       /* the linear solve failed or the model did not decrease: no evaluation */
+#define VELO_BA_PARAMETER 3     /* ended by the parameter tolerance */
+#define VELO_BA_FUNCTION 4      /* ended by the function tolerance */
+#define VELO_BA_GRADIENT 5      /* accepted, then ended by the gradient tolerance */
+typedef struct velo_ba_params {    /* 16 bytes */
+    double weight_3d;          /* the `weight` of bundle3D; 1.0 */
+    int32_t reserved[2];       /* 0 */
+} velo_ba_params;
+typedef struct velo_ba_iteration { /* 48 bytes */
+    int32_t status;            /* VELO_BA_* */
+    int32_t iteration;         /* from 1 */
+    double cost;               /* at the iteration's start */
+    double candidate_cost;     /* 0 for an invalid step */
+    double radius;             /* at the iteration's start */
+    double model_change;
+    double step_norm;
+} velo_ba_iteration;
+typedef struct velo_ba_summary {   /* 48 + 50 x 48 bytes */
+    int32_t termination;       /* VELO_CONVERGENCE / NO_CONVERGENCE / FAILURE */
+    int32_t iterations;
+    int32_t evaluations;
+    int32_t n_landmarks;       /* that took part */
+    int32_t n_blocks;
+    int32_t n_residuals;
+    int32_t n_trace;           /* records in trace: min(iterations, VELO_BA_MAX_TRACE) */
+    int32_t reserved;
+    double initial_cost;
+    double final_cost;
+    velo_ba_iteration trace[VELO_BA_MAX_TRACE];
+} velo_ba_summary;
+int velo_default_ba_params(velo_ba_params* params);
+/* params may be NULL (the defaults); poses_out and summary may be NULL. */
+int velo_landmarks_adjust(velo_ctx* ctx, const int32_t* frames, int32_t n_frames, int32_t n_fixed, const velo_ba_params* params,
+                          double* poses_out /* n_frames x 6 */, velo_ba_summary* summary);
+/* Diagnostics: the problem velo_landmarks_adjust would solve, evaluated at the stored state; nothing changes.  cost, the poses' part of
+ * J^T r (gradient [6 n_free]) and the poses' diagonal blocks of J^T J (JtJ_pose [n_free][36], row-major), robustified, unscaled. */
+int velo_landmarks_adjust_system(velo_ctx* ctx, const int32_t* frames, int32_t n_frames, int32_t n_fixed, const velo_ba_params* params,
+                                 double* cost, double* gradient, double* JtJ_pose);
+
 /* --- resident keypoint frames and the visual matches assembled from them (velo.h:562-590, velo.h:627-654, main.cpp:366-405) ---
  * Every context can hold one frame store: for every (frame, camera) put so far keypoints[cam][frame], keypoint_ids[cam][frame],
  * has_depth[cam][frame] and keypoints_with_depth[cam][frame], in one device arena; the host keeps a directory (frame, cam) ->

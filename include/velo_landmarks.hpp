@@ -6,6 +6,7 @@
 //                 store.observeFrame(frame, keypoints, keypoint_ids, has_depth, kp_with_depth);      // main.cpp:622-645
 //                 store.triangulateFrame(frame, landmarks, keypoint_added);                           // main.cpp:647-679
 //     before frameToFrame:  store.landmarksAtFrame(pose_inverse, frame - dframe, landmarks_at_frame);  // main.cpp:376-386
+//     every ba_every frames: store.bundleAdjust(window, n_fixed, ceres_poses_vec, landmarks);          // main.cpp:673-725
 //
 // Templated over the container types (cv::Point2f, pcl::PointCloud<pcl::PointXYZ>::Ptr, Eigen::Matrix4d or stand-ins): a keypoint
 // needs .x / .y, a cloud pointer ->points (a vector of points with .x / .y / .z) and a matrix operator()(row, col).
@@ -96,6 +97,38 @@ public:
             Point p;
             p.x = xyz[3 * k]; p.y = xyz[3 * k + 1]; p.z = xyz[3 * k + 2];
             landmarks_at_frame[ids[k]] = p;
+        }
+        return status_;
+    }
+
+    // The BUNDLE_ADJUST step (main.cpp:673-725) over the window `frames` (ascending; the first n_fixed stay constant): refines
+    // ceres_poses_vec[frame][0..5] of the free frames and landmarks->points[id] of the landmarks that took part, in the store and in
+    // the containers.  ceres_poses_vec[frame] needs operator[] over 6 doubles (double[6], std::vector<double>, ...).
+    template <class Poses, class CloudPtr>
+    int bundleAdjust(const std::vector<int>& frames, int n_fixed, Poses& ceres_poses_vec, CloudPtr& landmarks, velo_ba_summary* summary = 0,
+                     double weight_3d = 1.0) {
+        const size_t n = frames.size();
+        std::vector<int32_t> fr(frames.begin(), frames.end());
+        std::vector<double> poses(6 * (n ? n : 1));
+        velo_ba_params params;
+        if ((status_ = velo_default_ba_params(&params)) != VELO_OK) return status_;
+        params.weight_3d = weight_3d;
+        if ((status_ = velo_landmarks_adjust(ctx_, n ? &fr[0] : 0, (int32_t)n, n_fixed, &params, &poses[0], summary)) != VELO_OK) return status_;
+        for (size_t i = (size_t)n_fixed; i < n; i++)
+            for (int j = 0; j < 6; j++) ceres_poses_vec[frames[i]][j] = poses[6 * i + j];
+        int32_t info[8];
+        if ((status_ = velo_landmarks_info(ctx_, info)) != VELO_OK) return status_;
+        const size_t n_ids = (size_t)info[0];
+        if (n_ids == 0) return status_;
+        std::vector<int32_t> ids(n_ids);
+        std::vector<float> xyz(3 * n_ids);
+        std::vector<uint8_t> added(n_ids);
+        for (size_t id = 0; id < n_ids; id++) ids[id] = (int32_t)id;
+        if ((status_ = velo_landmarks_get(ctx_, &ids[0], (int32_t)n_ids, &xyz[0], &added[0], 0)) != VELO_OK) return status_;
+        if (landmarks->points.size() < n_ids) landmarks->points.resize(n_ids);
+        for (size_t id = 0; id < n_ids; id++) {
+            if (!added[id]) continue;
+            landmarks->points[id].x = xyz[3 * id]; landmarks->points[id].y = xyz[3 * id + 1]; landmarks->points[id].z = xyz[3 * id + 2];
         }
         return status_;
     }

@@ -135,6 +135,25 @@ class FrameCam:
                             (C.c_double * 4)(*self.window))
 
 
+class VeloBaParams(C.Structure):
+    _fields_ = [("weight_3d", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
+class VeloBaIteration(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iteration", C.c_int32), ("cost", C.c_double), ("candidate_cost", C.c_double),
+                ("radius", C.c_double), ("model_change", C.c_double), ("step_norm", C.c_double)]
+
+
+BA_MAX_FREE, BA_MAX_TRACE = 10, 50
+BA_ACCEPTED, BA_REJECTED, BA_INVALID, BA_PARAMETER, BA_FUNCTION, BA_GRADIENT = range(6)
+
+
+class VeloBaSummary(C.Structure):
+    _fields_ = [("termination", C.c_int32), ("iterations", C.c_int32), ("evaluations", C.c_int32), ("n_landmarks", C.c_int32),
+                ("n_blocks", C.c_int32), ("n_residuals", C.c_int32), ("n_trace", C.c_int32), ("reserved", C.c_int32),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double), ("trace", VeloBaIteration * BA_MAX_TRACE)]
+
+
 class VeloResidualStat(C.Structure):
     _fields_ = [("median", C.c_double), ("mean", C.c_double), ("count", C.c_int64)]
 
@@ -330,6 +349,9 @@ SIGNATURES = {
     "velo_landmarks_get": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "velo_landmarks_frame_count": (C.c_int, [_ctx, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
     "velo_landmarks_info": (C.c_int, [_ctx, C.c_void_p]),
+    "velo_default_ba_params": (C.c_int, [_P(VeloBaParams)]),
+    "velo_landmarks_adjust": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, _P(VeloBaParams), C.c_void_p, _P(VeloBaSummary)]),
+    "velo_landmarks_adjust_system": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, _P(VeloBaParams), _dp, C.c_void_p, C.c_void_p]),
     "velo_frames_reset": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_int32]),
     "velo_frames_put": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "velo_frames_drop": (C.c_int, [_ctx, C.c_int32]),
@@ -781,6 +803,37 @@ class Context:
         self._check(self._lib.velo_landmarks_info(self._h, C.c_void_p(a.ctypes.data)))
         return dict(n_ids=int(a[0]), log_entries=int(a[1]), log_capacity=int(a[2]), log_reallocations=int(a[3]), frame_capacity=int(a[4]),
                     n_cams=int(a[5]), observed=int(a[6]))
+
+    # -- bundle adjustment of a window of frames over the landmark store (main.cpp:673-725) ----------------------------------
+    @staticmethod
+    def _ba_arguments(frames, weight_3d):
+        fr = np.ascontiguousarray(np.asarray(frames, dtype=np.int32).reshape(-1))
+        p = VeloBaParams()
+        p.weight_3d = float(weight_3d)
+        return fr, p
+
+    def landmarks_adjust(self, frames, n_fixed: int = 1, weight_3d: float = 1.0):
+        """Bundle-adjusts the window `frames` (ascending; the first n_fixed are constants) over the store's observations:
+        (poses [n_frames, 6] f64 -- the fixed frames as they were, the free ones refined --, VeloBaSummary).  The points and the
+        store's frame table are updated; summary.trace[:summary.n_trace] holds one record per LM iteration."""
+        fr, p = self._ba_arguments(frames, weight_3d)
+        poses = np.zeros((max(len(fr), 1), 6), dtype=np.float64)
+        s = VeloBaSummary()
+        self._check(self._lib.velo_landmarks_adjust(self._h, C.c_void_p(fr.ctypes.data) if len(fr) else None, len(fr), int(n_fixed), C.byref(p),
+                                                    C.c_void_p(poses.ctypes.data), C.byref(s)))
+        return poses[:len(fr)], s
+
+    def landmarks_adjust_system(self, frames, n_fixed: int = 1, weight_3d: float = 1.0):
+        """The problem landmarks_adjust would solve, evaluated at the stored state (nothing changes): (cost, the poses' part of
+        J^T r [6 n_free], the poses' diagonal blocks of J^T J [n_free, 6, 6])"""
+        fr, p = self._ba_arguments(frames, weight_3d)
+        n_free = max(len(fr) - int(n_fixed), 1)
+        cost = C.c_double(0.0)
+        g = np.zeros(6 * n_free, dtype=np.float64)
+        H = np.zeros((n_free, 6, 6), dtype=np.float64)
+        self._check(self._lib.velo_landmarks_adjust_system(self._h, C.c_void_p(fr.ctypes.data) if len(fr) else None, len(fr), int(n_fixed), C.byref(p),
+                                                           C.byref(cost), C.c_void_p(g.ctypes.data), C.c_void_p(H.ctypes.data)))
+        return cost.value, g, H
 
     # -- resident keypoint frames and the visual matches assembled from them (velo.h:562-590, velo.h:627-654) ---------------
     def frames_reset(self, cam_trans, arena_capacity: int = 0):

@@ -29,6 +29,7 @@ struct LmStore {
     Event in_ev;                                    // h_in may be rewritten once this has passed
     DevBuf<unsigned char> d_in, d_out;
     DevBuf<velo_tri_obs> d_obs;                     // the gathered observation lists of a call
+    std::shared_ptr<void> ba;                       // the work buffers of velo_landmarks_adjust (BaWork, velo_api_ba.inl), made by its first call
 };
 
 namespace {
