@@ -734,6 +734,76 @@ int velo_landmarks_adjust(velo_ctx* ctx, const int32_t* frames, int32_t n_frames
 int velo_landmarks_adjust_system(velo_ctx* ctx, const int32_t* frames, int32_t n_frames, int32_t n_fixed, const velo_ba_params* params,
                                  double* cost, double* gradient, double* JtJ_pose);
 
+/* --- the pose graph of a drive and its batch optimisation (main.cpp:190-204, main.cpp:516-536, main.cpp:728-745) ---
+ * Every context can hold one pose graph: one node per frame and every accepted registration as an edge, on the device.  What
+ * velo_graph_optimize returns is what velo_landmarks_set_pose and velo_map_set_pose take: the corrected poses of a loop closure.
+ *   nodes     the 6 doubles of ceres_poses_vec[frame] (angle-axis, translation): the world pose of camera 0.  The reference's nodes of
+ *             the other cameras hang on it by noiseless6 extrinsic factors (main.cpp:196-203, 526-534): rigid copies, not modelled.
+ *   edges     (from, to, z, info) states pose_to = pose_from . Z, Z = pose_mat2vec(z): what frameToFrame returns (main.cpp:408,
+ *             518-524).  The residual is sqrt(info) x pose_vec2mat(Z^-1 . T_from^-1 . T_to), the angle-axis of the rotation and then the
+ *             translation -- the form of main.cpp:416-424; info is the s of Information(s . eye(6)) (noisy6: 1, noiseless6: 1000); the
+ *             loss is trivial.  Duplicate edges add up.
+ *   gauge     fixed nodes are constants (the reference's prior of weight 1000 on node 0 becomes "node 0 is fixed"); at least one.  An
+ *             edge between two fixed nodes adds its constant cost only.  A free node no edge touches keeps its bytes.
+ *   solver    Ceres' trust-region Levenberg-Marquardt over every node that has a pose and is not fixed, with the
+ *             settings of the context's velo_params and Jacobi scaling; the linear step is a block-Jacobi preconditioned conjugate
+ *             gradient on the damped normal equations, stopped when sqrt(r.M^-1 r) has fallen to cg_tolerance of its start or after
+ *             cg_max_iterations.  iSAM's own parametrisation (Euler angles), its Gauss-Newton / dog-leg and its incremental smoothing are
+ *             not reproduced.  Parameters move on accepted steps only; two identical calls on identical state give
+ *             identical bytes.
+ * velo_graph_reset creates or empties the store; edge_capacity: edges the device arrays hold before they are first reallocated (0: the
+ * default, 4096); they grow by doubling.  Frames < 2^22.  Refused before anything changes: VELO_ERR_INVALID for a NULL argument, a frame
+ * out of range, from == to, a non-finite pose or z, an info that is not positive and finite, fixed frames that are not ascending and
+ * distinct, n_fixed < 1; VELO_ERR_STATE without a store, for a fixed frame or an edge's end without a pose. */
+#define VELO_GRAPH_MAX_TRACE 50
+typedef struct velo_graph_params {     /* 32 bytes */
+    double cg_tolerance;       /* relative, on sqrt(r.M^-1 r); 1e-10: the inexact step then takes the LM decisions of a direct solve */
+    int32_t cg_max_iterations; /* per LM iteration; 2000 */
+    int32_t reserved[5];       /* 0 */
+} velo_graph_params;
+typedef struct velo_graph_iteration {  /* 64 bytes: velo_ba_iteration, then the linear solve */
+    int32_t status;            /* VELO_BA_* */
+    int32_t iteration;         /* from 1 */
+    double cost;               /* at the iteration's start */
+    double candidate_cost;     /* 0 for an invalid step */
+    double radius;             /* at the iteration's start */
+    double model_change;
+    double step_norm;
+    int32_t cg_iterations;
+    int32_t reserved;
+    double cg_residual;        /* sqrt(r.M^-1 r) over its start when CG stopped */
+} velo_graph_iteration;
+typedef struct velo_graph_summary {    /* 48 + 50 x 64 bytes */
+    int32_t termination;       /* VELO_CONVERGENCE / NO_CONVERGENCE / FAILURE */
+    int32_t iterations;
+    int32_t evaluations;
+    int32_t n_nodes;           /* that have a pose */
+    int32_t n_free;
+    int32_t n_edges;
+    int32_t n_trace;           /* records in trace: min(iterations, VELO_GRAPH_MAX_TRACE) */
+    int32_t reserved;
+    double initial_cost;
+    double final_cost;
+    velo_graph_iteration trace[VELO_GRAPH_MAX_TRACE];
+} velo_graph_summary;
+int velo_default_graph_params(velo_graph_params* params);
+int velo_graph_reset(velo_ctx* ctx, int32_t edge_capacity);
+/* one node, or the run first .. first + n - 1 (poses [n][6]); a node that has a pose is overwritten */
+int velo_graph_set_pose(velo_ctx* ctx, int32_t frame, const double pose6[6]);
+int velo_graph_set_poses(velo_ctx* ctx, int32_t first, int32_t n, const double* poses);
+/* appends n edges: from [n], to [n], z [n][6], info [n] */
+int velo_graph_add_edges(velo_ctx* ctx, int32_t n, const int32_t* from, const int32_t* to, const double* z, const double* info);
+/* fixed: n_fixed frames, ascending and distinct, each with a pose.  params may be NULL (the defaults), summary may be NULL. */
+int velo_graph_optimize(velo_ctx* ctx, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, velo_graph_summary* summary);
+/* poses of first .. first + n - 1 to out [n][6]; VELO_ERR_STATE when one of them has no pose */
+int velo_graph_get_poses(velo_ctx* ctx, int32_t first, int32_t n, double* out);
+/* info[8] = nodes with a pose, edges, edge capacity, edge reallocations, frames of the node table, optimisations run, 0, 0 */
+int velo_graph_info(velo_ctx* ctx, int32_t* info);
+/* Diagnostics: the problem velo_graph_optimize would solve, evaluated at the stored state; nothing changes.  The free nodes are the
+ * nodes with a pose that are not fixed, ascending: cost, J^T r (gradient [n_free][6]) and the diagonal blocks of J^T J (diag_blocks
+ * [n_free][36], row-major), unscaled.  Each output may be NULL. */
+int velo_graph_system(velo_ctx* ctx, const int32_t* fixed, int32_t n_fixed, double* cost, double* gradient, double* diag_blocks);
+
 /* --- resident keypoint frames and the visual matches assembled from them (velo.h:562-590, velo.h:627-654, main.cpp:366-405) ---
  * Every context can hold one frame store: for every (frame, camera) put so far keypoints[cam][frame], keypoint_ids[cam][frame],
  * has_depth[cam][frame] and keypoints_with_depth[cam][frame], in one device arena; the host keeps a directory (frame, cam) ->

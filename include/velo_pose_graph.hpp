@@ -1,0 +1,83 @@
+// velo_pose_graph.hpp -- header-only C++11 owner of a context's resident pose graph (velo_graph_*, include/velo_hip.h): one node per
+// frame, one edge per accepted registration, and the batch optimisation that turns a loop closure into corrected poses -- what the
+// reference's slam.add_node / add_factor / batch_optimization do (main.cpp:190-204, 516-536, 728-745).  Plain pointers and std::vector
+// only; every member returns the C-ABI's status (VELO_OK == 0) and velo_last_error() has the text.
+//
+//     velo_hip::PoseGraph graph(ctx);
+//     graph.setPose(frame, ceres_poses_vec[frame]);                 // a new node, or a node's new value
+//     graph.addEdge(frame - dframe, frame, dpose16, 1.0);            // what frameToFrame returned, row-major 4 x 4 (or its 6-vector)
+//     graph.optimize(fixed);                                         // fixed = {0}: the reference's prior on the first node
+//     graph.poses(0, n, &flat);                                      // n x 6, for velo_landmarks_set_pose / velo_map_set_pose
+#ifndef VELO_POSE_GRAPH_HPP_
+#define VELO_POSE_GRAPH_HPP_
+
+#include <cstddef>
+#include <vector>
+
+#include "velo_hip.h"
+
+namespace velo_hip {
+
+class PoseGraph {
+public:
+    struct Info { int nodes, edges, edge_capacity, edge_reallocations, frame_capacity, optimizations; };
+
+    explicit PoseGraph(velo_ctx* ctx, int edge_capacity = 0) : ctx_(ctx), status_(velo_graph_reset(ctx, edge_capacity)) {}
+
+    int status() const { return status_; }                 // of the constructor's velo_graph_reset
+
+    int setPose(int frame, const double pose6[6]) { return velo_graph_set_pose(ctx_, frame, pose6); }
+    int setPoses(int first, const std::vector<double>& flat) { return velo_graph_set_poses(ctx_, first, (int32_t)(flat.size() / 6), flat.empty() ? 0 : &flat[0]); }
+
+    // pose_to = pose_from . Z: Z as its 6-vector (angle-axis, translation) ...
+    int addEdge(int from, int to, const double z6[6], double info) {
+        const int32_t a = from, b = to;
+        return velo_graph_add_edges(ctx_, 1, &a, &b, z6, &info);
+    }
+    // ... or as a row-major 4 x 4 (Eigen::Matrix4d is column-major: pass its transpose's data, or fill the 16 doubles by (row, col))
+    int addEdgeMatrix(int from, int to, const double Z16[16], double info) {
+        double z6[6];
+        const int st = velo_pose_mat_to_vec(Z16, z6);
+        return st != VELO_OK ? st : addEdge(from, to, z6, info);
+    }
+    // many at once: z holds 6 doubles per edge
+    int addEdges(const std::vector<int>& from, const std::vector<int>& to, const std::vector<double>& z, const std::vector<double>& info) {
+        if (from.size() != to.size() || z.size() != 6 * from.size() || info.size() != from.size()) return VELO_ERR_INVALID;
+        if (from.empty()) return VELO_OK;
+        std::vector<int32_t> a(from.begin(), from.end()), b(to.begin(), to.end());
+        return velo_graph_add_edges(ctx_, (int32_t)a.size(), &a[0], &b[0], &z[0], &info[0]);
+    }
+
+    // refines every node that has a pose and is not in `fixed` (ascending frame numbers)
+    int optimize(const std::vector<int>& fixed, velo_graph_summary* summary = 0, const velo_graph_params* params = 0) {
+        std::vector<int32_t> f(fixed.begin(), fixed.end());
+        return velo_graph_optimize(ctx_, f.empty() ? 0 : &f[0], (int32_t)f.size(), params, summary);
+    }
+
+    // the nodes first .. first + n - 1, 6 doubles each
+    int poses(int first, int n, std::vector<double>* flat) const {
+        std::vector<double> out(6 * (size_t)(n > 0 ? n : 0) + 6);
+        const int st = velo_graph_get_poses(ctx_, first, n, &out[0]);
+        if (st != VELO_OK) return st;
+        out.resize(6 * (size_t)n);
+        flat->swap(out);
+        return VELO_OK;
+    }
+    int info(Info* out) const {
+        int32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        const int st = velo_graph_info(ctx_, v);
+        out->nodes = v[0]; out->edges = v[1]; out->edge_capacity = v[2]; out->edge_reallocations = v[3]; out->frame_capacity = v[4];
+        out->optimizations = v[5];
+        return st;
+    }
+
+private:
+    PoseGraph(const PoseGraph&);                           // one owner of the context's store
+    PoseGraph& operator=(const PoseGraph&);
+    velo_ctx* ctx_;
+    int status_;
+};
+
+}  // namespace velo_hip
+
+#endif  // VELO_POSE_GRAPH_HPP_

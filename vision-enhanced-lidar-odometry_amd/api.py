@@ -154,6 +154,25 @@ class VeloBaSummary(C.Structure):
                 ("initial_cost", C.c_double), ("final_cost", C.c_double), ("trace", VeloBaIteration * BA_MAX_TRACE)]
 
 
+class VeloGraphParams(C.Structure):
+    _fields_ = [("cg_tolerance", C.c_double), ("cg_max_iterations", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class VeloGraphIteration(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iteration", C.c_int32), ("cost", C.c_double), ("candidate_cost", C.c_double),
+                ("radius", C.c_double), ("model_change", C.c_double), ("step_norm", C.c_double), ("cg_iterations", C.c_int32),
+                ("reserved", C.c_int32), ("cg_residual", C.c_double)]
+
+
+GRAPH_MAX_TRACE = 50
+
+
+class VeloGraphSummary(C.Structure):
+    _fields_ = [("termination", C.c_int32), ("iterations", C.c_int32), ("evaluations", C.c_int32), ("n_nodes", C.c_int32),
+                ("n_free", C.c_int32), ("n_edges", C.c_int32), ("n_trace", C.c_int32), ("reserved", C.c_int32),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double), ("trace", VeloGraphIteration * GRAPH_MAX_TRACE)]
+
+
 class VeloResidualStat(C.Structure):
     _fields_ = [("median", C.c_double), ("mean", C.c_double), ("count", C.c_int64)]
 
@@ -352,6 +371,15 @@ SIGNATURES = {
     "velo_default_ba_params": (C.c_int, [_P(VeloBaParams)]),
     "velo_landmarks_adjust": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, _P(VeloBaParams), C.c_void_p, _P(VeloBaSummary)]),
     "velo_landmarks_adjust_system": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, _P(VeloBaParams), _dp, C.c_void_p, C.c_void_p]),
+    "velo_default_graph_params": (C.c_int, [_P(VeloGraphParams)]),
+    "velo_graph_reset": (C.c_int, [_ctx, C.c_int32]),
+    "velo_graph_set_pose": (C.c_int, [_ctx, C.c_int32, _dp]),
+    "velo_graph_set_poses": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p]),
+    "velo_graph_add_edges": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "velo_graph_optimize": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(VeloGraphParams), _P(VeloGraphSummary)]),
+    "velo_graph_get_poses": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p]),
+    "velo_graph_info": (C.c_int, [_ctx, C.c_void_p]),
+    "velo_graph_system": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _dp, C.c_void_p, C.c_void_p]),
     "velo_frames_reset": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_int32]),
     "velo_frames_put": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "velo_frames_drop": (C.c_int, [_ctx, C.c_int32]),
@@ -833,6 +861,75 @@ class Context:
         H = np.zeros((n_free, 6, 6), dtype=np.float64)
         self._check(self._lib.velo_landmarks_adjust_system(self._h, C.c_void_p(fr.ctypes.data) if len(fr) else None, len(fr), int(n_fixed), C.byref(p),
                                                            C.byref(cost), C.c_void_p(g.ctypes.data), C.c_void_p(H.ctypes.data)))
+        return cost.value, g, H
+
+    # -- the pose graph of a drive and its batch optimisation (main.cpp:190-204, 516-536, 728-745) ------------------------------
+    def graph_reset(self, edge_capacity: int = 0):
+        """Creates or empties the context's pose graph.  edge_capacity: edges before the device arrays first reallocate (0: the
+        library's default)."""
+        self._check(self._lib.velo_graph_reset(self._h, int(edge_capacity)))
+
+    def graph_set_pose(self, frame: int, pose6):
+        x = _dvec(pose6, 6)
+        self._check(self._lib.velo_graph_set_pose(self._h, int(frame), _ptr(x)))
+
+    def graph_set_poses(self, first: int, poses):
+        """the nodes first .. first + n - 1 from poses [n, 6]"""
+        x = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 6))
+        self._check(self._lib.velo_graph_set_poses(self._h, int(first), len(x), C.c_void_p(x.ctypes.data) if len(x) else None))
+
+    def graph_add_edges(self, frm, to, z, info):
+        """appends the edges (frm[k], to[k], z[k] (6 doubles: angle-axis, translation of Z with pose_to = pose_from . Z), info[k])"""
+        a = np.ascontiguousarray(np.asarray(frm, dtype=np.int32).reshape(-1))
+        b = np.ascontiguousarray(np.asarray(to, dtype=np.int32).reshape(-1))
+        zz = np.ascontiguousarray(np.asarray(z, dtype=np.float64).reshape(-1, 6))
+        w = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(-1))
+        if not len(a) == len(b) == len(zz) == len(w):
+            raise ValueError("graph_add_edges: one from, to, z and info per edge")
+        vp = lambda v: C.c_void_p(v.ctypes.data) if v.size else None   # noqa: E731
+        self._check(self._lib.velo_graph_add_edges(self._h, len(a), vp(a), vp(b), vp(zz), vp(w)))
+
+    @staticmethod
+    def _graph_params(cg_tolerance, cg_max_iterations):
+        if cg_tolerance is None and cg_max_iterations is None:
+            return None
+        p = VeloGraphParams()
+        p.cg_tolerance = 1e-10 if cg_tolerance is None else float(cg_tolerance)
+        p.cg_max_iterations = 2000 if cg_max_iterations is None else int(cg_max_iterations)
+        return C.byref(p)
+
+    def graph_optimize(self, fixed=(0,), cg_tolerance=None, cg_max_iterations=None) -> "VeloGraphSummary":
+        """Refines every node that has a pose and is not in `fixed` (ascending frame numbers) over all edges; the poses are read
+        with graph_get_poses.  summary.trace[:summary.n_trace] holds one record per LM iteration."""
+        fx = np.ascontiguousarray(np.asarray(fixed, dtype=np.int32).reshape(-1))
+        s = VeloGraphSummary()
+        self._check(self._lib.velo_graph_optimize(self._h, C.c_void_p(fx.ctypes.data) if len(fx) else None, len(fx),
+                                                  self._graph_params(cg_tolerance, cg_max_iterations), C.byref(s)))
+        return s
+
+    def graph_get_poses(self, first: int, n: int) -> np.ndarray:
+        out = np.zeros((max(int(n), 1), 6), dtype=np.float64)
+        self._check(self._lib.velo_graph_get_poses(self._h, int(first), int(n), C.c_void_p(out.ctypes.data)))
+        return out[:int(n)]
+
+    def graph_info(self) -> dict:
+        a = np.zeros(8, dtype=np.int32)
+        self._check(self._lib.velo_graph_info(self._h, C.c_void_p(a.ctypes.data)))
+        return dict(n_nodes=int(a[0]), n_edges=int(a[1]), edge_capacity=int(a[2]), edge_reallocations=int(a[3]), frame_capacity=int(a[4]),
+                    optimizations=int(a[5]))
+
+    def graph_system(self, fixed=(0,), n_free: Optional[int] = None):
+        """The problem graph_optimize would solve, evaluated at the stored state (nothing changes): (cost, J^T r [n_free, 6], the
+        diagonal blocks of J^T J [n_free, 6, 6]); the free nodes are the nodes with a pose that are not fixed, ascending."""
+        fx = np.ascontiguousarray(np.asarray(fixed, dtype=np.int32).reshape(-1))
+        if n_free is None:
+            n_free = self.graph_info()["n_nodes"] - len(fx)
+        n_free = max(int(n_free), 1)
+        cost = C.c_double(0.0)
+        g = np.zeros((n_free, 6), dtype=np.float64)
+        H = np.zeros((n_free, 6, 6), dtype=np.float64)
+        self._check(self._lib.velo_graph_system(self._h, C.c_void_p(fx.ctypes.data) if len(fx) else None, len(fx), C.byref(cost),
+                                                C.c_void_p(g.ctypes.data), C.c_void_p(H.ctypes.data)))
         return cost.value, g, H
 
     # -- resident keypoint frames and the visual matches assembled from them (velo.h:562-590, velo.h:627-654) ---------------

@@ -1,0 +1,424 @@
+// velo_api_graph.inl -- part of the host side of the C-ABI, included by velo_hip.hip (ONE translation unit; the order of the parts is the order of
+// definition).  C-ABI: the resident pose graph of a drive and its batch optimisation (velo_graph_*); the kernels and the scheme of one
+// LM iteration are in velo_graph_kernels.h.
+//
+// Who knows what: the DEVICE holds the edges (from, to, z, info; appended, never sent again) and every block the solver forms from them.
+// The HOST keeps the ints of the edges -- enough to refuse a call and to build the incidence lists -- and a pinned mirror of the poses:
+// a pose arrives from the host (velo_graph_set_pose) and leaves to it (velo_graph_get_poses), so the mirror is the one copy both
+// directions share, and a solve starts by sending it.  The LM decision is taken here, from one GraphRecord per iteration.
+struct GraphStore {
+    // device: the edges
+    DevBuf<int> from, to;
+    DevBuf<double> z, info;
+    size_t n_edges = 0, edge_cap = 0;
+    int edge_reallocs = 0, n_optimized = 0;
+    // the nodes: [2][frame_cap][6] on the device (current / candidate), [frame_cap][6] pinned
+    DevBuf<double> x;
+    PinBuf<double> h_x;
+    size_t frame_cap = 0;
+    std::vector<unsigned char> pose_set;
+    int n_nodes = 0;
+    // host: ints only
+    std::vector<int32_t> h_from, h_to;
+    // staging (an upload is followed by an event; a solve ends with a synchronisation) and the work buffers of a solve
+    PinBuf<> h_in, h_st, h_out;
+    Event in_ev;
+    DevBuf<int> node, inc_start, inc;
+    DevBuf<double> blk, nd, vec, part, nterm;
+    DevBuf<GraphRecord> rec;
+};
+
+namespace {
+
+constexpr size_t kGraphDefaultEdges = 4096;
+constexpr int kGraphVec = 6 + 6 + 21 + 4 * 6 + 2 * 6;      // per free node: scale, diag, chol, y, r, z, q, p[2]
+
+int graph_need_store(velo_ctx* c, const char* who) {
+    if (!c->graph) return fail(VELO_ERR_STATE, "%s: velo_graph_reset has not run on this context", who);
+    return VELO_OK;
+}
+
+struct GraphCall {
+    GraphArgs A;
+    std::vector<int32_t> free_nodes;
+    int n_free = 0, E = 0;
+};
+
+int graph_check(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, const char* who) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (n_fixed < 1) return fail(VELO_ERR_INVALID, "%s: %d fixed nodes; at least 1 fixes the gauge", who, n_fixed);
+    if (!fixed) return fail(VELO_ERR_INVALID, "%s: null fixed", who);
+    for (int i = 0; i < n_fixed; i++) {
+        if (fixed[i] < 0 || fixed[i] >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "%s: frame %d; 0..%d", who, fixed[i], kLmMaxFrame - 1);
+        if (i > 0 && fixed[i] <= fixed[i - 1]) return fail(VELO_ERR_INVALID, "%s: fixed frames must be ascending and distinct (%d after %d)", who, fixed[i], fixed[i - 1]);
+    }
+    if (params) {
+        if (!(params->cg_tolerance > 0.0 && params->cg_tolerance < 1.0)) return fail(VELO_ERR_INVALID, "%s: cg_tolerance must lie in (0, 1)", who);
+        if (params->cg_max_iterations < 1) return fail(VELO_ERR_INVALID, "%s: cg_max_iterations %d; at least 1", who, params->cg_max_iterations);
+    }
+    VELO_TRY(graph_need_store(c, who));
+    const GraphStore& S = *c->graph;
+    for (int i = 0; i < n_fixed; i++)
+        if ((size_t)fixed[i] >= S.pose_set.size() || !S.pose_set[(size_t)fixed[i]]) return fail(VELO_ERR_STATE, "%s: fixed frame %d has no pose: velo_graph_set_pose", who, fixed[i]);
+    for (size_t e = 0; e < S.n_edges; e++) {
+        const int32_t ends[2] = {S.h_from[e], S.h_to[e]};
+        for (int k = 0; k < 2; k++)
+            if ((size_t)ends[k] >= S.pose_set.size() || !S.pose_set[(size_t)ends[k]]) return fail(VELO_ERR_STATE, "%s: edge %zu ends at frame %d, which has no pose", who, e, ends[k]);
+    }
+    return VELO_OK;
+}
+
+// the free nodes, their incidence lists (ints only), the poses to both buffers; then the system at the stored state: linearise,
+// assemble, reduce
+int graph_begin(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, GraphCall* call) {
+    GraphStore& S = *c->graph;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t F = S.frame_cap, E = S.n_edges;
+    std::vector<int32_t> slot(F, -1);
+    std::vector<int32_t>& nodes = call->free_nodes;
+    nodes.clear();
+    for (size_t f = 0, k = 0; f < F; f++) {
+        while (k < (size_t)n_fixed && (size_t)fixed[k] < f) k++;
+        if (S.pose_set[f] && !(k < (size_t)n_fixed && (size_t)fixed[k] == f)) { slot[f] = (int32_t)nodes.size(); nodes.push_back((int32_t)f); }
+    }
+    const size_t n = nodes.size();
+    std::vector<int32_t> start(n + 1, 0), inc, other;
+    for (size_t e = 0; e < E; e++) {
+        if (slot[(size_t)S.h_from[e]] >= 0) start[(size_t)slot[(size_t)S.h_from[e]] + 1]++;
+        if (slot[(size_t)S.h_to[e]] >= 0) start[(size_t)slot[(size_t)S.h_to[e]] + 1]++;
+    }
+    for (size_t i = 0; i < n; i++) start[i + 1] += start[i];
+    inc.resize((size_t)start[n]);
+    other.resize(inc.size());
+    {
+        std::vector<int32_t> fill(start.begin(), start.end() - 1);
+        for (size_t e = 0; e < E; e++) {                               // ascending edge number within every node: the fixed order
+            const int32_t sf = slot[(size_t)S.h_from[e]], st = slot[(size_t)S.h_to[e]];
+            if (sf >= 0) { const size_t k = (size_t)fill[(size_t)sf]++; inc[k] = (int32_t)(2 * e); other[k] = st; }
+            if (st >= 0) { const size_t k = (size_t)fill[(size_t)st]++; inc[k] = (int32_t)(2 * e + 1); other[k] = sf; }
+        }
+    }
+    const int nb = std::max(1, cdiv((int)n, kGrThreads));
+    call->n_free = (int)n; call->E = (int)E;
+    VELO_TRY(S.node.reserve(n + 1));
+    VELO_TRY(S.inc_start.reserve(n + 1));
+    VELO_TRY(S.inc.reserve(2 * inc.size() + 1));
+    VELO_TRY(S.x.reserve(2 * F * 6 + 1));
+    VELO_TRY(S.blk.reserve(2 * E * kGrBlk + 1));
+    VELO_TRY(S.nd.reserve(2 * n * kGrNode + 1));
+    VELO_TRY(S.vec.reserve(n * kGraphVec + 1));
+    VELO_TRY(S.part.reserve(4 * (size_t)nb));
+    VELO_TRY(S.nterm.reserve(2 * n + 1));
+    VELO_TRY(S.rec.reserve(1));
+    VELO_TRY(S.h_out.reserve(sizeof(GraphRecord) + sizeof(double) * std::max(F * 6, n * kGrNode) + 64));
+    const size_t n_ints = n + (n + 1) + 2 * inc.size();
+    VELO_TRY(S.h_st.reserve(sizeof(int32_t) * (n_ints + 1)));
+    int32_t* st = (int32_t*)S.h_st.p;
+    if (n) std::memcpy(st, nodes.data(), sizeof(int32_t) * n);
+    std::memcpy(st + n, start.data(), sizeof(int32_t) * (n + 1));
+    if (!inc.empty()) {                                                // inc, then inc_other behind it, in one copy
+        std::memcpy(st + n + n + 1, inc.data(), sizeof(int32_t) * inc.size());
+        std::memcpy(st + n + n + 1 + inc.size(), other.data(), sizeof(int32_t) * inc.size());
+    }
+    if (n) HIP_TRY(hipMemcpyAsync(S.node.p, st, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(S.inc_start.p, st + n, sizeof(int32_t) * (n + 1), hipMemcpyHostToDevice, c->stream));
+    if (!inc.empty()) HIP_TRY(hipMemcpyAsync(S.inc.p, st + n + n + 1, sizeof(int32_t) * 2 * inc.size(), hipMemcpyHostToDevice, c->stream));
+    if (F) {
+        HIP_TRY(hipMemcpyAsync(S.x.p, S.h_x.p, sizeof(double) * F * 6, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(S.x.p + F * 6, S.h_x.p, sizeof(double) * F * 6, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(hipMemsetAsync(S.rec.p, 0, sizeof(GraphRecord), c->stream));
+    if (n) HIP_TRY(hipMemsetAsync(S.nterm.p, 0, sizeof(double) * 2 * n, c->stream));
+    GraphArgs& A = call->A;
+    std::memset(&A, 0, sizeof(A));
+    A.from = S.from.p; A.to = S.to.p; A.z = S.z.p; A.info = S.info.p;
+    A.x = S.x.p; A.x_stride = F * 6;
+    A.node = S.node.p; A.inc_start = S.inc_start.p; A.inc = S.inc.p; A.inc_other = S.inc.p + inc.size();
+    A.blk = S.blk.p; A.nd = S.nd.p;
+    double* v = S.vec.p;
+    A.scale = v; v += n * 6;
+    A.diag = v; v += n * 6;
+    A.chol = v; v += n * 21;
+    A.y = v; v += n * 6;
+    A.r = v; v += n * 6;
+    A.zv = v; v += n * 6;
+    A.q = v; v += n * 6;
+    A.p = v;
+    A.part_rho0 = S.part.p; A.part_rho = S.part.p + nb; A.part_sigma = S.part.p + 3 * (size_t)nb;
+    A.nterm = S.nterm.p; A.rec = S.rec.p;
+    A.E = (int)E; A.n_free = (int)n; A.nb = nb;
+    const double tol = params ? params->cg_tolerance : 1e-10;
+    A.cg_tol2 = tol * tol;
+    A.lm = lm_params(c->P);
+    if (E) hipLaunchKernelGGL(graph_linearize_kernel, dim3((unsigned)cdiv((int)E, kGrThreads)), dim3(kGrThreads), 0, c->stream, A, 0);
+    if (n) hipLaunchKernelGGL(graph_assemble_kernel, dim3((unsigned)nb), dim3(kGrThreads), 0, c->stream, A, 0, 0);
+    hipLaunchKernelGGL(graph_reduce_kernel, dim3(kGrRed), dim3(256), 0, c->stream, A, 0);
+    HIP_TRY(hipGetLastError());
+    return VELO_OK;
+}
+
+int graph_read_record(velo_ctx* c, GraphStore& S, GraphRecord** rec) {
+    HIP_TRY(hipMemcpyAsync(S.h_out.p, S.rec.p, sizeof(GraphRecord), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *rec = (GraphRecord*)S.h_out.p;
+    return VELO_OK;
+}
+
+int graph_put_poses(velo_ctx* c, int32_t first, int32_t n, const double* poses, const char* who) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (n < 0) return fail(VELO_ERR_INVALID, "%s: negative count", who);
+    if (first < 0 || (int64_t)first + n > kLmMaxFrame) return fail(VELO_ERR_INVALID, "%s: frames %d .. %lld; 0..%d", who, first, (long long)first + n - 1, kLmMaxFrame - 1);
+    if (n > 0 && !poses) return fail(VELO_ERR_INVALID, "%s: null poses", who);
+    for (size_t k = 0; k < 6 * (size_t)n; k++) if (!std::isfinite(poses[k])) return fail(VELO_ERR_INVALID, "%s: pose %zu, entry %zu is not finite", who, k / 6, k % 6);
+    VELO_TRY(graph_need_store(c, who));
+    if (n == 0) return VELO_OK;
+    GraphStore& S = *c->graph;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t last = (size_t)first + (size_t)n;
+    if (last > S.frame_cap) {                                          // the table grows geometrically: a new pinned mirror, filled from the old one
+        const size_t cap = std::max<size_t>({last, 2 * S.frame_cap, 256});
+        PinBuf<double> nh;
+        VELO_TRY(nh.reserve(sizeof(double) * cap * 6));
+        std::memset(nh.p, 0, sizeof(double) * cap * 6);
+        if (S.h_x.p) std::memcpy(nh.p, S.h_x.p, sizeof(double) * S.frame_cap * 6);      // (no copy out of it is in flight: every call that sends it synchronises)
+        S.h_x = std::move(nh);
+        S.frame_cap = cap;
+        S.pose_set.resize(cap, 0);
+    }
+    std::memcpy(S.h_x.p + (size_t)first * 6, poses, sizeof(double) * 6 * (size_t)n);
+    for (size_t f = (size_t)first; f < last; f++) if (!S.pose_set[f]) { S.pose_set[f] = 1; S.n_nodes++; }
+    return VELO_OK;
+}
+
+}  // namespace
+
+extern "C" {   // (continued from the previous part)
+int velo_default_graph_params(velo_graph_params* p) {
+    if (!p) return fail(VELO_ERR_INVALID, "null params");
+    std::memset(p, 0, sizeof(*p));
+    // 1e-10: with it the inexact step takes the LM decisions of a direct solve on every graph tried, and its cost differs from the direct
+    // solve's in the 11th digit; 2,000: four times what the longest solve of those graphs needed, a bound on the work of one LM iteration
+    p->cg_tolerance = 1e-10;
+    p->cg_max_iterations = 2000;
+    return VELO_OK;
+}
+
+int velo_graph_reset(velo_ctx* c, int32_t edge_capacity) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (edge_capacity < 0) return fail(VELO_ERR_INVALID, "negative edge capacity");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));           // nothing of the old store is in flight when it goes
+    c->graph.reset();
+    std::shared_ptr<GraphStore> S = std::make_shared<GraphStore>();
+    const size_t want = edge_capacity > 0 ? (size_t)edge_capacity : kGraphDefaultEdges;
+    VELO_TRY(S->from.reserve(want));
+    VELO_TRY(S->to.reserve(want));
+    VELO_TRY(S->z.reserve(want * 6));
+    VELO_TRY(S->info.reserve(want));
+    S->edge_cap = want;                                 // the buffers hold a little more; the arrays reallocate at what was asked for
+    c->graph = S;
+    return VELO_OK;
+}
+
+int velo_graph_set_pose(velo_ctx* c, int32_t frame, const double* pose6) { return graph_put_poses(c, frame, 1, pose6, "velo_graph_set_pose"); }
+
+int velo_graph_set_poses(velo_ctx* c, int32_t first, int32_t n, const double* poses) { return graph_put_poses(c, first, n, poses, "velo_graph_set_poses"); }
+
+int velo_graph_add_edges(velo_ctx* c, int32_t n, const int32_t* from, const int32_t* to, const double* z, const double* info) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (n < 0) return fail(VELO_ERR_INVALID, "negative edge count");
+    if (n > 0 && (!from || !to || !z || !info)) return fail(VELO_ERR_INVALID, "null edge array");
+    for (int e = 0; e < n; e++) {
+        if (from[e] < 0 || from[e] >= kLmMaxFrame || to[e] < 0 || to[e] >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "edge %d: frames %d -> %d; 0..%d", e, from[e], to[e], kLmMaxFrame - 1);
+        if (from[e] == to[e]) return fail(VELO_ERR_INVALID, "edge %d: from == to (%d)", e, from[e]);
+        for (int k = 0; k < 6; k++) if (!std::isfinite(z[6 * (size_t)e + k])) return fail(VELO_ERR_INVALID, "edge %d: z[%d] is not finite", e, k);
+        if (!(info[e] > 0.0 && std::isfinite(info[e]))) return fail(VELO_ERR_INVALID, "edge %d: info must be positive and finite", e);
+    }
+    VELO_TRY(graph_need_store(c, "velo_graph_add_edges"));
+    if (n == 0) return VELO_OK;
+    GraphStore& S = *c->graph;
+    if (S.n_edges + (size_t)n > (size_t)(1 << 30)) return fail(VELO_ERR_INVALID, "more than 2^30 edges");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t need = S.n_edges + (size_t)n;
+    if (need > S.edge_cap) {                                           // grow by doubling; what is there is kept
+        size_t cap = S.edge_cap;
+        while (cap < need) cap *= 2;
+        VELO_TRY(lm_regrow(c, &S.from, S.n_edges, cap, 0));
+        VELO_TRY(lm_regrow(c, &S.to, S.n_edges, cap, 0));
+        VELO_TRY(lm_regrow(c, &S.z, S.n_edges * 6, cap * 6, 0));
+        VELO_TRY(lm_regrow(c, &S.info, S.n_edges, cap, 0));
+        S.edge_cap = cap;
+        S.edge_reallocs++;
+    }
+    const size_t nz = (size_t)n, bytes = nz * (2 * sizeof(int32_t) + 7 * sizeof(double));
+    VELO_TRY(S.in_ev.wait_or_create());
+    VELO_TRY(S.h_in.reserve(bytes));
+    double* hz = (double*)S.h_in.p;
+    double* hi = hz + 6 * nz;
+    int32_t* hf = (int32_t*)(hi + nz);
+    int32_t* ht = hf + nz;
+    std::memcpy(hz, z, sizeof(double) * 6 * nz);
+    std::memcpy(hi, info, sizeof(double) * nz);
+    std::memcpy(hf, from, sizeof(int32_t) * nz);
+    std::memcpy(ht, to, sizeof(int32_t) * nz);
+    HIP_TRY(hipMemcpyAsync(S.z.p + 6 * S.n_edges, hz, sizeof(double) * 6 * nz, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(S.info.p + S.n_edges, hi, sizeof(double) * nz, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(S.from.p + S.n_edges, hf, sizeof(int32_t) * nz, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(S.to.p + S.n_edges, ht, sizeof(int32_t) * nz, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(S.in_ev, c->stream));
+    S.h_from.insert(S.h_from.end(), from, from + n);
+    S.h_to.insert(S.h_to.end(), to, to + n);
+    S.n_edges = need;
+    return VELO_OK;
+}
+
+int velo_graph_get_poses(velo_ctx* c, int32_t first, int32_t n, double* out) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (n < 0 || first < 0) return fail(VELO_ERR_INVALID, "velo_graph_get_poses: negative frame or count");
+    if (n > 0 && !out) return fail(VELO_ERR_INVALID, "velo_graph_get_poses: null output");
+    VELO_TRY(graph_need_store(c, "velo_graph_get_poses"));
+    const GraphStore& S = *c->graph;
+    for (int64_t f = first; f < (int64_t)first + n; f++)
+        if ((size_t)f >= S.pose_set.size() || !S.pose_set[(size_t)f]) return fail(VELO_ERR_STATE, "velo_graph_get_poses: frame %lld has no pose", (long long)f);
+    if (n > 0) std::memcpy(out, S.h_x.p + (size_t)first * 6, sizeof(double) * 6 * (size_t)n);
+    return VELO_OK;
+}
+
+int velo_graph_info(velo_ctx* c, int32_t* info) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (!info) return fail(VELO_ERR_INVALID, "null info");
+    VELO_TRY(graph_need_store(c, "velo_graph_info"));
+    const GraphStore& S = *c->graph;
+    info[0] = S.n_nodes; info[1] = (int32_t)S.n_edges; info[2] = (int32_t)S.edge_cap; info[3] = S.edge_reallocs;
+    info[4] = (int32_t)S.frame_cap; info[5] = S.n_optimized; info[6] = 0; info[7] = 0;
+    return VELO_OK;
+}
+
+int velo_graph_system(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, double* cost, double* gradient, double* diag_blocks) {
+    VELO_TRY(graph_check(c, fixed, n_fixed, nullptr, "velo_graph_system"));
+    GraphStore& S = *c->graph;
+    GraphCall call;
+    VELO_TRY(graph_begin(c, fixed, n_fixed, nullptr, &call));
+    const size_t n = (size_t)call.n_free;
+    unsigned char* tail = S.h_out.p + sizeof(GraphRecord);
+    if (n) HIP_TRY(hipMemcpyAsync(tail, S.nd.p, sizeof(double) * n * kGrNode, hipMemcpyDeviceToHost, c->stream));   // the state starts in buffer 0
+    GraphRecord* rec = nullptr;
+    VELO_TRY(graph_read_record(c, S, &rec));
+    if (cost) *cost = rec->red[0];
+    const double* nd = (const double*)tail;
+    for (size_t i = 0; i < n; i++) {
+        const double* U = nd + i * kGrNode;
+        for (int a = 0; a < 6; a++) {
+            if (gradient) gradient[6 * i + a] = U[21 + a];
+            for (int b = 0; b < 6 && diag_blocks; b++) {
+                const int lo = std::min(a, b), hi = std::max(a, b);
+                diag_blocks[36 * i + 6 * a + b] = U[lo * 6 - (lo * (lo - 1)) / 2 + (hi - lo)];
+            }
+        }
+    }
+    return VELO_OK;
+}
+
+int velo_graph_optimize(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, velo_graph_summary* summary) {
+    VELO_TRY(graph_check(c, fixed, n_fixed, params, "velo_graph_optimize"));
+    GraphStore& S = *c->graph;
+    GraphCall call;
+    VELO_TRY(graph_begin(c, fixed, n_fixed, params, &call));
+    const GraphArgs& A = call.A;
+    const LMParams Q = A.lm;
+    const int n = call.n_free, E = call.E, nb = A.nb;
+    const int cg_cap = params ? params->cg_max_iterations : 2000;
+    velo_graph_summary sum;
+    std::memset(&sum, 0, sizeof(sum));
+    sum.n_nodes = S.n_nodes; sum.n_free = n; sum.n_edges = E;
+    sum.evaluations = 1;
+    GraphRecord* rec = nullptr;
+    VELO_TRY(graph_read_record(c, S, &rec));
+    double cost = rec->red[0], x_norm = std::sqrt(rec->red[3]);
+    sum.initial_cost = cost;
+    int termination = VELO_NO_CONVERGENCE, cur = 0, it = 0, invalid = 0, refresh = 1, n_accepted = 0;
+    double radius = Q.initial_radius, decrease = 2.0;
+    const unsigned g_nodes = (unsigned)nb, g_edges = (unsigned)std::max(1, cdiv(E, kGrThreads));
+    if (n == 0 || E == 0 || rec->red[4] <= Q.gradient_tolerance) termination = VELO_CONVERGENCE;
+    else for (;;) {
+        // the head of an iteration (B1)
+        if (it + 1 > Q.max_num_iterations) { termination = VELO_NO_CONVERGENCE; break; }
+        if (radius < Q.min_radius) { termination = VELO_CONVERGENCE; break; }
+        it++;
+        // the linear step: CG in batches, one record per batch
+        HIP_TRY(hipMemsetAsync(S.rec.p, 0, sizeof(GraphRecord), c->stream));
+        hipLaunchKernelGGL(graph_cg_begin_kernel, dim3(g_nodes), dim3(kGrThreads), 0, c->stream, A, cur, radius, refresh);
+        int k = 0, batch = 32;
+        while (k < cg_cap) {
+            const int m = std::min(batch, cg_cap - k);
+            for (int j = 0; j < m; j++) {
+                hipLaunchKernelGGL(graph_cg_ap_kernel, dim3(g_nodes), dim3(kGrThreads), 0, c->stream, A, k + j, cur, radius);
+                hipLaunchKernelGGL(graph_cg_update_kernel, dim3(g_nodes), dim3(kGrThreads), 0, c->stream, A, k + j);
+            }
+            k += m;
+            HIP_TRY(hipGetLastError());
+            VELO_TRY(graph_read_record(c, S, &rec));
+            if (rec->cg_done) break;
+            batch = std::min(2 * batch, 256);
+        }
+        bool ok = rec->bad == 0;
+        if (ok) {                                                      // the candidate, linearised and reduced
+            hipLaunchKernelGGL(graph_step_kernel, dim3(g_nodes), dim3(kGrThreads), 0, c->stream, A, k, cur);
+            hipLaunchKernelGGL(graph_linearize_kernel, dim3(g_edges), dim3(kGrThreads), 0, c->stream, A, cur ^ 1);
+            hipLaunchKernelGGL(graph_assemble_kernel, dim3(g_nodes), dim3(kGrThreads), 0, c->stream, A, cur ^ 1, 1);
+            hipLaunchKernelGGL(graph_reduce_kernel, dim3(kGrRed), dim3(256), 0, c->stream, A, cur ^ 1);
+            HIP_TRY(hipGetLastError());
+            VELO_TRY(graph_read_record(c, S, &rec));
+            ok = rec->red[1] > 0.0 && std::isfinite(rec->red[1]);
+        }
+        velo_graph_iteration t;
+        std::memset(&t, 0, sizeof(t));
+        t.iteration = it; t.cost = cost; t.radius = radius; t.cg_iterations = rec->cg_iters; t.cg_residual = rec->cg_rel;
+        bool stop = false;
+        if (!ok) {
+            t.status = VELO_BA_INVALID;
+            if (++invalid >= Q.max_invalid) { termination = VELO_FAILURE; stop = true; }
+            else { radius = radius / decrease; decrease *= 2.0; refresh = 0; }
+        } else {
+            invalid = 0;
+            const double model_change = rec->red[1], dn = std::sqrt(rec->red[2]), cand_cost = rec->red[0];
+            sum.evaluations++;
+            t.candidate_cost = cand_cost; t.model_change = model_change; t.step_norm = dn;
+            const double cost_change = cost - cand_cost;
+            if (dn <= Q.parameter_tolerance * (x_norm + Q.parameter_tolerance)) { t.status = VELO_BA_PARAMETER; termination = VELO_CONVERGENCE; stop = true; }
+            else if (std::fabs(cost_change) <= Q.function_tolerance * cost) { t.status = VELO_BA_FUNCTION; termination = VELO_CONVERGENCE; stop = true; }
+            else {
+                const double q = cost_change / model_change;
+                if (q > Q.min_relative_decrease) {
+                    cur ^= 1; n_accepted++;
+                    cost = cand_cost;
+                    x_norm = std::sqrt(rec->red[3]);
+                    t.status = VELO_BA_ACCEPTED;
+                    if (rec->red[4] <= Q.gradient_tolerance) { t.status = VELO_BA_GRADIENT; termination = VELO_CONVERGENCE; stop = true; }
+                    else {
+                        const double u = 2.0 * q - 1.0;
+                        radius = std::min(Q.max_radius, radius / std::max(1.0 / 3.0, 1.0 - u * u * u));
+                        decrease = 2.0; refresh = 1;
+                    }
+                } else {
+                    t.status = VELO_BA_REJECTED;
+                    radius = radius / decrease; decrease *= 2.0; refresh = 0;
+                }
+            }
+        }
+        if (sum.n_trace < VELO_GRAPH_MAX_TRACE) sum.trace[sum.n_trace++] = t;
+        if (stop) break;
+    }
+    sum.termination = termination; sum.iterations = it; sum.final_cost = cost;
+    if (n_accepted > 0) {                                              // parameters move on accepted steps only
+        double* back = (double*)(S.h_out.p + sizeof(GraphRecord));
+        HIP_TRY(hipMemcpyAsync(back, S.x.p + (size_t)cur * A.x_stride, sizeof(double) * A.x_stride, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (int i = 0; i < n; i++) std::memcpy(S.h_x.p + (size_t)call.free_nodes[(size_t)i] * 6, back + (size_t)call.free_nodes[(size_t)i] * 6, sizeof(double) * 6);
+    }
+    S.n_optimized++;
+    if (summary) *summary = sum;
+    return VELO_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,638 @@
+// velo_graph_kernels.h -- the batch optimisation of a drive's pose graph (reference main.cpp:190-204 the prior, main.cpp:516-536 the
+// Pose3d_Pose3d factors, main.cpp:728-745 the solve).  Included by velo_hip.hip (declarations) and by velo_unit_graph.hip
+// (VELO_DEF_GRAPH: the definitions); gfx950 only.
+//
+// A node is the 6 doubles (angle-axis, translation) of a frame's world pose T; an edge (from, to, z, info) states T_to = T_from Z and
+// its residual is sqrt(info) * pose_vec(Z^-1 T_from^-1 T_to), the angle-axis of the rotation and then the translation (the form of
+// main.cpp:416-424).  Fixed nodes are constants.  The solver is the trust-region Levenberg-Marquardt of SURVEY.md B1 over the free
+// nodes; its linear step is a block-Jacobi preconditioned conjugate gradient on the damped, Jacobi-scaled normal equations
+//     (c H c + D / mu) y = -c g,      H = J^T J block-sparse: a 6 x 6 diagonal block per free node, one off-diagonal block per edge,
+// whose matrix is never assembled: a product gathers, per node, the node's diagonal block and the A^T B block of every incident edge.
+//     graph_linearize_kernel  one thread per edge: residual, the two 6 x 6 Jacobians, A^T A, B^T B, A^T B, A^T r, B^T r, the cost term
+//     graph_assemble_kernel   one thread per free node, over its incident edges in the host's fixed order: diagonal block, gradient,
+//                             at the start the Jacobi scale
+//     graph_cg_begin_kernel   one thread per free node: D, the Cholesky of the damped preconditioner block, y = 0, r = b, z = M^-1 r
+//     graph_cg_ap_kernel      CG, first half of iteration k:  beta, p = z + beta p, q = A p (the gather), partial sums of p.q
+//     graph_cg_update_kernel  CG, second half:  alpha, y += alpha p, r -= alpha q, z = M^-1 r, partial sums of r.z
+//     graph_step_kernel       one thread per free node: candidate pose, the node's share of the model change and of |step|^2
+//     graph_reduce_kernel     one workgroup per scalar: cost over edges; model change, |step|^2, |x|^2, gradient maximum over nodes
+// A dot product is one partial sum per workgroup (a fixed tree), and the NEXT launch adds the partial sums in a fixed order in every
+// workgroup: no atomics on sums, no grid-wide barrier, no workgroup waits for another.  The stopping test of CG is evaluated by
+// every workgroup on the same numbers; once it holds, the launches that were enqueued behind it return at once.  The host enqueues
+// iterations in batches and reads one GraphRecord per batch, and one per LM iteration, from which it takes the LM decision.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/velo_hip.h"
+#include "velo_kernels.h"
+#include "velo_device_math.h"
+
+#ifndef VELO_DEF_GRAPH
+#define VELO_DEF_GRAPH 0
+#endif
+
+namespace velo {
+
+constexpr int kGrBlk = 91;                       // per edge: upper A^T A (21), upper B^T B (21), A^T B (36), A^T r (6), B^T r (6), cost
+constexpr int kGrAtA = 0, kGrBtB = 21, kGrAtB = 42, kGrAtr = 78, kGrBtr = 84, kGrCost = 90;
+constexpr int kGrNode = 27;                      // per free node: upper diagonal block (21), gradient (6)
+constexpr int kGrThreads = 64;                   // threads of a workgroup of the per-node and per-edge kernels
+constexpr int kGrRed = 5;                        // cost, model change, |step|^2, |x|^2, gradient maximum
+
+struct GraphRecord {                             // what the host reads: 80 bytes
+    double red[kGrRed];
+    double cg_rel;                               // sqrt(rho_k / rho_0) when CG stopped
+    int cg_done, cg_iters, bad, pad;
+    double pad2[2];
+};
+
+struct GraphArgs {
+    // the store
+    const int* from; const int* to;              // [E]
+    const double* z; const double* info;         // [E][6], [E]
+    double* x;                                   // [2][x_stride]: poses by frame number, current / candidate
+    size_t x_stride;
+    // the call
+    const int* node;                             // [n_free] -> frame
+    const int* inc_start;                        // [n_free + 1]
+    const int* inc;                              // incident edges of a node, ascending: 2 edge + (1 if the node is the edge's `to`)
+    const int* inc_other;                        // beside inc: the free index of the edge's other end, -1 when that is a constant (so
+                                                 // the gather of a product has no chain of dependent loads edge -> frame -> index)
+    double* blk;                                 // [2][E][91]
+    double* nd;                                  // [2][n_free][27]
+    double* scale; double* diag;                 // [n_free][6]
+    double* chol;                                // [n_free][21]: lower triangle, row-major
+    double* y; double* r; double* zv; double* q; double* p;     // [n_free][6] each; p: [2][n_free][6]
+    double* part_rho0; double* part_rho; double* part_sigma;    // [nb], [2][nb], [nb]
+    double* nterm;                               // [n_free][2]: model change, |step|^2
+    GraphRecord* rec;
+    int E, n_free, nb;
+    double cg_tol2;
+    LMParams lm;
+};
+
+__device__ __forceinline__ int graph_upper6(int a, int b) { return a * 6 - (a * (a - 1)) / 2 + (b - a); }      // a <= b
+__device__ __forceinline__ int graph_lower6(int i, int j) { return (i * (i + 1)) / 2 + j; }                      // j <= i
+
+// R(w) and the left Jacobian J_l(w), R(w + d) = Exp(J_l d) R(w) to first order: column j of J_l is the axial vector of (dR / dw_j) R^T,
+// with dR / dw from the dual-number rotation of the three unit vectors (velo_device_math.h)
+__device__ __forceinline__ void graph_rot(const double w[3], double R[9], double Jl[9]) {
+    PoseRot P;
+    pose_rot_init(w, &P);
+    double dR[3][9];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double e[3] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0};
+        D3 c[3];
+        rotate_point(P, e, c);
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            R[i * 3 + k] = c[i].a;
+#pragma unroll
+            for (int j = 0; j < 3; j++) dR[j][i * 3 + k] = c[i].v[j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        double S[9];
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+#pragma unroll
+            for (int b = 0; b < 3; b++) S[a * 3 + b] = dR[j][a * 3] * R[b * 3] + dR[j][a * 3 + 1] * R[b * 3 + 1] + dR[j][a * 3 + 2] * R[b * 3 + 2];
+        }
+        Jl[0 * 3 + j] = 0.5 * (S[7] - S[5]);
+        Jl[1 * 3 + j] = 0.5 * (S[2] - S[6]);
+        Jl[2 * 3 + j] = 0.5 * (S[3] - S[1]);
+    }
+}
+
+__device__ __forceinline__ void graph_rot_value(const double w[3], double R[9]) {
+    PoseRot P;
+    pose_rot_init(w, &P);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double e[3] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0};
+        double c[3];
+        rotate_point_value(P, e, c);
+        R[k] = c[0]; R[3 + k] = c[1]; R[6 + k] = c[2];
+    }
+}
+
+// ceres::RotationMatrixToAngleAxis: through the quaternion (RotationMatrixToQuaternion, QuaternionToAngleAxis), angle in [0, pi]
+__device__ __forceinline__ void graph_log(const double R[9], double phi[3]) {
+    const double tr = R[0] + R[4] + R[8];
+    double q0, q1, q2, q3;
+    if (tr >= 0.0) {
+        double t = sqrt(tr + 1.0);
+        q0 = 0.5 * t; t = 0.5 / t;
+        q1 = (R[7] - R[5]) * t; q2 = (R[2] - R[6]) * t; q3 = (R[3] - R[1]) * t;
+    } else if (R[0] >= R[4] && R[0] >= R[8]) {
+        double t = sqrt(R[0] - R[4] - R[8] + 1.0);
+        q1 = 0.5 * t; t = 0.5 / t;
+        q0 = (R[7] - R[5]) * t; q2 = (R[3] + R[1]) * t; q3 = (R[6] + R[2]) * t;
+    } else if (R[4] >= R[8]) {
+        double t = sqrt(R[4] - R[8] - R[0] + 1.0);
+        q2 = 0.5 * t; t = 0.5 / t;
+        q0 = (R[2] - R[6]) * t; q3 = (R[7] + R[5]) * t; q1 = (R[1] + R[3]) * t;
+    } else {
+        double t = sqrt(R[8] - R[0] - R[4] + 1.0);
+        q3 = 0.5 * t; t = 0.5 / t;
+        q0 = (R[3] - R[1]) * t; q1 = (R[2] + R[6]) * t; q2 = (R[5] + R[7]) * t;
+    }
+    const double s2 = q1 * q1 + q2 * q2 + q3 * q3;
+    double k = 2.0;
+    if (s2 > 0.0) {
+        const double s = sqrt(s2);
+        const double two_theta = 2.0 * (q0 < 0.0 ? atan2(-s, -q0) : atan2(s, q0));
+        k = two_theta / s;
+    }
+    phi[0] = q1 * k; phi[1] = q2 * k; phi[2] = q3 * k;
+}
+
+// the inverse right Jacobian, Log(R Exp(e)) = phi + J_r^-1(phi) e to first order: I + K / 2 + (1 / t^2 - cot(t / 2) / (2 t)) K^2
+__device__ __forceinline__ void graph_jr_inv(const double phi[3], double J[9]) {
+    const double t2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2];
+    double coef;
+    if (t2 > 1e-6) {
+        const double t = sqrt(t2);
+        double sh, ch;
+        velo_sincos(0.5 * t, &sh, &ch);
+        coef = 1.0 / t2 - ch / (2.0 * t * sh);
+    } else {
+        coef = 1.0 / 12.0 + t2 / 720.0;
+    }
+    const double x = phi[0], y = phi[1], z = phi[2];
+    // K = [phi]x, K^2 = phi phi^T - t2 I
+    J[0] = 1.0 + coef * (x * x - t2); J[1] = -0.5 * z + coef * x * y;       J[2] = 0.5 * y + coef * x * z;
+    J[3] = 0.5 * z + coef * x * y;    J[4] = 1.0 + coef * (y * y - t2);     J[5] = -0.5 * x + coef * y * z;
+    J[6] = -0.5 * y + coef * x * z;   J[7] = 0.5 * x + coef * y * z;        J[8] = 1.0 + coef * (z * z - t2);
+}
+
+__device__ __forceinline__ void graph_mul3(const double A[9], const double B[9], double C[9]) {           // C = A B
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) C[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
+    }
+}
+__device__ __forceinline__ void graph_mul3_tn(const double A[9], const double B[9], double C[9]) {        // C = A^T B
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) C[i * 3 + j] = A[i] * B[j] + A[3 + i] * B[3 + j] + A[6 + i] * B[6 + j];
+    }
+}
+__device__ __forceinline__ void graph_mul3_tt(const double A[9], const double B[9], double C[9]) {        // C = A^T B^T
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) C[i * 3 + j] = A[i] * B[j * 3] + A[3 + i] * B[j * 3 + 1] + A[6 + i] * B[j * 3 + 2];
+    }
+}
+
+// ---- linearise: one thread per edge, at the poses of buffer `which` -------------------------------------------------------------
+__global__ void __launch_bounds__(kGrThreads)
+graph_linearize_kernel(GraphArgs G, int which)
+#if VELO_DEF_GRAPH
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= G.E) return;
+    const double* xf = G.x + (size_t)which * G.x_stride + (size_t)G.from[e] * 6;
+    const double* xt = G.x + (size_t)which * G.x_stride + (size_t)G.to[e] * 6;
+    const double* zz = G.z + (size_t)e * 6;
+    const double wf[3] = {xf[0], xf[1], xf[2]}, wt[3] = {xt[0], xt[1], xt[2]}, wz[3] = {zz[0], zz[1], zz[2]};
+    double Rf[9], Jlf[9], Rt[9], Jlt[9], Rz[9];
+    graph_rot(wf, Rf, Jlf);
+    graph_rot(wt, Rt, Jlt);
+    graph_rot_value(wz, Rz);
+    double Q[9], RE[9], phi[3], Ji[9];
+    graph_mul3_tt(Rz, Rf, Q);                                         // Rz^T Rf^T
+    graph_mul3(Q, Rt, RE);
+    graph_log(RE, phi);
+    graph_jr_inv(phi, Ji);
+    const double d[3] = {xt[3] - xf[3], xt[4] - xf[4], xt[5] - xf[5]};
+    double r[6];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        r[i] = phi[i];
+        r[3 + i] = (Q[i * 3] * d[0] + Q[i * 3 + 1] * d[1] + Q[i * 3 + 2] * d[2]) - (Rz[i] * zz[3] + Rz[3 + i] * zz[4] + Rz[6 + i] * zz[5]);
+    }
+    // A = d r / d x_from = [-Ji Rt^T Jl(wf), 0; Q [d]x Jl(wf), -Q],  B = d r / d x_to = [Ji Rt^T Jl(wt), 0; 0, Q]
+    double T[9], U[9], A[36], B[36];
+    graph_mul3_tn(Rt, Jlf, T);
+    graph_mul3(Ji, T, U);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) { A[i * 6 + j] = -U[i * 3 + j]; A[i * 6 + 3 + j] = 0.0; A[(3 + i) * 6 + 3 + j] = -Q[i * 3 + j]; }
+    }
+    const double Dx[9] = {0.0, -d[2], d[1], d[2], 0.0, -d[0], -d[1], d[0], 0.0};
+    graph_mul3(Dx, Jlf, T);
+    graph_mul3(Q, T, U);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) A[(3 + i) * 6 + j] = U[i * 3 + j];
+    }
+    graph_mul3_tn(Rt, Jlt, T);
+    graph_mul3(Ji, T, U);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) { B[i * 6 + j] = U[i * 3 + j]; B[i * 6 + 3 + j] = 0.0; B[(3 + i) * 6 + j] = 0.0; B[(3 + i) * 6 + 3 + j] = Q[i * 3 + j]; }
+    }
+    const double w = G.info[e];
+    double* out = G.blk + ((size_t)which * G.E + e) * kGrBlk;
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+#pragma unroll
+        for (int b = 0; b < 6; b++) {
+            double ab = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; k++) ab += A[k * 6 + a] * B[k * 6 + b];
+            out[kGrAtB + a * 6 + b] = w * ab;
+            if (b >= a) {
+                double aa = 0.0, bb = 0.0;
+#pragma unroll
+                for (int k = 0; k < 6; k++) { aa += A[k * 6 + a] * A[k * 6 + b]; bb += B[k * 6 + a] * B[k * 6 + b]; }
+                out[kGrAtA + graph_upper6(a, b)] = w * aa;
+                out[kGrBtB + graph_upper6(a, b)] = w * bb;
+            }
+        }
+        double ar = 0.0, br = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; k++) { ar += A[k * 6 + a] * r[k]; br += B[k * 6 + a] * r[k]; }
+        out[kGrAtr + a] = w * ar;
+        out[kGrBtr + a] = w * br;
+    }
+    double rr = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) rr += r[k] * r[k];
+    out[kGrCost] = 0.5 * (w * rr);
+}
+#else
+;
+#endif
+
+// ---- assemble: one thread per free node, its incident edges in the list's order ----------------------------------------------
+// mode 0: the start of a call, which also fixes the Jacobi scaling (B1: once)
+__global__ void __launch_bounds__(kGrThreads)
+graph_assemble_kernel(GraphArgs G, int which, int mode)
+#if VELO_DEF_GRAPH
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= G.n_free) return;
+    double acc[kGrNode];
+#pragma unroll
+    for (int a = 0; a < kGrNode; a++) acc[a] = 0.0;
+    const int end = G.inc_start[i + 1];
+    for (int k = G.inc_start[i]; k < end; k++) {
+        const int code = G.inc[k];
+        const double* b = G.blk + ((size_t)which * G.E + (code >> 1)) * kGrBlk;
+        const double* H = b + ((code & 1) ? kGrBtB : kGrAtA);
+        const double* g = b + ((code & 1) ? kGrBtr : kGrAtr);
+#pragma unroll
+        for (int a = 0; a < 21; a++) acc[a] += H[a];
+#pragma unroll
+        for (int a = 0; a < 6; a++) acc[21 + a] += g[a];
+    }
+    double* out = G.nd + ((size_t)which * G.n_free + i) * kGrNode;
+#pragma unroll
+    for (int a = 0; a < kGrNode; a++) out[a] = acc[a];
+    if (mode == 0) {
+#pragma unroll
+        for (int a = 0; a < 6; a++) G.scale[(size_t)i * 6 + a] = 1.0 / (1.0 + sqrt(acc[graph_upper6(a, a)]));
+    }
+}
+#else
+;
+#endif
+
+// ---- sums ------------------------------------------------------------------------------------------------------------------
+// one value per thread of a 64-thread workgroup -> their sum, by a fixed tree
+__device__ __forceinline__ double graph_block_sum(double* buf, double v) {
+    const int t = threadIdx.x;
+    buf[t] = v;
+    __syncthreads();
+    for (int s = kGrThreads / 2; s > 0; s >>= 1) {
+        if (t < s) buf[t] += buf[t + s];
+        __syncthreads();
+    }
+    const double out = buf[0];
+    __syncthreads();
+    return out;
+}
+// the partial sums of a previous launch, added in the same order by every workgroup
+__device__ __forceinline__ double graph_parts_sum(double* buf, const double* part, int nb) {
+    double acc = 0.0;
+    for (int k = threadIdx.x; k < nb; k += kGrThreads) acc += part[k];
+    return graph_block_sum(buf, acc);
+}
+
+// the record's CG words, read by one thread for the whole workgroup: bit 0 = CG has stopped, bit 1 = the step is invalid
+__device__ __forceinline__ int graph_cg_flags(const GraphRecord* rec) {
+    __shared__ int flags_s;
+    if (threadIdx.x == 0) flags_s = (rec->cg_done != 0 ? 1 : 0) | (rec->bad != 0 ? 2 : 0);
+    __syncthreads();
+    const int f = flags_s;
+    __syncthreads();
+    return f;
+}
+
+// L L^T = M for a 6 x 6 block in registers; L overwrites the lower triangle
+__device__ __forceinline__ bool graph_chol6(double M[36]) {
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double dj = M[j * 6 + j];
+#pragma unroll
+        for (int k = 0; k < j; k++) dj -= M[j * 6 + k] * M[j * 6 + k];
+        if (!(dj > 0.0) || !isfinite(dj)) { ok = false; dj = 1.0; }
+        const double l = sqrt(dj);
+        M[j * 6 + j] = l;
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+            double s = M[i * 6 + j];
+#pragma unroll
+            for (int k = 0; k < j; k++) s -= M[i * 6 + k] * M[j * 6 + k];
+            M[i * 6 + j] = s / l;
+        }
+    }
+    return ok;
+}
+// L L^T v = b with the packed lower triangle
+__device__ __forceinline__ void graph_chol_solve(const double* L, const double b[6], double v[6]) {
+    double t[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        double s = b[i];
+#pragma unroll
+        for (int k = 0; k < i; k++) s -= L[graph_lower6(i, k)] * t[k];
+        t[i] = s / L[graph_lower6(i, i)];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; i--) {
+        double s = t[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; k++) s -= L[graph_lower6(k, i)] * v[k];
+        v[i] = s / L[graph_lower6(i, i)];
+    }
+}
+
+// (c H_ii c) v for the node's upper-packed diagonal block
+__device__ __forceinline__ void graph_diag_mul(const double* H, const double c[6], const double v[6], double out[6]) {
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+        double s = 0.0;
+#pragma unroll
+        for (int b = 0; b < 6; b++) s += H[graph_upper6(a < b ? a : b, a < b ? b : a)] * (c[b] * v[b]);
+        out[a] = c[a] * s;
+    }
+}
+
+// ---- CG ---------------------------------------------------------------------------------------------------------------------
+// The start of an LM iteration's linear solve at buffer `cur`: D (refreshed after an accepted step), M_i = c H_ii c + D_i / mu and its
+// Cholesky, b = -c g, y = 0, r = b, z = M^-1 r, the partial sums of rho_0 = r.z.  The host has cleared the record's CG words before.
+__global__ void __launch_bounds__(kGrThreads)
+graph_cg_begin_kernel(GraphArgs G, int cur, double mu, int refresh)
+#if VELO_DEF_GRAPH
+{
+    __shared__ double buf[kGrThreads];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    double rz = 0.0;
+    if (i < G.n_free) {
+        const double* nd = G.nd + ((size_t)cur * G.n_free + i) * kGrNode;
+        double c[6], M[36], b[6], z[6];
+#pragma unroll
+        for (int a = 0; a < 6; a++) c[a] = G.scale[(size_t)i * 6 + a];
+#pragma unroll
+        for (int a = 0; a < 6; a++) {
+#pragma unroll
+            for (int bb = 0; bb < 6; bb++) M[a * 6 + bb] = nd[graph_upper6(a < bb ? a : bb, a < bb ? bb : a)] * c[a] * c[bb];
+        }
+#pragma unroll
+        for (int a = 0; a < 6; a++) {
+            double dg = G.diag[(size_t)i * 6 + a];
+            if (refresh) { dg = fmin(fmax(M[a * 6 + a], G.lm.min_diag), G.lm.max_diag); G.diag[(size_t)i * 6 + a] = dg; }
+            M[a * 6 + a] += dg / mu;
+            b[a] = -(nd[21 + a] * c[a]);
+        }
+        if (!graph_chol6(M)) atomicOr(&G.rec->bad, 1);
+        double L[21];
+#pragma unroll
+        for (int a = 0; a < 6; a++) {
+#pragma unroll
+            for (int bb = 0; bb <= a; bb++) { L[graph_lower6(a, bb)] = M[a * 6 + bb]; G.chol[(size_t)i * 21 + graph_lower6(a, bb)] = M[a * 6 + bb]; }
+        }
+        graph_chol_solve(L, b, z);
+#pragma unroll
+        for (int a = 0; a < 6; a++) {
+            G.y[(size_t)i * 6 + a] = 0.0;
+            G.r[(size_t)i * 6 + a] = b[a];
+            G.zv[(size_t)i * 6 + a] = z[a];
+            rz += b[a] * z[a];
+        }
+    }
+    const double s = graph_block_sum(buf, rz);
+    if (threadIdx.x == 0) { G.part_rho0[blockIdx.x] = s; G.part_rho[blockIdx.x] = s; }
+}
+#else
+;
+#endif
+
+// First half of CG iteration k.  rho_k lies in part_rho[k & 1], rho_(k-1) in the other half.  Stops -- and lets every later launch
+// return at once -- when rho_k <= tol^2 rho_0.  p_(k-1) is read from p[k & 1] and p_k written to p[(k + 1) & 1]: a neighbour's p_k is
+// recomputed from its z and p_(k-1), so no thread reads what another writes in this launch.
+__global__ void __launch_bounds__(kGrThreads)
+graph_cg_ap_kernel(GraphArgs G, int k, int cur, double mu)
+#if VELO_DEF_GRAPH
+{
+    __shared__ double buf[kGrThreads];
+    const int flags = graph_cg_flags(G.rec);
+    if (flags & 1) return;
+    const double rho = graph_parts_sum(buf, G.part_rho + (size_t)(k & 1) * G.nb, G.nb);
+    const double rho0 = graph_parts_sum(buf, G.part_rho0, G.nb);
+    if ((flags & 2) || !(rho > G.cg_tol2 * rho0)) {               // (also ends on a NaN)
+        if (blockIdx.x == 0 && threadIdx.x == 0) { G.rec->cg_iters = k; G.rec->cg_rel = rho0 > 0.0 ? sqrt(rho / rho0) : 0.0; G.rec->cg_done = 1; }
+        return;
+    }
+    double beta = 0.0;
+    if (k > 0) beta = rho / graph_parts_sum(buf, G.part_rho + (size_t)((k & 1) ^ 1) * G.nb, G.nb);
+    const size_t n6 = (size_t)G.n_free * 6;
+    const double* p_old = G.p + (size_t)(k & 1) * n6;
+    double* p_new = G.p + (size_t)((k + 1) & 1) * n6;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    double pq = 0.0;
+    if (i < G.n_free) {
+        double c[6], p[6], q[6];
+#pragma unroll
+        for (int a = 0; a < 6; a++) {
+            c[a] = G.scale[(size_t)i * 6 + a];
+            p[a] = G.zv[(size_t)i * 6 + a];
+            if (k > 0) p[a] += beta * p_old[(size_t)i * 6 + a];
+            p_new[(size_t)i * 6 + a] = p[a];
+        }
+        graph_diag_mul(G.nd + ((size_t)cur * G.n_free + i) * kGrNode, c, p, q);
+#pragma unroll
+        for (int a = 0; a < 6; a++) q[a] += (G.diag[(size_t)i * 6 + a] / mu) * p[a];
+        const int end = G.inc_start[i + 1];
+        for (int m = G.inc_start[i]; m < end; m++) {
+            const int code = G.inc[m], e = code >> 1, side = code & 1;
+            const int j = G.inc_other[m];
+            if (j < 0) continue;                                      // the other end is a constant
+            double v[6];
+#pragma unroll
+            for (int a = 0; a < 6; a++) {
+                double pj = G.zv[(size_t)j * 6 + a];
+                if (k > 0) pj += beta * p_old[(size_t)j * 6 + a];
+                v[a] = G.scale[(size_t)j * 6 + a] * pj;
+            }
+            const double* W = G.blk + ((size_t)cur * G.E + e) * kGrBlk + kGrAtB;
+#pragma unroll
+            for (int a = 0; a < 6; a++) {
+                double s = 0.0;
+#pragma unroll
+                for (int b = 0; b < 6; b++) s += (side ? W[b * 6 + a] : W[a * 6 + b]) * v[b];
+                q[a] += c[a] * s;
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < 6; a++) { G.q[(size_t)i * 6 + a] = q[a]; pq += p[a] * q[a]; }
+    }
+    const double s = graph_block_sum(buf, pq);
+    if (threadIdx.x == 0) G.part_sigma[blockIdx.x] = s;
+}
+#else
+;
+#endif
+
+// Second half of CG iteration k: alpha = rho_k / p.q, y += alpha p, r -= alpha q, z = M^-1 r, the partial sums of rho_(k+1)
+__global__ void __launch_bounds__(kGrThreads)
+graph_cg_update_kernel(GraphArgs G, int k)
+#if VELO_DEF_GRAPH
+{
+    __shared__ double buf[kGrThreads];
+    if (graph_cg_flags(G.rec) & 1) return;
+    const double rho = graph_parts_sum(buf, G.part_rho + (size_t)(k & 1) * G.nb, G.nb);
+    const double sigma = graph_parts_sum(buf, G.part_sigma, G.nb);
+    if (!(sigma > 0.0) || !isfinite(sigma)) {                          // A is positive definite: a breakdown is an invalid step
+        if (blockIdx.x == 0 && threadIdx.x == 0) { G.rec->cg_iters = k; G.rec->cg_rel = 0.0; G.rec->bad = 1; G.rec->cg_done = 1; }
+        return;
+    }
+    const double alpha = rho / sigma;
+    const double* p = G.p + (size_t)((k + 1) & 1) * (size_t)G.n_free * 6;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    double rz = 0.0;
+    if (i < G.n_free) {
+        double r[6], z[6], L[21];
+#pragma unroll
+        for (int a = 0; a < 21; a++) L[a] = G.chol[(size_t)i * 21 + a];
+#pragma unroll
+        for (int a = 0; a < 6; a++) {
+            G.y[(size_t)i * 6 + a] += alpha * p[(size_t)i * 6 + a];
+            r[a] = G.r[(size_t)i * 6 + a] - alpha * G.q[(size_t)i * 6 + a];
+            G.r[(size_t)i * 6 + a] = r[a];
+        }
+        graph_chol_solve(L, r, z);
+#pragma unroll
+        for (int a = 0; a < 6; a++) { G.zv[(size_t)i * 6 + a] = z[a]; rz += r[a] * z[a]; }
+    }
+    const double s = graph_block_sum(buf, rz);
+    if (threadIdx.x == 0) G.part_rho[(size_t)((k + 1) & 1) * G.nb + blockIdx.x] = s;
+}
+#else
+;
+#endif
+
+// ---- the candidate: x_cand = x + c y per free node, the node's share of the model change y.(c g + (c H c) y / 2) and of |c y|^2 --------
+// k: the CG iterations enqueued; a solve that ran into that cap records its count and residual here.
+__global__ void __launch_bounds__(kGrThreads)
+graph_step_kernel(GraphArgs G, int k, int cur)
+#if VELO_DEF_GRAPH
+{
+    __shared__ double buf[kGrThreads];
+    if (blockIdx.x == 0 && !(graph_cg_flags(G.rec) & 1)) {
+        const double rho = graph_parts_sum(buf, G.part_rho + (size_t)(k & 1) * G.nb, G.nb);
+        const double rho0 = graph_parts_sum(buf, G.part_rho0, G.nb);
+        if (threadIdx.x == 0) { G.rec->cg_iters = k; G.rec->cg_rel = rho0 > 0.0 ? sqrt(rho / rho0) : 0.0; }
+    }
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= G.n_free) return;
+    double c[6], y[6], hy[6];
+#pragma unroll
+    for (int a = 0; a < 6; a++) { c[a] = G.scale[(size_t)i * 6 + a]; y[a] = G.y[(size_t)i * 6 + a]; }
+    const double* nd = G.nd + ((size_t)cur * G.n_free + i) * kGrNode;
+    graph_diag_mul(nd, c, y, hy);
+    const int end = G.inc_start[i + 1];
+    for (int m = G.inc_start[i]; m < end; m++) {
+        const int code = G.inc[m], e = code >> 1, side = code & 1;
+        const int j = G.inc_other[m];
+        if (j < 0) continue;
+        double v[6];
+#pragma unroll
+        for (int a = 0; a < 6; a++) v[a] = G.scale[(size_t)j * 6 + a] * G.y[(size_t)j * 6 + a];
+        const double* W = G.blk + ((size_t)cur * G.E + e) * kGrBlk + kGrAtB;
+#pragma unroll
+        for (int a = 0; a < 6; a++) {
+            double s = 0.0;
+#pragma unroll
+            for (int b = 0; b < 6; b++) s += (side ? W[b * 6 + a] : W[a * 6 + b]) * v[b];
+            hy[a] += c[a] * s;
+        }
+    }
+    const size_t f6 = (size_t)G.node[i] * 6;
+    double model = 0.0, dn2 = 0.0;
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+        model += y[a] * (nd[21 + a] * c[a] + 0.5 * hy[a]);
+        const double d = y[a] * c[a];
+        dn2 += d * d;
+        G.x[(size_t)(cur ^ 1) * G.x_stride + f6 + a] = G.x[(size_t)cur * G.x_stride + f6 + a] + d;
+    }
+    G.nterm[(size_t)i * 2] = -model;
+    G.nterm[(size_t)i * 2 + 1] = dn2;
+}
+#else
+;
+#endif
+
+// ---- one workgroup per scalar of buffer `which`: thread t adds the entries t, t + 256, ... in order, then a fixed tree -------------
+__global__ void __launch_bounds__(256)
+graph_reduce_kernel(GraphArgs G, int which)
+#if VELO_DEF_GRAPH
+{
+    __shared__ double buf[256];
+    const int t = threadIdx.x, idx = blockIdx.x;
+    double acc = 0.0;
+    if (idx == 0) {
+        for (int e = t; e < G.E; e += 256) acc += G.blk[((size_t)which * G.E + e) * kGrBlk + kGrCost];
+    } else if (idx < 3) {
+        for (int i = t; i < G.n_free; i += 256) acc += G.nterm[(size_t)i * 2 + (idx - 1)];
+    } else if (idx == 3) {
+        for (int i = t; i < G.n_free; i += 256) {
+            const double* x = G.x + (size_t)which * G.x_stride + (size_t)G.node[i] * 6;
+            double s = 0.0;
+#pragma unroll
+            for (int a = 0; a < 6; a++) s += x[a] * x[a];
+            acc += s;
+        }
+    } else {
+        for (int i = t; i < G.n_free; i += 256) {
+            const double* g = G.nd + ((size_t)which * G.n_free + i) * kGrNode + 21;
+#pragma unroll
+            for (int a = 0; a < 6; a++) acc = fmax(acc, fabs(g[a]));
+        }
+    }
+    buf[t] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) buf[t] = idx == 4 ? fmax(buf[t], buf[t + s]) : buf[t] + buf[t + s];
+        __syncthreads();
+    }
+    if (t == 0) G.rec->red[idx] = buf[0];
+}
+#else
+;
+#endif
+
+}  // namespace velo

@@ -41,6 +41,7 @@
 #include "velo_detect_kernels.h"
 #include "velo_landmark_kernels.h"
 #include "velo_ba_kernels.h"
+#include "velo_graph_kernels.h"
 #include "velo_frame_kernels.h"
 #include "velo_map_kernels.h"
 #include "velo_block_list.h"
@@ -71,5 +72,6 @@ extern "C" int velo_launch_lm_solve_ag(int nb_max, int n, void* stream, const vo
 #include "velo_api_detect.inl"   // C-ABI: GFTT corner detection on the current images (detectFeatures, velo.h:118-177), of one context or of several in one call
 #include "velo_api_landmarks.inl"   // C-ABI: the resident landmark store (main.cpp:614-679, getLandmarksAtFrame) and its batch triangulation (velo_landmarks_*)
 #include "velo_api_ba.inl"   // C-ABI: bundle adjustment of a window of frames over the landmark store (velo_landmarks_adjust*)
+#include "velo_api_graph.inl"   // C-ABI: the resident pose graph of a drive and its batch optimisation (velo_graph_*)
 #include "velo_api_frames.inl"   // C-ABI: resident keypoint frames and the assembly of frameToFrame's visual matches from them (velo_frames_*, velo_build_matches*)
 #include "velo_api_map.inl"   // C-ABI: the device-resident sliding-window scan map of scan-to-map odometry (velo_map_*)

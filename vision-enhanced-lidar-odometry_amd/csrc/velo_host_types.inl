@@ -264,6 +264,7 @@ struct LkSlot {
 
 struct LmStore;   // the resident landmark store (velo_api_landmarks.inl)
 struct FrStore;   // the resident keypoint frames (velo_api_frames.inl)
+struct GraphStore;   // the resident pose graph (velo_api_graph.inl)
 
 struct velo_ctx {
     int device = 0;
@@ -524,6 +525,8 @@ struct velo_ctx {
     std::shared_ptr<LmStore> lm;
     // the resident keypoint frames (velo_frames_*): created by velo_frames_reset; velo_build_matches writes the visual set (vm, n_matches) from them
     std::shared_ptr<FrStore> fr;
+    // the resident pose graph (velo_graph_*): created by velo_graph_reset; nodes, edges and the solver's work buffers, which nothing else reads or writes
+    std::shared_ptr<GraphStore> graph;
     // front-end calls over several contexts (velo_api_track.inl): the FIRST context of a call lends its stream, staging and scratch buffers
     Event fb_here_ev;                    // "everything enqueued on this context's stream so far": the lending stream waits for it
     Event fb_done_ev;                    // recorded on the lending stream after an asynchronous batch call: the other streams wait for it
