@@ -751,15 +751,28 @@ int velo_landmarks_adjust_system(velo_ctx* ctx, const int32_t* frames, int32_t n
  *             cg_max_iterations.  iSAM's own parametrisation (Euler angles), its Gauss-Newton / dog-leg and its incremental smoothing are
  *             not reproduced.  Parameters move on accepted steps only; two identical calls on identical state give
  *             identical bytes.
+ *   envelope  params->reserved[0] selects the linear solver of a call.  VELO_GRAPH_SOLVER_CG (0, the default) is the CG above.
+ *             VELO_GRAPH_SOLVER_ENVELOPE (1) factors the same damped, Jacobi-scaled normal equations exactly: a block-skyline (envelope)
+ *             Cholesky in the reverse Cuthill-McKee order of the free nodes that velo_graph_order states, one workgroup per LM
+ *             iteration, then a forward and a back substitution.  It needs no tolerance, cap or preconditioner: cg_tolerance and
+ *             cg_max_iterations are validated and otherwise ignored, and every trace record has cg_iterations = 0, cg_residual = 0.  A
+ *             loop closure costs band width, not fill, so a whole drive converges where the CG runs into its cap.
+ *             params->reserved[1] caps its work, in 6 x 6 block products per factorisation: work = sum_i w_i (w_i + 1) / 2 with
+ *             w_i = i - first(i) in that order; 0 is the default, VELO_GRAPH_DEFAULT_MAX_WORK.  A graph whose order exceeds the cap is
+ *             refused with VELO_ERR_INVALID before a pose moves (the message states the work, the cap and the widest row): the caller can
+ *             fall back to the CG.  Any other reserved[0] and a negative reserved[1] are refused with VELO_ERR_INVALID.
  * velo_graph_reset creates or empties the store; edge_capacity: edges the device arrays hold before they are first reallocated (0: the
  * default, 4096); they grow by doubling.  Frames < 2^22.  Refused before anything changes: VELO_ERR_INVALID for a NULL argument, a frame
  * out of range, from == to, a non-finite pose or z, an info that is not positive and finite, fixed frames that are not ascending and
  * distinct, n_fixed < 1; VELO_ERR_STATE without a store, for a fixed frame or an edge's end without a pose. */
 #define VELO_GRAPH_MAX_TRACE 50
+#define VELO_GRAPH_SOLVER_CG 0                   /* reserved[0]: block-Jacobi preconditioned CG (the default) */
+#define VELO_GRAPH_SOLVER_ENVELOPE 1             /* reserved[0]: envelope Cholesky in reverse Cuthill-McKee order */
+#define VELO_GRAPH_DEFAULT_MAX_WORK (1 << 24)    /* reserved[1] == 0: block products per factorisation the envelope solver accepts */
 typedef struct velo_graph_params {     /* 32 bytes */
     double cg_tolerance;       /* relative, on sqrt(r.M^-1 r); 1e-10: the inexact step then takes the LM decisions of a direct solve */
     int32_t cg_max_iterations; /* per LM iteration; 2000 */
-    int32_t reserved[5];       /* 0 */
+    int32_t reserved[5];       /* [0]: VELO_GRAPH_SOLVER_*; [1]: the envelope solver's work cap (0: the default); [2..4]: 0 */
 } velo_graph_params;
 typedef struct velo_graph_iteration {  /* 64 bytes: velo_ba_iteration, then the linear solve */
     int32_t status;            /* VELO_BA_* */
@@ -797,8 +810,24 @@ int velo_graph_add_edges(velo_ctx* ctx, int32_t n, const int32_t* from, const in
 int velo_graph_optimize(velo_ctx* ctx, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, velo_graph_summary* summary);
 /* poses of first .. first + n - 1 to out [n][6]; VELO_ERR_STATE when one of them has no pose */
 int velo_graph_get_poses(velo_ctx* ctx, int32_t first, int32_t n, double* out);
-/* info[8] = nodes with a pose, edges, edge capacity, edge reallocations, frames of the node table, optimisations run, 0, 0 */
+/* info[8] = nodes with a pose, edges, edge capacity, edge reallocations, frames of the node table, optimisations run, and of the
+ * context's last envelope solve the widest row and the envelope's block count (both 0 until there has been one) */
 int velo_graph_info(velo_ctx* ctx, int32_t* info);
+/* The order the envelope solver factors in; a pure host function: no context, no GPU.  Nodes are 0 .. n_nodes - 1 (for
+ * velo_graph_optimize: the free nodes in ascending frame order), edges (a[e], b[e]) join two of them (edges that touch a fixed node
+ * are the caller's to drop); duplicates and both directions are merged.  perm[k] is the node at position k, first[k] the smallest
+ * position among k and its neighbours, stats[4] = the widest row max w_k (w_k = k - first[k]), the envelope blocks sum (w_k + 1), the
+ * work sum w_k (w_k + 1) / 2, the number of components.  The rule, to the letter:
+ *   degree      the number of distinct neighbours;
+ *   components  in ascending order of their smallest node;
+ *   start node  George-Liu's pseudo-peripheral node: begin at the component's node of least degree (lowest index on a tie) and
+ *               build its breadth-first level structure; take from the last level the node of least degree (lowest index on a tie)
+ *               and build its level structure; if that has strictly more levels, go on from that node, otherwise keep the node at hand;
+ *   Cuthill-McKee  from the start node; a dequeued node's unvisited neighbours are appended in ascending (degree, index);
+ *   result      the sequence of all components, reversed as a whole.
+ * A node without a neighbour is a component of its own and a row of width 0.  VELO_ERR_INVALID: a NULL argument (a and b may be NULL
+ * when n_edges is 0), a negative count, an end out of range, a[e] == b[e]. */
+int velo_graph_order(int32_t n_nodes, int32_t n_edges, const int32_t* a, const int32_t* b, int32_t* perm, int32_t* first, int64_t* stats);
 /* Diagnostics: the problem velo_graph_optimize would solve, evaluated at the stored state; nothing changes.  The free nodes are the
  * nodes with a pose that are not fixed, ascending: cost, J^T r (gradient [n_free][6]) and the diagonal blocks of J^T J (diag_blocks
  * [n_free][36], row-major), unscaled.  Each output may be NULL. */

@@ -7,6 +7,7 @@
 //     graph.setPose(frame, ceres_poses_vec[frame]);                 // a new node, or a node's new value
 //     graph.addEdge(frame - dframe, frame, dpose16, 1.0);            // what frameToFrame returned, row-major 4 x 4 (or its 6-vector)
 //     graph.optimize(fixed);                                         // fixed = {0}: the reference's prior on the first node
+//     graph.optimize(fixed, &summary, 0, VELO_GRAPH_SOLVER_ENVELOPE); // the same with the exact envelope solver: a whole drive
 //     graph.poses(0, n, &flat);                                      // n x 6, for velo_landmarks_set_pose / velo_map_set_pose
 #ifndef VELO_POSE_GRAPH_HPP_
 #define VELO_POSE_GRAPH_HPP_
@@ -20,7 +21,7 @@ namespace velo_hip {
 
 class PoseGraph {
 public:
-    struct Info { int nodes, edges, edge_capacity, edge_reallocations, frame_capacity, optimizations; };
+    struct Info { int nodes, edges, edge_capacity, edge_reallocations, frame_capacity, optimizations, envelope_widest_row, envelope_blocks; };
 
     explicit PoseGraph(velo_ctx* ctx, int edge_capacity = 0) : ctx_(ctx), status_(velo_graph_reset(ctx, edge_capacity)) {}
 
@@ -48,9 +49,19 @@ public:
         return velo_graph_add_edges(ctx_, (int32_t)a.size(), &a[0], &b[0], &z[0], &info[0]);
     }
 
-    // refines every node that has a pose and is not in `fixed` (ascending frame numbers)
-    int optimize(const std::vector<int>& fixed, velo_graph_summary* summary = 0, const velo_graph_params* params = 0) {
+    // refines every node that has a pose and is not in `fixed` (ascending frame numbers).  solver: VELO_GRAPH_SOLVER_CG (what params
+    // say, or the defaults) or VELO_GRAPH_SOLVER_ENVELOPE, the exact envelope Cholesky that carries a whole drive; max_work: its cap in
+    // block products per factorisation (0: the library's default) -- a graph over it is refused and nothing changes
+    int optimize(const std::vector<int>& fixed, velo_graph_summary* summary = 0, const velo_graph_params* params = 0,
+                 int solver = VELO_GRAPH_SOLVER_CG, int max_work = 0) {
         std::vector<int32_t> f(fixed.begin(), fixed.end());
+        velo_graph_params own;
+        if (solver != VELO_GRAPH_SOLVER_CG || max_work != 0) {
+            if (params) own = *params;
+            else { const int st = velo_default_graph_params(&own); if (st != VELO_OK) return st; }
+            own.reserved[0] = solver; own.reserved[1] = max_work;
+            params = &own;
+        }
         return velo_graph_optimize(ctx_, f.empty() ? 0 : &f[0], (int32_t)f.size(), params, summary);
     }
 
@@ -67,7 +78,7 @@ public:
         int32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         const int st = velo_graph_info(ctx_, v);
         out->nodes = v[0]; out->edges = v[1]; out->edge_capacity = v[2]; out->edge_reallocations = v[3]; out->frame_capacity = v[4];
-        out->optimizations = v[5];
+        out->optimizations = v[5]; out->envelope_widest_row = v[6]; out->envelope_blocks = v[7];
         return st;
     }
 

@@ -9,8 +9,10 @@ frames (5 mrad / 10 cm of jitter per pose), so that the last 1,541 frames drive 
 Every repetition rebuilds the store (a call moves the poses); only the optimize call is timed, and it ends in a device
 synchronisation.  Beside it: the same problem solved by the numpy restatement's sparse `direct` solver (tests/pose_graph_ref.py,
 SuperLU on the damped normal equations) on the host -- its whole time, dominated by the restatement's per-edge Python loop, and the
-time inside the linear solver alone, which is the figure to hold against the CG.  Nothing gates on this tool.
-Usage: python tools/pose_graph_bench.py [--reps 5] [--cg-tol 1e-10 1e-4] [--cg-max 2000] [--long-cap 10000] [--no-host] [--no-gpu] [--out profiles/r20_pose_graph.txt]"""
+time inside the linear solver alone, which is the figure to hold against the CG.  --solver envelope adds a line for the envelope solver
+(linear_solver="envelope": the exact Cholesky in reverse Cuthill-McKee order) beside the CG lines; --cg-tol with no value leaves the CG
+lines out.  Nothing gates on this tool.
+Usage: python tools/pose_graph_bench.py [--reps 5] [--cg-tol 1e-10 1e-4] [--cg-max 2000] [--long-cap 10000] [--solver envelope] [--no-host] [--no-gpu] [--out profiles/r20_pose_graph.txt]"""
 import argparse
 import os
 import sys
@@ -63,9 +65,10 @@ def med(v):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--cg-tol", type=float, nargs="+", default=[1e-10, 1e-4])
+    ap.add_argument("--cg-tol", type=float, nargs="*", default=[1e-10, 1e-4])
     ap.add_argument("--cg-max", type=int, default=2000)
     ap.add_argument("--long-cap", type=int, default=10000, help="one more run of the last tolerance with this cap on the CG iterations (0: none)")
+    ap.add_argument("--solver", choices=["envelope"], default=None, help="one more line: the same drive with this linear solver")
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--no-gpu", action="store_true")
     ap.add_argument("--out", default=None)
@@ -80,7 +83,9 @@ def main():
         frm, to = [e[0] for e in g["edges"]], [e[1] for e in g["edges"]]
         z, info = np.array([e[2] for e in g["edges"]]), [e[3] for e in g["edges"]]
         ctx = api.Context(0)
-        configs = [(tol, a.cg_max, a.reps) for tol in a.cg_tol] + [(a.cg_tol[-1], a.long_cap, 1)] * (a.long_cap > a.cg_max)
+        configs = [(tol, a.cg_max, a.reps) for tol in a.cg_tol]
+        if a.cg_tol and a.long_cap > a.cg_max:
+            configs.append((a.cg_tol[-1], a.long_cap, 1))
         for tol, cap, reps in configs:
             ms, s, out = [], None, None
             for rep in range(reps + 1):
@@ -98,6 +103,27 @@ def main():
             lines.append(f"GPU  cg_tolerance {tol:g}, cap {cap}: optimize {med(ms)} ms; {s.iterations} LM iterations ({t / max(s.iterations, 1):.2f} ms each), "
                          f"{sum(cg)} CG iterations ({1e3 * t / max(sum(cg), 1):.1f} us each, everything else included), per LM iteration {cg}; "
                          f"termination {s.termination}, cost {s.initial_cost:.4e} -> {s.final_cost:.4e}, largest position error {np.linalg.norm(out[:, 3:] - truth[:, 3:], axis=1).max():.2f} m")
+        if a.solver == "envelope":
+            ms, s = [], None
+            for rep in range(a.reps + 1):
+                ctx.graph_reset(len(frm))
+                ctx.graph_set_poses(0, start)
+                ctx.graph_add_edges(frm, to, z, info)
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                s = ctx.graph_optimize(g["fixed"], linear_solver="envelope")
+                if rep > 0:
+                    ms.append(1e3 * (time.perf_counter() - t0))
+            out = ctx.graph_get_poses(0, N)
+            gi = ctx.graph_info()
+            t = float(np.median(ms))
+            prob = G.problem_of(g)
+            slot = prob.slot
+            pairs = [(slot[e[0]], slot[e[1]]) for e in g["edges"] if e[0] in slot and e[1] in slot]
+            work = api.graph_order(prob.n_free, [p[0] for p in pairs], [p[1] for p in pairs])[2]["work"]
+            lines.append(f"GPU  envelope solver: optimize {med(ms)} ms; {s.iterations} LM iterations ({t / max(s.iterations, 1):.2f} ms each); "
+                         f"termination {s.termination}, cost {s.initial_cost:.4e} -> {s.final_cost:.4e}, largest position error {np.linalg.norm(out[:, 3:] - truth[:, 3:], axis=1).max():.2f} m; "
+                         f"widest row {gi['envelope_widest_row']} blocks, envelope {gi['envelope_blocks']} blocks, work {work} block products per factorisation")
         ctx.close()
     if not a.no_host:
         prob = G.problem_of(g)

@@ -165,6 +165,9 @@ class VeloGraphIteration(C.Structure):
 
 
 GRAPH_MAX_TRACE = 50
+GRAPH_SOLVER_CG, GRAPH_SOLVER_ENVELOPE = 0, 1          # velo_graph_params.reserved[0]
+GRAPH_SOLVERS = {"cg": GRAPH_SOLVER_CG, "envelope": GRAPH_SOLVER_ENVELOPE}
+GRAPH_DEFAULT_MAX_WORK = 1 << 24                       # velo_graph_params.reserved[1] == 0
 
 
 class VeloGraphSummary(C.Structure):
@@ -379,6 +382,7 @@ SIGNATURES = {
     "velo_graph_optimize": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(VeloGraphParams), _P(VeloGraphSummary)]),
     "velo_graph_get_poses": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p]),
     "velo_graph_info": (C.c_int, [_ctx, C.c_void_p]),
+    "velo_graph_order": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "velo_graph_system": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _dp, C.c_void_p, C.c_void_p]),
     "velo_frames_reset": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_int32]),
     "velo_frames_put": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
@@ -890,21 +894,28 @@ class Context:
         self._check(self._lib.velo_graph_add_edges(self._h, len(a), vp(a), vp(b), vp(zz), vp(w)))
 
     @staticmethod
-    def _graph_params(cg_tolerance, cg_max_iterations):
-        if cg_tolerance is None and cg_max_iterations is None:
+    def _graph_params(cg_tolerance, cg_max_iterations, linear_solver="cg", max_work=None):
+        if linear_solver not in GRAPH_SOLVERS and not isinstance(linear_solver, int):
+            raise ValueError(f"graph_optimize: linear_solver {linear_solver!r}; one of {sorted(GRAPH_SOLVERS)}")
+        solver = GRAPH_SOLVERS.get(linear_solver, linear_solver)
+        if cg_tolerance is None and cg_max_iterations is None and solver == GRAPH_SOLVER_CG and max_work is None:
             return None
         p = VeloGraphParams()
         p.cg_tolerance = 1e-10 if cg_tolerance is None else float(cg_tolerance)
         p.cg_max_iterations = 2000 if cg_max_iterations is None else int(cg_max_iterations)
+        p.reserved[0] = int(solver)
+        p.reserved[1] = 0 if max_work is None else int(max_work)
         return C.byref(p)
 
-    def graph_optimize(self, fixed=(0,), cg_tolerance=None, cg_max_iterations=None) -> "VeloGraphSummary":
+    def graph_optimize(self, fixed=(0,), cg_tolerance=None, cg_max_iterations=None, linear_solver="cg", max_work=None) -> "VeloGraphSummary":
         """Refines every node that has a pose and is not in `fixed` (ascending frame numbers) over all edges; the poses are read
-        with graph_get_poses.  summary.trace[:summary.n_trace] holds one record per LM iteration."""
+        with graph_get_poses.  summary.trace[:summary.n_trace] holds one record per LM iteration.  linear_solver: "cg" (the
+        block-Jacobi CG) or "envelope" (the exact envelope Cholesky in reverse Cuthill-McKee order; max_work caps its block products
+        per factorisation, None: the library's default; a graph over the cap is refused and nothing changes)."""
         fx = np.ascontiguousarray(np.asarray(fixed, dtype=np.int32).reshape(-1))
         s = VeloGraphSummary()
         self._check(self._lib.velo_graph_optimize(self._h, C.c_void_p(fx.ctypes.data) if len(fx) else None, len(fx),
-                                                  self._graph_params(cg_tolerance, cg_max_iterations), C.byref(s)))
+                                                  self._graph_params(cg_tolerance, cg_max_iterations, linear_solver, max_work), C.byref(s)))
         return s
 
     def graph_get_poses(self, first: int, n: int) -> np.ndarray:
@@ -916,7 +927,7 @@ class Context:
         a = np.zeros(8, dtype=np.int32)
         self._check(self._lib.velo_graph_info(self._h, C.c_void_p(a.ctypes.data)))
         return dict(n_nodes=int(a[0]), n_edges=int(a[1]), edge_capacity=int(a[2]), edge_reallocations=int(a[3]), frame_capacity=int(a[4]),
-                    optimizations=int(a[5]))
+                    optimizations=int(a[5]), envelope_widest_row=int(a[6]), envelope_blocks=int(a[7]))
 
     def graph_system(self, fixed=(0,), n_free: Optional[int] = None):
         """The problem graph_optimize would solve, evaluated at the stored state (nothing changes): (cost, J^T r [n_free, 6], the
@@ -1887,3 +1898,22 @@ def pose_mat_to_vec(T) -> np.ndarray:
     x = np.zeros(6)
     lib.velo_pose_mat_to_vec(_ptr(Tv), _ptr(x))
     return x
+
+
+def graph_order(n_nodes: int, a, b):
+    """velo_graph_order: the reverse Cuthill-McKee order the envelope solver of graph_optimize factors in (a host function: no
+    context, no GPU).  Nodes 0 .. n_nodes - 1, edges (a[e], b[e]).  Returns (perm [n] int32: the node at position k, first [n] int32:
+    the smallest position among k and its neighbours, stats: dict(widest_row, envelope_blocks, work, components))."""
+    lib = load_library()
+    ea = np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))
+    eb = np.ascontiguousarray(np.asarray(b, dtype=np.int32).reshape(-1))
+    if len(ea) != len(eb):
+        raise ValueError("graph_order: one a and one b per edge")
+    n = max(int(n_nodes), 0)
+    perm, first, stats = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32), np.zeros(4, dtype=np.int64)
+    vp = lambda v: C.c_void_p(v.ctypes.data) if v.size else None   # noqa: E731
+    st = lib.velo_graph_order(int(n_nodes), len(ea), vp(ea), vp(eb), vp(perm), vp(first), vp(stats))
+    if st != 0:
+        msg = lib.velo_last_error()
+        raise VeloError(f"velo status {st}: {msg.decode() if msg else ''}")
+    return perm[:n], first[:n], dict(widest_row=int(stats[0]), envelope_blocks=int(stats[1]), work=int(stats[2]), components=int(stats[3]))

@@ -26,6 +26,10 @@ struct GraphStore {
     DevBuf<int> node, inc_start, inc;
     DevBuf<double> blk, nd, vec, part, nterm;
     DevBuf<GraphRecord> rec;
+    // the envelope solver: the order's ints (perm, pos, first, rowptr, last) and the block skyline, which keeps its size between calls
+    DevBuf<int> env_idx;
+    DevBuf<double> env;
+    int env_widest = 0, env_blocks = 0;                  // of the last envelope solve (velo_graph_info)
 };
 
 namespace {
@@ -42,7 +46,94 @@ struct GraphCall {
     GraphArgs A;
     std::vector<int32_t> free_nodes;
     int n_free = 0, E = 0;
+    bool envelope = false;                               // set by the caller: graph_begin then orders the free nodes and checks the work
+    int64_t max_work = 0, env_stats[4] = {0, 0, 0, 0};
 };
+
+// velo_graph_order's rule (include/velo_hip.h), on checked arguments
+void graph_order(int32_t n, int32_t m, const int32_t* ea, const int32_t* eb, int32_t* perm, int32_t* first, int64_t* stats) {
+    const size_t N = (size_t)n;
+    std::vector<int32_t> start(N + 1, 0), adj;
+    for (int32_t e = 0; e < m; e++) { start[(size_t)ea[e] + 1]++; start[(size_t)eb[e] + 1]++; }
+    for (size_t i = 0; i < N; i++) start[i + 1] += start[i];
+    adj.resize((size_t)start[N]);
+    {
+        std::vector<int32_t> fill(start.begin(), start.end() - 1);
+        for (int32_t e = 0; e < m; e++) { adj[(size_t)fill[(size_t)ea[e]]++] = eb[e]; adj[(size_t)fill[(size_t)eb[e]]++] = ea[e]; }
+    }
+    std::vector<int32_t> deg(N, 0);
+    for (size_t i = 0; i < N; i++) {                                   // distinct neighbours, ascending, at the front of the node's list
+        int32_t* lo = adj.data() + start[i];
+        int32_t* hi = adj.data() + start[i + 1];
+        std::sort(lo, hi);
+        deg[i] = (int32_t)(std::unique(lo, hi) - lo);
+    }
+    auto less = [&](int32_t u, int32_t v) { return deg[(size_t)u] != deg[(size_t)v] ? deg[(size_t)u] < deg[(size_t)v] : u < v; };
+    std::vector<int32_t> seen(N, -1), queue(N), level(N, 0), order;
+    std::vector<unsigned char> placed(N, 0);
+    order.reserve(N);
+    int32_t stamp = 0;
+    // the breadth-first level structure rooted at r: the number of levels; queue[0 .. count) holds the component by level
+    auto levels = [&](int32_t r, size_t* count, size_t* last_begin) {
+        seen[(size_t)r] = ++stamp;
+        level[(size_t)r] = 0;
+        queue[0] = r;
+        size_t head = 0, tail = 1, lb = 0;
+        while (head < tail) {
+            const int32_t u = queue[head++];
+            if (level[(size_t)u] > level[(size_t)queue[lb]]) lb = head - 1;
+            for (int32_t k = 0; k < deg[(size_t)u]; k++) {
+                const int32_t v = adj[(size_t)start[(size_t)u] + (size_t)k];
+                if (seen[(size_t)v] != stamp) { seen[(size_t)v] = stamp; level[(size_t)v] = level[(size_t)u] + 1; queue[tail++] = v; }
+            }
+        }
+        *count = tail; *last_begin = lb;
+        return level[(size_t)queue[tail - 1]] + 1;
+    };
+    int64_t components = 0;
+    std::vector<int32_t> nb;
+    for (int32_t s = 0; s < n; s++) {
+        if (placed[(size_t)s]) continue;
+        components++;
+        size_t count = 0, lb = 0;
+        levels(s, &count, &lb);
+        int32_t root = queue[0];
+        for (size_t k = 1; k < count; k++) if (less(queue[k], root)) root = queue[k];
+        int32_t height = levels(root, &count, &lb);
+        for (;;) {
+            int32_t far = queue[lb];
+            for (size_t k = lb + 1; k < count; k++) if (less(queue[k], far)) far = queue[k];
+            const int32_t h = levels(far, &count, &lb);
+            if (h <= height) break;
+            root = far; height = h;
+        }
+        const size_t base = order.size();                              // Cuthill-McKee from the root; `order` is its own queue
+        order.push_back(root);
+        placed[(size_t)root] = 1;
+        for (size_t head = base; head < order.size(); head++) {
+            const int32_t u = order[head];
+            nb.clear();
+            for (int32_t k = 0; k < deg[(size_t)u]; k++) {
+                const int32_t v = adj[(size_t)start[(size_t)u] + (size_t)k];
+                if (!placed[(size_t)v]) { placed[(size_t)v] = 1; nb.push_back(v); }
+            }
+            std::sort(nb.begin(), nb.end(), less);
+            order.insert(order.end(), nb.begin(), nb.end());
+        }
+    }
+    std::vector<int32_t> pos(N);
+    for (size_t k = 0; k < N; k++) { perm[k] = order[N - 1 - k]; pos[(size_t)perm[k]] = (int32_t)k; }
+    int64_t widest = 0, blocks = 0, work = 0;
+    for (size_t k = 0; k < N; k++) {
+        const size_t u = (size_t)perm[k];
+        int32_t f = (int32_t)k;
+        for (int32_t q = 0; q < deg[u]; q++) f = std::min(f, pos[(size_t)adj[(size_t)start[u] + (size_t)q]]);
+        first[k] = f;
+        const int64_t w = (int64_t)k - f;
+        widest = std::max(widest, w); blocks += w + 1; work += w * (w + 1) / 2;
+    }
+    stats[0] = widest; stats[1] = blocks; stats[2] = work; stats[3] = components;
+}
 
 int graph_check(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, const char* who) {
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
@@ -55,6 +146,9 @@ int graph_check(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
     if (params) {
         if (!(params->cg_tolerance > 0.0 && params->cg_tolerance < 1.0)) return fail(VELO_ERR_INVALID, "%s: cg_tolerance must lie in (0, 1)", who);
         if (params->cg_max_iterations < 1) return fail(VELO_ERR_INVALID, "%s: cg_max_iterations %d; at least 1", who, params->cg_max_iterations);
+        if (params->reserved[0] != VELO_GRAPH_SOLVER_CG && params->reserved[0] != VELO_GRAPH_SOLVER_ENVELOPE)
+            return fail(VELO_ERR_INVALID, "%s: linear solver %d (reserved[0]); 0 (CG) or 1 (envelope)", who, params->reserved[0]);
+        if (params->reserved[1] < 0) return fail(VELO_ERR_INVALID, "%s: negative work cap %d (reserved[1])", who, params->reserved[1]);
     }
     VELO_TRY(graph_need_store(c, who));
     const GraphStore& S = *c->graph;
@@ -98,6 +192,31 @@ int graph_begin(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
             if (st >= 0) { const size_t k = (size_t)fill[(size_t)st]++; inc[k] = (int32_t)(2 * e + 1); other[k] = sf; }
         }
     }
+    // the envelope solver's order of the free nodes (velo_graph_order on the edges between two of them), refused here -- before anything is
+    // sent -- when its work exceeds the cap; ints: perm, pos, first, rowptr, last
+    std::vector<int32_t> env_ints;
+    if (call->envelope && n) {
+        std::vector<int32_t> ea, eb, perm(n), first(n);
+        for (size_t e = 0; e < E; e++) {
+            const int32_t sf = slot[(size_t)S.h_from[e]], st = slot[(size_t)S.h_to[e]];
+            if (sf >= 0 && st >= 0) { ea.push_back(sf); eb.push_back(st); }
+        }
+        graph_order((int32_t)n, (int32_t)ea.size(), ea.data(), eb.data(), perm.data(), first.data(), call->env_stats);
+        if (call->env_stats[2] > call->max_work)
+            return fail(VELO_ERR_INVALID, "velo_graph_optimize: the envelope solver's work is %lld block products, over the cap of %lld (widest row %lld blocks, %lld free nodes); "
+                        "raise reserved[1] or use the CG solver", (long long)call->env_stats[2], (long long)call->max_work, (long long)call->env_stats[0], (long long)n);
+        if (call->env_stats[1] > (int64_t)1 << 30) return fail(VELO_ERR_INVALID, "velo_graph_optimize: an envelope of %lld blocks; at most 2^30", (long long)call->env_stats[1]);
+        env_ints.resize(5 * n + 1);
+        int32_t* pos = env_ints.data() + n;
+        int32_t* rowptr = env_ints.data() + 3 * n;
+        int32_t* last = env_ints.data() + 4 * n + 1;
+        std::memcpy(env_ints.data(), perm.data(), sizeof(int32_t) * n);
+        std::memcpy(env_ints.data() + 2 * n, first.data(), sizeof(int32_t) * n);
+        rowptr[0] = 0;
+        for (size_t k = 0; k < n; k++) { pos[(size_t)perm[k]] = (int32_t)k; rowptr[k + 1] = rowptr[k] + ((int32_t)k - first[k] + 1); last[k] = (int32_t)k; }
+        for (size_t k = 0; k < n; k++) last[(size_t)first[k]] = std::max(last[(size_t)first[k]], (int32_t)k);
+        for (size_t k = 1; k < n; k++) last[k] = std::max(last[k], last[k - 1]);      // the last row whose first column is <= k
+    }
     const int nb = std::max(1, cdiv((int)n, kGrThreads));
     call->n_free = (int)n; call->E = (int)E;
     VELO_TRY(S.node.reserve(n + 1));
@@ -112,8 +231,16 @@ int graph_begin(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
     VELO_TRY(S.rec.reserve(1));
     VELO_TRY(S.h_out.reserve(sizeof(GraphRecord) + sizeof(double) * std::max(F * 6, n * kGrNode) + 64));
     const size_t n_ints = n + (n + 1) + 2 * inc.size();
-    VELO_TRY(S.h_st.reserve(sizeof(int32_t) * (n_ints + 1)));
+    if (!env_ints.empty()) {
+        VELO_TRY(S.env_idx.reserve(env_ints.size()));
+        VELO_TRY(S.env.reserve((size_t)call->env_stats[1] * 36));
+    }
+    VELO_TRY(S.h_st.reserve(sizeof(int32_t) * (n_ints + env_ints.size() + 1)));
     int32_t* st = (int32_t*)S.h_st.p;
+    if (!env_ints.empty()) {
+        std::memcpy(st + n_ints, env_ints.data(), sizeof(int32_t) * env_ints.size());
+        HIP_TRY(hipMemcpyAsync(S.env_idx.p, st + n_ints, sizeof(int32_t) * env_ints.size(), hipMemcpyHostToDevice, c->stream));
+    }
     if (n) std::memcpy(st, nodes.data(), sizeof(int32_t) * n);
     std::memcpy(st + n, start.data(), sizeof(int32_t) * (n + 1));
     if (!inc.empty()) {                                                // inc, then inc_other behind it, in one copy
@@ -147,6 +274,10 @@ int graph_begin(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
     A.part_rho0 = S.part.p; A.part_rho = S.part.p + nb; A.part_sigma = S.part.p + 3 * (size_t)nb;
     A.nterm = S.nterm.p; A.rec = S.rec.p;
     A.E = (int)E; A.n_free = (int)n; A.nb = nb;
+    if (!env_ints.empty()) {
+        A.env_perm = S.env_idx.p; A.env_pos = S.env_idx.p + n; A.env_first = S.env_idx.p + 2 * n; A.env_rowptr = S.env_idx.p + 3 * n;
+        A.env_last = S.env_idx.p + 4 * n + 1; A.env = S.env.p;
+    }
     const double tol = params ? params->cg_tolerance : 1e-10;
     A.cg_tol2 = tol * tol;
     A.lm = lm_params(c->P);
@@ -290,7 +421,18 @@ int velo_graph_info(velo_ctx* c, int32_t* info) {
     VELO_TRY(graph_need_store(c, "velo_graph_info"));
     const GraphStore& S = *c->graph;
     info[0] = S.n_nodes; info[1] = (int32_t)S.n_edges; info[2] = (int32_t)S.edge_cap; info[3] = S.edge_reallocs;
-    info[4] = (int32_t)S.frame_cap; info[5] = S.n_optimized; info[6] = 0; info[7] = 0;
+    info[4] = (int32_t)S.frame_cap; info[5] = S.n_optimized; info[6] = S.env_widest; info[7] = S.env_blocks;
+    return VELO_OK;
+}
+
+int velo_graph_order(int32_t n_nodes, int32_t n_edges, const int32_t* a, const int32_t* b, int32_t* perm, int32_t* first, int64_t* stats) {
+    if (n_nodes < 0 || n_edges < 0) return fail(VELO_ERR_INVALID, "velo_graph_order: negative count");
+    if (!perm || !first || !stats || (n_edges > 0 && (!a || !b))) return fail(VELO_ERR_INVALID, "velo_graph_order: null argument");
+    for (int32_t e = 0; e < n_edges; e++) {
+        if (a[e] < 0 || a[e] >= n_nodes || b[e] < 0 || b[e] >= n_nodes) return fail(VELO_ERR_INVALID, "velo_graph_order: edge %d joins %d and %d; nodes 0..%d", e, a[e], b[e], n_nodes - 1);
+        if (a[e] == b[e]) return fail(VELO_ERR_INVALID, "velo_graph_order: edge %d: a == b (%d)", e, a[e]);
+    }
+    graph_order(n_nodes, n_edges, a, b, perm, first, stats);
     return VELO_OK;
 }
 
@@ -323,11 +465,14 @@ int velo_graph_optimize(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, cons
     VELO_TRY(graph_check(c, fixed, n_fixed, params, "velo_graph_optimize"));
     GraphStore& S = *c->graph;
     GraphCall call;
+    call.envelope = params && params->reserved[0] == VELO_GRAPH_SOLVER_ENVELOPE;
+    call.max_work = params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
     VELO_TRY(graph_begin(c, fixed, n_fixed, params, &call));
     const GraphArgs& A = call.A;
     const LMParams Q = A.lm;
     const int n = call.n_free, E = call.E, nb = A.nb;
     const int cg_cap = params ? params->cg_max_iterations : 2000;
+    const bool envelope = call.envelope;
     velo_graph_summary sum;
     std::memset(&sum, 0, sizeof(sum));
     sum.n_nodes = S.n_nodes; sum.n_free = n; sum.n_edges = E;
@@ -345,11 +490,17 @@ int velo_graph_optimize(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, cons
         if (it + 1 > Q.max_num_iterations) { termination = VELO_NO_CONVERGENCE; break; }
         if (radius < Q.min_radius) { termination = VELO_CONVERGENCE; break; }
         it++;
-        // the linear step: CG in batches, one record per batch
+        // the linear step: the envelope's fill, factor, solve and one record; or CG in batches, one record per batch
         HIP_TRY(hipMemsetAsync(S.rec.p, 0, sizeof(GraphRecord), c->stream));
-        hipLaunchKernelGGL(graph_cg_begin_kernel, dim3(g_nodes), dim3(kGrThreads), 0, c->stream, A, cur, radius, refresh);
         int k = 0, batch = 32;
-        while (k < cg_cap) {
+        if (envelope) {
+            hipLaunchKernelGGL(graph_env_fill_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, A, cur, radius, refresh);
+            hipLaunchKernelGGL(graph_env_factor_kernel, dim3(1), dim3(kGrEnvFactorThreads), 0, c->stream, A);
+            hipLaunchKernelGGL(graph_env_solve_kernel, dim3(1), dim3(kGrEnvSolveThreads), 0, c->stream, A, cur);
+            HIP_TRY(hipGetLastError());
+            VELO_TRY(graph_read_record(c, S, &rec));
+        } else hipLaunchKernelGGL(graph_cg_begin_kernel, dim3(g_nodes), dim3(kGrThreads), 0, c->stream, A, cur, radius, refresh);
+        while (!envelope && k < cg_cap) {
             const int m = std::min(batch, cg_cap - k);
             for (int j = 0; j < m; j++) {
                 hipLaunchKernelGGL(graph_cg_ap_kernel, dim3(g_nodes), dim3(kGrThreads), 0, c->stream, A, k + j, cur, radius);
@@ -417,6 +568,7 @@ int velo_graph_optimize(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, cons
         for (int i = 0; i < n; i++) std::memcpy(S.h_x.p + (size_t)call.free_nodes[(size_t)i] * 6, back + (size_t)call.free_nodes[(size_t)i] * 6, sizeof(double) * 6);
     }
     S.n_optimized++;
+    if (envelope) { S.env_widest = (int)call.env_stats[0]; S.env_blocks = (int)call.env_stats[1]; }
     if (summary) *summary = sum;
     return VELO_OK;
 }

@@ -20,6 +20,8 @@
 // workgroup: no atomics on sums, no grid-wide barrier, no workgroup waits for another.  The stopping test of CG is evaluated by
 // every workgroup on the same numbers; once it holds, the launches that were enqueued behind it return at once.  The host enqueues
 // iterations in batches and reads one GraphRecord per batch, and one per LM iteration, from which it takes the LM decision.
+// A call may select the envelope solver for the linear step instead (velo_graph_params.reserved[0]): the same system, assembled as a
+// block skyline and factored exactly -- graph_env_fill_kernel, graph_env_factor_kernel, graph_env_solve_kernel at the end of this file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -69,6 +71,13 @@ struct GraphArgs {
     int E, n_free, nb;
     double cg_tol2;
     LMParams lm;
+    // the envelope solver (null for a CG call): the order of the free nodes and the block skyline in it
+    const int* env_perm;                         // [n_free]: position -> free index
+    const int* env_pos;                          // [n_free]: free index -> position
+    const int* env_first;                        // [n_free]: the first column of row i (a position)
+    const int* env_rowptr;                       // [n_free + 1]: row i holds the blocks of columns first(i) .. i from here, in blocks
+    const int* env_last;                         // [n_free]: the last row with first <= k, what elimination step k reaches
+    double* env;                                 // [blocks][36], row-major 6 x 6
 };
 
 __device__ __forceinline__ int graph_upper6(int a, int b) { return a * 6 - (a * (a - 1)) / 2 + (b - a); }      // a <= b
@@ -630,6 +639,260 @@ graph_reduce_kernel(GraphArgs G, int which)
         __syncthreads();
     }
     if (t == 0) G.rec->red[idx] = buf[0];
+}
+#else
+;
+#endif
+
+// ---- the envelope solver: an exact Cholesky of (c H c + D / mu) in the order of velo_graph_order ------------------------------------
+// Row i of the block skyline (i: a position in the order) holds the 6 x 6 row-major blocks of columns first(i) .. i, at
+// env + 36 rowptr[i].  Three launches per LM iteration, on one stream:
+//     graph_env_fill_kernel    one wave per row, lane l < 36 owns entry l of every block of its row: zero, the damped diagonal block,
+//                              then c_i (A^T B)_e c_j for the incident edges whose other end is free and earlier, in the list's order
+//     graph_env_factor_kernel  ONE workgroup, in place, right-looking: per step k the Cholesky of the pivot block (thread 0), the
+//                              panel L(i,k) = A(i,k) L(k,k)^-T (a thread per block row), the update A(i,j) -= L(i,k) L(j,k)^T (a
+//                              thread per block row); a __syncthreads after each; every entry is one fixed-order expression
+//     graph_env_solve_kernel   ONE workgroup: b = -c g in the order, forward substitution by rows, back substitution by columns, y
+// The panel and the update walk the rows (k, last(k)] and skip a row whose first column lies behind k: the test is uniform per row.
+// Nothing waits for another workgroup.  The strict upper triangle of a diagonal block is never read after the fill.
+constexpr int kGrEnvFactorThreads = 1024;
+constexpr int kGrEnvGroups = kGrEnvFactorThreads / 6;          // groups of 6 threads (a block's rows), one block pair at a time each
+constexpr int kGrEnvSolveThreads = 256;
+constexpr int kGrEnvChunks = kGrEnvSolveThreads / 6;           // partial sums of a row's forward substitution
+
+__global__ void __launch_bounds__(64)
+graph_env_fill_kernel(GraphArgs G, int cur, double mu, int refresh)
+#if VELO_DEF_GRAPH
+{
+    const int i = blockIdx.x, l = threadIdx.x;
+    if (i >= G.n_free || l >= 36) return;
+    const int a = l / 6, b = l % 6;
+    const int node = G.env_perm[i], first = G.env_first[i], w = i - first;
+    double* row = G.env + (size_t)G.env_rowptr[i] * 36;
+    for (int k = 0; k < w; k++) row[(size_t)k * 36 + l] = 0.0;
+    const double* nd = G.nd + ((size_t)cur * G.n_free + node) * kGrNode;
+    const double ca = G.scale[(size_t)node * 6 + a], cb = G.scale[(size_t)node * 6 + b];
+    double d = nd[graph_upper6(a < b ? a : b, a < b ? b : a)] * ca * cb;
+    if (a == b) {                                                      // D as the CG's M_i has it: clipped, refreshed on acceptance
+        double dg = G.diag[(size_t)node * 6 + a];
+        if (refresh) { dg = fmin(fmax(d, G.lm.min_diag), G.lm.max_diag); G.diag[(size_t)node * 6 + a] = dg; }
+        d += dg / mu;
+    }
+    row[(size_t)w * 36 + l] = d;
+    const int end = G.inc_start[node + 1];
+    for (int m = G.inc_start[node]; m < end; m++) {
+        const int j = G.inc_other[m];
+        if (j < 0) continue;                                           // the other end is a constant
+        const int pj = G.env_pos[j];
+        if (pj >= i) continue;                                         // the later end's row holds this block
+        const int code = G.inc[m];
+        const double* W = G.blk + ((size_t)cur * G.E + (code >> 1)) * kGrBlk + kGrAtB;
+        const double v = (code & 1) ? W[b * 6 + a] : W[a * 6 + b];    // transposed on the `to` side
+        row[(size_t)(pj - first) * 36 + l] += (ca * v) * G.scale[(size_t)j * 6 + b];
+    }
+}
+#else
+;
+#endif
+
+// graph_chol6 with one division per column, not one per entry: the pivot's Cholesky is a single thread's chain of dependent fp64
+// operations in every elimination step, and a division is some forty of them.  inv: 1 / the diagonal of L.
+__device__ __forceinline__ bool graph_env_chol6(double M[36], double inv[6]) {
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double dj = M[j * 6 + j];
+#pragma unroll
+        for (int k = 0; k < j; k++) dj -= M[j * 6 + k] * M[j * 6 + k];
+        if (!(dj > 0.0) || !isfinite(dj)) { ok = false; dj = 1.0; }
+        const double l = sqrt(dj);
+        M[j * 6 + j] = l;
+        inv[j] = 1.0 / l;
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+            double s = M[i * 6 + j];
+#pragma unroll
+            for (int k = 0; k < j; k++) s -= M[i * 6 + k] * M[j * 6 + k];
+            M[i * 6 + j] = s * inv[j];
+        }
+    }
+    return ok;
+}
+
+__global__ void __launch_bounds__(kGrEnvFactorThreads)
+graph_env_factor_kernel(GraphArgs G)
+#if VELO_DEF_GRAPH
+{
+    __shared__ double piv[36];                                         // L(k,k), lower triangle
+    __shared__ double pinv[6];                                         // 1 / its diagonal
+    __shared__ int bad_s;
+    const int t = threadIdx.x, n = G.n_free;
+    const int ea = t % 6, g = t / 6;
+    if (t == 0) { bad_s = 0; G.rec->cg_done = 1; }                     // no CG ran: the record keeps cg_iters = 0, cg_rel = 0
+    for (int k = 0; k < n; k++) {
+        const int fk = G.env_first[k];
+        if (t == 0) {
+            double* D = G.env + ((size_t)G.env_rowptr[k] + (size_t)(k - fk)) * 36;
+            double M[36];
+#pragma unroll
+            for (int x = 0; x < 36; x++) M[x] = D[x];
+            double inv[6];
+            if (!graph_env_chol6(M, inv)) bad_s = 1;
+#pragma unroll
+            for (int r = 0; r < 6; r++) {
+#pragma unroll
+                for (int c = 0; c <= r; c++) { D[r * 6 + c] = M[r * 6 + c]; piv[r * 6 + c] = M[r * 6 + c]; }
+                pinv[r] = inv[r];
+            }
+        }
+        __syncthreads();
+        if (bad_s) {                                                   // a pivot that is not positive and finite: an invalid step
+            if (t == 0) G.rec->bad = 1;
+            return;
+        }
+        const int m = G.env_last[k] - k;                               // the rows k + 1 .. k + m can hold a block in column k
+        for (int u = t; u < m * 6; u += kGrEnvFactorThreads) {         // the panel: row r of L(i,k) = A(i,k) L(k,k)^-T
+            const int i = k + 1 + u / 6, r = u % 6, fi = G.env_first[i];
+            if (fi > k) continue;
+            double* A = G.env + ((size_t)G.env_rowptr[i] + (size_t)(k - fi)) * 36 + r * 6;
+            double x[6];
+#pragma unroll
+            for (int c = 0; c < 6; c++) {
+                double s = A[c];
+#pragma unroll
+                for (int q = 0; q < c; q++) s -= x[q] * piv[c * 6 + q];
+                x[c] = s * pinv[c];
+            }
+#pragma unroll
+            for (int c = 0; c < 6; c++) A[c] = x[c];
+        }
+        __syncthreads();
+        if (g < kGrEnvGroups) {                                        // the update: row ea of A(i,j) -= L(i,k) L(j,k)^T, i >= j > k
+            int ii = 0, jj = g;                                        // pair number p = ii (ii + 1) / 2 + jj, p = g, g + groups, ...
+            for (;;) {
+                while (jj > ii) { jj -= ii + 1; ii++; }
+                if (ii >= m) break;
+                const int i = k + 1 + ii, j = k + 1 + jj, fi = G.env_first[i], fj = G.env_first[j];
+                if (fi <= k && fj <= k) {                              // then first(i) <= k < j: (i,j) lies inside the envelope
+                    const double* Li = G.env + ((size_t)G.env_rowptr[i] + (size_t)(k - fi)) * 36 + ea * 6;
+                    const double* Lj = G.env + ((size_t)G.env_rowptr[j] + (size_t)(k - fj)) * 36;
+                    double* A = G.env + ((size_t)G.env_rowptr[i] + (size_t)(j - fi)) * 36 + ea * 6;
+                    double li[6], lj[36], s[6];                        // every load of the pair is requested before its first store
+#pragma unroll
+                    for (int c = 0; c < 6; c++) { li[c] = Li[c]; s[c] = A[c]; }
+#pragma unroll
+                    for (int x = 0; x < 36; x++) lj[x] = Lj[x];
+#pragma unroll
+                    for (int b = 0; b < 6; b++) {
+#pragma unroll
+                        for (int c = 0; c < 6; c++) s[b] -= li[c] * lj[b * 6 + c];
+                    }
+#pragma unroll
+                    for (int b = 0; b < 6; b++) A[b] = s[b];
+                }
+                jj += kGrEnvGroups;
+            }
+        }
+        __syncthreads();
+    }
+}
+#else
+;
+#endif
+
+__global__ void __launch_bounds__(kGrEnvSolveThreads)
+graph_env_solve_kernel(GraphArgs G, int cur)
+#if VELO_DEF_GRAPH
+{
+    __shared__ double part[kGrEnvChunks * 6];
+    __shared__ double xs[6];
+    if (G.rec->bad != 0) return;                                       // (the same word for every thread: the factorisation's launch wrote it)
+    const int t = threadIdx.x, n = G.n_free;
+    const int a = t % 6, ch = t / 6;
+    double* v = G.r;                                                   // [n_free][6] by position: b, then L^-1 b, then the solution
+    for (int u = t; u < n * 6; u += kGrEnvSolveThreads) {
+        const int node = G.env_perm[u / 6], c = u % 6;
+        v[u] = -(G.nd[((size_t)cur * n + node) * kGrNode + 21 + c] * G.scale[(size_t)node * 6 + c]);
+    }
+    __syncthreads();
+    for (int i = 0; i < n; i++) {                                      // forward, by rows: x_i = L(i,i)^-1 (b_i - sum_j L(i,j) x_j)
+        const int fi = G.env_first[i], w = i - fi;
+        const double* row = G.env + (size_t)G.env_rowptr[i] * 36;
+        if (ch < kGrEnvChunks) {
+            double s = 0.0;
+            for (int j = ch; j < w; j += kGrEnvChunks) {
+                const double* L = row + (size_t)j * 36 + a * 6;
+                const double* x = v + (size_t)(fi + j) * 6;
+#pragma unroll
+                for (int c = 0; c < 6; c++) s += L[c] * x[c];
+            }
+            part[ch * 6 + a] = s;
+        }
+        __syncthreads();
+        if (t < 64) {                                                  // the first wave: lane a sums the chunks in order, every lane then
+            double s = 0.0;                                            // solves the 6 x 6 triangle and lane a keeps component a
+            if (t < 6) {
+                s = v[(size_t)i * 6 + t];
+                const int nc = w < kGrEnvChunks ? w : kGrEnvChunks;
+                for (int c = 0; c < nc; c++) s -= part[c * 6 + t];
+            }
+            double x[6];
+#pragma unroll
+            for (int c = 0; c < 6; c++) x[c] = __shfl(s, c);
+            if (t < 6) {
+                const double* D = row + (size_t)w * 36;
+#pragma unroll
+                for (int r = 0; r < 6; r++) {
+                    double q = x[r];
+#pragma unroll
+                    for (int c = 0; c < r; c++) q -= D[r * 6 + c] * x[c];
+                    x[r] = q / D[r * 6 + r];
+                }
+                double mine = x[0];
+#pragma unroll
+                for (int c = 1; c < 6; c++) if (t == c) mine = x[c];
+                v[(size_t)i * 6 + t] = mine;
+            }
+        }
+        __syncthreads();
+    }
+    for (int i = n - 1; i >= 0; i--) {                                 // back, by columns: x_i = L(i,i)^-T b_i, then b_j -= L(i,j)^T x_i
+        const int fi = G.env_first[i], w = i - fi;
+        const double* row = G.env + (size_t)G.env_rowptr[i] * 36;
+        if (t < 64) {
+            const double s = t < 6 ? v[(size_t)i * 6 + t] : 0.0;
+            double x[6];
+#pragma unroll
+            for (int c = 0; c < 6; c++) x[c] = __shfl(s, c);
+            if (t < 6) {
+                const double* D = row + (size_t)w * 36;
+#pragma unroll
+                for (int r = 5; r >= 0; r--) {
+                    double q = x[r];
+#pragma unroll
+                    for (int c = r + 1; c < 6; c++) q -= D[c * 6 + r] * x[c];
+                    x[r] = q / D[r * 6 + r];
+                }
+                double mine = x[0];
+#pragma unroll
+                for (int c = 1; c < 6; c++) if (t == c) mine = x[c];
+                v[(size_t)i * 6 + t] = mine;
+                xs[t] = mine;
+            }
+        }
+        __syncthreads();
+        for (int u = t; u < w * 6; u += kGrEnvSolveThreads) {
+            const int j = u / 6, c = u % 6;
+            const double* L = row + (size_t)j * 36;
+            double s = v[(size_t)(fi + j) * 6 + c];
+#pragma unroll
+            for (int r = 0; r < 6; r++) s -= L[r * 6 + c] * xs[r];
+            v[(size_t)(fi + j) * 6 + c] = s;
+        }
+        __syncthreads();
+    }
+    for (int u = t; u < n * 6; u += kGrEnvSolveThreads)               // the step y, by free index, where graph_step_kernel reads it
+        G.y[(size_t)G.env_perm[u / 6] * 6 + u % 6] = v[u];
 }
 #else
 ;
