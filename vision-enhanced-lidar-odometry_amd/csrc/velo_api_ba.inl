@@ -138,16 +138,7 @@ int velo_landmarks_adjust_system(velo_ctx* c, const int32_t* frames, int32_t n_f
     HIP_TRY(hipStreamSynchronize(c->stream));
     const double* red = (const double*)W.h_out.p;
     if (cost) *cost = red[n_free * kBaRed];
-    for (int k = 0; k < n_free; k++) {
-        const double* U = red + k * kBaRed;
-        for (int a = 0; a < 6; a++) {
-            if (gradient) gradient[6 * k + a] = U[21 + a];
-            for (int b = 0; b < 6 && JtJ_pose; b++) {
-                const int lo = std::min(a, b), hi = std::max(a, b);
-                JtJ_pose[36 * k + 6 * a + b] = U[lo * 6 - (lo * (lo - 1)) / 2 + (hi - lo)];
-            }
-        }
-    }
+    for (int k = 0; k < n_free; k++) expand_upper6(red + k * kBaRed, gradient ? gradient + 6 * k : nullptr, JtJ_pose ? JtJ_pose + 36 * k : nullptr);
     return VELO_OK;
 }
 
@@ -205,8 +196,8 @@ int velo_landmarks_adjust(velo_ctx* c, const int32_t* frames, int32_t n_frames, 
         HIP_TRY(hipStreamSynchronize(c->stream));
         const BaState* st = (const BaState*)tail;
         const double* xc = (const double*)(tail + sizeof(BaState)) + (size_t)st->cur * n_frames * 6;
-        sum.final_cost = st->cost;
-        if (st->n_accepted > 0) {
+        sum.final_cost = st->tr.cost;
+        if (st->tr.n_accepted > 0) {
             for (int i = n_fixed; i < n_frames; i++) {
                 for (int j = 0; j < 6; j++) poses[(size_t)i * 6 + j] = xc[(size_t)i * 6 + j];
                 VELO_TRY(velo_landmarks_set_pose(c, frames[i], &poses[(size_t)i * 6]));    // the frame table's one host path

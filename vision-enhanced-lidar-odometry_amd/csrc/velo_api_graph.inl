@@ -42,6 +42,12 @@ int graph_need_store(velo_ctx* c, const char* who) {
     return VELO_OK;
 }
 
+velo_graph_params graph_params(const velo_graph_params* params) {     // a call's own, or the defaults
+    velo_graph_params p;
+    velo_default_graph_params(&p);
+    return params ? *params : p;
+}
+
 struct GraphCall {
     GraphArgs A;
     std::vector<int32_t> free_nodes;
@@ -164,7 +170,7 @@ int graph_check(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
 
 // the free nodes, their incidence lists (ints only), the poses to both buffers; then the system at the stored state: linearise,
 // assemble, reduce
-int graph_begin(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, GraphCall* call) {
+int graph_begin(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params& params, GraphCall* call) {
     GraphStore& S = *c->graph;
     HIP_TRY(hipSetDevice(c->device));
     const size_t F = S.frame_cap, E = S.n_edges;
@@ -278,8 +284,7 @@ int graph_begin(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
         A.env_perm = S.env_idx.p; A.env_pos = S.env_idx.p + n; A.env_first = S.env_idx.p + 2 * n; A.env_rowptr = S.env_idx.p + 3 * n;
         A.env_last = S.env_idx.p + 4 * n + 1; A.env = S.env.p;
     }
-    const double tol = params ? params->cg_tolerance : 1e-10;
-    A.cg_tol2 = tol * tol;
+    A.cg_tol2 = params.cg_tolerance * params.cg_tolerance;
     A.lm = lm_params(c->P);
     if (E) hipLaunchKernelGGL(graph_linearize_kernel, dim3((unsigned)cdiv((int)E, kGrThreads)), dim3(kGrThreads), 0, c->stream, A, 0);
     if (n) hipLaunchKernelGGL(graph_assemble_kernel, dim3((unsigned)nb), dim3(kGrThreads), 0, c->stream, A, 0, 0);
@@ -440,7 +445,7 @@ int velo_graph_system(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, double
     VELO_TRY(graph_check(c, fixed, n_fixed, nullptr, "velo_graph_system"));
     GraphStore& S = *c->graph;
     GraphCall call;
-    VELO_TRY(graph_begin(c, fixed, n_fixed, nullptr, &call));
+    VELO_TRY(graph_begin(c, fixed, n_fixed, graph_params(nullptr), &call));
     const size_t n = (size_t)call.n_free;
     unsigned char* tail = S.h_out.p + sizeof(GraphRecord);
     if (n) HIP_TRY(hipMemcpyAsync(tail, S.nd.p, sizeof(double) * n * kGrNode, hipMemcpyDeviceToHost, c->stream));   // the state starts in buffer 0
@@ -448,62 +453,49 @@ int velo_graph_system(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, double
     VELO_TRY(graph_read_record(c, S, &rec));
     if (cost) *cost = rec->red[0];
     const double* nd = (const double*)tail;
-    for (size_t i = 0; i < n; i++) {
-        const double* U = nd + i * kGrNode;
-        for (int a = 0; a < 6; a++) {
-            if (gradient) gradient[6 * i + a] = U[21 + a];
-            for (int b = 0; b < 6 && diag_blocks; b++) {
-                const int lo = std::min(a, b), hi = std::max(a, b);
-                diag_blocks[36 * i + 6 * a + b] = U[lo * 6 - (lo * (lo - 1)) / 2 + (hi - lo)];
-            }
-        }
-    }
+    for (size_t i = 0; i < n; i++) expand_upper6(nd + i * kGrNode, gradient ? gradient + 6 * i : nullptr, diag_blocks ? diag_blocks + 36 * i : nullptr);
     return VELO_OK;
 }
 
 int velo_graph_optimize(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, velo_graph_summary* summary) {
     VELO_TRY(graph_check(c, fixed, n_fixed, params, "velo_graph_optimize"));
     GraphStore& S = *c->graph;
+    const velo_graph_params P = graph_params(params);
     GraphCall call;
-    call.envelope = params && params->reserved[0] == VELO_GRAPH_SOLVER_ENVELOPE;
-    call.max_work = params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
-    VELO_TRY(graph_begin(c, fixed, n_fixed, params, &call));
+    call.envelope = P.reserved[0] == VELO_GRAPH_SOLVER_ENVELOPE;
+    call.max_work = P.reserved[1] > 0 ? P.reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
+    VELO_TRY(graph_begin(c, fixed, n_fixed, P, &call));
     const GraphArgs& A = call.A;
     const LMParams Q = A.lm;
     const int n = call.n_free, E = call.E, nb = A.nb;
-    const int cg_cap = params ? params->cg_max_iterations : 2000;
+    const int cg_cap = P.cg_max_iterations;
     const bool envelope = call.envelope;
     velo_graph_summary sum;
     std::memset(&sum, 0, sizeof(sum));
     sum.n_nodes = S.n_nodes; sum.n_free = n; sum.n_edges = E;
-    sum.evaluations = 1;
     GraphRecord* rec = nullptr;
     VELO_TRY(graph_read_record(c, S, &rec));
-    double cost = rec->red[0], x_norm = std::sqrt(rec->red[3]);
-    sum.initial_cost = cost;
-    int termination = VELO_NO_CONVERGENCE, cur = 0, it = 0, invalid = 0, refresh = 1, n_accepted = 0;
-    double radius = Q.initial_radius, decrease = 2.0;
+    TrustRegion T;                                                     // B1, on the host (velo_trust_region.h)
+    tr_start(Q, &T, rec->red[0], std::sqrt(rec->red[3]), rec->red[4]);
+    sum.initial_cost = T.cost;
+    if (n == 0 || E == 0) tr_stop(&T, VELO_CONVERGENCE);
+    int cur = 0;
     const unsigned g_nodes = (unsigned)nb, g_edges = (unsigned)std::max(1, cdiv(E, kGrThreads));
-    if (n == 0 || E == 0 || rec->red[4] <= Q.gradient_tolerance) termination = VELO_CONVERGENCE;
-    else for (;;) {
-        // the head of an iteration (B1)
-        if (it + 1 > Q.max_num_iterations) { termination = VELO_NO_CONVERGENCE; break; }
-        if (radius < Q.min_radius) { termination = VELO_CONVERGENCE; break; }
-        it++;
+    while (!T.done && !tr_head(Q, &T)) {
         // the linear step: the envelope's fill, factor, solve and one record; or CG in batches, one record per batch
         HIP_TRY(hipMemsetAsync(S.rec.p, 0, sizeof(GraphRecord), c->stream));
         int k = 0, batch = 32;
         if (envelope) {
-            hipLaunchKernelGGL(graph_env_fill_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, A, cur, radius, refresh);
+            hipLaunchKernelGGL(graph_env_fill_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, A, cur, T.radius, T.refresh);
             hipLaunchKernelGGL(graph_env_factor_kernel, dim3(1), dim3(kGrEnvFactorThreads), 0, c->stream, A);
             hipLaunchKernelGGL(graph_env_solve_kernel, dim3(1), dim3(kGrEnvSolveThreads), 0, c->stream, A, cur);
             HIP_TRY(hipGetLastError());
             VELO_TRY(graph_read_record(c, S, &rec));
-        } else hipLaunchKernelGGL(graph_cg_begin_kernel, dim3(g_nodes), dim3(kGrThreads), 0, c->stream, A, cur, radius, refresh);
+        } else hipLaunchKernelGGL(graph_cg_begin_kernel, dim3(g_nodes), dim3(kGrThreads), 0, c->stream, A, cur, T.radius, T.refresh);
         while (!envelope && k < cg_cap) {
             const int m = std::min(batch, cg_cap - k);
             for (int j = 0; j < m; j++) {
-                hipLaunchKernelGGL(graph_cg_ap_kernel, dim3(g_nodes), dim3(kGrThreads), 0, c->stream, A, k + j, cur, radius);
+                hipLaunchKernelGGL(graph_cg_ap_kernel, dim3(g_nodes), dim3(kGrThreads), 0, c->stream, A, k + j, cur, T.radius);
                 hipLaunchKernelGGL(graph_cg_update_kernel, dim3(g_nodes), dim3(kGrThreads), 0, c->stream, A, k + j);
             }
             k += m;
@@ -524,44 +516,17 @@ int velo_graph_optimize(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, cons
         }
         velo_graph_iteration t;
         std::memset(&t, 0, sizeof(t));
-        t.iteration = it; t.cost = cost; t.radius = radius; t.cg_iterations = rec->cg_iters; t.cg_residual = rec->cg_rel;
-        bool stop = false;
-        if (!ok) {
-            t.status = VELO_BA_INVALID;
-            if (++invalid >= Q.max_invalid) { termination = VELO_FAILURE; stop = true; }
-            else { radius = radius / decrease; decrease *= 2.0; refresh = 0; }
-        } else {
-            invalid = 0;
-            const double model_change = rec->red[1], dn = std::sqrt(rec->red[2]), cand_cost = rec->red[0];
-            sum.evaluations++;
-            t.candidate_cost = cand_cost; t.model_change = model_change; t.step_norm = dn;
-            const double cost_change = cost - cand_cost;
-            if (dn <= Q.parameter_tolerance * (x_norm + Q.parameter_tolerance)) { t.status = VELO_BA_PARAMETER; termination = VELO_CONVERGENCE; stop = true; }
-            else if (std::fabs(cost_change) <= Q.function_tolerance * cost) { t.status = VELO_BA_FUNCTION; termination = VELO_CONVERGENCE; stop = true; }
-            else {
-                const double q = cost_change / model_change;
-                if (q > Q.min_relative_decrease) {
-                    cur ^= 1; n_accepted++;
-                    cost = cand_cost;
-                    x_norm = std::sqrt(rec->red[3]);
-                    t.status = VELO_BA_ACCEPTED;
-                    if (rec->red[4] <= Q.gradient_tolerance) { t.status = VELO_BA_GRADIENT; termination = VELO_CONVERGENCE; stop = true; }
-                    else {
-                        const double u = 2.0 * q - 1.0;
-                        radius = std::min(Q.max_radius, radius / std::max(1.0 / 3.0, 1.0 - u * u * u));
-                        decrease = 2.0; refresh = 1;
-                    }
-                } else {
-                    t.status = VELO_BA_REJECTED;
-                    radius = radius / decrease; decrease *= 2.0; refresh = 0;
-                }
-            }
+        t.iteration = T.iteration; t.cost = T.cost; t.radius = T.radius; t.cg_iterations = rec->cg_iters; t.cg_residual = rec->cg_rel;
+        if (!ok) t.status = tr_invalid(Q, &T);
+        else {
+            t.candidate_cost = rec->red[0]; t.model_change = rec->red[1]; t.step_norm = std::sqrt(rec->red[2]);
+            t.status = tr_candidate(Q, &T, t.candidate_cost, t.model_change, t.step_norm);
+            if (t.status == VELO_BA_ACCEPTED) { cur ^= 1; t.status = tr_accept(Q, &T, std::sqrt(rec->red[3]), rec->red[4]); }
         }
         if (sum.n_trace < VELO_GRAPH_MAX_TRACE) sum.trace[sum.n_trace++] = t;
-        if (stop) break;
     }
-    sum.termination = termination; sum.iterations = it; sum.final_cost = cost;
-    if (n_accepted > 0) {                                              // parameters move on accepted steps only
+    sum.termination = T.termination; sum.iterations = T.iteration; sum.evaluations = T.evaluations; sum.final_cost = T.cost;
+    if (T.n_accepted > 0) {                                            // parameters move on accepted steps only
         double* back = (double*)(S.h_out.p + sizeof(GraphRecord));
         HIP_TRY(hipMemcpyAsync(back, S.x.p + (size_t)cur * A.x_stride, sizeof(double) * A.x_stride, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));

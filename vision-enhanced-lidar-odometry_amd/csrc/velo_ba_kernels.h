@@ -3,7 +3,7 @@
 // definitions); gfx950 only.
 //
 // Unknowns: the 6 doubles of every FREE frame of the window and the 3 doubles of every participating landmark.  The solver is the
-// trust-region Levenberg-Marquardt of SURVEY.md B1 (the loop of tri_solve, velo_tri_kernels.h) over all of them; its linear step is the
+// trust-region Levenberg-Marquardt of SURVEY.md B1 (the controller of velo_trust_region.h) over all of them; its linear step is the
 // Schur complement on the landmark blocks.  With H = [U W; W^T V] the Jacobi-scaled J^T J, D the clipped diagonal and mu the radius:
 //     A_l = V_l + D_l / mu                                   3 x 3 per landmark, solved with tri_chol3
 //     S   = U + D_c / mu - sum_l W_l A_l^-1 W_l^T            6 n_free square, factored by ONE workgroup in LDS
@@ -47,9 +47,9 @@ struct BaRecord {                                // what the host reads after ev
 
 struct BaState {
     BaRecord rec;
-    double cost, initial_cost, radius, decrease, x_norm;
+    TrustRegion tr;
     double pose_model, pose_dn2, pose_xn2[2];
-    int cur, refresh, invalid, iteration, step_ok, bad, n_accepted, pad;
+    int cur, step_ok, bad, pad;
     double scale_c[6 * kBaMaxFree], diag_c[6 * kBaMaxFree], step_c[6 * kBaMaxFree], delta_c[6 * kBaMaxFree];
 };
 
@@ -79,7 +79,6 @@ struct BaArgs {
     double weight_3d;
 };
 
-__device__ __forceinline__ int ba_upper6(int a, int b) { return a * 6 - (a * (a - 1)) / 2 + (b - a); }      // a <= b
 __device__ __forceinline__ int ba_pair(int k, int m, int n) { return k * n - (k * (k - 1)) / 2 + (m - k); }   // k <= m < n
 
 // ---- selection -------------------------------------------------------------------------------------------------------------
@@ -167,7 +166,7 @@ ba_compact_kernel(BaArgs A, int L_cap)
         for (int k = 0; k < 256; k++) { base[k] = s; s += cnt[k]; sb += blocks[k]; sr += res[k]; }
         A.hdr[0] = s; A.hdr[1] = sb; A.hdr[2] = sr;
         BaState* st = A.st;
-        st->cur = 0; st->refresh = 1; st->invalid = 0; st->iteration = 0; st->step_ok = 0; st->bad = 0; st->n_accepted = 0;
+        st->cur = 0; st->step_ok = 0; st->bad = 0;                    // (ba_decide_kernel starts st->tr)
         st->rec.status = 0; st->rec.iteration = 0; st->rec.done = 0; st->rec.termination = VELO_NO_CONVERGENCE; st->rec.evaluations = 0;
     }
     __syncthreads();
@@ -339,8 +338,8 @@ ba_linearize_kernel(BaArgs A, int mode)
         const double cp[3] = {A.scale_p[3 * l], A.scale_p[3 * l + 1], A.scale_p[3 * l + 2]};
         double dp[3] = {A.diag_p[3 * l], A.diag_p[3 * l + 1], A.diag_p[3 * l + 2]};
         double Vs[9], A3[9];
-        ba_point_block(v, cp, dp, st->refresh != 0, st->radius, A.P.lm, Vs, A3);
-        if (st->refresh != 0 && lane == 0) { A.diag_p[3 * l] = dp[0]; A.diag_p[3 * l + 1] = dp[1]; A.diag_p[3 * l + 2] = dp[2]; }
+        ba_point_block(v, cp, dp, st->tr.refresh != 0, st->tr.radius, A.P.lm, Vs, A3);
+        if (st->tr.refresh != 0 && lane == 0) { A.diag_p[3 * l] = dp[0]; A.diag_p[3 * l + 1] = dp[1]; A.diag_p[3 * l + 2] = dp[2]; }
         double ws[3] = {0.0, 0.0, 0.0};                               // W^T (pose step), unscaled
         const unsigned mask = A.fmask[l];
         for (int k = 0; k < nf; k++) {
@@ -509,8 +508,8 @@ ba_schur_kernel(BaArgs A)
     const int n_pairs = nf * (nf + 1) / 2;
     const BaState* st = A.st;
     const int cur = st->cur;
-    const bool refresh = st->refresh != 0;
-    const double mu = st->radius;
+    const bool refresh = st->tr.refresh != 0;
+    const double mu = st->tr.radius;
     const size_t L = (size_t)A.L;
     int k = 0, m = 0;
     const bool rhs = (int)blockIdx.x >= n_pairs;
@@ -586,7 +585,7 @@ ba_solve_kernel(BaArgs A)
     const int cur = st->cur;
     const int n_pairs = nf * (nf + 1) / 2;
     const double* red = A.red + (size_t)cur * (nf * kBaRed + kBaScalars);
-    const double mu = st->radius;
+    const double mu = st->tr.radius;
     if (i == 0) { ok_s = 1; st->bad = 0; }
     if (i < n) sc[i] = st->scale_c[i];
     __syncthreads();
@@ -595,10 +594,10 @@ ba_solve_kernel(BaArgs A)
         const double* U = red + k * kBaRed;
         const double ci = sc[i];
         double di = st->diag_c[i];
-        if (st->refresh) { di = fmin(fmax(U[ba_upper6(a, a)] * ci * ci, A.P.lm.min_diag), A.P.lm.max_diag); st->diag_c[i] = di; }
+        if (st->tr.refresh) { di = fmin(fmax(U[upper6(a, a)] * ci * ci, A.P.lm.min_diag), A.P.lm.max_diag); st->diag_c[i] = di; }
         for (int j = 0; j < n; j++) {
             const int m = j / 6, b = j % 6;
-            double val = k == m ? U[ba_upper6(min(a, b), max(a, b))] : 0.0;
+            double val = k == m ? U[upper6(min(a, b), max(a, b))] : 0.0;
             const double e = k <= m ? A.sch[(size_t)ba_pair(k, m, nf) * 36 + a * 6 + b] : A.sch[(size_t)ba_pair(m, k, nf) * 36 + b * 6 + a];
             val -= e;
             S[i][j] = val * ci * sc[j];
@@ -664,7 +663,7 @@ ba_solve_kernel(BaArgs A)
         const int k = i / 6, a = i % 6;
         const double* U = red + k * kBaRed;
         double s = 0.0;
-        for (int b = 0; b < 6; b++) s += U[ba_upper6(min(a, b), max(a, b))] * sc[i] * sc[6 * k + b] * y[6 * k + b];
+        for (int b = 0; b < 6; b++) s += U[upper6(min(a, b), max(a, b))] * sc[i] * sc[6 * k + b] * y[6 * k + b];
         us[i] = s;
     }
     __syncthreads();
@@ -686,7 +685,7 @@ ba_solve_kernel(BaArgs A)
 ;
 #endif
 
-// ---- the B1 transition (the bookkeeping of tri_solve, on the reduced numbers) ---------------------------------------------------
+// ---- the B1 transition: velo_trust_region.h on the reduced numbers -------------------------------------------------------------
 // mode 0: after the first linearisation.  mode 1: after a candidate has been linearised and reduced.
 __global__ void __launch_bounds__(64)
 ba_decide_kernel(BaArgs A, int mode)
@@ -697,63 +696,38 @@ ba_decide_kernel(BaArgs A, int mode)
     const LMParams& Q = A.P.lm;
     const int nf = A.W.n_free, n = 6 * nf, stride = nf * kBaRed + kBaScalars;
     BaRecord& R = st->rec;
+    TrustRegion T = st->tr;
     auto gradient_max = [&](const double* red) {
         double g = red[nf * kBaRed + 4];
         for (int k = 0; k < nf; k++) for (int a = 0; a < 6; a++) g = fmax(g, fabs(red[k * kBaRed + 21 + a]));
         return g;
     };
+    R.candidate_cost = 0.0; R.model_change = 0.0; R.step_norm = 0.0;
     if (mode == 0) {
         const double* red = A.red + (size_t)st->cur * stride;
         double xn2 = 0.0;
         for (int r = 0; r < n; r++) { const double v = A.xc[((size_t)st->cur * A.W.n_frames + A.W.n_fixed) * 6 + r]; xn2 += v * v; }
         st->pose_xn2[st->cur] = xn2;
-        st->cost = red[nf * kBaRed]; st->initial_cost = st->cost;
-        st->x_norm = sqrt(xn2 + red[nf * kBaRed + 3]);
-        st->radius = Q.initial_radius; st->decrease = 2.0; st->refresh = 1; st->invalid = 0; st->iteration = 0;
-        for (int k = 0; k < nf; k++) for (int a = 0; a < 6; a++) st->scale_c[6 * k + a] = 1.0 / (1.0 + sqrt(red[k * kBaRed + ba_upper6(a, a)]));
-        R.evaluations = 1; R.iteration = 0; R.status = 0; R.cost = st->cost; R.candidate_cost = 0.0; R.radius = st->radius; R.model_change = 0.0; R.step_norm = 0.0;
-        R.done = 0; R.termination = VELO_NO_CONVERGENCE;
-        if (gradient_max(red) <= Q.gradient_tolerance) { R.done = 1; R.termination = VELO_CONVERGENCE; return; }
+        for (int k = 0; k < nf; k++) for (int a = 0; a < 6; a++) st->scale_c[6 * k + a] = 1.0 / (1.0 + sqrt(red[k * kBaRed + upper6(a, a)]));
+        tr_start(Q, &T, red[nf * kBaRed], sqrt(xn2 + red[nf * kBaRed + 3]), gradient_max(red));
+        R.iteration = 0; R.status = 0; R.cost = T.cost; R.radius = T.radius;
     } else {
         const int cand = st->cur ^ 1;
         const double* red = A.red + (size_t)cand * stride;
-        const int it = st->iteration;
-        R.iteration = it; R.cost = st->cost; R.radius = st->radius; R.candidate_cost = 0.0; R.model_change = 0.0; R.step_norm = 0.0;
+        R.iteration = T.iteration; R.cost = T.cost; R.radius = T.radius;
         const double model_change = -(st->pose_model + red[nf * kBaRed + 1]);
         const bool ok = st->step_ok != 0 && st->bad == 0 && model_change > 0.0 && isfinite(model_change);
-        if (!ok) {
-            R.status = VELO_BA_INVALID;
-            if (++st->invalid >= Q.max_invalid) { R.done = 1; R.termination = VELO_FAILURE; return; }
-            st->radius = st->radius / st->decrease; st->decrease *= 2.0; st->refresh = 0;
-        } else {
-            st->invalid = 0;
+        if (!ok) R.status = tr_invalid(Q, &T);
+        else {
             const double dn = sqrt(st->pose_dn2 + red[nf * kBaRed + 2]);
             const double cand_cost = red[nf * kBaRed];
-            R.evaluations++;
             R.candidate_cost = cand_cost; R.model_change = model_change; R.step_norm = dn;
-            if (dn <= Q.parameter_tolerance * (st->x_norm + Q.parameter_tolerance)) { R.status = VELO_BA_PARAMETER; R.done = 1; R.termination = VELO_CONVERGENCE; return; }
-            const double cost_change = st->cost - cand_cost;
-            if (fabs(cost_change) <= Q.function_tolerance * st->cost) { R.status = VELO_BA_FUNCTION; R.done = 1; R.termination = VELO_CONVERGENCE; return; }
-            const double q = cost_change / model_change;
-            if (q > Q.min_relative_decrease) {
-                st->cur = cand; st->n_accepted++;
-                st->cost = cand_cost;
-                st->x_norm = sqrt(st->pose_xn2[cand] + red[nf * kBaRed + 3]);
-                R.status = VELO_BA_ACCEPTED;
-                if (gradient_max(red) <= Q.gradient_tolerance) { R.status = VELO_BA_GRADIENT; R.done = 1; R.termination = VELO_CONVERGENCE; return; }
-                const double t = 2.0 * q - 1.0;
-                st->radius = fmin(Q.max_radius, st->radius / fmax(1.0 / 3.0, 1.0 - t * t * t));
-                st->decrease = 2.0; st->refresh = 1;
-            } else {
-                R.status = VELO_BA_REJECTED;
-                st->radius = st->radius / st->decrease; st->decrease *= 2.0; st->refresh = 0;
-            }
+            R.status = tr_candidate(Q, &T, cand_cost, model_change, dn);
+            if (R.status == VELO_BA_ACCEPTED) { st->cur = cand; R.status = tr_accept(Q, &T, sqrt(st->pose_xn2[cand] + red[nf * kBaRed + 3]), gradient_max(red)); }
         }
     }
-    // the head of the next iteration
-    if (st->iteration + 1 > Q.max_num_iterations) { R.done = 1; R.termination = VELO_NO_CONVERGENCE; return; }
-    if (st->radius < Q.min_radius) { R.done = 1; R.termination = VELO_CONVERGENCE; return; }
-    st->iteration++;
+    if (!T.done) tr_head(Q, &T);                                      // the head of the next iteration
+    R.done = T.done; R.termination = T.termination; R.evaluations = T.evaluations; st->tr = T;
 }
 #else
 ;

@@ -5,7 +5,7 @@
 // A node is the 6 doubles (angle-axis, translation) of a frame's world pose T; an edge (from, to, z, info) states T_to = T_from Z and
 // its residual is sqrt(info) * pose_vec(Z^-1 T_from^-1 T_to), the angle-axis of the rotation and then the translation (the form of
 // main.cpp:416-424).  Fixed nodes are constants.  The solver is the trust-region Levenberg-Marquardt of SURVEY.md B1 over the free
-// nodes; its linear step is a block-Jacobi preconditioned conjugate gradient on the damped, Jacobi-scaled normal equations
+// nodes (the controller of velo_trust_region.h, run by the host); its linear step is a block-Jacobi preconditioned conjugate gradient on the damped, Jacobi-scaled normal equations
 //     (c H c + D / mu) y = -c g,      H = J^T J block-sparse: a 6 x 6 diagonal block per free node, one off-diagonal block per edge,
 // whose matrix is never assembled: a product gathers, per node, the node's diagonal block and the A^T B block of every incident edge.
 //     graph_linearize_kernel  one thread per edge: residual, the two 6 x 6 Jacobians, A^T A, B^T B, A^T B, A^T r, B^T r, the cost term
@@ -80,7 +80,6 @@ struct GraphArgs {
     double* env;                                 // [blocks][36], row-major 6 x 6
 };
 
-__device__ __forceinline__ int graph_upper6(int a, int b) { return a * 6 - (a * (a - 1)) / 2 + (b - a); }      // a <= b
 __device__ __forceinline__ int graph_lower6(int i, int j) { return (i * (i + 1)) / 2 + j; }                      // j <= i
 
 // R(w) and the left Jacobian J_l(w), R(w + d) = Exp(J_l d) R(w) to first order: column j of J_l is the axial vector of (dR / dw_j) R^T,
@@ -264,8 +263,8 @@ graph_linearize_kernel(GraphArgs G, int which)
                 double aa = 0.0, bb = 0.0;
 #pragma unroll
                 for (int k = 0; k < 6; k++) { aa += A[k * 6 + a] * A[k * 6 + b]; bb += B[k * 6 + a] * B[k * 6 + b]; }
-                out[kGrAtA + graph_upper6(a, b)] = w * aa;
-                out[kGrBtB + graph_upper6(a, b)] = w * bb;
+                out[kGrAtA + upper6(a, b)] = w * aa;
+                out[kGrBtB + upper6(a, b)] = w * bb;
             }
         }
         double ar = 0.0, br = 0.0;
@@ -310,7 +309,7 @@ graph_assemble_kernel(GraphArgs G, int which, int mode)
     for (int a = 0; a < kGrNode; a++) out[a] = acc[a];
     if (mode == 0) {
 #pragma unroll
-        for (int a = 0; a < 6; a++) G.scale[(size_t)i * 6 + a] = 1.0 / (1.0 + sqrt(acc[graph_upper6(a, a)]));
+        for (int a = 0; a < 6; a++) G.scale[(size_t)i * 6 + a] = 1.0 / (1.0 + sqrt(acc[upper6(a, a)]));
     }
 }
 #else
@@ -394,7 +393,7 @@ __device__ __forceinline__ void graph_diag_mul(const double* H, const double c[6
     for (int a = 0; a < 6; a++) {
         double s = 0.0;
 #pragma unroll
-        for (int b = 0; b < 6; b++) s += H[graph_upper6(a < b ? a : b, a < b ? b : a)] * (c[b] * v[b]);
+        for (int b = 0; b < 6; b++) s += H[upper6(a < b ? a : b, a < b ? b : a)] * (c[b] * v[b]);
         out[a] = c[a] * s;
     }
 }
@@ -417,7 +416,7 @@ graph_cg_begin_kernel(GraphArgs G, int cur, double mu, int refresh)
 #pragma unroll
         for (int a = 0; a < 6; a++) {
 #pragma unroll
-            for (int bb = 0; bb < 6; bb++) M[a * 6 + bb] = nd[graph_upper6(a < bb ? a : bb, a < bb ? bb : a)] * c[a] * c[bb];
+            for (int bb = 0; bb < 6; bb++) M[a * 6 + bb] = nd[upper6(a < bb ? a : bb, a < bb ? bb : a)] * c[a] * c[bb];
         }
 #pragma unroll
         for (int a = 0; a < 6; a++) {
@@ -672,7 +671,7 @@ graph_env_fill_kernel(GraphArgs G, int cur, double mu, int refresh)
     for (int k = 0; k < w; k++) row[(size_t)k * 36 + l] = 0.0;
     const double* nd = G.nd + ((size_t)cur * G.n_free + node) * kGrNode;
     const double ca = G.scale[(size_t)node * 6 + a], cb = G.scale[(size_t)node * 6 + b];
-    double d = nd[graph_upper6(a < b ? a : b, a < b ? b : a)] * ca * cb;
+    double d = nd[upper6(a < b ? a : b, a < b ? b : a)] * ca * cb;
     if (a == b) {                                                      // D as the CG's M_i has it: clipped, refreshed on acceptance
         double dg = G.diag[(size_t)node * 6 + a];
         if (refresh) { dg = fmin(fmax(d, G.lm.min_diag), G.lm.max_diag); G.diag[(size_t)node * 6 + a] = dg; }

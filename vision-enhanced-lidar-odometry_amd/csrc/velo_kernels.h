@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "velo_device_math.h"
+#include "velo_trust_region.h"   // LMParams
 
 // ---- translation units (round 6) ---------------------------------------------------------------------------------------------------------
 // The library is built from several units compiled side by side (build.py): velo_hip.hip holds the host side of the C-ABI and DEFINES NO
@@ -3078,11 +3079,6 @@ __global__ void __launch_bounds__(128) visual_gate_batch_kernel(GateBatch G)
 
 // ---- LM state (row S1) ------------------------------------------------------------------------------------------------------
 enum { PHASE_INIT = 0, PHASE_CAND = 1 };
-struct LMParams {
-    int max_num_iterations, max_invalid;
-    double function_tolerance, gradient_tolerance, parameter_tolerance;
-    double initial_radius, max_radius, min_radius, min_relative_decrease, min_diag, max_diag;
-};
 struct LMState {
     double x[6];        // last accepted iterate (the reference's `transform`)
     double xc[6];       // candidate x + delta

@@ -125,31 +125,23 @@ __device__ __forceinline__ bool tri_chol3(const double A[9], const double b[3], 
     return isfinite(y[0]) && isfinite(y[1]) && isfinite(y[2]);
 }
 
-// Ceres' trust-region LM with default options, 3 unknowns -- the loop of the main path's lm_step.
+// Ceres' trust-region LM with default options, 3 unknowns: the damped 3 x 3 step here, the bookkeeping in velo_trust_region.h.
 // `eval(x, &E)` fills cost, J^T J, J^T r at x; with a wave-wide evaluation every lane runs this bookkeeping identically.
+__device__ __forceinline__ double tri_norm3(const double v[3]) { return sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
+__device__ __forceinline__ double tri_absmax3(const double v[3]) { return fmax(fmax(fabs(v[0]), fabs(v[1])), fabs(v[2])); }
+
 template <typename Eval>
 __device__ __forceinline__ void tri_solve(Eval&& eval, const TriParams& P, double x[3], velo_tri_result* S) {
     const LMParams& Q = P.lm;
     TriEval E;
     eval(x, &E);
-    S->evaluations++;
     S->n_solves++;
-    S->lm_iterations = 0;
-    double cost = E.cost;
-    S->final_cost = cost;
-    double x_norm = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-    if (fmax(fmax(fabs(E.g[0]), fabs(E.g[1])), fabs(E.g[2])) <= Q.gradient_tolerance) { S->termination = VELO_CONVERGENCE; return; }
+    TrustRegion T;
+    tr_start(Q, &T, E.cost, tri_norm3(x), tri_absmax3(E.g));
     double scale[3], diag[3] = {0.0, 0.0, 0.0};
 #pragma unroll
     for (int j = 0; j < 3; j++) scale[j] = 1.0 / (1.0 + sqrt(E.H[j * 3 + j]));
-    double radius = Q.initial_radius, decrease = 2.0;
-    bool reuse_diag = false;
-    int invalid = 0;
-    S->termination = VELO_NO_CONVERGENCE;
-    for (int it = 1;; it++) {
-        if (it > Q.max_num_iterations) { S->termination = VELO_NO_CONVERGENCE; break; }
-        if (radius < Q.min_radius) { S->termination = VELO_CONVERGENCE; break; }
-        S->lm_iterations = it;
+    while (!T.done && !tr_head(Q, &T)) {
         double Hs[9], gs[3], A[9];
 #pragma unroll
         for (int i = 0; i < 3; i++) {
@@ -157,17 +149,16 @@ __device__ __forceinline__ void tri_solve(Eval&& eval, const TriParams& P, doubl
 #pragma unroll
             for (int j = 0; j < 3; j++) Hs[i * 3 + j] = E.H[i * 3 + j] * scale[i] * scale[j];
         }
-        if (!reuse_diag) {
+        if (T.refresh) {
 #pragma unroll
             for (int j = 0; j < 3; j++) diag[j] = fmin(fmax(Hs[j * 3 + j], Q.min_diag), Q.max_diag);
         }
 #pragma unroll
         for (int i = 0; i < 9; i++) A[i] = Hs[i];
 #pragma unroll
-        for (int j = 0; j < 3; j++) { const double l = sqrt(diag[j] / radius); A[j * 3 + j] += l * l; }
+        for (int j = 0; j < 3; j++) { const double l = sqrt(diag[j] / T.radius); A[j * 3 + j] += l * l; }
         double y[3], step[3] = {0.0, 0.0, 0.0};
         bool ok = tri_chol3(A, gs, y);
-        reuse_diag = true;
         double model_change = 0.0;
         if (ok) {
             double gd = 0.0, dHd = 0.0;
@@ -182,37 +173,18 @@ __device__ __forceinline__ void tri_solve(Eval&& eval, const TriParams& P, doubl
             model_change = -(gd + 0.5 * dHd);
             if (!(model_change > 0.0)) ok = false;
         }
-        if (!ok) {
-            if (++invalid >= Q.max_invalid) { S->termination = VELO_FAILURE; break; }
-            radius = radius / decrease; decrease *= 2.0; reuse_diag = true;
-            continue;
-        }
-        invalid = 0;
-        double xc[3], dn = 0.0;
+        if (!ok) { tr_invalid(Q, &T); continue; }
+        double xc[3], d[3];
 #pragma unroll
-        for (int i = 0; i < 3; i++) { const double d = step[i] * scale[i]; xc[i] = x[i] + d; dn += d * d; }
-        dn = sqrt(dn);
+        for (int i = 0; i < 3; i++) { d[i] = step[i] * scale[i]; xc[i] = x[i] + d[i]; }
         TriEval Ec;
         eval(xc, &Ec);
-        S->evaluations++;
-        if (dn <= Q.parameter_tolerance * (x_norm + Q.parameter_tolerance)) { S->termination = VELO_CONVERGENCE; break; }
-        const double cost_change = cost - Ec.cost;
-        if (fabs(cost_change) <= Q.function_tolerance * cost) { S->termination = VELO_CONVERGENCE; break; }
-        const double q = cost_change / model_change;
-        if (q > Q.min_relative_decrease) {
-            x[0] = xc[0]; x[1] = xc[1]; x[2] = xc[2];
-            cost = Ec.cost; E = Ec;
-            x_norm = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-            if (fmax(fmax(fabs(E.g[0]), fabs(E.g[1])), fabs(E.g[2])) <= Q.gradient_tolerance) { S->termination = VELO_CONVERGENCE; break; }
-            const double t = 2.0 * q - 1.0;
-            radius = radius / fmax(1.0 / 3.0, 1.0 - t * t * t);
-            radius = fmin(Q.max_radius, radius);
-            decrease = 2.0; reuse_diag = false;
-        } else {
-            radius = radius / decrease; decrease *= 2.0; reuse_diag = true;
+        if (tr_candidate(Q, &T, Ec.cost, model_change, tri_norm3(d)) == VELO_BA_ACCEPTED) {
+            x[0] = xc[0]; x[1] = xc[1]; x[2] = xc[2]; E = Ec;
+            tr_accept(Q, &T, tri_norm3(x), tri_absmax3(E.g));
         }
     }
-    S->final_cost = cost;
+    S->lm_iterations = T.iteration; S->evaluations += T.evaluations; S->termination = T.termination; S->final_cost = T.cost;
 }
 
 __global__ void __launch_bounds__(64)
