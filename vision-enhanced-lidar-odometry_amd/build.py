@@ -26,7 +26,7 @@ SOURCES = {"velo_hip.hip": [], "velo_unit_load.hip": [], "velo_unit_assoc.hip": 
            "velo_unit_match.hip": [], "velo_unit_track.hip": [], "velo_unit_detect.hip": [], "velo_unit_landmarks.hip": [], "velo_unit_ba.hip": [], "velo_unit_graph.hip": [], "velo_unit_frames.hip": [], "velo_unit_map.hip": [], "velo_lm_ag.hip": ["-mllvm", "-disable-machine-licm"]}
 KERNEL_UNITS = ["velo_unit_load.hip", "velo_unit_assoc.hip", "velo_unit_lm_a.hip", "velo_unit_lm_b.hip", "velo_unit_match.hip",
                 "velo_unit_track.hip", "velo_unit_detect.hip", "velo_unit_landmarks.hip", "velo_unit_ba.hip", "velo_unit_graph.hip", "velo_unit_frames.hip", "velo_unit_map.hip", "velo_lm_ag.hip"]   # the units that hold device code (tools/kernel_resources.py)
-HEADERS = ["velo_kernels.h", "velo_lm_ag_kernels.h", "velo_depth_kernels.h", "velo_tri_kernels.h", "velo_match_kernels.h", "velo_track_kernels.h", "velo_detect_kernels.h", "velo_landmark_kernels.h", "velo_ba_kernels.h", "velo_graph_kernels.h", "velo_frame_kernels.h", "velo_map_kernels.h", "velo_device_math.h", "velo_trust_region.h", "velo_block_list.h", os.path.join(ROOT, "include", "velo_hip.h"),
+HEADERS = ["velo_kernels.h", "velo_lm_ag_kernels.h", "velo_depth_kernels.h", "velo_tri_kernels.h", "velo_match_kernels.h", "velo_track_kernels.h", "velo_detect_kernels.h", "velo_landmark_kernels.h", "velo_ba_kernels.h", "velo_graph_kernels.h", "velo_frame_kernels.h", "velo_map_kernels.h", "velo_device_math.h", "velo_trust_region.h", "velo_block_list.h", "velo_stage_layout.h", os.path.join(ROOT, "include", "velo_hip.h"),
            # the parts of the host side (velo_hip.hip includes them in this order: one translation unit)
            "velo_host_types.inl", "velo_host_index.inl", "velo_host_assoc.inl", "velo_host_lm.inl", "velo_host_loaders.inl", "velo_host_pool.inl",
            "velo_api_context.inl", "velo_api_solve.inl", "velo_host_chain.inl", "velo_host_batch.inl", "velo_api_pose_comm.inl", "velo_api_next_rows.inl",

@@ -30,7 +30,7 @@ int ba_check(velo_ctx* c, const int32_t* frames, int32_t n_frames, int32_t n_fix
     const int64_t n_free = (int64_t)n_frames - n_fixed;
     if (n_free < 1 || n_free > VELO_BA_MAX_FREE) return fail(VELO_ERR_INVALID, "%s: %lld free frames; 1..%d", who, (long long)n_free, VELO_BA_MAX_FREE);
     for (int i = 0; i < n_frames; i++) {
-        if (frames[i] < 0 || frames[i] >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "%s: frame %d; 0..%d", who, frames[i], kLmMaxFrame - 1);
+        VELO_TRY(check_frame(frames[i], who));
         if (i > 0 && frames[i] <= frames[i - 1]) return fail(VELO_ERR_INVALID, "%s: frames must be ascending and distinct (%d after %d)", who, frames[i], frames[i - 1]);
     }
     if (params && !(params->weight_3d > 0.0 && std::isfinite(params->weight_3d))) return fail(VELO_ERR_INVALID, "%s: weight_3d must be positive and finite", who);

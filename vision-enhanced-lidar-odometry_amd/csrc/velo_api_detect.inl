@@ -1,7 +1,7 @@
 // velo_api_detect.inl -- part of the host side of the C-ABI, included by velo_hip.hip (ONE translation unit; the order of the parts is the order of
 // definition).  C-ABI: GFTT corner detection on the current resident images (velo_detect_features[_batch]: detectFeatures,
 // velo.h:118-177; velo_get_corner_response); kernels in velo_detect_kernels.h.  One implementation over a list of contexts, which the
-// single-context entry hands a list of one (velo_api_track.inl says who lends what).
+// single-context entry hands a list of one (velo_api_track.inl says who lends what; the staged tables are laid out by a StageLayout).
 namespace {
 
 constexpr int kGfDetectUnits = 64;         // cameras per detection launch set (a call with more runs in chunks)
@@ -33,7 +33,7 @@ int gf_check_jobs(const velo_detect_job* jobs, int32_t n_jobs, int32_t capacity,
     for (int j = 0; j < n_jobs; j++) {
         if (jobs[j].n_existing < 0) return fail(VELO_ERR_INVALID, "job %d: negative point count %d", j, jobs[j].n_existing);
         if (jobs[j].n_existing > 0 && !jobs[j].existing_xy) return fail(VELO_ERR_INVALID, "job %d: null points", j);
-        if (jobs[j].cam < 0 || jobs[j].cam >= kLkMaxCams) return fail(VELO_ERR_INVALID, "job %d: camera %d; 0..%d", j, jobs[j].cam, kLkMaxCams - 1);
+        VELO_TRY(check_cam(jobs[j].cam, kLkMaxCams, "job", j));
         *total += jobs[j].n_existing;
     }
     if (n_jobs > 4096) return fail(VELO_ERR_INVALID, "%d jobs in one call; at most 4096", n_jobs);
@@ -81,18 +81,19 @@ int gf_run(velo_ctx** ctxs, int n_ctx, const std::vector<GfUnitRef>& units, int 
     K.md2f = (float)(p->min_distance * p->min_distance);
     int64_t total = 0;
     for (int k = 0; k < nj; k++) total += jobs[sel[k]].n_existing;
-    const size_t unit_bytes = fb_align64(sizeof(GfUnit) * (size_t)nu);
-    const size_t job_bytes = fb_align64(sizeof(GfJob) * (size_t)nj);
-    const size_t in_bytes = unit_bytes + job_bytes + sizeof(float2) * (size_t)total;
-    const size_t cnt_bytes = fb_align64(sizeof(int) * 3 * (size_t)nj);
     const size_t n_slots = (size_t)nj * cap_d;
-    const size_t out_bytes = cnt_bytes + n_slots * (sizeof(float2) + sizeof(float) + 1);
-    VELO_TRY(c->h_gf_in.reserve(in_bytes));
-    VELO_TRY(c->h_gf_out.reserve(out_bytes));
-    VELO_TRY(c->gf_in.reserve(in_bytes));
-    VELO_TRY(c->gf_out.reserve(out_bytes));
+    StageLayout in, out;
+    const auto gunits = in.add<GfUnit>((size_t)nu);
+    const auto gjobs = in.add<GfJob>((size_t)nj);
+    const auto have = in.add<float2>((size_t)total);
+    const auto cnt = out.add<int>(3 * (size_t)nj);
+    const auto oxy = out.add<float2>(n_slots);                   // on the line behind the counts; response and fresh packed behind it
+    const auto oresp = out.add<float>(n_slots, 4);
+    const auto ofresh = out.add<unsigned char>(n_slots, 1);
+    VELO_TRY(c->gf_in.reserve(in.bytes));
+    VELO_TRY(c->gf_out.reserve(out.bytes));
     {
-        GfUnit* hu = (GfUnit*)c->h_gf_in.p;
+        GfUnit* hu = gunits.in(c->gf_in.h.p);
         for (int u = 0; u < nu; u++) {
             const LkSlot& S = *lk_slot(ctxs[units[u0 + u].ctx], false);
             GfUnit& U = hu[u];
@@ -105,8 +106,8 @@ int gf_run(velo_ctx** ctxs, int n_ctx, const std::vector<GfUnitRef>& units, int 
             U.hdr = c->gf_hdr.p + (size_t)u * kGfHdrStride;
             U.w = S.w; U.h = S.h; U.stride = S.pyr.lv[0].stride; U.sstride = sstride[u];
         }
-        GfJob* hj = (GfJob*)(c->h_gf_in.p + unit_bytes);
-        float* hp = (float*)(c->h_gf_in.p + unit_bytes + job_bytes);
+        GfJob* hj = gjobs.in(c->gf_in.h.p);
+        float* hp = (float*)have.in(c->gf_in.h.p);
         int first = 0;
         for (int k = 0; k < nj; k++) {
             const velo_detect_job& J = jobs[sel[k]];
@@ -118,38 +119,36 @@ int gf_run(velo_ctx** ctxs, int n_ctx, const std::vector<GfUnitRef>& units, int 
     std::vector<char> used(n_ctx, 0);
     for (int u = 0; u < nu; u++) used[units[u0 + u].ctx] = 1;
     VELO_TRY(fb_gather(ctxs, n_ctx, &used));
-    HIP_TRY(hipMemcpyAsync(c->gf_in.p, c->h_gf_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->gf_in.d.p, c->gf_in.h.p, in.bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->gf_hdr.p, 0, sizeof(int) * kGfHdrStride * (size_t)nu, c->stream));
     HIP_TRY(hipMemsetAsync(c->gf_state.p, 0, t_state, c->stream));                          // the zero border of the state maps
-    HIP_TRY(hipMemsetAsync(c->gf_out.p, 0, cnt_bytes, c->stream));
-    const GfUnit* d_units = (const GfUnit*)c->gf_in.p;
+    HIP_TRY(hipMemsetAsync(c->gf_out.d.p, 0, oxy.off, c->stream));                          // the counts, up to the line xy starts on
+    const GfUnit* d_units = gunits.in(c->gf_in.d.p);
     hipLaunchKernelGGL(gf_response_kernel, dim3((unsigned)cdiv(max_w, kGfTile), (unsigned)cdiv(max_h, kGfTile), (unsigned)nu), dim3(kGfTile * kGfTile), 0,
                        c->stream, d_units, K);
     hipLaunchKernelGGL(gf_candidates_kernel, dim3((unsigned)cdiv(max_w, 64), (unsigned)cdiv(max_h, 4), (unsigned)nu), dim3(256), 0, c->stream, d_units, K);
     for (int r = 0; r < kGfRoundLaunches; r++)
         hipLaunchKernelGGL(gf_round_kernel, dim3(kGfRoundBlocks, (unsigned)nu), dim3(256), 0, c->stream, d_units, K);
     hipLaunchKernelGGL(gf_finish_kernel, dim3((unsigned)nu), dim3(kGfFinishThreads), 0, c->stream, d_units, K);
-    int* d_counts = (int*)c->gf_out.p;
-    float2* d_xy = (float2*)(c->gf_out.p + cnt_bytes);
-    float* d_resp = (float*)(c->gf_out.p + cnt_bytes + n_slots * sizeof(float2));
-    unsigned char* d_fresh = c->gf_out.p + cnt_bytes + n_slots * (sizeof(float2) + sizeof(float));
-    hipLaunchKernelGGL(gf_output_kernel, dim3(kGfOutBlocks, (unsigned)nj), dim3(256), 0, c->stream, d_units, K, (const GfJob*)(c->gf_in.p + unit_bytes),
-                       (const float2*)(c->gf_in.p + unit_bytes + job_bytes), d_counts, d_xy, d_resp, d_fresh);
+    void* dout = c->gf_out.d.p;
+    hipLaunchKernelGGL(gf_output_kernel, dim3(kGfOutBlocks, (unsigned)nj), dim3(256), 0, c->stream, d_units, K, (const GfJob*)gjobs.in(c->gf_in.d.p),
+                       (const float2*)have.in(c->gf_in.d.p), cnt.in(dout), oxy.in(dout), oresp.in(dout), ofresh.in(dout));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_gf_out.p, c->gf_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->gf_out.h.p, c->gf_out.d.p, out.bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->gf_units = nu;
-    const int* h_counts = (const int*)c->h_gf_out.p;
-    const unsigned char* h_xy = c->h_gf_out.p + cnt_bytes;
-    const unsigned char* h_resp = h_xy + n_slots * sizeof(float2);
-    const unsigned char* h_fresh = h_resp + n_slots * sizeof(float);
+    const void* hout = c->gf_out.h.p;
+    const int* h_counts = cnt.in(hout);
+    const float2* h_xy = oxy.in(hout);
+    const float* h_resp = oresp.in(hout);
+    const unsigned char* h_fresh = ofresh.in(hout);
     for (int k = 0; k < nj; k++) {
         const size_t j = (size_t)sel[k];
         std::memcpy(counts + 3 * j, h_counts + 3 * k, sizeof(int) * 3);
         const size_t m = (size_t)std::min(h_counts[3 * k], cap_d);            // what lies past it in the caller's arrays stays as it was
         if (m == 0) continue;
-        std::memcpy(xy + 2 * j * capacity, h_xy + sizeof(float2) * (size_t)k * cap_d, sizeof(float2) * m);
-        std::memcpy(response + j * capacity, h_resp + sizeof(float) * (size_t)k * cap_d, sizeof(float) * m);
+        std::memcpy(xy + 2 * j * capacity, h_xy + (size_t)k * cap_d, sizeof(float2) * m);
+        std::memcpy(response + j * capacity, h_resp + (size_t)k * cap_d, sizeof(float) * m);
         std::memcpy(fresh + j * capacity, h_fresh + (size_t)k * cap_d, m);
     }
     return VELO_OK;
@@ -224,9 +223,10 @@ int velo_get_corner_response(velo_ctx* c, int32_t cam, float* out, int64_t capac
     // a table of one unit whose only live fields are the image, the map and the header (the response kernel reads nothing else)
     VELO_TRY(c->gf_eig.reserve((size_t)S.w * S.h));
     VELO_TRY(c->gf_hdr.reserve(kGfHdrStride));
-    VELO_TRY(c->h_gf_in.reserve(sizeof(GfUnit)));
-    VELO_TRY(c->gf_in.reserve(sizeof(GfUnit)));
-    GfUnit& U = *(GfUnit*)c->h_gf_in.p;
+    StageLayout in;
+    const auto unit = in.add<GfUnit>(1);
+    VELO_TRY(c->gf_in.reserve(in.bytes));
+    GfUnit& U = *unit.in(c->gf_in.h.p);
     std::memset(&U, 0, sizeof(U));
     U.plane = S.pix.p + (size_t)cam * S.cam_pix + S.pyr.lv[0].off;
     U.eig = c->gf_eig.p;
@@ -235,11 +235,11 @@ int velo_get_corner_response(velo_ctx* c, int32_t cam, float* out, int64_t capac
     GfParams K;
     std::memset(&K, 0, sizeof(K));
     K.scale2 = gf_scale2();
-    HIP_TRY(hipMemcpyAsync(c->gf_in.p, c->h_gf_in.p, sizeof(GfUnit), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->gf_in.d.p, c->gf_in.h.p, in.bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->gf_hdr.p, 0, sizeof(int) * kGfHdrStride, c->stream));
     c->gf_units = 1;
     hipLaunchKernelGGL(gf_response_kernel, dim3((unsigned)cdiv(S.w, kGfTile), (unsigned)cdiv(S.h, kGfTile), 1), dim3(kGfTile * kGfTile), 0, c->stream,
-                       (const GfUnit*)c->gf_in.p, K);
+                       (const GfUnit*)unit.in(c->gf_in.d.p), K);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, c->gf_eig.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -52,9 +52,8 @@ struct FrStore {
     struct RowEntry { Block blk; int n = 0; };
     std::unordered_map<int64_t, RowEntry> rdir;
     PinStage put_stage, rows_stage;                 // staging of velo_frames_put and of velo_frames_put_descriptors
-    // staging of velo_build_matches (a batch call uses the first context's); every call ends in a synchronisation, so nothing guards it
-    PinBuf<> h_in, h_out;
-    DevBuf<unsigned char> d_in, d_out;
+    // staging of the launch sets (a batch call uses the first context's), laid out call by call (velo_stage_layout.h); every call ends in a synchronisation, so nothing guards it
+    StagePair in, out;
     DevBuf<unsigned char> d_prune;                  // scratch of a prune call: the keep maps | the gathered blocks | the gathered rows
     // scratch of a frame put with its depth: the call's upload (tables | ring offsets | block images | rows) | every unit's stacks, points, flags, records
     DevBuf<unsigned char> d_depth;
@@ -68,6 +67,14 @@ constexpr size_t kFrAlign = 16;                                 // words: every 
 constexpr size_t kFrDefaultRows = (1u << 20) / 64;              // rows
 
 inline size_t fr_round(size_t words) { return (words + kFrAlign - 1) / kFrAlign * kFrAlign; }
+
+// the units of a call cut into chunks of kFrChunk keypoints, unit after unit: unit u owns the chunks [chunk0[u], chunk0[u + 1])
+struct FrChunks {
+    std::vector<int> chunk0{0};
+    int n_chunks = 0, max_chunks = 0;
+    void add(int n) { max_chunks = std::max(max_chunks, cdiv(n, kFrChunk)); n_chunks += cdiv(n, kFrChunk); chunk0.push_back(n_chunks); }
+    int of(int u) const { return chunk0[(size_t)u + 1] - chunk0[(size_t)u]; }
+};
 
 int fr_need_store(velo_ctx* c, const char* who) {
     if (!c->fr) return fail(VELO_ERR_STATE, "%s: velo_frames_reset has not run on this context", who);
@@ -153,8 +160,7 @@ int fr_check_build_args(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, cons
     if (capacity < 0) return fail(VELO_ERR_INVALID, "negative capacity");
     if (match_thresh && std::isnan(*match_thresh)) return fail(VELO_ERR_INVALID, "match_thresh is NaN");
     for (int i = 0; i < n_ctx; i++)
-        for (int f : {frames1[i], frames2[i]})
-            if (f < 0 || f >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "context %d: frame %d; 0..%d", i, f, kLmMaxFrame - 1);
+        for (int f : {frames1[i], frames2[i]}) VELO_TRY(check_frame(f, "context", i));
     if (pose2_inv)
         for (int k = 0; k < 16 * n_ctx; k++) if (!std::isfinite(pose2_inv[k])) return fail(VELO_ERR_INVALID, "context %d: pose2_inv[%d] is not finite", k / 16, k % 16);
     return fb_check_devices(ctxs, n_ctx);
@@ -174,19 +180,17 @@ int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32
     FrStore* L = c0->fr.get();
     HIP_TRY(hipSetDevice(c0->device));
     // the units of the call, context-major and camera-major, and every context's share of the outputs
-    int n_units = 0, n_chunks = 0, max_n1 = 0, max_chunks = 0;
+    int n_units = 0, max_n1 = 0;
     size_t all_n2 = 0;
-    std::vector<int> unit0(n_ctx + 1, 0), chunk0;
+    std::vector<int> unit0(n_ctx + 1, 0);
+    FrChunks ck;
     std::vector<size_t> pair0(n_ctx + 1, 0);
     for (int i = 0; i < n_ctx; i++) {
         const FrStore& S = *ctxs[i]->fr;
         for (int cam = 0; cam < S.n_cams; cam++) {
             const FrStore::Entry& e1 = S.dir.at(lm_key(frames1[i], cam));
             const FrStore::Entry& e2 = S.dir.at(lm_key(frames2[i], cam));
-            const int ch = cdiv(e2.n, kFrChunk);
-            chunk0.push_back(n_chunks);
-            n_chunks += ch;
-            max_chunks = std::max(max_chunks, ch);
+            ck.add(e2.n);
             max_n1 = std::max(max_n1, e1.n);
             all_n2 += (size_t)e2.n;
             n_units++;
@@ -194,7 +198,6 @@ int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32
         unit0[i + 1] = n_units;
         pair0[i + 1] = all_n2;
     }
-    chunk0.push_back(n_chunks);
     // room: slot tables, the visual sets, the staging
     std::vector<char> refill(n_ctx, 0);
     for (int i = 0; i < n_ctx; i++) {
@@ -213,20 +216,19 @@ int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32
         if (S.slots_dirty) refill[i] = 1;
         VELO_TRY(fr_reserve_visual(c, pair0[i + 1] - pair0[i]));
     }
-    const size_t unit_bytes = fb_align64(sizeof(FrUnit) * (size_t)n_units);
-    const size_t in_bytes = unit_bytes + sizeof(FrCtx) * (size_t)n_ctx;
-    const size_t cnt_bytes = fb_align64(sizeof(int) * (size_t)n_chunks);
-    const size_t out_bytes = cnt_bytes + sizeof(int) * 2 * all_n2;
-    VELO_TRY(L->h_in.reserve(in_bytes));
-    VELO_TRY(L->h_out.reserve(std::max<size_t>(out_bytes, 64)));
-    VELO_TRY(L->d_in.reserve(in_bytes));
-    VELO_TRY(L->d_out.reserve(std::max<size_t>(out_bytes, 64)));
-    int* d_counts = (int*)L->d_out.p;
-    int* d_pairs = (int*)(L->d_out.p + cnt_bytes);
+    StageLayout in, out;
+    const auto units = in.add<FrUnit>((size_t)n_units);
+    const auto kctx = in.add<FrCtx>((size_t)n_ctx);
+    const auto counts = out.add<int>((size_t)ck.n_chunks);
+    const auto pairs = out.add<int>(2 * all_n2);
+    VELO_TRY(L->in.reserve(in.bytes));
+    VELO_TRY(L->out.reserve(std::max<size_t>(out.bytes, 64)));
+    int* d_counts = counts.in(L->out.d.p);
+    int* d_pairs = pairs.in(L->out.d.p);
     {
-        FrUnit* hu = (FrUnit*)L->h_in.p;
-        FrCtx* hc = (FrCtx*)(L->h_in.p + unit_bytes);
-        std::memset(L->h_in.p, 0, in_bytes);
+        FrUnit* hu = units.in(L->in.h.p);
+        FrCtx* hc = kctx.in(L->in.h.p);
+        std::memset(L->in.h.p, 0, in.bytes);
         for (int i = 0; i < n_ctx; i++) {
             velo_ctx* c = ctxs[i];
             const FrStore& S = *c->fr;
@@ -237,8 +239,8 @@ int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32
                 U.slots = S.slots.p + (size_t)cam * S.slot_ids;
                 U.slot_ids = (int)S.slot_ids;
                 U.ctx = i; U.cam = cam;
-                U.chunk0 = chunk0[(size_t)(unit0[i] + cam)];
-                U.ctx_chunk0 = chunk0[(size_t)unit0[i]];
+                U.chunk0 = ck.chunk0[(size_t)(unit0[i] + cam)];
+                U.ctx_chunk0 = ck.chunk0[(size_t)unit0[i]];
                 for (int k = 0; k < 3; k++) U.t_cam[k] = S.cam_t[3 * cam + k];
             }
             fr_fill_ctx(c, i, d_pairs + 2 * pair0[i], pose2_inv, &hc[i]);
@@ -252,21 +254,21 @@ int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32
         S.slots_dirty = true;                                        // until the clear launch is known to have run
         VELO_TRY(fr_clear_vflags(ctxs[i], pair0[i + 1] - pair0[i], st));
     }
-    HIP_TRY(hipMemcpyAsync(L->d_in.p, L->h_in.p, in_bytes, hipMemcpyHostToDevice, st));
-    const FrUnit* d_units = (const FrUnit*)L->d_in.p;
-    const FrCtx* d_ctxs = (const FrCtx*)(L->d_in.p + unit_bytes);
-    if (n_chunks > 0) {
-        const dim3 g1((unsigned)std::max(cdiv(max_n1, 256), 1), (unsigned)n_units), g2((unsigned)max_chunks, (unsigned)n_units);
+    HIP_TRY(hipMemcpyAsync(L->in.d.p, L->in.h.p, in.bytes, hipMemcpyHostToDevice, st));
+    const FrUnit* d_units = units.in(L->in.d.p);
+    const FrCtx* d_ctxs = kctx.in(L->in.d.p);
+    if (ck.n_chunks > 0) {
+        const dim3 g1((unsigned)std::max(cdiv(max_n1, 256), 1), (unsigned)n_units), g2((unsigned)ck.max_chunks, (unsigned)n_units);
         if (max_n1 > 0) hipLaunchKernelGGL(fr_fill_kernel, g1, dim3(256), 0, st, d_units);
         hipLaunchKernelGGL(fr_count_kernel, g2, dim3(kFrChunk), 0, st, d_units, d_counts);
         hipLaunchKernelGGL(fr_emit_kernel, g2, dim3(kFrChunk), 0, st, d_units, d_ctxs, (const int*)d_counts);
         if (max_n1 > 0) hipLaunchKernelGGL(fr_clear_kernel, g1, dim3(256), 0, st, d_units);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(L->h_out.p, L->d_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(L->out.h.p, L->out.d.p, out.bytes, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
-    const int* h_counts = (const int*)L->h_out.p;
-    const int* h_pairs = (const int*)(L->h_out.p + cnt_bytes);
+    const int* h_counts = counts.in(L->out.h.p);
+    const int* h_pairs = pairs.in(L->out.h.p);
     for (int i = 0; i < n_ctx; i++) {
         FrStore& S = *ctxs[i]->fr;
         S.slots_dirty = false;
@@ -274,7 +276,7 @@ int fr_build_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32
         for (int cam = 0; cam < S.n_cams; cam++) {
             const int u = unit0[i] + cam;
             per_cam[cam] = 0;
-            for (int k = chunk0[(size_t)u]; k < chunk0[(size_t)u + 1]; k++) per_cam[cam] += h_counts[k];
+            for (int k = ck.chunk0[(size_t)u]; k < ck.chunk0[(size_t)u + 1]; k++) per_cam[cam] += h_counts[k];
         }
         fr_leave_visual(ctxs[i], i, per_cam, h_pairs + 2 * pair0[i], n_per_cam, pairs_out, capacity, n_out);
         fr_stamp_visual(ctxs[i], frames1[i]);
@@ -343,26 +345,27 @@ int fr_desc_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32_
     // room: the visual sets, the staging
     if (build)
         for (int i = 0; i < n_ctx; i++) VELO_TRY(fr_reserve_visual(ctxs[i], pair0[i + 1] - pair0[i]));
-    // device input: jobs | units | contexts; device output: the filter's four arrays | the records' pairs, context after context
-    const size_t job_bytes = fb_align64(sizeof(MatchResJob) * (size_t)n_jobs);
-    const size_t unit_bytes = build ? fb_align64(sizeof(FrDescUnit) * (size_t)n_jobs) : 0;
-    const size_t in_bytes = job_bytes + unit_bytes + (build ? sizeof(FrCtx) * (size_t)n_ctx : 0);
-    const size_t filt_ints = 4 * (size_t)nq + 2 * (size_t)n_jobs;
-    const size_t back_ints = 2 * (size_t)n_jobs + (build ? 2 * (size_t)nq : 0);          // {min_dist, n_kept} per job | pairs: what comes back
-    const size_t out_bytes = sizeof(int) * (filt_ints + (build ? 2 * (size_t)nq : 0));
-    VELO_TRY(L->h_in.reserve(in_bytes));
-    VELO_TRY(L->h_out.reserve(sizeof(int) * back_ints));
-    VELO_TRY(L->d_in.reserve(in_bytes));
-    VELO_TRY(L->d_out.reserve(out_bytes));
+    // device input: jobs | units | contexts; device output: the filter's four arrays, ONE part that the filter kernel lays out
+    // itself (4 nq + 2 j) | the records' pairs, context after context, packed behind it
+    StageLayout in, out;
+    const auto mjobs = in.add<MatchResJob>((size_t)n_jobs);
+    const auto units = in.add<FrDescUnit>(build ? (size_t)n_jobs : 0);
+    const auto kctx = in.add<FrCtx>(build ? (size_t)n_ctx : 0);
+    const auto filt = out.add<int>(4 * (size_t)nq + 2 * (size_t)n_jobs);
+    const auto pairs = out.add<int>(build ? 2 * (size_t)nq : 0, 4);
+    const size_t back_ints = 2 * (size_t)n_jobs + pairs.n;                               // {min_dist, n_kept} per job | pairs: what comes back
+    VELO_TRY(L->in.reserve(in.bytes));
+    VELO_TRY(L->out.h.reserve(sizeof(int) * back_ints));
+    VELO_TRY(L->out.d.reserve(out.bytes));
     VELO_TRY(L->d_keys.reserve((size_t)nq + (size_t)n_jobs));
-    int* d_filt = (int*)L->d_out.p;
+    int* d_filt = filt.in(L->out.d.p);
     int* d_job_out = d_filt + 4 * (size_t)nq;
-    int* d_pairs = d_filt + filt_ints;
-    std::memset(L->h_in.p, 0, in_bytes);
-    std::memcpy(L->h_in.p, jobs.data(), sizeof(MatchResJob) * (size_t)n_jobs);
+    int* d_pairs = pairs.in(L->out.d.p);
+    std::memset(L->in.h.p, 0, in.bytes);
+    std::memcpy(mjobs.in(L->in.h.p), jobs.data(), mjobs.size());
     if (build) {
-        FrDescUnit* hu = (FrDescUnit*)(L->h_in.p + job_bytes);
-        FrCtx* hc = (FrCtx*)(L->h_in.p + job_bytes + unit_bytes);
+        FrDescUnit* hu = units.in(L->in.h.p);
+        FrCtx* hc = kctx.in(L->in.h.p);
         for (int i = 0; i < n_ctx; i++) {
             velo_ctx* c = ctxs[i];
             const FrStore& S = *c->fr;
@@ -383,9 +386,9 @@ int fr_desc_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32_
     if (build)
         for (int i = 0; i < n_ctx; i++) VELO_TRY(fr_clear_vflags(ctxs[i], pair0[i + 1] - pair0[i], st));
     if (n_jobs > 0) {
-        HIP_TRY(hipMemcpyAsync(L->d_in.p, L->h_in.p, in_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(L->in.d.p, L->in.h.p, in.bytes, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(L->d_keys.p, 0xFF, sizeof(unsigned) * ((size_t)nq + (size_t)n_jobs), st));   // kMatchNone
-        const MatchResJob* d_jobs = (const MatchResJob*)L->d_in.p;
+        const MatchResJob* d_jobs = mjobs.in(L->in.d.p);
         unsigned* keys = L->d_keys.p;
         unsigned* dmin = L->d_keys.p + nq;
         if (blocks > 0)
@@ -394,13 +397,13 @@ int fr_desc_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames1, const int32_
                            (const unsigned*)dmin, match_thresh, nq, d_filt);
         if (build && max_nq > 0)
             hipLaunchKernelGGL(fr_emit_desc_kernel, dim3((unsigned)cdiv(max_nq, 256), (unsigned)n_jobs), dim3(256), 0, st,
-                               (const FrDescUnit*)(L->d_in.p + job_bytes), (const FrCtx*)(L->d_in.p + job_bytes + unit_bytes),
+                               (const FrDescUnit*)units.in(L->in.d.p), (const FrCtx*)kctx.in(L->in.d.p),
                                (const int*)d_job_out, (const int*)(d_filt + 2 * (size_t)nq));
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(L->h_out.p, d_job_out, sizeof(int) * back_ints, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(L->out.h.p, d_job_out, sizeof(int) * back_ints, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
-    const int* h_job = (const int*)L->h_out.p;
+    const int* h_job = (const int*)L->out.h.p;
     if (!build) {
         for (int j = 0; j < n_jobs; j++) { min_d[j] = h_job[2 * j]; kept[j] = h_job[2 * j + 1]; }
         return VELO_OK;
@@ -453,9 +456,11 @@ int fr_prune_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, int keep_cam
     std::vector<FrStore::Entry*> ent;
     std::vector<FrStore::RowEntry*> rent;
     std::vector<Span> span;
-    std::vector<int> unit0(n_ctx + 1, 0), chunk0;
-    size_t map_bytes = 0, out_words = 0, row_count = 0, all_n = 0;
-    int n_chunks = 0, max_chunks = 0, max_src = by_list ? (int)n_keep : 0;
+    std::vector<int> unit0(n_ctx + 1, 0);
+    FrChunks ck;
+    StageLayout maps;                                                // every unit's keep map on a 64-byte line of its own
+    size_t out_words = 0, row_count = 0, all_n = 0;
+    int max_src = by_list ? (int)n_keep : 0;
     for (int i = 0; i < n_ctx; i++) {
         FrStore& S = *ctxs[i]->fr;
         for (int cam = by_list ? keep_cam : 0; cam < (by_list ? keep_cam + 1 : S.n_cams); cam++) {
@@ -463,12 +468,8 @@ int fr_prune_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, int keep_cam
             auto r = S.rdir.find(lm_key(frames[i], cam));
             ent.push_back(&e);
             rent.push_back(r != S.rdir.end() ? &r->second : nullptr);
-            span.push_back(Span{map_bytes, out_words, row_count, all_n});
-            chunk0.push_back(n_chunks);
-            const int ch = cdiv(e.n, kFrChunk);
-            n_chunks += ch;
-            max_chunks = std::max(max_chunks, ch);
-            map_bytes += fb_align64((size_t)e.n);
+            span.push_back(Span{maps.add<unsigned char>((size_t)e.n).off, out_words, row_count, all_n});
+            ck.add(e.n);
             out_words += fr_round(7 * (size_t)e.n);                  // at most n kept, every one with a depth point of its own
             if (r != S.rdir.end()) row_count += (size_t)e.n;
             all_n += (size_t)e.n;
@@ -476,31 +477,32 @@ int fr_prune_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, int keep_cam
         unit0[i + 1] = (int)ent.size();
         if (!by_list) max_src = std::max(max_src, ctxs[i]->n_matches);
     }
-    chunk0.push_back(n_chunks);
     const int n_units = (int)ent.size();
     // device input: units | sources | the keep list; device output, copied back in one piece: the chunk counts | the kept indices
-    const size_t unit_bytes = fb_align64(sizeof(FrPruneUnit) * (size_t)n_units), src_bytes = fb_align64(sizeof(FrPruneSrc) * (size_t)n_ctx);
-    const size_t in_bytes = unit_bytes + src_bytes + sizeof(int) * (size_t)(by_list ? n_keep : 0);
-    const size_t cnt_bytes = fb_align64(sizeof(int) * (size_t)n_chunks);
-    const size_t back_bytes = cnt_bytes + sizeof(int) * all_n;
-    const size_t scratch = map_bytes + sizeof(int) * out_words + 64 * row_count;
-    VELO_TRY(L->h_in.reserve(in_bytes));
-    VELO_TRY(L->h_out.reserve(std::max<size_t>(back_bytes, 64)));
-    VELO_TRY(L->d_in.reserve(in_bytes));
-    VELO_TRY(L->d_out.reserve(std::max<size_t>(back_bytes, 64)));
-    if (scratch > L->d_prune.cap) {                                     // geometric, and kept
+    StageLayout in, out, scratch;                                    // (the scratch: keep maps in whole lines | gathered blocks | gathered rows)
+    const auto units = in.add<FrPruneUnit>((size_t)n_units);
+    const auto srcs = in.add<FrPruneSrc>((size_t)n_ctx);
+    const auto keep = in.add<int>((size_t)(by_list ? n_keep : 0));
+    const auto counts = out.add<int>((size_t)ck.n_chunks);
+    const auto kept = out.add<int>(all_n);
+    const auto smap = scratch.add<unsigned char>(maps.align(64));
+    const auto sblocks = scratch.add<int>(out_words);
+    const auto srows = scratch.add<uint4>(4 * row_count);
+    VELO_TRY(L->in.reserve(in.bytes));
+    VELO_TRY(L->out.reserve(std::max<size_t>(out.bytes, 64)));
+    if (scratch.bytes > L->d_prune.cap) {                               // geometric, and kept
         HIP_TRY(hipStreamSynchronize(c0->stream));                       // the copies of the call before may still read the old scratch
-        VELO_TRY(L->d_prune.reserve(std::max(scratch, 2 * L->d_prune.cap)));
+        VELO_TRY(L->d_prune.reserve(std::max(scratch.bytes, 2 * L->d_prune.cap)));
     }
-    unsigned char* d_map = L->d_prune.p;
-    int* d_blocks = (int*)(L->d_prune.p + map_bytes);
-    uint4* d_rows = (uint4*)(L->d_prune.p + map_bytes + sizeof(int) * out_words);
-    int* d_counts = (int*)L->d_out.p;
-    int* d_kept = (int*)(L->d_out.p + cnt_bytes);
+    unsigned char* d_map = smap.in(L->d_prune.p);
+    int* d_blocks = sblocks.in(L->d_prune.p);
+    uint4* d_rows = srows.in(L->d_prune.p);
+    int* d_counts = counts.in(L->out.d.p);
+    int* d_kept = kept.in(L->out.d.p);
     {
-        FrPruneUnit* hu = (FrPruneUnit*)L->h_in.p;
-        FrPruneSrc* hs = (FrPruneSrc*)(L->h_in.p + unit_bytes);
-        std::memset(L->h_in.p, 0, in_bytes);
+        FrPruneUnit* hu = units.in(L->in.h.p);
+        FrPruneSrc* hs = srcs.in(L->in.h.p);
+        std::memset(L->in.h.p, 0, in.bytes);
         for (int i = 0; i < n_ctx; i++) {
             velo_ctx* c = ctxs[i];
             const FrStore& S = *c->fr;
@@ -512,44 +514,44 @@ int fr_prune_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, int keep_cam
                 U.out = d_blocks + span[u].out;
                 U.rows_out = d_rows + 4 * span[u].rows;
                 U.kept = d_kept + span[u].kept;
-                U.chunk0 = chunk0[(size_t)u]; U.n_chunks = chunk0[(size_t)u + 1] - chunk0[(size_t)u];
+                U.chunk0 = ck.chunk0[(size_t)u]; U.n_chunks = ck.of(u);
             }
             FrPruneSrc& R = hs[i];
             R.unit0 = unit0[i]; R.n_cams = unit0[i + 1] - unit0[i];
             if (by_list) {
-                R.keep = (const int*)(L->d_in.p + unit_bytes + src_bytes); R.n = n_keep;
-                if (n_keep > 0) std::memcpy(L->h_in.p + unit_bytes + src_bytes, keep_idx, sizeof(int) * (size_t)n_keep);
+                R.keep = keep.in(L->in.d.p); R.n = n_keep;
+                if (n_keep > 0) std::memcpy(keep.in(L->in.h.p), keep_idx, keep.size());
             } else { R.vm = c->vm.p; R.vflags = c->vflags.p; R.n = c->n_matches; }
         }
     }
     VELO_TRY(fb_gather(ctxs, n_ctx, nullptr));
     hipStream_t st = c0->stream;
-    if (n_chunks > 0) {
-        HIP_TRY(hipMemcpyAsync(L->d_in.p, L->h_in.p, in_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(d_map, 0, map_bytes, st));
-        const FrPruneUnit* d_units = (const FrPruneUnit*)L->d_in.p;
-        const dim3 g((unsigned)max_chunks, (unsigned)n_units);
+    if (ck.n_chunks > 0) {
+        HIP_TRY(hipMemcpyAsync(L->in.d.p, L->in.h.p, in.bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_map, 0, smap.size(), st));
+        const FrPruneUnit* d_units = units.in(L->in.d.p);
+        const dim3 g((unsigned)ck.max_chunks, (unsigned)n_units);
         if (max_src > 0)
             hipLaunchKernelGGL(fr_mark_kernel, dim3((unsigned)cdiv(max_src, 256), (unsigned)n_ctx), dim3(256), 0, st, d_units,
-                               (const FrPruneSrc*)(L->d_in.p + unit_bytes));
+                               (const FrPruneSrc*)srcs.in(L->in.d.p));
         hipLaunchKernelGGL(fr_prune_count_kernel, g, dim3(kFrChunk), 0, st, d_units, d_counts);
         hipLaunchKernelGGL(fr_prune_move_kernel, g, dim3(kFrChunk), 0, st, d_units, (const int*)d_counts);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(L->h_out.p, L->d_out.p, back_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(L->out.h.p, L->out.d.p, out.bytes, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
     // The host now knows every unit's new size: it places the block (in place unless shared depth points made the cloud longer than the
     // block holds) and queues the copies out of the scratch behind the launches -- the only writes into an arena.  A unit's directory
     // entry changes after the last call of that unit that can fail.
-    const int* h_counts = (const int*)L->h_out.p;
-    const int* h_kept = (const int*)(L->h_out.p + cnt_bytes);
+    const int* h_counts = counts.in(L->out.h.p);
+    const int* h_kept = kept.in(L->out.h.p);
     for (int i = 0; i < n_ctx; i++) {
         velo_ctx* c = ctxs[i];
         FrStore& S = *c->fr;
         int total = 0;
         for (int u = unit0[i]; u < unit0[i + 1]; u++) {
             int m = 0, m_wd = 0;
-            for (int k = chunk0[(size_t)u]; k < chunk0[(size_t)u + 1]; k++) { m += h_counts[k] & 0xffff; m_wd += h_counts[k] >> 16; }
+            for (int k = ck.chunk0[(size_t)u]; k < ck.chunk0[(size_t)u + 1]; k++) { m += h_counts[k] & 0xffff; m_wd += h_counts[k] >> 16; }
             FrStore::Entry& e = *ent[u];
             const size_t words = 4 * (size_t)m + 3 * (size_t)m_wd;
             BlockList::Plan plan;
@@ -638,11 +640,12 @@ int fr_put_frame_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, const in
     // where everything lies: the upload (units | every context's ring offsets | every unit's block image | its rows) and, behind it in
     // the same device buffer, every unit's share of the scratch.  A unit without keypoints projects nothing and owns no scratch.
     const int n_units = (int)span.size();
-    std::vector<int> chunk0, n_rings(n_ctx, 0), n_pts(n_ctx, 0);
+    std::vector<int> n_rings(n_ctx, 0), n_pts(n_ctx, 0);
+    FrChunks ck;
     std::vector<size_t> off_at(n_ctx, 0);
-    size_t cur = 0;
-    auto take = [&cur](size_t bytes) { const size_t at = cur; cur = fb_align64(cur + bytes); return at; };
-    (void)take(sizeof(FrDepthUnit) * (size_t)n_units);
+    StageLayout lay;                                                 // ONE device buffer: the upload and the scratch behind it, every part on a line of its own
+    auto take = [&lay](size_t bytes) { return lay.add<unsigned char>(bytes).off; };
+    const auto units = lay.add<FrDepthUnit>((size_t)n_units);
     for (int i = 0; i < n_ctx; i++) {
         const velo_ctx* c = ctxs[i];
         n_rings[i] = std::max((int)(of_target[i] ? c->T->h_tgt_off : c->h_src_off).size() - 1, 0);
@@ -651,16 +654,13 @@ int fr_put_frame_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, const in
     }
     for (Span& sp : span) sp.img = take(sizeof(int) * fr_round(7 * (size_t)sp.K->n));          // at most n depth points
     for (Span& sp : span) if (sp.K->rows && sp.K->n > 0) sp.rows = take(64 * (size_t)sp.K->n);
-    const size_t in_bytes = cur;
-    int n_chunks = 0, max_chunks = 0, max_n = 0, max_rings = 0;
+    const size_t in_bytes = lay.align(64);                           // what is uploaded: whole lines
+    int max_n = 0, max_rings = 0;
     for (int i = 0; i < n_ctx; i++)
         for (int u = unit0[i]; u < unit0[i + 1]; u++) {
             Span& sp = span[(size_t)u];
             const size_t n = (size_t)sp.K->n;
-            const int ch = cdiv(sp.K->n, kFrChunk);
-            chunk0.push_back(n_chunks);
-            n_chunks += ch;
-            max_chunks = std::max(max_chunks, ch);
+            ck.add(sp.K->n);
             max_n = std::max(max_n, sp.K->n);
             if (n == 0) continue;
             max_rings = std::max(max_rings, n_rings[i]);
@@ -671,12 +671,11 @@ int fr_put_frame_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, const in
             sp.flag = take(sizeof(int) * n);
             if (observe) { sp.obs = take(sizeof(velo_tri_obs) * n); sp.obs_ids = take(sizeof(int) * n); }
         }
-    chunk0.push_back(n_chunks);
-    const size_t all_bytes = cur;
-    const size_t cnt_bytes = std::max<size_t>(sizeof(int) * (size_t)n_chunks, 64);
-    VELO_TRY(L->h_in.reserve(in_bytes));
-    VELO_TRY(L->h_out.reserve(cnt_bytes));
-    VELO_TRY(L->d_out.reserve(cnt_bytes));
+    const size_t all_bytes = lay.align(64);
+    StageLayout out;
+    const auto counts = out.add<int>((size_t)ck.n_chunks);
+    VELO_TRY(L->in.h.reserve(in_bytes));
+    VELO_TRY(L->out.reserve(std::max<size_t>(out.bytes, 64)));
     if (all_bytes > L->d_depth.cap) {                                   // geometric, and kept
         HIP_TRY(hipStreamSynchronize(c0->stream));                       // the copies of the call before may still read the old scratch
         VELO_TRY(L->d_depth.reserve(std::max(all_bytes, 2 * L->d_depth.cap)));
@@ -713,13 +712,13 @@ int fr_put_frame_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, const in
     }
     unsigned char* dev = L->d_depth.p;
     {
-        FrDepthUnit* hu = (FrDepthUnit*)L->h_in.p;
-        std::memset(hu, 0, sizeof(FrDepthUnit) * (size_t)n_units);
+        FrDepthUnit* hu = units.in(L->in.h.p);
+        std::memset(hu, 0, units.size());
         for (int i = 0; i < n_ctx; i++) {
             const velo_ctx* c = ctxs[i];
             const FrStore& S = *c->fr;
             const std::vector<int>& h_off = of_target[i] ? c->T->h_tgt_off : c->h_src_off;
-            int* ho = (int*)(L->h_in.p + off_at[i]);
+            int* ho = (int*)(L->in.h.p + off_at[i]);
             ho[0] = 0;
             if (n_rings[i] > 0) std::memcpy(ho, h_off.data(), sizeof(int) * ((size_t)n_rings[i] + 1));
             for (int u = unit0[i]; u < unit0[i + 1]; u++) {
@@ -729,7 +728,7 @@ int fr_put_frame_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, const in
                 const size_t n = (size_t)K.n;
                 FrDepthUnit& U = hu[u];
                 U.n = K.n; U.frame = frames[i]; U.cam = cam;
-                U.chunk0 = chunk0[(size_t)u]; U.n_chunks = chunk0[(size_t)u + 1] - chunk0[(size_t)u];
+                U.chunk0 = ck.chunk0[(size_t)u]; U.n_chunks = ck.of(u);
                 U.image = (int*)(dev + sp.img);
                 if (n == 0) continue;
                 U.pts = (const float4*)(of_target[i] ? c->T->tgt.p : c->src.p);
@@ -740,20 +739,20 @@ int fr_put_frame_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, const in
                 U.pstack = (float4*)(dev + sp.pstack); U.vstack = (float4*)(dev + sp.vstack); U.ring_cnt = (int*)(dev + sp.ring_cnt);
                 U.kp_point = (float4*)(dev + sp.kp_point); U.flag = (int*)(dev + sp.flag);
                 if (observe) { U.obs = (velo_tri_obs*)(dev + sp.obs); U.obs_ids = (int*)(dev + sp.obs_ids); }
-                int* img = (int*)(L->h_in.p + sp.img);               // has_depth and the cloud are the device's to write
+                int* img = (int*)(L->in.h.p + sp.img);               // has_depth and the cloud are the device's to write
                 std::memcpy(img, K.ids, sizeof(int) * n);
                 std::memcpy(img + 2 * n, K.keypoints_xy, sizeof(float) * 2 * n);
-                if (K.rows) std::memcpy(L->h_in.p + sp.rows, K.rows, 64 * n);
+                if (K.rows) std::memcpy(L->in.h.p + sp.rows, K.rows, 64 * n);
             }
         }
     }
     VELO_TRY(fb_gather(ctxs, n_ctx, nullptr));
     hipStream_t st = c0->stream;
-    int* d_counts = (int*)L->d_out.p;
-    if (n_chunks > 0) {
-        HIP_TRY(hipMemcpyAsync(dev, L->h_in.p, in_bytes, hipMemcpyHostToDevice, st));
-        const FrDepthUnit* d_units = (const FrDepthUnit*)dev;
-        const dim3 g((unsigned)max_chunks, (unsigned)n_units);
+    int* d_counts = counts.in(L->out.d.p);
+    if (ck.n_chunks > 0) {
+        HIP_TRY(hipMemcpyAsync(dev, L->in.h.p, in_bytes, hipMemcpyHostToDevice, st));
+        const FrDepthUnit* d_units = units.in(dev);
+        const dim3 g((unsigned)ck.max_chunks, (unsigned)n_units);
         if (max_rings > 0) hipLaunchKernelGGL(fr_depth_project_kernel, dim3((unsigned)max_rings, (unsigned)n_units), dim3(256), 0, st, d_units);
         hipLaunchKernelGGL(fr_depth_assoc_kernel, dim3((unsigned)cdiv(max_n, 4), (unsigned)n_units), dim3(256), 0, st, d_units, thresh);
         hipLaunchKernelGGL(fr_depth_count_kernel, g, dim3(kFrChunk), 0, st, d_units, d_counts);
@@ -775,13 +774,13 @@ int fr_put_frame_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, const in
             }
         }
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(L->h_out.p, L->d_out.p, sizeof(int) * (size_t)n_chunks, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(L->out.h.p, L->out.d.p, out.bytes, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
     // The host now knows every block's size: it places the blocks in camera order -- the keypoint block as velo_frames_put would, the row
     // block as velo_frames_put_descriptors after it -- on COPIES of the arenas' lists, queues the copies out of the scratch behind the
     // launches, and hands lists and directories back after the last call that can fail.
-    const int* h_counts = (const int*)L->h_out.p;
+    const int* h_counts = counts.in(L->out.h.p);
     struct Change { int64_t key; FrStore::Entry e; bool has_rows; FrStore::RowEntry r; };
     struct Pending { BlockList kl, rl; std::vector<Change> ch; };
     std::vector<Pending> pend(n_ctx);
@@ -794,7 +793,7 @@ int fr_put_frame_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, const in
             const Span& sp = span[(size_t)u];
             const int n = sp.K->n;
             int n_wd = 0;
-            for (int k = chunk0[(size_t)u]; k < chunk0[(size_t)u + 1]; k++) n_wd += h_counts[k];
+            for (int k = ck.chunk0[(size_t)u]; k < ck.chunk0[(size_t)u + 1]; k++) n_wd += h_counts[k];
             const size_t words = 4 * (size_t)n + 3 * (size_t)n_wd;
             Change C;
             C.key = lm_key(frames[i], u - unit0[i]);
@@ -881,8 +880,8 @@ int velo_frames_reset(velo_ctx* c, int32_t n_cams, const float* cam_trans, int32
 int velo_frames_put(velo_ctx* c, int32_t frame, int32_t cam, const int32_t* ids, const float* keypoints_xy, const int32_t* has_depth,
                     const float* kp_with_depth_xyz, int32_t n_with_depth, int32_t n) {
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
-    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
-    if (cam < 0 || cam >= kLmMaxCams) return fail(VELO_ERR_INVALID, "camera %d; 0..%d", cam, kLmMaxCams - 1);
+    VELO_TRY(check_frame(frame));
+    VELO_TRY(check_cam(cam, kLmMaxCams));
     if (n < 0 || n_with_depth < 0) return fail(VELO_ERR_INVALID, "negative count");
     if (n > 0 && (!ids || !keypoints_xy || !has_depth)) return fail(VELO_ERR_INVALID, "null ids / keypoints / has_depth");
     if (n_with_depth > 0 && !kp_with_depth_xyz) return fail(VELO_ERR_INVALID, "a cloud of %d points and a null pointer", n_with_depth);
@@ -927,7 +926,7 @@ int velo_frames_put(velo_ctx* c, int32_t frame, int32_t cam, const int32_t* ids,
 
 int velo_frames_drop(velo_ctx* c, int32_t frame) {
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
-    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
+    VELO_TRY(check_frame(frame));
     VELO_TRY(fr_need_store(c, "velo_frames_drop"));
     FrStore& S = *c->fr;
     for (int cam = 0; cam < S.n_cams; cam++) {
@@ -942,8 +941,8 @@ int velo_frames_drop(velo_ctx* c, int32_t frame) {
 
 int velo_frames_put_descriptors(velo_ctx* c, int32_t frame, int32_t cam, const uint8_t* rows, int32_t n) {
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
-    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
-    if (cam < 0 || cam >= kLmMaxCams) return fail(VELO_ERR_INVALID, "camera %d; 0..%d", cam, kLmMaxCams - 1);
+    VELO_TRY(check_frame(frame));
+    VELO_TRY(check_cam(cam, kLmMaxCams));
     if (n < 0) return fail(VELO_ERR_INVALID, "negative count");
     if (n > 0 && !rows) return fail(VELO_ERR_INVALID, "null descriptor rows");
     if (n > kMatchMaxRows) return fail(VELO_ERR_INVALID, "%d descriptor rows; the match key indexes at most %d", n, kMatchMaxRows);
@@ -983,7 +982,7 @@ int velo_frames_desc_info(velo_ctx* c, int32_t* info) {
 
 int velo_frames_count(velo_ctx* c, int32_t frame, int32_t* n_per_cam, int32_t* n_total) {
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
-    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
+    VELO_TRY(check_frame(frame));
     VELO_TRY(fr_need_store(c, "velo_frames_count"));
     const FrStore& S = *c->fr;
     int total = 0;
@@ -1040,19 +1039,18 @@ int velo_match_frames(velo_ctx* c, int32_t frame1, const int32_t* frames2, int32
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
     if (n_cand < 0) return fail(VELO_ERR_INVALID, "negative candidate count %d", n_cand);
     if (std::isnan(match_thresh)) return fail(VELO_ERR_INVALID, "match_thresh is NaN");
-    if (frame1 < 0 || frame1 >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame1, kLmMaxFrame - 1);
+    VELO_TRY(check_frame(frame1));
     if (n_cand == 0) return VELO_OK;
     if (!frames2 || !n_kept || !min_dist) return fail(VELO_ERR_INVALID, "null frames2 / n_kept / min_dist");
-    for (int k = 0; k < n_cand; k++)
-        if (frames2[k] < 0 || frames2[k] >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "candidate %d: frame %d; 0..%d", k, frames2[k], kLmMaxFrame - 1);
+    for (int k = 0; k < n_cand; k++) VELO_TRY(check_frame(frames2[k], "candidate", k));
     return fr_desc_run(&c, 1, &frame1, frames2, n_cand, false, nullptr, match_thresh, nullptr, nullptr, 0, nullptr, n_kept, min_dist);
 }
 
 int velo_frames_get(velo_ctx* c, int32_t frame, int32_t cam, int32_t* ids, float* keypoints_xy, int32_t* has_depth, float* kp_with_depth_xyz,
                     uint8_t* rows, int32_t capacity, int32_t capacity_with_depth, int32_t* n, int32_t* n_with_depth, int32_t* has_rows) {
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
-    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
-    if (cam < 0 || cam >= kLmMaxCams) return fail(VELO_ERR_INVALID, "camera %d; 0..%d", cam, kLmMaxCams - 1);
+    VELO_TRY(check_frame(frame));
+    VELO_TRY(check_cam(cam, kLmMaxCams));
     if (capacity < 0 || capacity_with_depth < 0) return fail(VELO_ERR_INVALID, "negative capacity");
     VELO_TRY(fr_need_store(c, "velo_frames_get"));
     const FrStore& S = *c->fr;
@@ -1078,8 +1076,8 @@ int velo_frames_get(velo_ctx* c, int32_t frame, int32_t cam, int32_t* ids, float
 int velo_frames_keep(velo_ctx* c, int32_t frame, int32_t cam, const int32_t* keep_idx, int32_t n_keep, int32_t* kept_out, int32_t capacity,
                      int32_t* n_kept, int32_t* n_with_depth) {
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
-    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
-    if (cam < 0 || cam >= kLmMaxCams) return fail(VELO_ERR_INVALID, "camera %d; 0..%d", cam, kLmMaxCams - 1);
+    VELO_TRY(check_frame(frame));
+    VELO_TRY(check_cam(cam, kLmMaxCams));
     if (n_keep < 0 || capacity < 0) return fail(VELO_ERR_INVALID, "negative count");
     if (n_keep > 0 && !keep_idx) return fail(VELO_ERR_INVALID, "a keep list of %d indices and a null pointer", n_keep);
     return fr_prune_run(&c, 1, &frame, cam, keep_idx, n_keep, n_kept, n_with_depth, kept_out, capacity, nullptr);
@@ -1090,8 +1088,7 @@ int velo_frames_prune_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* frame
     VELO_TRY(fb_check_list(ctxs, n_ctx));
     if (!frames) return fail(VELO_ERR_INVALID, "null frames");
     if (capacity < 0) return fail(VELO_ERR_INVALID, "negative capacity");
-    for (int i = 0; i < n_ctx; i++)
-        if (frames[i] < 0 || frames[i] >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "context %d: frame %d; 0..%d", i, frames[i], kLmMaxFrame - 1);
+    for (int i = 0; i < n_ctx; i++) VELO_TRY(check_frame(frames[i], "context", i));
     VELO_TRY(fb_check_devices(ctxs, n_ctx));
     return fr_prune_run(ctxs, n_ctx, frames, -1, nullptr, 0, n_kept, n_with_depth, kept_out, capacity, n_out);
 }
@@ -1107,8 +1104,7 @@ int velo_frames_put_frame_batch(velo_ctx** ctxs, int32_t n_ctx, const int32_t* f
     if (!frames || !of_target) return fail(VELO_ERR_INVALID, "null frames / of_target");
     if (!cams) return fail(VELO_ERR_INVALID, "null cams");
     if (flags & ~VELO_PUT_OBSERVE) return fail(VELO_ERR_INVALID, "unknown flags 0x%x", (unsigned)flags);
-    for (int i = 0; i < n_ctx; i++)
-        if (frames[i] < 0 || frames[i] >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "context %d: frame %d; 0..%d", i, frames[i], kLmMaxFrame - 1);
+    for (int i = 0; i < n_ctx; i++) VELO_TRY(check_frame(frames[i], "context", i));
     VELO_TRY(fb_check_devices(ctxs, n_ctx));
     return fr_put_frame_run(ctxs, n_ctx, frames, of_target, cams, depth_assoc_thresh, flags, n_with_depth);
 }

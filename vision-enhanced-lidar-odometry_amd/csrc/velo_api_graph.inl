@@ -146,7 +146,7 @@ int graph_check(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
     if (n_fixed < 1) return fail(VELO_ERR_INVALID, "%s: %d fixed nodes; at least 1 fixes the gauge", who, n_fixed);
     if (!fixed) return fail(VELO_ERR_INVALID, "%s: null fixed", who);
     for (int i = 0; i < n_fixed; i++) {
-        if (fixed[i] < 0 || fixed[i] >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "%s: frame %d; 0..%d", who, fixed[i], kLmMaxFrame - 1);
+        VELO_TRY(check_frame(fixed[i], who));
         if (i > 0 && fixed[i] <= fixed[i - 1]) return fail(VELO_ERR_INVALID, "%s: fixed frames must be ascending and distinct (%d after %d)", who, fixed[i], fixed[i - 1]);
     }
     if (params) {

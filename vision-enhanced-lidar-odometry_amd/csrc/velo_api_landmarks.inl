@@ -24,10 +24,9 @@ struct LmStore {
     std::unordered_map<int64_t, std::vector<int32_t>> lists;   // frame * 8 + cam -> ids[cam][frame]
     std::vector<int32_t> h_count;
     std::vector<unsigned char> h_added;
-    // staging (a batch call uses the first context's)
-    PinBuf<> h_in, h_out;
-    Event in_ev;                                    // h_in may be rewritten once this has passed
-    DevBuf<unsigned char> d_in, d_out;
+    // staging (a batch call uses the first context's): a call's upload and its read-back, laid out call by call (velo_stage_layout.h)
+    StagePair in, out;
+    Event in_ev;                                    // in.h may be rewritten once this has passed
     DevBuf<velo_tri_obs> d_obs;                     // the gathered observation lists of a call
     std::shared_ptr<void> ba;                       // the work buffers of velo_landmarks_adjust (BaWork, velo_api_ba.inl), made by its first call
 };
@@ -35,7 +34,6 @@ struct LmStore {
 namespace {
 
 constexpr int kLmMaxCams = 8;
-constexpr int kLmMaxFrame = 1 << 22;
 constexpr int kLmMaxId = 1 << 26;
 constexpr size_t kLmDefaultLog = 65536;
 
@@ -97,20 +95,19 @@ int lm_triangulate_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, int32_
     velo_ctx* c = ctxs[0];
     LmStore* L = c->lm.get();
     HIP_TRY(hipSetDevice(c->device));
-    const size_t unit_bytes = fb_align64(sizeof(LmUnit) * (size_t)n_ctx);
-    const size_t item_bytes = fb_align64(sizeof(LmItem) * (size_t)n);
-    const size_t in_bytes = unit_bytes + item_bytes + sizeof(int) * ((size_t)n + 1);
-    const size_t res_bytes = fb_align64(sizeof(velo_tri_result) * (size_t)n);
-    const size_t out_bytes = res_bytes + sizeof(float) * 3 * (size_t)n;
+    StageLayout in, out;
+    const auto units = in.add<LmUnit>((size_t)n_ctx);
+    const auto litems = in.add<LmItem>((size_t)n);
+    const auto offs = in.add<int>((size_t)n + 1);
+    const auto res = out.add<velo_tri_result>((size_t)n);
+    const auto pts = out.add<float>(3 * (size_t)n);
     VELO_TRY(L->in_ev.wait_or_create());
-    VELO_TRY(L->h_in.reserve(in_bytes));
-    VELO_TRY(L->h_out.reserve(out_bytes));
-    VELO_TRY(L->d_in.reserve(in_bytes));
-    VELO_TRY(L->d_out.reserve(out_bytes));
+    VELO_TRY(L->in.reserve(in.bytes));
+    VELO_TRY(L->out.reserve(out.bytes));
     VELO_TRY(L->d_obs.reserve((size_t)off.back()));
     {
-        LmUnit* hu = (LmUnit*)L->h_in.p;
-        std::memset(hu, 0, unit_bytes);
+        LmUnit* hu = units.in(L->in.h.p);
+        std::memset(hu, 0, litems.off);                          // the units and the padding behind them
         for (int i = 0; i < n_ctx; i++) {
             const velo_ctx* ci = ctxs[i];
             const LmStore& S = *ci->lm;
@@ -120,24 +117,23 @@ int lm_triangulate_run(velo_ctx** ctxs, int n_ctx, const int32_t* frames, int32_
             U.P.lm = lm_params(ci->P);
             U.P.loss_a = ci->P.loss_thresh_3D2D; U.P.loss_w = ci->P.weight_3D2D;    // velo.h:1116-1119
         }
-        std::memcpy(L->h_in.p + unit_bytes, items.data(), sizeof(LmItem) * (size_t)n);
-        std::memcpy(L->h_in.p + unit_bytes + item_bytes, off.data(), sizeof(int) * ((size_t)n + 1));
+        std::memcpy(litems.in(L->in.h.p), items.data(), litems.size());
+        std::memcpy(offs.in(L->in.h.p), off.data(), offs.size());
     }
     VELO_TRY(fb_gather(ctxs, n_ctx, &used));
-    HIP_TRY(hipMemcpyAsync(L->d_in.p, L->h_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(L->in.d.p, L->in.h.p, in.bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipEventRecord(L->in_ev, c->stream));
-    const LmUnit* d_units = (const LmUnit*)L->d_in.p;
-    const LmItem* d_items = (const LmItem*)(L->d_in.p + unit_bytes);
-    const int* d_off = (const int*)(L->d_in.p + unit_bytes + item_bytes);
-    velo_tri_result* d_res = (velo_tri_result*)L->d_out.p;
-    float* d_pts = (float*)(L->d_out.p + res_bytes);
+    const LmUnit* d_units = units.in(L->in.d.p);
+    const LmItem* d_items = litems.in(L->in.d.p);
+    const int* d_off = offs.in(L->in.d.p);
     hipLaunchKernelGGL(lm_gather_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, d_units, d_items, d_off, n, L->d_obs.p);
-    hipLaunchKernelGGL(lm_solve_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, d_units, d_items, (const velo_tri_obs*)L->d_obs.p, d_off, n, d_pts, d_res);
+    hipLaunchKernelGGL(lm_solve_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, d_units, d_items, (const velo_tri_obs*)L->d_obs.p, d_off, n, pts.in(L->out.d.p),
+                       res.in(L->out.d.p));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(L->h_out.p, L->d_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(L->out.h.p, L->out.d.p, out.bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const velo_tri_result* h_res = (const velo_tri_result*)L->h_out.p;
-    const float* h_pts = (const float*)(L->h_out.p + res_bytes);
+    const velo_tri_result* h_res = res.in(L->out.h.p);
+    const float* h_pts = pts.in(L->out.h.p);
     for (int i = 0; i < n_ctx; i++) {
         LmStore& S = *ctxs[i]->lm;
         const int b = first[i], m = first[i + 1] - b, w = std::min(m, (int)capacity);
@@ -177,7 +173,7 @@ int velo_landmarks_reset(velo_ctx* c, int32_t n_cams, const float* cam_trans, in
 
 int velo_landmarks_set_pose(velo_ctx* c, int32_t frame, const double* pose6) {
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
-    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
+    VELO_TRY(check_frame(frame));
     if (!pose6) return fail(VELO_ERR_INVALID, "null pose");
     for (int k = 0; k < 6; k++) if (!std::isfinite(pose6[k])) return fail(VELO_ERR_INVALID, "pose[%d] is not finite", k);
     VELO_TRY(lm_need_store(c, "velo_landmarks_set_pose"));
@@ -209,8 +205,8 @@ int velo_landmarks_set_pose(velo_ctx* c, int32_t frame, const double* pose6) {
 int velo_landmarks_observe(velo_ctx* c, int32_t frame, int32_t cam, const int32_t* ids, const float* keypoints_xy, const int32_t* has_depth,
                            const float* kp_with_depth_xyz, int32_t n_with_depth, int32_t n) {
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
-    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
-    if (cam < 0 || cam >= kLmMaxCams) return fail(VELO_ERR_INVALID, "camera %d; 0..%d", cam, kLmMaxCams - 1);
+    VELO_TRY(check_frame(frame));
+    VELO_TRY(check_cam(cam, kLmMaxCams));
     if (n < 0 || n_with_depth < 0) return fail(VELO_ERR_INVALID, "negative count");
     if (n > 0 && (!ids || !keypoints_xy || !has_depth)) return fail(VELO_ERR_INVALID, "null ids / keypoints / has_depth");
     int32_t max_id = -1;
@@ -250,18 +246,18 @@ int velo_landmarks_observe(velo_ctx* c, int32_t frame, int32_t cam, const int32_
         S.log_cap = cap;
         S.log_reallocs++;
     }
-    const size_t obs_bytes = fb_align64(sizeof(velo_tri_obs) * (size_t)n);
-    const size_t in_bytes = obs_bytes + sizeof(int) * (size_t)n;
+    StageLayout in;
+    const auto obs = in.add<velo_tri_obs>((size_t)n);
+    const auto oids = in.add<int>((size_t)n);
     if (n > 0) {
         VELO_TRY(S.in_ev.wait_or_create());
-        VELO_TRY(S.h_in.reserve(in_bytes));
-        VELO_TRY(S.d_in.reserve(in_bytes));
+        VELO_TRY(S.in.reserve(in.bytes));
     }
     // the device first, the host's bookkeeping after the last call that can fail: a failed call leaves the store as it was (what a
     // failed launch may have written lies beyond log_len and in id tables whose counts the host does not trust over its own)
     if (n > 0) {
-        velo_tri_obs* ho = (velo_tri_obs*)S.h_in.p;
-        int* hi = (int*)(S.h_in.p + obs_bytes);
+        velo_tri_obs* ho = obs.in(S.in.h.p);
+        int* hi = oids.in(S.in.h.p);
         for (int i = 0; i < n; i++) {
             velo_tri_obs& o = ho[i];
             o.frame = frame; o.cam = cam;
@@ -269,9 +265,9 @@ int velo_landmarks_observe(velo_ctx* c, int32_t frame, int32_t cam, const int32_
             else { const float* p = kp_with_depth_xyz + 3 * (size_t)has_depth[i]; o.kind = VELO_TRI_OBS_3D; o.s[0] = p[0]; o.s[1] = p[1]; o.s[2] = p[2]; }
             hi[i] = ids[i];
         }
-        HIP_TRY(hipMemcpyAsync(S.d_in.p, S.h_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(S.in.d.p, S.in.h.p, in.bytes, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipEventRecord(S.in_ev, c->stream));
-        hipLaunchKernelGGL(lm_append_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, c->stream, (const velo_tri_obs*)S.d_in.p, (const int*)(S.d_in.p + obs_bytes), n,
+        hipLaunchKernelGGL(lm_append_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, c->stream, (const velo_tri_obs*)obs.in(S.in.d.p), (const int*)oids.in(S.in.d.p), n,
                            (int)S.log_len, S.log.p, S.prev.p, S.head.p, S.count.p);
         HIP_TRY(hipGetLastError());
     }
@@ -292,7 +288,7 @@ int velo_landmarks_triangulate_batch(velo_ctx** ctxs, int32_t n_ctx, const int32
     if (!frames) return fail(VELO_ERR_INVALID, "null frames");
     if (!n_out) return fail(VELO_ERR_INVALID, "null n_out");
     if (capacity < 0) return fail(VELO_ERR_INVALID, "negative capacity");
-    for (int i = 0; i < n_ctx; i++) if (frames[i] < 0 || frames[i] >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "context %d: frame %d; 0..%d", i, frames[i], kLmMaxFrame - 1);
+    for (int i = 0; i < n_ctx; i++) VELO_TRY(check_frame(frames[i], "context", i));
     VELO_TRY(fb_check_devices(ctxs, n_ctx));
     return lm_triangulate_run(ctxs, n_ctx, frames, ids_out, points_out, results_out, capacity, n_out);
 }
@@ -305,7 +301,7 @@ int velo_landmarks_triangulate(velo_ctx* c, int32_t frame, int32_t* ids_out, flo
 
 int velo_landmarks_at_frame(velo_ctx* c, int32_t frame, const double* pose_inv16, int32_t* ids_out, float* xyz_out, int32_t capacity, int32_t* n_out) {
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
-    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
+    VELO_TRY(check_frame(frame));
     if (!pose_inv16) return fail(VELO_ERR_INVALID, "null pose_inv");
     if (!n_out) return fail(VELO_ERR_INVALID, "null n_out");
     if (capacity < 0) return fail(VELO_ERR_INVALID, "negative capacity");
@@ -321,22 +317,22 @@ int velo_landmarks_at_frame(velo_ctx* c, int32_t frame, const double* pose_inv16
     if (ids_out) std::memcpy(ids_out, ids.data(), sizeof(int32_t) * (size_t)n);
     if (!xyz_out) return VELO_OK;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t in_bytes = sizeof(int) * (size_t)n, out_bytes = sizeof(float) * 3 * (size_t)n;
+    StageLayout in, out;
+    const auto want = in.add<int>((size_t)n);
+    const auto xyz = out.add<float>(3 * (size_t)n);
     VELO_TRY(S.in_ev.wait_or_create());
-    VELO_TRY(S.h_in.reserve(in_bytes));
-    VELO_TRY(S.h_out.reserve(out_bytes));
-    VELO_TRY(S.d_in.reserve(in_bytes));
-    VELO_TRY(S.d_out.reserve(out_bytes));
-    std::memcpy(S.h_in.p, ids.data(), in_bytes);
+    VELO_TRY(S.in.reserve(in.bytes));
+    VELO_TRY(S.out.reserve(out.bytes));
+    std::memcpy(want.in(S.in.h.p), ids.data(), want.size());
     LmPose M;
     std::memcpy(M.m, pose_inv16, sizeof(M.m));
-    HIP_TRY(hipMemcpyAsync(S.d_in.p, S.h_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(S.in.d.p, S.in.h.p, in.bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipEventRecord(S.in_ev, c->stream));
-    hipLaunchKernelGGL(lm_at_frame_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, c->stream, (const int*)S.d_in.p, n, (const float*)S.pts.p, M, (float*)S.d_out.p);
+    hipLaunchKernelGGL(lm_at_frame_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, c->stream, (const int*)want.in(S.in.d.p), n, (const float*)S.pts.p, M, xyz.in(S.out.d.p));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(S.h_out.p, S.d_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(S.out.h.p, S.out.d.p, out.bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    std::memcpy(xyz_out, S.h_out.p, out_bytes);
+    std::memcpy(xyz_out, xyz.in(S.out.h.p), xyz.size());
     return VELO_OK;
 }
 
@@ -349,31 +345,31 @@ int velo_landmarks_get(velo_ctx* c, const int32_t* ids, int32_t n, float* xyz, u
     if (n == 0) return VELO_OK;
     LmStore& S = *c->lm;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t in_bytes = sizeof(int) * (size_t)n;
-    const size_t xyz_bytes = sizeof(float) * 3 * (size_t)n, cnt_bytes = sizeof(int) * (size_t)n;
-    const size_t out_bytes = xyz_bytes + cnt_bytes + (size_t)n;
+    StageLayout in, out;
+    const auto want = in.add<int>((size_t)n);
+    const auto oxyz = out.add<float>(3 * (size_t)n);             // the three arrays packed
+    const auto ocnt = out.add<int>((size_t)n, 4);
+    const auto oadd = out.add<unsigned char>((size_t)n, 1);
     VELO_TRY(S.in_ev.wait_or_create());
-    VELO_TRY(S.h_in.reserve(in_bytes));
-    VELO_TRY(S.h_out.reserve(out_bytes));
-    VELO_TRY(S.d_in.reserve(in_bytes));
-    VELO_TRY(S.d_out.reserve(out_bytes));
-    std::memcpy(S.h_in.p, ids, in_bytes);
-    HIP_TRY(hipMemcpyAsync(S.d_in.p, S.h_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
+    VELO_TRY(S.in.reserve(in.bytes));
+    VELO_TRY(S.out.reserve(out.bytes));
+    std::memcpy(want.in(S.in.h.p), ids, want.size());
+    HIP_TRY(hipMemcpyAsync(S.in.d.p, S.in.h.p, in.bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipEventRecord(S.in_ev, c->stream));
-    hipLaunchKernelGGL(lm_get_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, c->stream, (const int*)S.d_in.p, n, (int)S.n_ids, (const float*)S.pts.p,
-                       (const unsigned char*)S.added.p, (const int*)S.count.p, (float*)S.d_out.p, (int*)(S.d_out.p + xyz_bytes), S.d_out.p + xyz_bytes + cnt_bytes);
+    hipLaunchKernelGGL(lm_get_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, c->stream, (const int*)want.in(S.in.d.p), n, (int)S.n_ids, (const float*)S.pts.p,
+                       (const unsigned char*)S.added.p, (const int*)S.count.p, oxyz.in(S.out.d.p), ocnt.in(S.out.d.p), oadd.in(S.out.d.p));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(S.h_out.p, S.d_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(S.out.h.p, S.out.d.p, out.bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (xyz) std::memcpy(xyz, S.h_out.p, xyz_bytes);
-    if (obs_count) std::memcpy(obs_count, S.h_out.p + xyz_bytes, cnt_bytes);
-    if (added) std::memcpy(added, S.h_out.p + xyz_bytes + cnt_bytes, (size_t)n);
+    if (xyz) std::memcpy(xyz, oxyz.in(S.out.h.p), oxyz.size());
+    if (obs_count) std::memcpy(obs_count, ocnt.in(S.out.h.p), ocnt.size());
+    if (added) std::memcpy(added, oadd.in(S.out.h.p), oadd.size());
     return VELO_OK;
 }
 
 int velo_landmarks_frame_count(velo_ctx* c, int32_t frame, int32_t* n_seen, int32_t* n_to_triangulate) {
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
-    if (frame < 0 || frame >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "frame %d; 0..%d", frame, kLmMaxFrame - 1);
+    VELO_TRY(check_frame(frame));
     VELO_TRY(lm_need_store(c, "velo_landmarks_frame_count"));
     const LmStore& S = *c->lm;
     std::vector<int32_t> ids;

@@ -55,23 +55,23 @@ int velo_match_descriptors(velo_ctx* c, const velo_desc_job* jobs, int32_t n_job
     const int nq = (int)total_q;
 
     HIP_TRY(hipSetDevice(c->device));
-    const size_t job_bytes = (sizeof(MatchJob) * (size_t)n_jobs + 63) & ~(size_t)63;   // the rows start 64-byte aligned
-    const size_t in_bytes = job_bytes + 64 * (size_t)n_rows;
-    const size_t out_ints = 4 * (size_t)nq + 2 * (size_t)n_jobs;
-    VELO_TRY(c->h_md_in.reserve(in_bytes));
+    StageLayout in;
+    const auto mjobs = in.add<MatchJob>((size_t)n_jobs);
+    const auto rows = in.add<uint4>(4 * (size_t)n_rows);                       // the rows start 64-byte aligned
+    const size_t out_ints = 4 * (size_t)nq + 2 * (size_t)n_jobs;               // the filter kernel's own layout: one part
+    VELO_TRY(c->md_in.reserve(in.bytes));
     VELO_TRY(c->h_md_out.reserve(sizeof(int) * out_ints));
-    VELO_TRY(c->md_in.reserve(in_bytes));
     VELO_TRY(c->md_keys.reserve((size_t)nq + (size_t)n_jobs));
     VELO_TRY(c->md_out.reserve(out_ints));
-    std::memcpy(c->h_md_in.p, hj.data(), sizeof(MatchJob) * (size_t)n_jobs);
+    std::memcpy(mjobs.in(c->md_in.h.p), hj.data(), mjobs.size());
     {
-        unsigned char* w = c->h_md_in.p + job_bytes;
+        unsigned char* w = (unsigned char*)rows.in(c->md_in.h.p);
         for (const auto& s : sets) { std::memcpy(w, s.first, 64 * (size_t)s.second); w += 64 * (size_t)s.second; }
     }
-    HIP_TRY(hipMemcpyAsync(c->md_in.p, c->h_md_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->md_in.d.p, c->md_in.h.p, in.bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->md_keys.p, 0xFF, sizeof(unsigned) * ((size_t)nq + (size_t)n_jobs), c->stream));   // kMatchNone
-    const MatchJob* djobs = (const MatchJob*)c->md_in.p;
-    const uint4* drows = (const uint4*)(c->md_in.p + job_bytes);
+    const MatchJob* djobs = mjobs.in(c->md_in.d.p);
+    const uint4* drows = rows.in(c->md_in.d.p);
     unsigned* keys = c->md_keys.p;
     unsigned* dmin = c->md_keys.p + nq;
     if (blocks > 0) {

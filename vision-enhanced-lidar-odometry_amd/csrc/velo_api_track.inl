@@ -4,16 +4,15 @@
 //
 // Every stage of the visual front end (images and tracking here, detection in velo_api_detect.inl) has ONE implementation, over a list
 // of contexts; the single-context entries hand it a list of one.  Who owns what: the FIRST context of a call (ctxs[0]) lends its
-// stream, its pinned staging and its scratch buffers (lk_raw / lk_in / lk_out, gf_*); every context keeps its own image slots, and the
-// kernels write / read them through per-unit tables that ride in the call's one upload.  Mixed image sizes are served by the SAME
-// launches: a table entry carries its unit's size, grids are sized for the largest unit.
+// stream and its staging pairs (lk_raw / lk_in / lk_out, gf_*: pinned and device buffer, velo_host_types.inl); every context keeps its
+// own image slots, and the kernels write / read them through per-unit tables that ride in the call's one upload, laid out by a
+// StageLayout (velo_stage_layout.h).  Mixed image sizes are served by the SAME launches: a table entry carries its unit's size, grids
+// are sized for the largest unit.  The checks of the list and the hand-over are velo_host_types.inl's (fb_*).
 // Hand-over between the streams: the lending stream first waits for an event recorded on every other named context's stream; the
 // synchronous entries (track, detect) end in a synchronisation of the lending stream, after which nothing of the call is in flight;
 // the asynchronous one (set_images) records an event on the lending stream that every other context's stream then waits for.  With
 // one context there is no other stream: no event is recorded or waited for.
 namespace {
-
-constexpr int kFbMaxCtx = 256;             // contexts per call
 
 int lk_level_count(int w, int h, int win, int max_level) {      // buildOpticalFlowPyramid's deepest level (tests/lk_ref.py level_count)
     for (int lev = 0; lev <= max_level; lev++) {
@@ -68,58 +67,6 @@ int lk_check_jobs(const velo_track_job* jobs, int32_t n_jobs, const float* next_
     return VELO_OK;
 }
 
-// the checks of the context list that read no context
-int fb_check_list(velo_ctx** ctxs, int n_ctx) {
-    if (!ctxs) return fail(VELO_ERR_INVALID, "null context list");
-    if (n_ctx < 1 || n_ctx > kFbMaxCtx) return fail(VELO_ERR_INVALID, "%d contexts; 1..%d", n_ctx, kFbMaxCtx);
-    for (int i = 0; i < n_ctx; i++) {
-        if (!ctxs[i]) return fail(VELO_ERR_INVALID, "context %d is null", i);
-        for (int j = 0; j < i; j++) if (ctxs[j] == ctxs[i]) return fail(VELO_ERR_INVALID, "batch entries %d and %d are the same context", j, i);
-    }
-    return VELO_OK;
-}
-
-int fb_check_devices(velo_ctx** ctxs, int n_ctx) {
-    for (int i = 1; i < n_ctx; i++)
-        if (ctxs[i]->device != ctxs[0]->device)
-            return fail(VELO_ERR_INVALID, "contexts on different devices: entry %d is on device %d, entry 0 on device %d", i, ctxs[i]->device, ctxs[0]->device);
-    return VELO_OK;
-}
-
-// job_ctx of the batch entries; null (the single-context entries pass it): every job runs on context 0
-int fb_check_job_ctx(const int32_t* job_ctx, int n_jobs, int n_ctx) {
-    if (!job_ctx) return VELO_OK;
-    for (int j = 0; j < n_jobs; j++)
-        if (job_ctx[j] < 0 || job_ctx[j] >= n_ctx) return fail(VELO_ERR_INVALID, "job %d: context index %d; 0..%d", j, job_ctx[j], n_ctx - 1);
-    return VELO_OK;
-}
-inline int fb_ctx_of(const int32_t* job_ctx, int j) { return job_ctx ? job_ctx[j] : 0; }
-
-// the lending stream runs after everything already enqueued on the stream of every other context in `used` (null: all)
-int fb_gather(velo_ctx** ctxs, int n_ctx, const std::vector<char>* used) {
-    velo_ctx* c0 = ctxs[0];
-    for (int i = 1; i < n_ctx; i++) {
-        if (used && !(*used)[i]) continue;
-        velo_ctx* c = ctxs[i];
-        if (c->stream == c0->stream) continue;
-        VELO_TRY(c->fb_here_ev.ensure());
-        HIP_TRY(hipEventRecord(c->fb_here_ev, c->stream));
-        HIP_TRY(hipStreamWaitEvent(c0->stream, c->fb_here_ev, 0));
-    }
-    return VELO_OK;
-}
-
-// whatever is enqueued later on any other context's stream runs after what the lending stream holds now
-int fb_release(velo_ctx** ctxs, int n_ctx) {
-    velo_ctx* c0 = ctxs[0];
-    if (n_ctx < 2) return VELO_OK;
-    VELO_TRY(c0->fb_done_ev.ensure());
-    HIP_TRY(hipEventRecord(c0->fb_done_ev, c0->stream));
-    for (int i = 1; i < n_ctx; i++)
-        if (ctxs[i]->stream != c0->stream) HIP_TRY(hipStreamWaitEvent(ctxs[i]->stream, c0->fb_done_ev, 0));
-    return VELO_OK;
-}
-
 // index of the level table of a w x h image in `pyrs` (appended when new)
 int fb_pyr_index(std::vector<LkPyr>* pyrs, std::vector<long long>* cam_pix, int w, int h) {
     for (size_t k = 0; k < pyrs->size(); k++) if ((*pyrs)[k].lv[0].w == w && (*pyrs)[k].lv[0].h == h) return (int)k;
@@ -130,8 +77,6 @@ int fb_pyr_index(std::vector<LkPyr>* pyrs, std::vector<long long>* cam_pix, int 
     cam_pix->push_back(cp);
     return (int)pyrs->size() - 1;
 }
-
-inline size_t fb_align64(size_t n) { return (n + 63) & ~(size_t)63; }
 
 // velo_set_images[_batch]: imgs[i * n_cams + k] is camera k of context i, sizes[3 i ..] = {width, height, stride} of context i
 int lk_set_images(velo_ctx** ctxs, int n_ctx, const uint8_t* const* imgs, int n_cams, const int32_t* sizes) {
@@ -160,11 +105,11 @@ int lk_set_images(velo_ctx** ctxs, int n_ctx, const uint8_t* const* imgs, int n_
         raw_bytes += (size_t)n_cams * sizes[3 * i] * sizes[3 * i + 1];
     }
     const int n_units = n_ctx * n_cams;
-    const size_t unit_bytes = fb_align64(sizeof(LkBuildUnit) * (size_t)n_units);
-    const size_t pyr_bytes = fb_align64(sizeof(LkPyr) * pyrs.size());
-    const size_t in_bytes = unit_bytes + pyr_bytes + raw_bytes;
-    VELO_TRY(c->h_lk_raw.reserve(in_bytes));
-    VELO_TRY(c->lk_raw.reserve(in_bytes));
+    StageLayout in;
+    const auto units = in.add<LkBuildUnit>((size_t)n_units);
+    const auto levels = in.add<LkPyr>(pyrs.size());
+    const auto raw = in.add<unsigned char>(raw_bytes);
+    VELO_TRY(c->lk_raw.reserve(in.bytes));
     // The slot every context is about to fill is its previous one (current -> previous is a rotation, no copy).  Every allocation comes
     // first and nothing rotates unless everything was allocated: a failure leaves every context's current and previous images as they
     // were, except a previous slot whose buffer had to be replaced.
@@ -177,26 +122,26 @@ int lk_set_images(velo_ctx** ctxs, int n_ctx, const uint8_t* const* imgs, int n_
     }
     for (int i = 0; i < n_ctx; i++) ctxs[i]->lk_slot[ctxs[i]->lk_cur ^ 1].valid = false;
     {
-        LkBuildUnit* hu = (LkBuildUnit*)c->h_lk_raw.p;
-        std::memcpy(c->h_lk_raw.p + unit_bytes, pyrs.data(), sizeof(LkPyr) * pyrs.size());
-        size_t off = unit_bytes + pyr_bytes;
+        LkBuildUnit* hu = units.in(c->lk_raw.h.p);
+        std::memcpy(levels.in(c->lk_raw.h.p), pyrs.data(), levels.size());
+        size_t off = 0;                                       // into the raw images
         for (int i = 0; i < n_ctx; i++) {
             const int w = sizes[3 * i], h = sizes[3 * i + 1], st = sizes[3 * i + 2];
             LkSlot& S = ctxs[i]->lk_slot[ctxs[i]->lk_cur ^ 1];
             for (int k = 0; k < n_cams; k++) {
                 LkBuildUnit& U = hu[i * n_cams + k];
-                U.raw = c->lk_raw.p + off;
+                U.raw = raw.in(c->lk_raw.d.p) + off;
                 U.pix = S.pix.p + (size_t)k * cam_pix[pyr_of[i]];
                 U.der = S.der.p + (size_t)k * cam_pix[pyr_of[i]];
                 U.pyr = pyr_of[i]; U.pad_ = 0;
                 const uint8_t* src = imgs[(size_t)i * n_cams + k];
-                for (int y = 0; y < h; y++) std::memcpy(c->h_lk_raw.p + off + (size_t)y * w, src + (size_t)y * st, (size_t)w);
+                for (int y = 0; y < h; y++) std::memcpy(raw.in(c->lk_raw.h.p) + off + (size_t)y * w, src + (size_t)y * st, (size_t)w);
                 off += (size_t)w * h;
             }
         }
     }
     VELO_TRY(fb_gather(ctxs, n_ctx, nullptr));
-    HIP_TRY(hipMemcpyAsync(c->lk_raw.p, c->h_lk_raw.p, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->lk_raw.d.p, c->lk_raw.h.p, in.bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipEventRecord(c->lk_upload_ev, c->stream));
     int max_levels = 0;
     for (const LkPyr& P : pyrs) max_levels = std::max(max_levels, P.n_levels);
@@ -204,8 +149,8 @@ int lk_set_images(velo_ctx** ctxs, int n_ctx, const uint8_t* const* imgs, int n_
         int mw = 0, mh = 0;                                   // the largest unit that has this level
         for (const LkPyr& P : pyrs) if (lev < P.n_levels) { mw = std::max(mw, P.lv[lev].w); mh = std::max(mh, P.lv[lev].h); }
         const dim3 grid((unsigned)cdiv(mw + 2 * kLkPad, kLkTile), (unsigned)cdiv(mh + 2 * kLkPad, kLkTile), (unsigned)n_units);
-        hipLaunchKernelGGL(lk_build_kernel, grid, dim3(kLkTile * kLkTile), 0, c->stream, (const LkBuildUnit*)c->lk_raw.p,
-                           (const LkPyr*)(c->lk_raw.p + unit_bytes), lev);
+        hipLaunchKernelGGL(lk_build_kernel, grid, dim3(kLkTile * kLkTile), 0, c->stream, units.in(c->lk_raw.d.p),
+                           levels.in(c->lk_raw.d.p), lev);
     }
     HIP_TRY(hipGetLastError());
     VELO_TRY(fb_release(ctxs, n_ctx));
@@ -252,18 +197,19 @@ int lk_track(velo_ctx** ctxs, int n_ctx, const int32_t* job_ctx, const velo_trac
     std::vector<long long> cam_pix;
     std::vector<int> pyr_of(n_ctx, -1);
     for (int i = 0; i < n_ctx; i++) if (used[i]) pyr_of[i] = fb_pyr_index(&pyrs, &cam_pix, lk_slot(ctxs[i], false)->w, lk_slot(ctxs[i], false)->h);
-    const size_t job_bytes = fb_align64(sizeof(LkJob) * (size_t)n_jobs);
-    const size_t pyr_bytes = fb_align64(sizeof(LkPyr) * pyrs.size());
-    const size_t in_bytes = job_bytes + pyr_bytes + sizeof(float2) * (size_t)n;
-    const size_t out_bytes = sizeof(float2) * (size_t)n + 2 * (size_t)n;
-    VELO_TRY(c->h_lk_in.reserve(in_bytes));
-    VELO_TRY(c->h_lk_out.reserve(out_bytes));
-    VELO_TRY(c->lk_in.reserve(in_bytes));
-    VELO_TRY(c->lk_out.reserve(out_bytes));
+    StageLayout in, out;
+    const auto ljobs = in.add<LkJob>((size_t)n_jobs);
+    const auto levels = in.add<LkPyr>(pyrs.size());
+    const auto pts = in.add<float2>((size_t)n);
+    const auto oxy = out.add<float2>((size_t)n);
+    const auto ost = out.add<unsigned char>((size_t)n, 1);      // packed: status and kept start wherever the points end
+    const auto okp = out.add<unsigned char>((size_t)n, 1);
+    VELO_TRY(c->lk_in.reserve(in.bytes));
+    VELO_TRY(c->lk_out.reserve(out.bytes));
     {
-        LkJob* hj = (LkJob*)c->h_lk_in.p;
-        std::memcpy(c->h_lk_in.p + job_bytes, pyrs.data(), sizeof(LkPyr) * pyrs.size());
-        float* hp = (float*)(c->h_lk_in.p + job_bytes + pyr_bytes);
+        LkJob* hj = ljobs.in(c->lk_in.h.p);
+        std::memcpy(levels.in(c->lk_in.h.p), pyrs.data(), levels.size());
+        float* hp = (float*)pts.in(c->lk_in.h.p);
         int first = 0;
         for (int j = 0; j < n_jobs; j++) {
             const int i = fb_ctx_of(job_ctx, j);
@@ -280,19 +226,15 @@ int lk_track(velo_ctx** ctxs, int n_ctx, const int32_t* job_ctx, const velo_trac
         }
     }
     VELO_TRY(fb_gather(ctxs, n_ctx, &used));
-    HIP_TRY(hipMemcpyAsync(c->lk_in.p, c->h_lk_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->lk_in.d.p, c->lk_in.h.p, in.bytes, hipMemcpyHostToDevice, c->stream));
     LkParams K;
     std::memset(&K, 0, sizeof(K));
     K.win = p->window; K.max_count = p->max_count;
     K.min_eig = (float)p->min_eig_threshold;
     K.eps2 = p->epsilon * p->epsilon;
     K.flow_outlier = p->flow_outlier;
-    const LkJob* djobs = (const LkJob*)c->lk_in.p;
-    const LkPyr* dpyrs = (const LkPyr*)(c->lk_in.p + job_bytes);
-    const float2* dpts = (const float2*)(c->lk_in.p + job_bytes + pyr_bytes);
-    float2* oxy = (float2*)c->lk_out.p;
-    unsigned char* ost = c->lk_out.p + sizeof(float2) * (size_t)n;
-    unsigned char* okp = ost + n;
+    const void* din = c->lk_in.d.p;
+    void* dout = c->lk_out.d.p;
     unsigned long long* diag = nullptr;
 #ifdef VELO_DIAGNOSTICS
     VELO_TRY(c->lk_diag.reserve(2 * kLkLevels));
@@ -302,17 +244,18 @@ int lk_track(velo_ctx** ctxs, int n_ctx, const int32_t* job_ctx, const velo_trac
     const dim3 grid((unsigned)cdiv(n, kLkThreads / 64));
     const int npl = cdiv(p->window * p->window, 64);
     if (npl <= 4)
-        hipLaunchKernelGGL(lk_track_kernel_4, grid, dim3(kLkThreads), 0, c->stream, djobs, n_jobs, dpyrs, dpts, n, K, oxy, ost, okp, diag);
+        hipLaunchKernelGGL(lk_track_kernel_4, grid, dim3(kLkThreads), 0, c->stream, ljobs.in(din), n_jobs, levels.in(din), pts.in(din), n, K, oxy.in(dout), ost.in(dout), okp.in(dout), diag);
     else if (npl <= 8)
-        hipLaunchKernelGGL(lk_track_kernel_8, grid, dim3(kLkThreads), 0, c->stream, djobs, n_jobs, dpyrs, dpts, n, K, oxy, ost, okp, diag);
+        hipLaunchKernelGGL(lk_track_kernel_8, grid, dim3(kLkThreads), 0, c->stream, ljobs.in(din), n_jobs, levels.in(din), pts.in(din), n, K, oxy.in(dout), ost.in(dout), okp.in(dout), diag);
     else
-        hipLaunchKernelGGL(lk_track_kernel_16, grid, dim3(kLkThreads), 0, c->stream, djobs, n_jobs, dpyrs, dpts, n, K, oxy, ost, okp, diag);
+        hipLaunchKernelGGL(lk_track_kernel_16, grid, dim3(kLkThreads), 0, c->stream, ljobs.in(din), n_jobs, levels.in(din), pts.in(din), n, K, oxy.in(dout), ost.in(dout), okp.in(dout), diag);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_lk_out.p, c->lk_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->lk_out.h.p, c->lk_out.d.p, out.bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    std::memcpy(next_xy, c->h_lk_out.p, sizeof(float2) * (size_t)n);
-    std::memcpy(status, c->h_lk_out.p + sizeof(float2) * (size_t)n, (size_t)n);
-    std::memcpy(kept, c->h_lk_out.p + sizeof(float2) * (size_t)n + n, (size_t)n);
+    const void* hout = c->lk_out.h.p;
+    std::memcpy(next_xy, oxy.in(hout), oxy.size());
+    std::memcpy(status, ost.in(hout), ost.size());
+    std::memcpy(kept, okp.in(hout), okp.size());
     return VELO_OK;
 }
 

@@ -45,6 +45,7 @@
 #include "velo_frame_kernels.h"
 #include "velo_map_kernels.h"
 #include "velo_block_list.h"
+#include "velo_stage_layout.h"
 
 using namespace velo;
 
@@ -55,7 +56,7 @@ extern "C" int velo_launch_lm_solve_ag(int nb_max, int n, void* stream, const vo
 // ---- the host side, in parts (round 6: one 4,700-line file before) ---------------------------------------------------------------------
 // ONE translation unit: the parts share unnamed-namespace helpers and static functions, and their order is the order of definition.
 // The kernels live elsewhere: every family is defined in a velo_unit_*.hip of its own (velo_kernels.h, "translation units").
-#include "velo_host_types.inl"   // error state, device buffers, the search index, TargetData and velo_ctx: what one context holds
+#include "velo_host_types.inl"   // error state, device and pinned buffers, staging pairs, the search index, TargetData and velo_ctx: what one context holds; what calls over a list of contexts share
 #include "velo_host_index.inl"   // launch timing, uploads, the index build (build_grid), the query list in patch order
 #include "velo_host_assoc.inl"   // pose scalars, parameter blocks, evaluation plan, seeds and askers, the association driver of one context (do_associate)
 #include "velo_host_lm.inl"   // peer checks, association timing read-out, the visual gate, the Levenberg-Marquardt driver of one context (do_solve)

@@ -111,6 +111,14 @@ struct PinBuf {
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 };
 
+// a pinned staging buffer and the device buffer it is copied to or from, reserved together, each by its own growth rule; where the
+// parts of such a buffer lie is a StageLayout's to say (velo_stage_layout.h)
+struct StagePair {
+    PinBuf<> h;
+    DevBuf<unsigned char> d;
+    int reserve(size_t bytes) { VELO_TRY(h.reserve(bytes)); return d.reserve(bytes); }
+};
+
 // One owner for every runtime handle that is not memory with a size: move-only, null by default, destroyed with its holder.  It converts to
 // the raw handle, so launch, record and wait sites read as they would with a bare one; put() is where a create call writes a fresh handle.
 template <typename H, auto Destroy>
@@ -489,10 +497,9 @@ struct velo_ctx {
     int tri_variant = 1;                 // 1 = one wave per landmark (default), 0 = one thread per landmark (VELO_TRI_VARIANT)
 
     // descriptor matching (velo_match_descriptors): buffers of its own, which no registration reads or writes
-    DevBuf<unsigned char> md_in;         // one staged upload: job table | the distinct descriptor rows (64 bytes each)
+    StagePair md_in;                     // one staged upload: job table | the distinct descriptor rows (64 bytes each)
     DevBuf<unsigned> md_keys;            // [sum n_query] nearest-row keys | [n_jobs] min_dist
     DevBuf<int> md_out;                  // train_idx | distance | pairs (per job from its first query) | {min_dist, n_kept} per job
-    PinBuf<> h_md_in;                    // pinned staging of md_in
     PinBuf<int> h_md_out;                // pinned landing of md_out
     int match_variant = 1;               // 1 = int8 MFMA (product), 0 = XOR + popcount (VELO_MATCH_VARIANT, diagnostics build only)
 
@@ -500,13 +507,10 @@ struct velo_ctx {
     // registration reads or writes
     LkSlot lk_slot[2];                   // current = lk_slot[lk_cur], previous = the other (velo_set_images rotates them)
     int lk_cur = 0;
-    DevBuf<unsigned char> lk_raw;        // unit table | level tables | the frame's raw images, one upload
-    PinBuf<> h_lk_raw;                   // pinned staging of lk_raw
-    Event lk_upload_ev;                  // h_lk_raw may be rewritten once this has passed
-    DevBuf<unsigned char> lk_in;         // job table | level tables | points
-    DevBuf<unsigned char> lk_out;        // next_xy | status | kept
-    PinBuf<> h_lk_in;
-    PinBuf<> h_lk_out;
+    StagePair lk_raw;                    // unit table | level tables | the frame's raw images, one upload
+    Event lk_upload_ev;                  // lk_raw.h may be rewritten once this has passed
+    StagePair lk_in;                     // job table | level tables | points
+    StagePair lk_out;                    // next_xy | status | kept
     DevBuf<unsigned long long> lk_diag;  // diagnostics build: iterations / entries per level (velo_diag_track_counters)
     bool lk_diag_init = false;
 
@@ -516,10 +520,8 @@ struct velo_ctx {
     DevBuf<unsigned> gf_cand;            // units x (h x w) candidate indices | units x (h x w) undecided at the finish
     DevBuf<unsigned long long> gf_keys;  // units x keys_cap accepted keys
     DevBuf<int> gf_hdr;                  // units x kGfHdrStride (a 128-byte line per unit)
-    DevBuf<unsigned char> gf_in;         // unit table | job table | existing points
-    DevBuf<unsigned char> gf_out;        // counts | per job xy, response, fresh
-    PinBuf<> h_gf_in;
-    PinBuf<> h_gf_out;
+    StagePair gf_in;                     // unit table | job table | existing points
+    StagePair gf_out;                    // counts | per job xy, response, fresh
     int gf_units = 0;                    // units of the last launch set this context led (velo_diag_detect_counters)
     // the resident landmark store (velo_landmarks_*): created by velo_landmarks_reset, buffers of its own, which no registration reads or writes
     std::shared_ptr<LmStore> lm;
@@ -527,7 +529,7 @@ struct velo_ctx {
     std::shared_ptr<FrStore> fr;
     // the resident pose graph (velo_graph_*): created by velo_graph_reset; nodes, edges and the solver's work buffers, which nothing else reads or writes
     std::shared_ptr<GraphStore> graph;
-    // front-end calls over several contexts (velo_api_track.inl): the FIRST context of a call lends its stream, staging and scratch buffers
+    // front-end calls over several contexts (fb_gather / fb_release below): the FIRST context of a call lends its stream, staging and scratch buffers
     Event fb_here_ev;                    // "everything enqueued on this context's stream so far": the lending stream waits for it
     Event fb_done_ev;                    // recorded on the lending stream after an asynchronous batch call: the other streams wait for it
 
@@ -580,3 +582,73 @@ struct velo_ctx {
     void timing_mark(TimingMark* m) const { if (timing >= 2) { m->kacc = kacc; m->klog_used = klog_used; m->assoc_events_used = assoc_events_used; } }
     void timing_rewind(const TimingMark& m) { if (timing >= 2) { kacc = m.kacc; klog_used = m.klog_used; assoc_events_used = m.assoc_events_used; } }
 };
+
+// ---- what the entry points over a LIST of contexts share (images, tracking, detection, the landmark and frame stores, the scan map):
+// the checks of the list, the hand-over between the contexts' streams, and the range checks of frame and camera indices ------------------
+namespace {
+constexpr int kFbMaxCtx = 256;             // contexts per call
+constexpr int kLmMaxFrame = 1 << 22;       // frame indices of the landmark store, the frame store, BA and the pose graph
+
+// the checks of the context list that read no context
+int fb_check_list(velo_ctx** ctxs, int n_ctx) {
+    if (!ctxs) return fail(VELO_ERR_INVALID, "null context list");
+    if (n_ctx < 1 || n_ctx > kFbMaxCtx) return fail(VELO_ERR_INVALID, "%d contexts; 1..%d", n_ctx, kFbMaxCtx);
+    for (int i = 0; i < n_ctx; i++) {
+        if (!ctxs[i]) return fail(VELO_ERR_INVALID, "context %d is null", i);
+        for (int j = 0; j < i; j++) if (ctxs[j] == ctxs[i]) return fail(VELO_ERR_INVALID, "batch entries %d and %d are the same context", j, i);
+    }
+    return VELO_OK;
+}
+
+int fb_check_devices(velo_ctx** ctxs, int n_ctx) {
+    for (int i = 1; i < n_ctx; i++)
+        if (ctxs[i]->device != ctxs[0]->device)
+            return fail(VELO_ERR_INVALID, "contexts on different devices: entry %d is on device %d, entry 0 on device %d", i, ctxs[i]->device, ctxs[0]->device);
+    return VELO_OK;
+}
+
+// job_ctx of the batch entries; null (the single-context entries pass it): every job runs on context 0
+int fb_check_job_ctx(const int32_t* job_ctx, int n_jobs, int n_ctx) {
+    if (!job_ctx) return VELO_OK;
+    for (int j = 0; j < n_jobs; j++)
+        if (job_ctx[j] < 0 || job_ctx[j] >= n_ctx) return fail(VELO_ERR_INVALID, "job %d: context index %d; 0..%d", j, job_ctx[j], n_ctx - 1);
+    return VELO_OK;
+}
+inline int fb_ctx_of(const int32_t* job_ctx, int j) { return job_ctx ? job_ctx[j] : 0; }
+
+// the lending stream runs after everything already enqueued on the stream of every other context in `used` (null: all)
+int fb_gather(velo_ctx** ctxs, int n_ctx, const std::vector<char>* used) {
+    velo_ctx* c0 = ctxs[0];
+    for (int i = 1; i < n_ctx; i++) {
+        if (used && !(*used)[i]) continue;
+        velo_ctx* c = ctxs[i];
+        if (c->stream == c0->stream) continue;
+        VELO_TRY(c->fb_here_ev.ensure());
+        HIP_TRY(hipEventRecord(c->fb_here_ev, c->stream));
+        HIP_TRY(hipStreamWaitEvent(c0->stream, c->fb_here_ev, 0));
+    }
+    return VELO_OK;
+}
+
+// whatever is enqueued later on any other context's stream runs after what the lending stream holds now
+int fb_release(velo_ctx** ctxs, int n_ctx) {
+    velo_ctx* c0 = ctxs[0];
+    if (n_ctx < 2) return VELO_OK;
+    VELO_TRY(c0->fb_done_ev.ensure());
+    HIP_TRY(hipEventRecord(c0->fb_done_ev, c0->stream));
+    for (int i = 1; i < n_ctx; i++)
+        if (ctxs[i]->stream != c0->stream) HIP_TRY(hipStreamWaitEvent(ctxs[i]->stream, c0->fb_done_ev, 0));
+    return VELO_OK;
+}
+
+// `name` v of [0, n); the message says where the value came from: nothing, "what: " (idx < 0) or "what idx: "
+int check_range(const char* name, int v, int n, const char* what, int idx) {
+    if (v >= 0 && v < n) return VELO_OK;
+    if (!what) return fail(VELO_ERR_INVALID, "%s %d; 0..%d", name, v, n - 1);
+    if (idx < 0) return fail(VELO_ERR_INVALID, "%s: %s %d; 0..%d", what, name, v, n - 1);
+    return fail(VELO_ERR_INVALID, "%s %d: %s %d; 0..%d", what, idx, name, v, n - 1);
+}
+inline int check_frame(int frame, const char* what = nullptr, int idx = -1) { return check_range("frame", frame, kLmMaxFrame, what, idx); }
+inline int check_cam(int cam, int n_cams, const char* what = nullptr, int idx = -1) { return check_range("camera", cam, n_cams, what, idx); }
+
+}  // namespace
