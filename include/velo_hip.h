@@ -761,6 +761,19 @@ int velo_landmarks_adjust_system(velo_ctx* ctx, const int32_t* frames, int32_t n
  *             w_i = i - first(i) in that order; 0 is the default, VELO_GRAPH_DEFAULT_MAX_WORK.  A graph whose order exceeds the cap is
  *             refused with VELO_ERR_INVALID before a pose moves (the message states the work, the cap and the widest row): the caller can
  *             fall back to the CG.  Any other reserved[0] and a negative reserved[1] are refused with VELO_ERR_INVALID.
+ *   weighted  velo_graph_add_edges_weighted gives an edge a 6 x 6 information W and, optionally, a robust loss.  For edge e let r be the
+ *             UNWEIGHTED 6-vector pose_vec(Z^-1 . T_from^-1 . T_to) (rotation, then translation) and A, B its Jacobians with respect to
+ *             the two nodes.  s = r^T W r, W symmetric positive definite in the residual's order.  The edge's cost term is rho(s) / 2:
+ *             rho(s) = s for the trivial loss (loss_scale 0), rho(s) = b ln(1 + s / b), b = a^2, for Cauchy(a) (loss_scale a > 0;
+ *             ceres::CauchyLoss(a)).  The normal-equation blocks are rho'(s) . A^T W A, rho'(s) . B^T W B, rho'(s) . A^T W B and the
+ *             gradients rho'(s) . A^T W r, rho'(s) . B^T W r: Ceres' corrector in its rho'' <= 0 branch (residual and Jacobian scaled
+ *             by sqrt(rho'), alpha = 0) -- Cauchy's rho'' is negative everywhere, so this is Ceres' behaviour, not an approximation.
+ *             W is stored as its Cholesky factor, W = L L^T, and s is formed as |L^T r|^2.  The trust-region controller, both linear
+ *             solvers, velo_graph_system, the summary's costs and the trace see the weighted, robustified problem.  Once a store holds
+ *             a weighted edge, a scalar edge is info . I with the trivial loss there, whether it was added before or after; the two
+ *             entries mix freely and edge order is addition order.  A store that never saw a weighted edge runs the scalar kernel
+ *             and gives the bytes it always gave; velo_graph_reset returns a store to that state.  The reference's noisy6 (isotropic,
+ *             trivial loss) stays the default; matrix information and Cauchy are this library's additions.
  * velo_graph_reset creates or empties the store; edge_capacity: edges the device arrays hold before they are first reallocated (0: the
  * default, 4096); they grow by doubling.  Frames < 2^22.  Refused before anything changes: VELO_ERR_INVALID for a NULL argument, a frame
  * out of range, from == to, a non-finite pose or z, an info that is not positive and finite, fixed frames that are not ascending and
@@ -806,6 +819,24 @@ int velo_graph_set_pose(velo_ctx* ctx, int32_t frame, const double pose6[6]);
 int velo_graph_set_poses(velo_ctx* ctx, int32_t first, int32_t n, const double* poses);
 /* appends n edges: from [n], to [n], z [n][6], info [n] */
 int velo_graph_add_edges(velo_ctx* ctx, int32_t n, const int32_t* from, const int32_t* to, const double* z, const double* info);
+/* n edges with a full information matrix and, optionally, a robust loss.
+ * info21: [n][21], the upper triangle of W row by row ((0,0),(0,1)..(0,5),(1,1)..).
+ * loss_scale: [n] or NULL (all trivial): 0 = trivial, a > 0 = Cauchy(a) on s = r^T W r.
+ * Refuses what velo_graph_add_edges refuses, and with VELO_ERR_INVALID a NULL info21, a non-finite entry, a W whose Cholesky
+ * factorisation in double meets a pivot that is not positive and finite (the message names the edge's index in the call), a loss_scale
+ * that is negative or not finite.  A refused call changes nothing. */
+int velo_graph_add_edges_weighted(velo_ctx* ctx, int32_t n, const int32_t* from, const int32_t* to, const double* z, const double* info21,
+                                  const double* loss_scale);
+/* Per edge, in the order the edges were added (both entries count), at the STORED poses: chi2[i] = s, weight[i] = rho'(s) (1 for a
+ * trivial edge; a scalar-only store answers info . |r|^2 and 1, and stays scalar-only).  Nothing changes.  Either output may be NULL.
+ * VELO_ERR_STATE without a store or for an end without a pose, VELO_ERR_INVALID for a range outside [0, edges]. */
+int velo_graph_edge_stats(velo_ctx* ctx, int32_t first, int32_t n, double* chi2, double* weight);
+/* A registration's information as an edge's: a pure host function, no context, no GPU.  z: the registration's result; JtJ36: its 6 x 6
+ * at that result, as velo_evaluate returns it.  Writes W as info21: W = Bz^-T H Bz^-1, Bz = blockdiag(Rz^T J_l(w_z), Rz^T), the
+ * Jacobian of the edge residual with respect to the pose 6-vector at x = z; H is symmetrised as (H + H^T) / 2 first.  VELO_ERR_INVALID
+ * for a NULL or non-finite input.  Definiteness is not tested here: velo_graph_add_edges_weighted does that, and a caller may add
+ * eps . I in between. */
+int velo_graph_edge_information(const double z[6], const double JtJ36[36], double info21[21]);
 /* fixed: n_fixed frames, ascending and distinct, each with a pose.  params may be NULL (the defaults), summary may be NULL. */
 int velo_graph_optimize(velo_ctx* ctx, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, velo_graph_summary* summary);
 /* poses of first .. first + n - 1 to out [n][6]; VELO_ERR_STATE when one of them has no pose */

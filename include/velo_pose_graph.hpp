@@ -6,6 +6,7 @@
 //     velo_hip::PoseGraph graph(ctx);
 //     graph.setPose(frame, ceres_poses_vec[frame]);                 // a new node, or a node's new value
 //     graph.addEdge(frame - dframe, frame, dpose16, 1.0);            // what frameToFrame returned, row-major 4 x 4 (or its 6-vector)
+//     graph.addRegistration(loop_from, frame, z6, JtJ36, 2.0);       // a loop closure with velo_evaluate's 6 x 6 and Cauchy(2)
 //     graph.optimize(fixed);                                         // fixed = {0}: the reference's prior on the first node
 //     graph.optimize(fixed, &summary, 0, VELO_GRAPH_SOLVER_ENVELOPE); // the same with the exact envelope solver: a whole drive
 //     graph.poses(0, n, &flat);                                      // n x 6, for velo_landmarks_set_pose / velo_map_set_pose
@@ -47,6 +48,28 @@ public:
         if (from.empty()) return VELO_OK;
         std::vector<int32_t> a(from.begin(), from.end()), b(to.begin(), to.end());
         return velo_graph_add_edges(ctx_, (int32_t)a.size(), &a[0], &b[0], &z[0], &info[0]);
+    }
+
+    // an edge with a 6 x 6 information (info21: W's upper triangle, row by row) and a loss: 0 = trivial, a > 0 = Cauchy(a) on r^T W r
+    int addEdgeWeighted(int from, int to, const double z6[6], const double info21[21], double loss_scale = 0.0) {
+        const int32_t a = from, b = to;
+        return velo_graph_add_edges_weighted(ctx_, 1, &a, &b, z6, info21, &loss_scale);
+    }
+    // a registration as an edge: z6 its result, JtJ36 its 6 x 6 at that result as velo_evaluate returns it (velo_graph_edge_information)
+    int addRegistration(int from, int to, const double z6[6], const double JtJ36[36], double loss_scale = 0.0) {
+        double info21[21];
+        const int st = velo_graph_edge_information(z6, JtJ36, info21);
+        return st != VELO_OK ? st : addEdgeWeighted(from, to, z6, info21, loss_scale);
+    }
+    // chi2 = r^T W r and weight = rho'(chi2) of the edges first .. first + n - 1 at the stored poses, in the order they were added
+    int edgeStats(int first, int n, std::vector<double>* chi2, std::vector<double>* weight) const {
+        std::vector<double> s((size_t)(n > 0 ? n : 0) + 1), w(s.size());
+        const int st = velo_graph_edge_stats(ctx_, first, n, &s[0], &w[0]);
+        if (st != VELO_OK) return st;
+        s.resize((size_t)n); w.resize((size_t)n);
+        if (chi2) chi2->swap(s);
+        if (weight) weight->swap(w);
+        return VELO_OK;
     }
 
     // refines every node that has a pose and is not in `fixed` (ascending frame numbers).  solver: VELO_GRAPH_SOLVER_CG (what params

@@ -379,6 +379,9 @@ SIGNATURES = {
     "velo_graph_set_pose": (C.c_int, [_ctx, C.c_int32, _dp]),
     "velo_graph_set_poses": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p]),
     "velo_graph_add_edges": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "velo_graph_add_edges_weighted": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "velo_graph_edge_stats": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "velo_graph_edge_information": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "velo_graph_optimize": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(VeloGraphParams), _P(VeloGraphSummary)]),
     "velo_graph_get_poses": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p]),
     "velo_graph_info": (C.c_int, [_ctx, C.c_void_p]),
@@ -892,6 +895,36 @@ class Context:
             raise ValueError("graph_add_edges: one from, to, z and info per edge")
         vp = lambda v: C.c_void_p(v.ctypes.data) if v.size else None   # noqa: E731
         self._check(self._lib.velo_graph_add_edges(self._h, len(a), vp(a), vp(b), vp(zz), vp(w)))
+
+    def graph_add_edges_weighted(self, frm, to, z, info, loss_scale=None):
+        """appends edges with a 6 x 6 information W each and, optionally, a robust loss.  info: [n, 6, 6] (symmetric) or [n, 21], W's
+        upper triangle row by row; loss_scale [n] or None (all trivial): 0 = trivial, a > 0 = Cauchy(a) on s = r^T W r."""
+        a = np.ascontiguousarray(np.asarray(frm, dtype=np.int32).reshape(-1))
+        b = np.ascontiguousarray(np.asarray(to, dtype=np.int32).reshape(-1))
+        zz = np.ascontiguousarray(np.asarray(z, dtype=np.float64).reshape(-1, 6))
+        w = np.asarray(info, dtype=np.float64)
+        if w.ndim == 3 and w.shape[1:] == (6, 6):
+            if not np.array_equal(w, np.transpose(w, (0, 2, 1))):
+                raise ValueError("graph_add_edges_weighted: an information matrix is not symmetric")
+            w = w[:, np.triu_indices(6)[0], np.triu_indices(6)[1]]
+        elif not (w.ndim == 2 and w.shape[1] == 21):
+            raise ValueError("graph_add_edges_weighted: info is [n, 6, 6] or [n, 21]")
+        w = np.ascontiguousarray(w)
+        ls = None if loss_scale is None else np.ascontiguousarray(np.asarray(loss_scale, dtype=np.float64).reshape(-1))
+        if not len(a) == len(b) == len(zz) == len(w) or (ls is not None and len(ls) != len(a)):
+            raise ValueError("graph_add_edges_weighted: one from, to, z, info and loss_scale per edge")
+        vp = lambda v: C.c_void_p(v.ctypes.data) if v is not None and v.size else None   # noqa: E731
+        self._check(self._lib.velo_graph_add_edges_weighted(self._h, len(a), vp(a), vp(b), vp(zz), vp(w), vp(ls)))
+
+    def graph_edge_stats(self, first: int = 0, n: Optional[int] = None):
+        """(chi2, weight) of the edges first .. first + n - 1 (None: to the last) at the stored poses, in the order they were added:
+        chi2 = r^T W r, weight = rho'(chi2), 1 for a trivial loss.  Nothing changes."""
+        if n is None:
+            n = self.graph_info()["n_edges"] - int(first)
+        chi2 = np.zeros(max(int(n), 1), dtype=np.float64)
+        weight = np.zeros(max(int(n), 1), dtype=np.float64)
+        self._check(self._lib.velo_graph_edge_stats(self._h, int(first), int(n), C.c_void_p(chi2.ctypes.data), C.c_void_p(weight.ctypes.data)))
+        return chi2[:max(int(n), 0)], weight[:max(int(n), 0)]
 
     @staticmethod
     def _graph_params(cg_tolerance, cg_max_iterations, linear_solver="cg", max_work=None):
@@ -1898,6 +1931,22 @@ def pose_mat_to_vec(T) -> np.ndarray:
     x = np.zeros(6)
     lib.velo_pose_mat_to_vec(_ptr(Tv), _ptr(x))
     return x
+
+
+def graph_edge_information(z, JtJ) -> np.ndarray:
+    """velo_graph_edge_information: the 6 x 6 information W of the edge a registration makes (a host function: no context, no GPU).
+    z: the registration's result (6); JtJ: its 6 x 6 at that result, as evaluate returns it."""
+    zz = _dvec(z, 6)
+    H = np.ascontiguousarray(np.asarray(JtJ, dtype=np.float64).reshape(36))
+    out = np.zeros(21, dtype=np.float64)
+    lib = load_library()
+    st = lib.velo_graph_edge_information(C.c_void_p(zz.ctypes.data), C.c_void_p(H.ctypes.data), C.c_void_p(out.ctypes.data))
+    if st != 0:
+        msg = lib.velo_last_error()
+        raise VeloError(f"velo status {st}: {msg.decode() if msg else ''}")
+    W = np.zeros((6, 6))
+    W[np.triu_indices(6)] = out
+    return W + np.triu(W, 1).T
 
 
 def graph_order(n_nodes: int, a, b):

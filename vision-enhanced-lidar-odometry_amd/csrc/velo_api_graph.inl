@@ -10,6 +10,10 @@ struct GraphStore {
     // device: the edges
     DevBuf<int> from, to;
     DevBuf<double> z, info;
+    // a store that has seen velo_graph_add_edges_weighted: per edge the Cholesky factor of its 6 x 6 information (21 doubles) and its loss
+    // scale; a scalar edge is info . I with the trivial loss there (graph_promote_kernel), and `info` is no longer read for any edge
+    DevBuf<double> winfo, wloss, estat;
+    bool weighted = false;
     size_t n_edges = 0, edge_cap = 0;
     int edge_reallocs = 0, n_optimized = 0;
     // the nodes: [2][frame_cap][6] on the device (current / candidate), [frame_cap][6] pinned
@@ -50,6 +54,7 @@ velo_graph_params graph_params(const velo_graph_params* params) {     // a call'
 
 struct GraphCall {
     GraphArgs A;
+    GraphWeights W = {nullptr, nullptr, nullptr};        // of a weighted store
     std::vector<int32_t> free_nodes;
     int n_free = 0, E = 0;
     bool envelope = false;                               // set by the caller: graph_begin then orders the free nodes and checks the work
@@ -168,6 +173,13 @@ int graph_check(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
     return VELO_OK;
 }
 
+// the linearisation of buffer `which`: a store that has never seen a weighted edge runs the scalar kernel
+void graph_linearize(velo_ctx* c, const GraphArgs& A, const GraphWeights& W, int which) {
+    const dim3 grid((unsigned)std::max(1, cdiv(A.E, kGrThreads)));
+    if (W.winfo) hipLaunchKernelGGL(graph_linearize_weighted_kernel, grid, dim3(kGrThreads), 0, c->stream, A, W, which);
+    else hipLaunchKernelGGL(graph_linearize_kernel, grid, dim3(kGrThreads), 0, c->stream, A, which);
+}
+
 // the free nodes, their incidence lists (ints only), the poses to both buffers; then the system at the stored state: linearise,
 // assemble, reduce
 int graph_begin(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params& params, GraphCall* call) {
@@ -230,6 +242,7 @@ int graph_begin(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
     VELO_TRY(S.inc.reserve(2 * inc.size() + 1));
     VELO_TRY(S.x.reserve(2 * F * 6 + 1));
     VELO_TRY(S.blk.reserve(2 * E * kGrBlk + 1));
+    if (S.weighted) VELO_TRY(S.estat.reserve(2 * E * 2 + 1));
     VELO_TRY(S.nd.reserve(2 * n * kGrNode + 1));
     VELO_TRY(S.vec.reserve(n * kGraphVec + 1));
     VELO_TRY(S.part.reserve(4 * (size_t)nb));
@@ -284,9 +297,10 @@ int graph_begin(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
         A.env_perm = S.env_idx.p; A.env_pos = S.env_idx.p + n; A.env_first = S.env_idx.p + 2 * n; A.env_rowptr = S.env_idx.p + 3 * n;
         A.env_last = S.env_idx.p + 4 * n + 1; A.env = S.env.p;
     }
+    if (S.weighted) { call->W.winfo = S.winfo.p; call->W.loss = S.wloss.p; call->W.estat = S.estat.p; }
     A.cg_tol2 = params.cg_tolerance * params.cg_tolerance;
     A.lm = lm_params(c->P);
-    if (E) hipLaunchKernelGGL(graph_linearize_kernel, dim3((unsigned)cdiv((int)E, kGrThreads)), dim3(kGrThreads), 0, c->stream, A, 0);
+    if (E) graph_linearize(c, A, call->W, 0);
     if (n) hipLaunchKernelGGL(graph_assemble_kernel, dim3((unsigned)nb), dim3(kGrThreads), 0, c->stream, A, 0, 0);
     hipLaunchKernelGGL(graph_reduce_kernel, dim3(kGrRed), dim3(256), 0, c->stream, A, 0);
     HIP_TRY(hipGetLastError());
@@ -323,6 +337,99 @@ int graph_put_poses(velo_ctx* c, int32_t first, int32_t n, const double* poses, 
     }
     std::memcpy(S.h_x.p + (size_t)first * 6, poses, sizeof(double) * 6 * (size_t)n);
     for (size_t f = (size_t)first; f < last; f++) if (!S.pose_set[f]) { S.pose_set[f] = 1; S.n_nodes++; }
+    return VELO_OK;
+}
+
+// what every entry that appends edges refuses of edge e's ends and measurement
+int graph_check_edge(int e, const int32_t* from, const int32_t* to, const double* z) {
+    if (from[e] < 0 || from[e] >= kLmMaxFrame || to[e] < 0 || to[e] >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "edge %d: frames %d -> %d; 0..%d", e, from[e], to[e], kLmMaxFrame - 1);
+    if (from[e] == to[e]) return fail(VELO_ERR_INVALID, "edge %d: from == to (%d)", e, from[e]);
+    for (int k = 0; k < 6; k++) if (!std::isfinite(z[6 * (size_t)e + k])) return fail(VELO_ERR_INVALID, "edge %d: z[%d] is not finite", e, k);
+    return VELO_OK;
+}
+
+// W = L L^T in double from W's upper triangle (row by row); L: the lower triangle, row-major packed.  False for a pivot that is not
+// positive and finite.
+bool graph_host_chol6(const double* upper21, double* L21) {
+    double M[36];
+    for (int i = 0, o = 0; i < 6; i++)
+        for (int j = i; j < 6; j++, o++) M[i * 6 + j] = M[j * 6 + i] = upper21[o];
+    for (int j = 0; j < 6; j++) {
+        double dj = M[j * 6 + j];
+        for (int k = 0; k < j; k++) dj -= M[j * 6 + k] * M[j * 6 + k];
+        if (!(dj > 0.0) || !std::isfinite(dj)) return false;
+        const double l = std::sqrt(dj);
+        M[j * 6 + j] = l;
+        for (int i = j + 1; i < 6; i++) {
+            double acc = M[i * 6 + j];
+            for (int k = 0; k < j; k++) acc -= M[i * 6 + k] * M[j * 6 + k];
+            M[i * 6 + j] = acc / l;
+            if (!std::isfinite(M[i * 6 + j])) return false;
+        }
+    }
+    for (int i = 0, o = 0; i < 6; i++)
+        for (int j = 0; j <= i; j++, o++) L21[o] = M[i * 6 + j];
+    return true;
+}
+
+// appends n checked edges: scalar ones (info) or weighted ones (L: 21 doubles per edge, loss: one).  The first weighted edge turns the
+// store into a weighted one: its columns are allocated and the scalar edges it holds are restated there.
+int graph_append(velo_ctx* c, int32_t n, const int32_t* from, const int32_t* to, const double* z, const double* info, const double* L, const double* loss) {
+    GraphStore& S = *c->graph;
+    if (S.n_edges + (size_t)n > (size_t)(1 << 30)) return fail(VELO_ERR_INVALID, "more than 2^30 edges");
+    HIP_TRY(hipSetDevice(c->device));
+    if (L && !S.weighted) {
+        VELO_TRY(S.winfo.reserve(S.edge_cap * 21));
+        VELO_TRY(S.wloss.reserve(S.edge_cap));
+        if (S.n_edges) {
+            hipLaunchKernelGGL(graph_promote_kernel, dim3((unsigned)cdiv((int)S.n_edges, kGrThreads)), dim3(kGrThreads), 0, c->stream, S.info.p, S.winfo.p, S.wloss.p, 0, (int)S.n_edges);
+            HIP_TRY(hipGetLastError());
+        }
+        S.weighted = true;
+    }
+    const size_t need = S.n_edges + (size_t)n;
+    if (need > S.edge_cap) {                                           // grow by doubling; what is there is kept
+        size_t cap = S.edge_cap;
+        while (cap < need) cap *= 2;
+        VELO_TRY(lm_regrow(c, &S.from, S.n_edges, cap, 0));
+        VELO_TRY(lm_regrow(c, &S.to, S.n_edges, cap, 0));
+        VELO_TRY(lm_regrow(c, &S.z, S.n_edges * 6, cap * 6, 0));
+        VELO_TRY(lm_regrow(c, &S.info, S.n_edges, cap, 0));
+        if (S.weighted) {
+            VELO_TRY(lm_regrow(c, &S.winfo, S.n_edges * 21, cap * 21, 0));
+            VELO_TRY(lm_regrow(c, &S.wloss, S.n_edges, cap, 0));
+        }
+        S.edge_cap = cap;
+        S.edge_reallocs++;
+    }
+    const size_t nz = (size_t)n, per = info ? 1 : 22, bytes = nz * (2 * sizeof(int32_t) + (6 + per) * sizeof(double));
+    VELO_TRY(S.in_ev.wait_or_create());
+    VELO_TRY(S.h_in.reserve(bytes));
+    double* hz = (double*)S.h_in.p;
+    double* hi = hz + 6 * nz;                                          // info [n], or L [n][21] and the loss scales [n] behind it
+    int32_t* hf = (int32_t*)(hi + per * nz);
+    int32_t* ht = hf + nz;
+    std::memcpy(hz, z, sizeof(double) * 6 * nz);
+    if (info) std::memcpy(hi, info, sizeof(double) * nz);
+    else { std::memcpy(hi, L, sizeof(double) * 21 * nz); std::memcpy(hi + 21 * nz, loss, sizeof(double) * nz); }
+    std::memcpy(hf, from, sizeof(int32_t) * nz);
+    std::memcpy(ht, to, sizeof(int32_t) * nz);
+    HIP_TRY(hipMemcpyAsync(S.z.p + 6 * S.n_edges, hz, sizeof(double) * 6 * nz, hipMemcpyHostToDevice, c->stream));
+    if (info) HIP_TRY(hipMemcpyAsync(S.info.p + S.n_edges, hi, sizeof(double) * nz, hipMemcpyHostToDevice, c->stream));
+    else {
+        HIP_TRY(hipMemcpyAsync(S.winfo.p + 21 * S.n_edges, hi, sizeof(double) * 21 * nz, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(S.wloss.p + S.n_edges, hi + 21 * nz, sizeof(double) * nz, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(S.from.p + S.n_edges, hf, sizeof(int32_t) * nz, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(S.to.p + S.n_edges, ht, sizeof(int32_t) * nz, hipMemcpyHostToDevice, c->stream));
+    if (info && S.weighted) {                                          // a scalar edge in a weighted store
+        hipLaunchKernelGGL(graph_promote_kernel, dim3((unsigned)cdiv(n, kGrThreads)), dim3(kGrThreads), 0, c->stream, S.info.p, S.winfo.p, S.wloss.p, (int)S.n_edges, n);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(S.in_ev, c->stream));
+    S.h_from.insert(S.h_from.end(), from, from + n);
+    S.h_to.insert(S.h_to.end(), to, to + n);
+    S.n_edges = need;
     return VELO_OK;
 }
 
@@ -365,46 +472,103 @@ int velo_graph_add_edges(velo_ctx* c, int32_t n, const int32_t* from, const int3
     if (n < 0) return fail(VELO_ERR_INVALID, "negative edge count");
     if (n > 0 && (!from || !to || !z || !info)) return fail(VELO_ERR_INVALID, "null edge array");
     for (int e = 0; e < n; e++) {
-        if (from[e] < 0 || from[e] >= kLmMaxFrame || to[e] < 0 || to[e] >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "edge %d: frames %d -> %d; 0..%d", e, from[e], to[e], kLmMaxFrame - 1);
-        if (from[e] == to[e]) return fail(VELO_ERR_INVALID, "edge %d: from == to (%d)", e, from[e]);
-        for (int k = 0; k < 6; k++) if (!std::isfinite(z[6 * (size_t)e + k])) return fail(VELO_ERR_INVALID, "edge %d: z[%d] is not finite", e, k);
+        VELO_TRY(graph_check_edge(e, from, to, z));
         if (!(info[e] > 0.0 && std::isfinite(info[e]))) return fail(VELO_ERR_INVALID, "edge %d: info must be positive and finite", e);
     }
     VELO_TRY(graph_need_store(c, "velo_graph_add_edges"));
     if (n == 0) return VELO_OK;
-    GraphStore& S = *c->graph;
-    if (S.n_edges + (size_t)n > (size_t)(1 << 30)) return fail(VELO_ERR_INVALID, "more than 2^30 edges");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t need = S.n_edges + (size_t)n;
-    if (need > S.edge_cap) {                                           // grow by doubling; what is there is kept
-        size_t cap = S.edge_cap;
-        while (cap < need) cap *= 2;
-        VELO_TRY(lm_regrow(c, &S.from, S.n_edges, cap, 0));
-        VELO_TRY(lm_regrow(c, &S.to, S.n_edges, cap, 0));
-        VELO_TRY(lm_regrow(c, &S.z, S.n_edges * 6, cap * 6, 0));
-        VELO_TRY(lm_regrow(c, &S.info, S.n_edges, cap, 0));
-        S.edge_cap = cap;
-        S.edge_reallocs++;
+    return graph_append(c, n, from, to, z, info, nullptr, nullptr);
+}
+
+int velo_graph_add_edges_weighted(velo_ctx* c, int32_t n, const int32_t* from, const int32_t* to, const double* z, const double* info21, const double* loss_scale) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (n < 0) return fail(VELO_ERR_INVALID, "negative edge count");
+    if (n > 0 && (!from || !to || !z || !info21)) return fail(VELO_ERR_INVALID, "null edge array");
+    std::vector<double> L(21 * (size_t)std::max(n, 0));
+    for (int e = 0; e < n; e++) {
+        VELO_TRY(graph_check_edge(e, from, to, z));
+        const double* u = info21 + 21 * (size_t)e;
+        for (int k = 0; k < 21; k++) if (!std::isfinite(u[k])) return fail(VELO_ERR_INVALID, "edge %d: info21[%d] is not finite", e, k);
+        if (!graph_host_chol6(u, L.data() + 21 * (size_t)e)) return fail(VELO_ERR_INVALID, "edge %d: its information matrix is not positive definite (the Cholesky factorisation met a pivot that is not positive and finite)", e);
+        if (loss_scale && !(loss_scale[e] >= 0.0 && std::isfinite(loss_scale[e]))) return fail(VELO_ERR_INVALID, "edge %d: loss_scale must be 0 (trivial) or positive and finite (Cauchy)", e);
     }
-    const size_t nz = (size_t)n, bytes = nz * (2 * sizeof(int32_t) + 7 * sizeof(double));
-    VELO_TRY(S.in_ev.wait_or_create());
-    VELO_TRY(S.h_in.reserve(bytes));
-    double* hz = (double*)S.h_in.p;
-    double* hi = hz + 6 * nz;
-    int32_t* hf = (int32_t*)(hi + nz);
-    int32_t* ht = hf + nz;
-    std::memcpy(hz, z, sizeof(double) * 6 * nz);
-    std::memcpy(hi, info, sizeof(double) * nz);
-    std::memcpy(hf, from, sizeof(int32_t) * nz);
-    std::memcpy(ht, to, sizeof(int32_t) * nz);
-    HIP_TRY(hipMemcpyAsync(S.z.p + 6 * S.n_edges, hz, sizeof(double) * 6 * nz, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(S.info.p + S.n_edges, hi, sizeof(double) * nz, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(S.from.p + S.n_edges, hf, sizeof(int32_t) * nz, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(S.to.p + S.n_edges, ht, sizeof(int32_t) * nz, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipEventRecord(S.in_ev, c->stream));
-    S.h_from.insert(S.h_from.end(), from, from + n);
-    S.h_to.insert(S.h_to.end(), to, to + n);
-    S.n_edges = need;
+    VELO_TRY(graph_need_store(c, "velo_graph_add_edges_weighted"));
+    if (n == 0) return VELO_OK;
+    std::vector<double> zero;
+    if (!loss_scale) { zero.assign((size_t)n, 0.0); loss_scale = zero.data(); }
+    return graph_append(c, n, from, to, z, nullptr, L.data(), loss_scale);
+}
+
+int velo_graph_edge_stats(velo_ctx* c, int32_t first, int32_t n, double* chi2, double* weight) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    VELO_TRY(graph_need_store(c, "velo_graph_edge_stats"));
+    GraphStore& S = *c->graph;
+    if (first < 0 || n < 0 || (size_t)first + (size_t)n > S.n_edges) return fail(VELO_ERR_INVALID, "velo_graph_edge_stats: edges %d .. %lld; the store holds %zu", first, (long long)first + n - 1, S.n_edges);
+    for (size_t e = (size_t)first; e < (size_t)first + (size_t)n; e++) {
+        const int32_t ends[2] = {S.h_from[e], S.h_to[e]};
+        for (int k = 0; k < 2; k++)
+            if ((size_t)ends[k] >= S.pose_set.size() || !S.pose_set[(size_t)ends[k]]) return fail(VELO_ERR_STATE, "velo_graph_edge_stats: edge %zu ends at frame %d, which has no pose", e, ends[k]);
+    }
+    if (n == 0) return VELO_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    // the edges first .. first + n - 1 as a graph of their own: the stored poses to buffer 0, one linearisation there, which moves nothing
+    const size_t F = S.frame_cap, E = S.n_edges, nz = (size_t)n;
+    VELO_TRY(S.x.reserve(2 * F * 6 + 1));
+    VELO_TRY(S.blk.reserve(2 * E * kGrBlk + 1));
+    if (S.weighted) VELO_TRY(S.estat.reserve(2 * E * 2 + 1));
+    VELO_TRY(S.h_out.reserve(sizeof(GraphRecord) + sizeof(double) * std::max(F * 6, 2 * nz) + 64));
+    HIP_TRY(hipMemcpyAsync(S.x.p, S.h_x.p, sizeof(double) * F * 6, hipMemcpyHostToDevice, c->stream));
+    GraphArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.from = S.from.p + first; A.to = S.to.p + first; A.z = S.z.p + 6 * (size_t)first; A.info = S.info.p + first;
+    A.x = S.x.p; A.x_stride = F * 6; A.blk = S.blk.p; A.E = n;
+    GraphWeights W = {nullptr, nullptr, nullptr};
+    if (S.weighted) { W.winfo = S.winfo.p + 21 * (size_t)first; W.loss = S.wloss.p + first; W.estat = S.estat.p; }
+    graph_linearize(c, A, W, 0);
+    HIP_TRY(hipGetLastError());
+    double* out = (double*)S.h_out.p;
+    if (S.weighted) HIP_TRY(hipMemcpyAsync(out, S.estat.p, sizeof(double) * 2 * nz, hipMemcpyDeviceToHost, c->stream));
+    else HIP_TRY(hipMemcpy2DAsync(out, sizeof(double), S.blk.p + kGrCost, sizeof(double) * kGrBlk, sizeof(double), nz, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < nz; k++) {                                  // a scalar store's cost term is info |r|^2 / 2 and its loss trivial
+        if (chi2) chi2[k] = S.weighted ? out[2 * k] : 2.0 * out[k];
+        if (weight) weight[k] = S.weighted ? out[2 * k + 1] : 1.0;
+    }
+    return VELO_OK;
+}
+
+int velo_graph_edge_information(const double z[6], const double JtJ36[36], double info21[21]) {
+    if (!z || !JtJ36 || !info21) return fail(VELO_ERR_INVALID, "velo_graph_edge_information: null argument");
+    for (int k = 0; k < 6; k++) if (!std::isfinite(z[k])) return fail(VELO_ERR_INVALID, "velo_graph_edge_information: z[%d] is not finite", k);
+    for (int k = 0; k < 36; k++) if (!std::isfinite(JtJ36[k])) return fail(VELO_ERR_INVALID, "velo_graph_edge_information: JtJ36[%d] is not finite", k);
+    // Bz^-1 = blockdiag(J_r^-1(w_z), Rz): Rz^T J_l(w) is the right Jacobian J_r(w), and J_r^-1 = I + K / 2 + (1 / t^2 - cot(t / 2) / (2 t)) K^2
+    double T[16], M[36];
+    VELO_TRY(velo_pose_vec_to_mat(z, T));
+    const double x = z[0], y = z[1], w = z[2], t2 = x * x + y * y + w * w;
+    double coef;
+    if (t2 > 1e-6) {
+        const double t = std::sqrt(t2);
+        coef = 1.0 / t2 - std::cos(0.5 * t) / (2.0 * t * std::sin(0.5 * t));
+    } else coef = 1.0 / 12.0 + t2 / 720.0;
+    const double Ji[9] = {1.0 + coef * (x * x - t2), -0.5 * w + coef * x * y, 0.5 * y + coef * x * w,
+                          0.5 * w + coef * x * y, 1.0 + coef * (y * y - t2), -0.5 * x + coef * y * w,
+                          -0.5 * y + coef * x * w, 0.5 * x + coef * y * w, 1.0 + coef * (w * w - t2)};
+    for (int k = 0; k < 36; k++) M[k] = 0.0;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) { M[i * 6 + j] = Ji[i * 3 + j]; M[(3 + i) * 6 + 3 + j] = T[i * 4 + j]; }
+    double HM[36];                                                     // ((H + H^T) / 2) M, then M^T of it
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) {
+            double acc = 0.0;
+            for (int k = 0; k < 6; k++) acc += (0.5 * (JtJ36[i * 6 + k] + JtJ36[k * 6 + i])) * M[k * 6 + j];
+            HM[i * 6 + j] = acc;
+        }
+    for (int i = 0, o = 0; i < 6; i++)
+        for (int j = i; j < 6; j++, o++) {
+            double a = 0.0, b = 0.0;                                   // (i, j) and (j, i), which differ by rounding only
+            for (int k = 0; k < 6; k++) { a += M[k * 6 + i] * HM[k * 6 + j]; b += M[k * 6 + j] * HM[k * 6 + i]; }
+            info21[o] = 0.5 * (a + b);
+        }
     return VELO_OK;
 }
 
@@ -480,7 +644,7 @@ int velo_graph_optimize(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, cons
     sum.initial_cost = T.cost;
     if (n == 0 || E == 0) tr_stop(&T, VELO_CONVERGENCE);
     int cur = 0;
-    const unsigned g_nodes = (unsigned)nb, g_edges = (unsigned)std::max(1, cdiv(E, kGrThreads));
+    const unsigned g_nodes = (unsigned)nb;
     while (!T.done && !tr_head(Q, &T)) {
         // the linear step: the envelope's fill, factor, solve and one record; or CG in batches, one record per batch
         HIP_TRY(hipMemsetAsync(S.rec.p, 0, sizeof(GraphRecord), c->stream));
@@ -507,7 +671,7 @@ int velo_graph_optimize(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, cons
         bool ok = rec->bad == 0;
         if (ok) {                                                      // the candidate, linearised and reduced
             hipLaunchKernelGGL(graph_step_kernel, dim3(g_nodes), dim3(kGrThreads), 0, c->stream, A, k, cur);
-            hipLaunchKernelGGL(graph_linearize_kernel, dim3(g_edges), dim3(kGrThreads), 0, c->stream, A, cur ^ 1);
+            graph_linearize(c, A, call.W, cur ^ 1);
             hipLaunchKernelGGL(graph_assemble_kernel, dim3(g_nodes), dim3(kGrThreads), 0, c->stream, A, cur ^ 1, 1);
             hipLaunchKernelGGL(graph_reduce_kernel, dim3(kGrRed), dim3(256), 0, c->stream, A, cur ^ 1);
             HIP_TRY(hipGetLastError());

@@ -9,6 +9,8 @@
 //     (c H c + D / mu) y = -c g,      H = J^T J block-sparse: a 6 x 6 diagonal block per free node, one off-diagonal block per edge,
 // whose matrix is never assembled: a product gathers, per node, the node's diagonal block and the A^T B block of every incident edge.
 //     graph_linearize_kernel  one thread per edge: residual, the two 6 x 6 Jacobians, A^T A, B^T B, A^T B, A^T r, B^T r, the cost term
+//     graph_linearize_weighted_kernel  the same for a store that holds a 6 x 6 information or a Cauchy loss on some edge: whitens
+//                             with the information's Cholesky factor, scales by rho'
 //     graph_assemble_kernel   one thread per free node, over its incident edges in the host's fixed order: diagonal block, gradient,
 //                             at the start the Jacobi scale
 //     graph_cg_begin_kernel   one thread per free node: D, the Cholesky of the damped preconditioner block, y = 0, r = b, z = M^-1 r
@@ -78,6 +80,15 @@ struct GraphArgs {
     const int* env_rowptr;                       // [n_free + 1]: row i holds the blocks of columns first(i) .. i from here, in blocks
     const int* env_last;                         // [n_free]: the last row with first <= k, what elimination step k reaches
     double* env;                                 // [blocks][36], row-major 6 x 6
+};
+
+// What a weighted store has beside GraphArgs (null for a scalar one): matrix information and robust losses.  An argument of its own,
+// of graph_linearize_weighted_kernel alone: every graph kernel takes GraphArgs by value, and the CG path is 200,000 launches per call on
+// a drive -- with these 24 bytes inside GraphArgs that path measured 1 to 2 % slower for a store that has no use for them.
+struct GraphWeights {
+    const double* winfo;                         // [E][21]: the Cholesky factor L of W = L L^T, lower triangle, row-major packed
+    const double* loss;                          // [E]: 0 = trivial, a > 0 = Cauchy(a) on s = r^T W r
+    double* estat;                               // [2][E][2]: s and rho'(s) of the last linearisation of each buffer
 };
 
 __device__ __forceinline__ int graph_lower6(int i, int j) { return (i * (i + 1)) / 2 + j; }                      // j <= i
@@ -199,12 +210,9 @@ __device__ __forceinline__ void graph_mul3_tt(const double A[9], const double B[
 }
 
 // ---- linearise: one thread per edge, at the poses of buffer `which` -------------------------------------------------------------
-__global__ void __launch_bounds__(kGrThreads)
-graph_linearize_kernel(GraphArgs G, int which)
-#if VELO_DEF_GRAPH
-{
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= G.E) return;
+// the unweighted residual r = pose_vec(Z^-1 T_from^-1 T_to) of edge e and its Jacobians A (from), B (to), row-major 6 x 6: the text both
+// linearise kernels share
+__device__ __forceinline__ void graph_edge_terms(const GraphArgs& G, int e, int which, double r[6], double A[36], double B[36]) {
     const double* xf = G.x + (size_t)which * G.x_stride + (size_t)G.from[e] * 6;
     const double* xt = G.x + (size_t)which * G.x_stride + (size_t)G.to[e] * 6;
     const double* zz = G.z + (size_t)e * 6;
@@ -219,14 +227,13 @@ graph_linearize_kernel(GraphArgs G, int which)
     graph_log(RE, phi);
     graph_jr_inv(phi, Ji);
     const double d[3] = {xt[3] - xf[3], xt[4] - xf[4], xt[5] - xf[5]};
-    double r[6];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         r[i] = phi[i];
         r[3 + i] = (Q[i * 3] * d[0] + Q[i * 3 + 1] * d[1] + Q[i * 3 + 2] * d[2]) - (Rz[i] * zz[3] + Rz[3 + i] * zz[4] + Rz[6 + i] * zz[5]);
     }
     // A = d r / d x_from = [-Ji Rt^T Jl(wf), 0; Q [d]x Jl(wf), -Q],  B = d r / d x_to = [Ji Rt^T Jl(wt), 0; 0, Q]
-    double T[9], U[9], A[36], B[36];
+    double T[9], U[9];
     graph_mul3_tn(Rt, Jlf, T);
     graph_mul3(Ji, T, U);
 #pragma unroll
@@ -249,8 +256,10 @@ graph_linearize_kernel(GraphArgs G, int which)
 #pragma unroll
         for (int j = 0; j < 3; j++) { B[i * 6 + j] = U[i * 3 + j]; B[i * 6 + 3 + j] = 0.0; B[(3 + i) * 6 + j] = 0.0; B[(3 + i) * 6 + 3 + j] = Q[i * 3 + j]; }
     }
-    const double w = G.info[e];
-    double* out = G.blk + ((size_t)which * G.E + e) * kGrBlk;
+}
+
+// w A^T A, w B^T B (upper), w A^T B, w A^T r, w B^T r into the edge's block
+__device__ __forceinline__ void graph_edge_products(double* out, const double A[36], const double B[36], const double r[6], double w) {
 #pragma unroll
     for (int a = 0; a < 6; a++) {
 #pragma unroll
@@ -273,10 +282,97 @@ graph_linearize_kernel(GraphArgs G, int which)
         out[kGrAtr + a] = w * ar;
         out[kGrBtr + a] = w * br;
     }
+}
+
+__global__ void __launch_bounds__(kGrThreads)
+graph_linearize_kernel(GraphArgs G, int which)
+#if VELO_DEF_GRAPH
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= G.E) return;
+    double r[6], A[36], B[36];
+    graph_edge_terms(G, e, which, r, A, B);
+    const double w = G.info[e];
+    double* out = G.blk + ((size_t)which * G.E + e) * kGrBlk;
+    graph_edge_products(out, A, B, r, w);
     double rr = 0.0;
 #pragma unroll
     for (int k = 0; k < 6; k++) rr += r[k] * r[k];
     out[kGrCost] = 0.5 * (w * rr);
+}
+#else
+;
+#endif
+
+// The same for a store with matrix information and robust losses (velo_graph_add_edges_weighted).  winfo holds per edge the Cholesky
+// factor L of its information W = L L^T (lower triangle, row-major packed).  The thread whitens in place, rows ascending -- row i of
+// L^T A needs the rows >= i only, so no second 6 x 6 is alive --: A <- L^T A, B <- L^T B, r <- L^T r; then s = |r|^2 = r^T W r, the
+// loss rho(s) = s (loss 0) or a^2 ln(1 + s / a^2) (Cauchy(a), ceres::CauchyLoss), and the products above with w = rho'(s): Ceres'
+// corrector with alpha = 0, which is exact for a loss whose second derivative is negative.  Every sum has a fixed order.  (s, rho') go
+// to estat for velo_graph_edge_stats.
+__global__ void __launch_bounds__(kGrThreads)
+graph_linearize_weighted_kernel(GraphArgs G, GraphWeights Wt, int which)
+#if VELO_DEF_GRAPH
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= G.E) return;
+    double r[6], A[36], B[36];
+    graph_edge_terms(G, e, which, r, A, B);
+    const double* Lp = Wt.winfo + (size_t)e * 21;
+    double L[21];
+#pragma unroll
+    for (int a = 0; a < 21; a++) L[a] = Lp[a];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            double sa = 0.0, sb = 0.0;
+#pragma unroll
+            for (int k = i; k < 6; k++) { sa += L[graph_lower6(k, i)] * A[k * 6 + c]; sb += L[graph_lower6(k, i)] * B[k * 6 + c]; }
+            A[i * 6 + c] = sa;
+            B[i * 6 + c] = sb;
+        }
+        double sr = 0.0;
+#pragma unroll
+        for (int k = i; k < 6; k++) sr += L[graph_lower6(k, i)] * r[k];
+        r[i] = sr;
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) s += r[k] * r[k];
+    const double a = Wt.loss[e];
+    double rho = s, w = 1.0;
+    if (a > 0.0) {
+        const double b = a * a, t = 1.0 + s / b;
+        rho = b * log(t);
+        w = 1.0 / t;
+    }
+    double* out = G.blk + ((size_t)which * G.E + e) * kGrBlk;
+    graph_edge_products(out, A, B, r, w);
+    out[kGrCost] = 0.5 * rho;
+    double* st = Wt.estat + ((size_t)which * G.E + e) * 2;
+    st[0] = s;
+    st[1] = w;
+}
+#else
+;
+#endif
+
+// a scalar edge in a weighted store: W = info I, that is L = sqrt(info) I, and the trivial loss; one thread per edge of [first, first + n)
+__global__ void __launch_bounds__(kGrThreads)
+graph_promote_kernel(const double* info, double* winfo, double* loss, int first, int n)
+#if VELO_DEF_GRAPH
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const size_t e = (size_t)first + (size_t)k;
+    const double l = sqrt(info[e]);
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+#pragma unroll
+        for (int j = 0; j <= i; j++) winfo[e * 21 + graph_lower6(i, j)] = i == j ? l : 0.0;
+    }
+    loss[e] = 0.0;
 }
 #else
 ;
