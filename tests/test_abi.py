@@ -149,3 +149,19 @@ def test_product_library_reads_only_the_documented_environment_knobs():
     header = open(os.path.join(ROOT, "include", "velo_hip.h")).read()
     for k in PRODUCT_KNOBS:
         assert k in header, k                              # documented where the boundary is declared
+
+
+AB_KERNELS = (b"19assoc_search_kernel", b"22assoc_search_v3_kernel", b"17assoc_lane_kernel", b"23assoc_lane_batch_kernel",
+              b"20assoc_prepare_kernel", b"20assoc_cluster_kernel")
+
+
+def test_product_library_holds_no_ab_association_kernel():
+    """The A/B association kernels (velo_assoc_ab_kernels.h) are launched by the -DVELO_DIAGNOSTICS build only, so only that build
+    holds them -- checked on the binaries themselves, by the length-prefixed part of their mangled names."""
+    build.build_hip()
+    product = open(build.LIB, "rb").read()
+    found = [k.decode() for k in AB_KERNELS if k in product]
+    assert not found, found
+    diag = open(build.build_hip(diagnostics=True), "rb").read()
+    missing = [k.decode() for k in AB_KERNELS if k not in diag]
+    assert not missing, missing

@@ -20,17 +20,17 @@ LIB = os.path.join(CSRC, "libvelo_hip.so")
 LIB_DIAG = os.path.join(CSRC, "libvelo_hip_diag.so")     # the tools' build: -DVELO_DIAGNOSTICS (stamps, counters, VELO_DEBUG_SKIP)
 # Translation units, each with the flags only it gets, compiled side by side and linked into ONE shared library (round 6: ~10 s instead of
 # 27 s for the product build).  velo_hip.hip is the host side of the C-ABI and defines no kernel; every kernel family is defined -- its device
-# code generated -- in exactly one velo_unit_*.hip (velo_kernels.h, "translation units"); velo_lm_ag.hip is the one-launch Levenberg-Marquardt
-# solve, built without machine-level loop-invariant code motion (velo_lm_ag_kernels.h says why).
+# code generated -- in exactly one velo_unit_*.hip (velo_kernels.h, "translation units"; the A/B association kernels of
+# velo_assoc_ab_kernels.h only with -DVELO_DIAGNOSTICS); velo_lm_ag.hip is the one-launch Levenberg-Marquardt solve, built without
+# machine-level loop-invariant code motion (velo_lm_ag_kernels.h says why).
 SOURCES = {"velo_hip.hip": [], "velo_unit_load.hip": [], "velo_unit_assoc.hip": [], "velo_unit_lm_a.hip": [], "velo_unit_lm_b.hip": [],
            "velo_unit_match.hip": [], "velo_unit_track.hip": [], "velo_unit_detect.hip": [], "velo_unit_landmarks.hip": [], "velo_unit_ba.hip": [], "velo_unit_graph.hip": [], "velo_unit_frames.hip": [], "velo_unit_map.hip": [], "velo_lm_ag.hip": ["-mllvm", "-disable-machine-licm"]}
 KERNEL_UNITS = ["velo_unit_load.hip", "velo_unit_assoc.hip", "velo_unit_lm_a.hip", "velo_unit_lm_b.hip", "velo_unit_match.hip",
-                "velo_unit_track.hip", "velo_unit_detect.hip", "velo_unit_landmarks.hip", "velo_unit_ba.hip", "velo_unit_graph.hip", "velo_unit_frames.hip", "velo_unit_map.hip", "velo_lm_ag.hip"]   # the units that hold device code (tools/kernel_resources.py)
-HEADERS = ["velo_kernels.h", "velo_lm_ag_kernels.h", "velo_depth_kernels.h", "velo_tri_kernels.h", "velo_match_kernels.h", "velo_track_kernels.h", "velo_detect_kernels.h", "velo_landmark_kernels.h", "velo_ba_kernels.h", "velo_graph_kernels.h", "velo_frame_kernels.h", "velo_map_kernels.h", "velo_device_math.h", "velo_trust_region.h", "velo_block_list.h", "velo_stage_layout.h", os.path.join(ROOT, "include", "velo_hip.h"),
-           # the parts of the host side (velo_hip.hip includes them in this order: one translation unit)
-           "velo_host_types.inl", "velo_host_index.inl", "velo_host_assoc.inl", "velo_host_lm.inl", "velo_host_loaders.inl", "velo_host_pool.inl",
-           "velo_api_context.inl", "velo_api_solve.inl", "velo_host_chain.inl", "velo_host_batch.inl", "velo_api_pose_comm.inl", "velo_api_next_rows.inl",
-           "velo_api_match.inl", "velo_api_track.inl", "velo_api_detect.inl", "velo_api_landmarks.inl", "velo_api_ba.inl", "velo_api_graph.inl", "velo_api_frames.inl", "velo_api_map.inl"]
+                "velo_unit_track.hip", "velo_unit_detect.hip", "velo_unit_landmarks.hip", "velo_unit_ba.hip", "velo_unit_graph.hip", "velo_unit_frames.hip", "velo_unit_map.hip", "velo_lm_ag.hip"]   # the units that hold device code (tools/kernel_resources.py, tools/kernel_digest.py)
+
+# what the units include, for the staleness test: every header and every part of the host side (*.inl) in csrc/, and the C-ABI header --
+# read from the directory, so a new file cannot be forgotten
+HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inl"))) + [os.path.join(ROOT, "include", "velo_hip.h")]
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
@@ -64,7 +64,7 @@ def build_hip(force: bool = False, verbose: bool = False, extra_flags=(), diagno
     VELO_DEBUG_SKIP hooks exist only there, so a leaked environment variable cannot corrupt a product registration)."""
     hipcc = shutil.which("hipcc") or os.path.join(_rocm(), "bin", "hipcc")
     srcs = [os.path.join(CSRC, s) for s in SOURCES]          # (the units share the kernel headers: any change rebuilds all of them)
-    deps = srcs + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HEADERS] + [os.path.abspath(__file__)]
+    deps = srcs + HEADERS + [os.path.abspath(__file__)]
     out = out or (LIB_DIAG if diagnostics else LIB)      # out: an A/B build of the same source somewhere else (tools/ab_env.py, VELO_LIB_PATH)
     os.makedirs(os.path.dirname(out), exist_ok=True)
     if diagnostics:

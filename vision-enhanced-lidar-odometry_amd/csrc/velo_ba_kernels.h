@@ -20,7 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/velo_hip.h"
-#include "velo_kernels.h"
+#include "velo_scan_types.h"
 #include "velo_tri_kernels.h"
 #include "velo_landmark_kernels.h"
 

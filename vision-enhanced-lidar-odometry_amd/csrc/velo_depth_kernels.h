@@ -1,5 +1,5 @@
 // velo_depth_kernels.h -- SURVEY.md 8(f) row 3: projectLidarToCamera + featureDepthAssociation (reference velo.h:329-497)
-// on the device.  Included by velo_hip.hip after velo_kernels.h (uses its scan kernels); gfx950 only.
+// on the device.  Its kernels belong to the VELO_DEF_LOAD family (velo_unit_load.hip defines them); gfx950 only.
 //
 // Data layout: the occlusion stacks of all rings live in two float4 arrays parallel to the ring-major cloud --
 // ring s owns slots [off[s], off[s] + cnt[s]) of
@@ -7,7 +7,11 @@
 //     vstack[j] = {x, y, z, 0} of the UN-shifted point                                  (`scans_valid`, velo.h:368)
 // so a ring's list can never outgrow the ring and no compaction is needed before the keypoint search.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "velo_scan_types.h"   // block_exclusive_scan
+
+#ifndef VELO_DEF_LOAD
+#define VELO_DEF_LOAD 0
+#endif
 
 namespace velo {
 

@@ -43,7 +43,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/velo_hip.h"
-#include "velo_kernels.h"
+#include "velo_scan_types.h"
 #include "velo_depth_kernels.h"
 #include "velo_landmark_kernels.h"
 

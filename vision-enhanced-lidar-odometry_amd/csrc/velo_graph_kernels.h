@@ -28,7 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/velo_hip.h"
-#include "velo_kernels.h"
+#include "velo_scan_types.h"
 #include "velo_device_math.h"
 
 #ifndef VELO_DEF_GRAPH

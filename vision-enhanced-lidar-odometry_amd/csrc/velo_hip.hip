@@ -34,6 +34,9 @@
 
 #include "../../include/velo_hip.h"
 #include "velo_kernels.h"
+#ifdef VELO_DIAGNOSTICS
+#include "velo_assoc_ab_kernels.h"   // the A/B association kernels: launched by the tools' build only
+#endif
 #include "velo_depth_kernels.h"
 #include "velo_tri_kernels.h"
 #include "velo_match_kernels.h"

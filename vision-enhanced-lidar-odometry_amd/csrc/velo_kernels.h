@@ -2,7 +2,7 @@
 //
 // Kernel map (SURVEY.md section 8(a) rows in brackets):
 //   pack_points_kernel, bbox_kernel, grid_count/scan/scatter  [T1]  target index: uniform grid, cell >= gate radius
-//   assoc_search_kernel                                      [A1-A6] query transform, exact per-ring 1-NN via the
+//   assoc_search_v5_kernel                                   [A1-A6] query transform, exact per-ring 1-NN via the
 //                                                                    27-cell neighbourhood, top-2 rings, ring neighbour,
 //                                                                    triangle normal -> correspondence table
 //   visual_gate_kernel                                       [G1]   visual block choice + outlier gate
@@ -14,14 +14,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "velo_device_math.h"
-#include "velo_trust_region.h"   // LMParams
+#include "velo_scan_types.h"   // constants, grid, pose scalars, hand-over records; velo_device_math.h, velo_trust_region.h (LMParams)
 
 // ---- translation units (round 6) ---------------------------------------------------------------------------------------------------------
 // The library is built from several units compiled side by side (build.py): velo_hip.hip holds the host side of the C-ABI and DEFINES NO
 // KERNEL; each kernel family is defined -- its device code generated -- in exactly one unit:
 //     VELO_DEF_LOAD   velo_unit_load.hip    scan ingestion, index build, the group loaders, the widened rows (projection, depth, triangulation)
-//     VELO_DEF_ASSOC  velo_unit_assoc.hip   the association family (tube / direct / asker / lane / box-walk kernels, seeds, merge)
+//     VELO_DEF_ASSOC  velo_unit_assoc.hip   the association family (tube / direct / asker kernels, seeds, merge; with -DVELO_DIAGNOSTICS also velo_assoc_ab_kernels.h)
 //     VELO_DEF_LMA    velo_unit_lm_a.hip    visual gate, residual statistics, the sweep and step kernels, one-launch iterations, peer exchange
 //     VELO_DEF_LMB    velo_unit_lm_b.hip    the fused sweep + step family of the lock-step groups, single-launch solves, chain finish, functors
 // Every other unit sees a kernel's DECLARATION (the `#else ;` branch behind its signature) and launches it through the host stub the
@@ -41,96 +40,6 @@
 #endif
 
 namespace velo {
-
-constexpr int kWave = 64;
-constexpr int kNumAcc = 28;           // 21 upper-triangular JtJ + 6 Jtr + cost
-constexpr int kEvalThreads = 256;
-constexpr int kMaxEvalBlocks = 512;
-constexpr int kAssocThreads = 256;
-
-// ---- uniform grid over the target cloud (one per distinct gate radius) ------------------------------------
-struct GridDesc {
-    float ox, oy, oz;       // origin = bbox min
-    float inv_h;            // 1 / cell size (one fine grid, cell ~ 1.01 x the smallest gate radius, serves every gate)
-    int nx, ny, nz;
-    int ncells;
-};
-
-// Cell-sorted copy of the target: float4 {x, y, z, bits(global ring-major target index)} + the point's ring, so that a
-// workgroup can stage whole cell runs into LDS with one coalesced 16-byte load per candidate.  kGridPad sentinel
-// entries (x = +inf) follow the last real point.
-constexpr int kGridPad = 16;
-struct GridView {
-    GridDesc d;
-    const int* __restrict__ cell_start;      // dense: [ncells + 1] start of every cell; compressed: start of every OCCUPIED cell, [n_occupied + 1]
-    const float4* __restrict__ sorted;       // [n_finite + kGridPad]
-    const int* __restrict__ sring;           // ring of sorted[j]
-    // Compressed table (large grids: an accumulated map's millions of cells, of which a few per cent hold points): per row (y, z) of
-    // the grid `wpr` 64-bit words, bit x & 63 of word x >> 6 = "cell x of this row is occupied", and the number of occupied cells before
-    // each word.  start(row, x) = cell_start[wprefix[w] + popcount(wmask[w] below bit x)] -- 0.19 bytes per cell instead of 4, so the
-    // table of the 2M-point map (11 M cells) is 2 MB and stays in every XCD's L2, at the price of one dependent load per look-up.
-    const unsigned long long* __restrict__ wmask;   // null: dense table
-    const int* __restrict__ wprefix;
-    int wpr;                                  // words per row = ceil(nx / 64)
-};
-// first sorted point of cell x (0..nx: nx = one past the row's last cell) of grid row `row` = z * ny + y
-__device__ __forceinline__ int grid_start(const GridView& G, int row, int x) {
-    if (G.wmask == nullptr) return G.cell_start[row * G.d.nx + x];
-    const int w = row * G.wpr + (x >> 6);
-    const unsigned long long m = G.wmask[w];
-    const int k = G.wprefix[w] + __popcll(m & ((1ull << (x & 63)) - 1ull));
-    return G.cell_start[k];
-}
-
-// ---- pose scalars of one association round, computed on the HOST in double with the same libm the CPU
-// restatement uses, so that the float coordinates of the transformed queries are bit-identical (row A1) -----
-struct PoseScalars {
-    double w[3];     // omega
-    double t[3];
-    double c, s;     // cos / sin(theta)
-    double u[3];     // omega / theta
-    double omc;      // 1 - cos(theta)
-    int small;       // theta^2 <= DBL_EPSILON -> first-order branch
-};
-
-// the same for host and device: with the pinned sin / cos (velo_device_math.h) and correctly rounded sqrt and division the device
-// computes a round's pose scalars with the bits the host (and the oracle) gets, so a frame_to_frame can run as ONE chain of launches
-__host__ __device__ inline void pose_scalars_compute(const double x[6], PoseScalars* S) {
-    for (int k = 0; k < 3; k++) { S->w[k] = x[k]; S->t[k] = x[3 + k]; S->u[k] = 0.0; }
-    S->c = 0.0; S->s = 0.0; S->omc = 0.0;
-    const double theta2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
-    if (theta2 > 2.220446049250313e-16) {
-        const double theta = sqrt(theta2);
-        velo_sincos(theta, &S->s, &S->c);
-        const double ti = 1.0 / theta;
-        S->u[0] = x[0] * ti; S->u[1] = x[1] * ti; S->u[2] = x[2] * ti;
-        S->omc = 1.0 - S->c;
-        S->small = 0;
-    } else {
-        S->small = 1;
-    }
-}
-// Device-driven rounds ("chain mode"): the LM step that finishes a solve leaves the pose scalars of its result here, and the next
-// round's association kernel reads them -- no host round trip between a solve and the next association.  ready = 0 while a solve
-// is running: an association kernel that finds it so was enqueued behind a solve that needed more launches than the host had
-// predicted; it raises the chain's failure flag and everything behind it returns at once (the host then repeats the call).
-struct PoseRecord {
-    PoseScalars P;
-    int ready;
-    int pad;
-};
-// what the host wants to know about a finished solve (velo_solve_summary), left by the step that finished it
-struct SolveLog {
-    double x[6];
-    double initial_cost, final_cost;
-    int termination, iter, evals, n_valid;
-};
-
-__device__ __forceinline__ int cell_coord(float p, float o, float inv_h, int n) {
-    float f = (p - o) * inv_h;
-    f = fminf(fmaxf(f, -2.0f), (float)(n + 1));
-    return (int)floorf(f);
-}
 
 // (velo_lm_ag.hip, the translation unit of the all-gather solve, defines VELO_UNIT_LM_ONLY: it needs the solver half of this header only, and every
 //  kernel it would compile here -- ingest, index build, the association family -- would be a second, unused copy in the shared library)
@@ -488,9 +397,6 @@ __device__ __forceinline__ void run_of_lane(int c, int lane, bool* head, int* fi
     const int f = 63 - __clzll((long long)((hm & upto) | 1ull));                 // (| 1: keeps clz defined on lanes before the first run)
     const unsigned long long stop = (hm | ~vm) & ~upto;                          // the next run or the next lane without a cell
     *head = h; *first = f; *len = (stop ? (int)__ffsll((long long)stop) - 1 : 64) - f;
-#ifdef VELO_NO_RUN_AGG                                                   // A/B build: one atomic per point, as before round 3
-    *head = c >= 0; *first = lane; *len = 1;
-#endif
 }
 __global__ void grid_count_kernel(GridDesc g, const float4* __restrict__ pts, int n, int* __restrict__ cell_of, int* __restrict__ table)
 #if VELO_DEF_LOAD
@@ -570,25 +476,7 @@ __global__ void grid_ccount_kernel(GridDesc g, int* __restrict__ cell_of, int n,
 ;
 #endif
 
-constexpr int kScanThreads = 256;
-constexpr int kScanItems = 8;                      // per thread
-constexpr int kScanTile = kScanThreads * kScanItems;
-
-__device__ __forceinline__ int block_exclusive_scan(int v, int* total) {
-    __shared__ int wave_sums[kScanThreads / kWave];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(inc, off); if (lane >= off) inc += t; }
-    if (lane == 63) wave_sums[wid] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kScanThreads / kWave; w++) { const int s = wave_sums[w]; if (w < wid) base += s; tot += s; }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
+// (kScanThreads / kScanItems / kScanTile and block_exclusive_scan, which the depth rows and the frame kernels use as well: velo_scan_types.h)
 // Exclusive scan in ONE pass over the data (decoupled look-back): a workgroup takes the next tile by ticket (so every tile before
 // it is already running), scans it locally, publishes its total, and wave 0 looks back over the tiles before it -- 64 status
 // words at a time, each {flag, value} in one 64-bit word read with a device-scope atomic -- adding totals until it meets a tile
@@ -1206,58 +1094,6 @@ __global__ void merge_partials_kernel(const PartialRec* __restrict__ tables, int
 ;
 #endif
 
-// Reference association search (VELO_ASSOC_VARIANT=0, kept for A/B checks): one lane per query, each lane walks the
-// x-runs of its own (2 reach + 1)^3 cell neighbourhood, reach = ceil(gate radius / cell).
-__global__ void __launch_bounds__(kAssocThreads)
-assoc_search_kernel(PoseScalars P, GridView G, const float4* __restrict__ src, const int* __restrict__ q_src, int q_begin, int q_end,
-                    const float4* __restrict__ tgt, const int* __restrict__ tgt_off, const int* __restrict__ ring_of,
-                    unsigned gate_bits, double norm_cond, int reach, AssocOut out, int want_aux)
-#if VELO_DEF_ASSOC
-{
-    const int qi = q_begin + blockIdx.x * blockDim.x + threadIdx.x;
-    const bool active = qi < q_end;
-    const unsigned long long key_inf = ((unsigned long long)gate_bits + 1ull) << 32;
-    float4 psrc = make_float4(0.f, 0.f, 0.f, 0.f);
-    float qx = 0.f, qy = 0.f, qz = 0.f;
-    unsigned long long b1 = key_inf, b2 = key_inf;
-    int b1ring = -1;
-    if (active) {
-        psrc = src[q_src[qi]];
-        transform_query(P, psrc, &qx, &qy, &qz);
-        const GridDesc& g = G.d;
-        const int cx = cell_coord(qx, g.ox, g.inv_h, g.nx), cy = cell_coord(qy, g.oy, g.inv_h, g.ny), cz = cell_coord(qz, g.oz, g.inv_h, g.nz);
-        const int x0 = max(cx - reach, 0), x1 = min(cx + reach, g.nx - 1);
-        const int y0 = max(cy - reach, 0), y1 = min(cy + reach, g.ny - 1);
-        const int z0 = max(cz - reach, 0), z1 = min(cz + reach, g.nz - 1);
-        if (x0 <= x1) {
-            for (int z = z0; z <= z1; z++) {
-                for (int y = y0; y <= y1; y++) {
-                    const int row = (z * g.ny + y);
-                    const int j0 = grid_start(G, row, x0), j1 = grid_start(G, row, x1 + 1);
-                    for (int j = j0; j < j1; j++) {
-                        const float4 sp = G.sorted[j];
-                        const float d2 = dist2_f(qx, qy, qz, sp.x, sp.y, sp.z);
-                        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)__float_as_int(sp.w);
-                        if (key < b2) {                                  // implies d2 <= gate (keys start at key_inf)
-                            const int ring = G.sring[j];
-                            if (key < b1) {
-                                if (ring != b1ring) b2 = b1;
-                                b1 = key; b1ring = ring;
-                            } else if (ring != b1ring) {
-                                b2 = key;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-    }
-    if (active) finish_correspondence(qi, psrc, qx, qy, qz, b1, b2, key_inf, tgt, tgt_off, ring_of, norm_cond, out, want_aux != 0);
-}
-#else
-;
-#endif
-
 // ---- running (best1, best2) over distinct rings ---------------------------------------------------------------------
 struct Top2 {
     unsigned long long b1, b2;
@@ -1287,256 +1123,9 @@ __device__ __forceinline__ int wave_max_i(int v) {
     return v;
 }
 
-// ---- association search: LDS-staged shrinking-radius box walk (VELO_ASSOC_VARIANT=4; superseded by the tube kernel below, ----
-// ---- kept for A/B and as the second independent implementation the parity tests compare against) ---------------------------
-// A workgroup of NW waves owns 64 consecutive queries; lane i of EVERY wave holds query i (source scans are ring-ordered,
-// so the 64 points are spatial neighbours).  The waves cluster the queries (cells within +-W of a seed lane's cell) and
-// search ONE fine grid (cell ~ the smallest gate radius, shared by all outer iterations) in growing boxes around the
-// cluster's cell bounding box: expansion e = 1, 2, 4, ... cells.  Per phase
-//   1. one thread per grid row of the new shell reads the row's cell offsets (vector loads) -> list of candidate runs,
-//      workgroup prefix sum of their lengths;
-//   2. the runs are copied into an LDS tile by ALL threads with coalesced 16-byte loads (every thread finds its source
-//      run by binary search in the LDS prefix array) -- hundreds of loads in flight instead of a dependent chain;
-//   3. each wave sweeps a slice of the tile: the candidate is read from LDS with one broadcast ds_read_b128 and tested by
-//      all 64 lanes (queries) at once;
-//   4. the waves merge their per-lane (best1, best2) through LDS (top-2-distinct-rings is associative and idempotent).
-// After a phase that covered expansion e every unvisited point is separated from every member query by >= e whole cells,
-// so the walk stops once (e * cell)^2 > max over member lanes of b2d (second-best squared distance, or the gate when a
-// lane has no second ring yet): no unvisited point can enter any lane's result.  In the dense part of a scan this ends
-// after the first phase; the answer is still the exact exhaustive one.
-#ifndef VELO_ASSOC_SYNC_LEAN
-#define VELO_ASSOC_SYNC_LEAN 1
-#endif
+// the LDS tile of the staged searches (the tube kernel below, the box walk and the pipelined search of velo_assoc_ab_kernels.h)
 constexpr int kTileCap = 512;      // candidates per LDS tile (keeps the workgroup under 20 KB of LDS: 8 workgroups per CU)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// DBG = true compiles the diagnostic hooks selected at run time by `dbg` (bit 0/1/2: skip sweep / tiles / rows, 3: cycle stamps,
-// 4: counters, 5: workgroup times, bits 8+: first expansion); the product instantiation has none of them -- they cost 56 spilled
-// SGPRs and 9 spilled VGPRs when left in.
-template <int NW, int MINW, bool DBG>
-__global__ void __launch_bounds__(NW * 64, MINW)
-assoc_search_v3_kernel(PoseScalars P, GridView G, const float4* __restrict__ src, const int* __restrict__ q_src, int q_begin, int q_end,
-                       const float4* __restrict__ tgt, const int* __restrict__ tgt_off, const int* __restrict__ ring_of,
-                       unsigned gate_bits, double norm_cond, int cluster_w, float h_safe, AssocOut out, int want_aux, int dbg, int xcd_map) {
-    constexpr int NT = NW * 64;
-    constexpr int NRUN = 2 * NT;                       // two run slots per row, NT rows per row chunk
-    // tile: candidates stored as PAIRS -- {x0,x1,y0,y1} and {z0,z1,bits(g0),bits(g1)} -- so that the sweep handles two
-    // candidates per packed-f32 instruction after two broadcast ds_read_b128
-    __shared__ float4 s_xy[kTileCap / 2];
-    __shared__ float4 s_zg[kTileCap / 2];
-    __shared__ int s_ring[kTileCap];
-    __shared__ int s_run_j0[NRUN];
-    __shared__ int s_run_off[NRUN + 1];
-    __shared__ int s_wave_tot[NW];
-    __shared__ unsigned long long m1[NW][64], m2[NW][64];
-    __shared__ int mr[NW][64];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // diagnostic build only (DBG && (dbg & 8)): per-section cycle totals of wave 0, added to out.dbg[0..7]
-    long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long tlast = (DBG && (dbg & 8)) ? (long long)__builtin_readcyclecounter() : 0;
-#define VELO_STAMP(k) do { if (DBG && (dbg & 8)) { const long long now__ = (long long)__builtin_readcyclecounter(); tacc[k] += now__ - tlast; tlast = now__; } } while (0)
-    // XCD-aware group mapping: workgroups are dealt round-robin over the 8 XCDs, so blockIdx % 8 selects the XCD; give
-    // each XCD one CONTIGUOUS eighth of the ring-ordered groups -- spatial neighbours then share that XCD's 4 MB L2
-    // (cell table rows and candidate cells are re-read by adjacent groups).  Placement affects speed only.
-    const int n_groups = (q_end - q_begin + 63) >> 6;
-    const int per_xcd = (n_groups + 7) >> 3;
-    const int group = xcd_map ? (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    if (group >= n_groups || (xcd_map && (int)(blockIdx.x >> 3) >= per_xcd)) return;
-    if ((DBG && (dbg & 32)) && threadIdx.x == 0) out.wg_times[2 * group] = __builtin_amdgcn_s_memrealtime();
-    const int qi = q_begin + group * 64 + lane;
-    const bool active = qi < q_end;
-    const unsigned long long key_inf = ((unsigned long long)gate_bits + 1ull) << 32;
-    float qx = 0.f, qy = 0.f, qz = 0.f;
-    Top2 t;
-    t.b1 = key_inf; t.b2 = key_inf; t.b1ring = -1; t.b2ring = -1; t.b2d = __uint_as_float(gate_bits + 1u);
-    const GridDesc g = G.d;
-    int cx = 0, cy = 0, cz = 0;
-    if (active) {
-        const float4 psrc = src[q_src[qi]];                           // re-read at the end instead of living in 4 registers
-        transform_query(P, psrc, &qx, &qy, &qz);
-        cx = cell_coord(qx, g.ox, g.inv_h, g.nx); cy = cell_coord(qy, g.oy, g.inv_h, g.ny); cz = cell_coord(qz, g.oz, g.inv_h, g.nz);
-    }
-    VELO_STAMP(0);
-    const f32x2 qx2 = {qx, qx}, qy2 = {qy, qy}, qz2 = {qz, qz};
-    float* s_xy_f = reinterpret_cast<float*>(s_xy);
-    float* s_zg_f = reinterpret_cast<float*>(s_zg);
-    bool pending = active;
-    for (;;) {                                                         // clusters (identical control flow in every wave)
-        const unsigned long long pm = __ballot(pending);
-        if (pm == 0ull) break;
-        const int leader = (int)__ffsll((long long)pm) - 1;
-        const int scx = __builtin_amdgcn_readlane(cx, leader), scy = __builtin_amdgcn_readlane(cy, leader), scz = __builtin_amdgcn_readlane(cz, leader);
-        const bool member = pending && abs(cx - scx) <= cluster_w && abs(cy - scy) <= cluster_w && abs(cz - scz) <= cluster_w;
-        const int big = 1 << 28;
-        const int bx0 = __builtin_amdgcn_readfirstlane(wave_min_i(member ? cx : big)), bx1 = __builtin_amdgcn_readfirstlane(wave_max_i(member ? cx : -big));
-        const int by0 = __builtin_amdgcn_readfirstlane(wave_min_i(member ? cy : big)), by1 = __builtin_amdgcn_readfirstlane(wave_max_i(member ? cy : -big));
-        const int bz0 = __builtin_amdgcn_readfirstlane(wave_min_i(member ? cz : big)), bz1 = __builtin_amdgcn_readfirstlane(wave_max_i(member ? cz : -big));
-        VELO_STAMP(1);
-        if ((DBG && (dbg & 16)) && tid == 0) atomicAdd(&out.dbg[0], 1ull);
-        int e_prev = -1;                                               // expansion already covered (-1: nothing yet)
-        int e = DBG ? max(1, dbg >> 8) : 1;                                     // first expansion (tuning knob, default 1)
-        for (;;) {                                                     // phases: e = 1, then (if needed) the reach the bounds demand
-            // box of this phase (clipped) and of the previous one (unclipped; empty when e_prev < 0)
-            const int X0 = max(bx0 - e, 0), X1 = min(bx1 + e, g.nx - 1);
-            const int Y0 = max(by0 - e, 0), Y1 = min(by1 + e, g.ny - 1);
-            const int Z0 = max(bz0 - e, 0), Z1 = min(bz1 + e, g.nz - 1);
-            const int px0 = bx0 - e_prev, px1 = bx1 + e_prev, py0 = by0 - e_prev, py1 = by1 + e_prev, pz0 = bz0 - e_prev, pz1 = bz1 + e_prev;
-            const int nyb = Y1 - Y0 + 1, nzb = Z1 - Z0 + 1;
-            const int nrows = (X0 <= X1 && nyb > 0 && nzb > 0) ? nyb * nzb : 0;
-            for (int rbase = 0; rbase < ((DBG && (dbg & 4)) ? 0 : nrows); rbase += NT) {          // row chunks (one row per thread)
-                // ---- 1. run list ----
-                int ja0 = 0, la = 0, jb0 = 0, lb = 0;
-                const int r = rbase + tid;
-                if (r < nrows) {
-                    const int y = Y0 + r % nyb, z = Z0 + r / nyb;
-                    const int row = (z * g.ny + y);
-                    const bool fresh = e_prev < 0 || y < py0 || y > py1 || z < pz0 || z > pz1;
-                    if (fresh) {
-                        ja0 = grid_start(G, row, X0); la = grid_start(G, row, X1 + 1) - ja0;
-                    } else {                                            // old row: only the cells left of px0 and right of px1 are new
-                        const int a1 = min(px0 - 1, X1), b0 = max(px1 + 1, X0);
-                        if (X0 <= a1) { ja0 = grid_start(G, row, X0); la = grid_start(G, row, a1 + 1) - ja0; }
-                        if (b0 <= X1) { jb0 = grid_start(G, row, b0); lb = grid_start(G, row, X1 + 1) - jb0; }
-                    }
-                }
-                // workgroup exclusive scan of (la + lb)
-                const int mine = la + lb;
-                int inc = mine;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off); if (lane >= off) inc += v; }
-                if (lane == 63) s_wave_tot[wid] = inc;
-                __syncthreads();
-                int wbase = 0, total = 0;
-#pragma unroll
-                for (int w = 0; w < NW; w++) { const int v = s_wave_tot[w]; if (w < wid) wbase += v; total += v; }
-                const int ex = wbase + inc - mine;
-                s_run_j0[2 * tid] = ja0; s_run_off[2 * tid] = ex;
-                s_run_j0[2 * tid + 1] = jb0; s_run_off[2 * tid + 1] = ex + la;
-                if (tid == 0) s_run_off[NRUN] = total;
-                __syncthreads();
-                VELO_STAMP(2);
-                if ((DBG && (dbg & 16)) && tid == 0) { atomicAdd(&out.dbg[1], 1ull); atomicAdd(&out.dbg[2], (unsigned long long)total); if (e_prev >= 0) atomicAdd(&out.dbg[3], (unsigned long long)total); atomicAdd(&out.dbg[4], (unsigned long long)nrows); atomicAdd(&out.dbg[5], (unsigned long long)e); }
-                if (DBG && (dbg & 2)) total = 0;
-                // ---- 2./3. tiles ----
-                for (int tbase = 0; tbase < total; tbase += kTileCap) {
-                    const int tn = min(total - tbase, kTileCap);
-                    const int tn2 = (tn + 1) & ~1;                     // the sweep consumes pairs
-                    for (int i = tid; i < tn2; i += NT) {
-                        float4 c = make_float4(__builtin_inff(), __builtin_inff(), __builtin_inff(), __int_as_float(0x7fffffff));
-                        int cr = 0x7fffffff;
-                        if (i < tn) {
-                            const int slot = tbase + i;
-                            int lo = 0;                                // largest k with s_run_off[k] <= slot (NRUN is a power of two)
-#pragma unroll
-                            for (int step = NRUN / 2; step > 0; step >>= 1) {
-                                if (s_run_off[lo + step] <= slot) lo += step;
-                            }
-                            const int j = s_run_j0[lo] + (slot - s_run_off[lo]);
-                            c = G.sorted[j];
-                            cr = G.sring[j];
-                        }
-                        const int pr = i >> 1, hb = i & 1;
-                        s_xy_f[4 * pr + hb] = c.x; s_xy_f[4 * pr + 2 + hb] = c.y;
-                        s_zg_f[4 * pr + hb] = c.z; s_zg_f[4 * pr + 2 + hb] = c.w;
-                        s_ring[i] = cr;
-                    }
-                    __syncthreads();
-                    VELO_STAMP(3);
-                    // each wave sweeps a contiguous slice of the tile's pairs for all 64 queries
-                    const int npairs = tn2 >> 1;
-                    const int per = (npairs + NW - 1) / NW;
-                    const int p0 = wid * per, p1 = min(p0 + per, npairs);
-                    if (member && !(DBG && (dbg & 1))) {
-                        // 4 pairs (8 candidates) per trip: all LDS reads first, then the packed distance math, then the
-                        // (rare) updates -- keeps 8 ds_read_b128 in flight instead of one dependent read per pair
-                        int pi = p0;
-                        for (; pi + 4 <= p1; pi += 4) {
-                            float4 a[4], bq[4];
-#pragma unroll
-                            for (int u = 0; u < 4; u++) { a[u] = s_xy[pi + u]; bq[u] = s_zg[pi + u]; }
-                            f32x2 d2[4];
-#pragma unroll
-                            for (int u = 0; u < 4; u++) {
-                                const f32x2 cxp = {a[u].x, a[u].y}, cyp = {a[u].z, a[u].w}, czp = {bq[u].x, bq[u].y};
-                                const f32x2 dx = qx2 - cxp, dy = qy2 - cyp, dz = qz2 - czp;
-                                f32x2 d = dx * dx;                     // x -> y -> z accumulation, no FMA (-ffp-contract=off)
-                                d = d + dy * dy;
-                                d = d + dz * dz;
-                                d2[u] = d;
-                            }
-                            float dmin = fminf(fminf(fminf(d2[0].x, d2[0].y), fminf(d2[1].x, d2[1].y)), fminf(fminf(d2[2].x, d2[2].y), fminf(d2[3].x, d2[3].y)));
-                            if (dmin <= t.b2d) {                       // some candidate of the 8 may matter for this lane
-#pragma unroll
-                                for (int u = 0; u < 4; u++) {
-                                    if (d2[u].x <= t.b2d) {
-                                        const unsigned long long key = ((unsigned long long)__float_as_uint(d2[u].x) << 32) | (unsigned)__float_as_int(bq[u].z);
-                                        top2_update(t, key, s_ring[2 * (pi + u)]);
-                                    }
-                                    if (d2[u].y <= t.b2d) {
-                                        const unsigned long long key = ((unsigned long long)__float_as_uint(d2[u].y) << 32) | (unsigned)__float_as_int(bq[u].w);
-                                        top2_update(t, key, s_ring[2 * (pi + u) + 1]);
-                                    }
-                                }
-                            }
-                        }
-                        for (; pi < p1; pi++) {
-                            const float4 a = s_xy[pi], bq = s_zg[pi];
-                            const f32x2 cxp = {a.x, a.y}, cyp = {a.z, a.w}, czp = {bq.x, bq.y};
-                            const f32x2 dx = qx2 - cxp, dy = qy2 - cyp, dz = qz2 - czp;
-                            f32x2 d2 = dx * dx;
-                            d2 = d2 + dy * dy;
-                            d2 = d2 + dz * dz;
-                            if (d2.x <= t.b2d) {
-                                const unsigned long long key = ((unsigned long long)__float_as_uint(d2.x) << 32) | (unsigned)__float_as_int(bq.z);
-                                top2_update(t, key, s_ring[2 * pi]);
-                            }
-                            if (d2.y <= t.b2d) {
-                                const unsigned long long key = ((unsigned long long)__float_as_uint(d2.y) << 32) | (unsigned)__float_as_int(bq.w);
-                                top2_update(t, key, s_ring[2 * pi + 1]);
-                            }
-                        }
-                    }
-                    VELO_STAMP(4);
-                    __syncthreads();
-                    VELO_STAMP(5);
-                }
-            }
-            // ---- 4. merge across waves ----
-            if (NW > 1) {
-                m1[wid][lane] = t.b1; m2[wid][lane] = t.b2; mr[wid][lane] = t.b1ring;
-                __syncthreads();
-#pragma unroll
-                for (int w = 0; w < NW; w++) {
-                    if (w == wid) continue;
-                    const unsigned long long c1 = m1[w][lane], c2 = m2[w][lane];
-                    if (c1 < t.b2) top2_update(t, c1, mr[w][lane]);
-                    if (c2 < t.b2) top2_update(t, c2, ring_of[(int)(unsigned)(c2 & 0xffffffffull) - out.first_point]);
-                }
-                __syncthreads();
-            }
-            // ---- stop test (identical in every wave: all hold the same merged state) ----
-            // Every unvisited point is separated from every member query by >= e whole cells.  b2d only shrinks, so the
-            // radius the CURRENT bounds allow is enough for one more phase to finish the cluster.
-            const float rw = __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane(wave_max_i(member ? (int)__float_as_uint(t.b2d) : 0)));
-            const float reach = (float)e * h_safe;
-            VELO_STAMP(6);
-            if (reach * reach > rw) break;
-            e_prev = e;
-            e = max(e + 1, (int)ceilf(sqrtf(rw) / h_safe));
-            if ((float)e * h_safe * ((float)e * h_safe) <= rw) e++;     // rounding guard: the next test must pass
-        }
-        pending = pending && !member;
-    }
-    if (NW > 1 && wid != 0) return;
-    if (active) finish_correspondence(qi, src[q_src[qi]], qx, qy, qz, t.b1, t.b2, key_inf, tgt, tgt_off, ring_of, norm_cond, out, want_aux != 0);
-    VELO_STAMP(7);
-    if ((DBG && (dbg & 32)) && tid == 0) out.wg_times[2 * group + 1] = __builtin_amdgcn_s_memrealtime();
-    if ((DBG && (dbg & 8)) && tid == 0) { for (int k = 0; k < 8; k++) atomicAdd((unsigned long long*)&out.dbg[k], (unsigned long long)tacc[k]); }
-#undef VELO_STAMP
-}
 
 // Cells that can hold a point closer than r to the query: [cell(q - r), cell(q + r)] per axis (the cell function is monotone);
 // clip = additionally restricted to the query's own cell +- 1 (what phase 1 of the tube kernel visits).  Cheap enough (6 cell
@@ -1646,9 +1235,6 @@ assoc_search_v5_body(const PoseScalars& P_in, const PoseRecord* __restrict__ P_d
     Top2 t;
     t.b1 = key_inf; t.b2 = key_inf; t.b1ring = -1; t.b2ring = -1; t.b2d = __uint_as_float(gate_bits + 1u);
     const GridDesc g = G.d;
-    // Set-up once per GROUP, not once per wave: wave 0 transforms the 64 queries (double precision) and enters the warm-start
-    // seeds, the other waves pick the result up from LDS (scratch aliases the tile, which is not in use yet).
-#if VELO_ASSOC_SYNC_LEAN
     // Round 5: EVERY wave sets itself up -- the same coalesced loads (three of the four waves hit the L2 lines the first one pulled), the
     // same arithmetic, hence the same state in every wave -- instead of wave 0 computing and handing over through LDS behind two workgroup
     // barriers.  A barrier costs this kernel ~1 us (four waves, each sharing its SIMD with four other workgroups' waves); the redundant
@@ -1663,6 +1249,10 @@ assoc_search_v5_body(const PoseScalars& P_in, const PoseRecord* __restrict__ P_d
             int2 sr = make_int2(-1, -1);
             if (seeded) { sa = out.prev_a[qi]; sb = out.prev_b[qi]; sr = out.prev_r[qi]; }
             transform_query(P, psrc, &qx, &qy, &qz);
+            // Warm start: the two winners of the previous round (same source, same target, slightly different pose) are real
+            // candidates of this round, so entering them first changes nothing in the result (top-2 is idempotent) but starts the
+            // search with a tight second-best bound: almost every later candidate fails the cheap trip test and the per-query
+            // second phase is rarely needed.  Seeds beyond the current gate are dropped like any other candidate.
             if (__float_as_int(sa.w) >= 0) {
                 const float d = dist2_f(sa.x, sa.y, sa.z, qx, qy, qz);
                 if (__float_as_uint(d) <= gate_bits) top2_update(t, ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)(__float_as_int(sa.w) + out.first_point), sr.x);
@@ -1676,44 +1266,6 @@ assoc_search_v5_body(const PoseScalars& P_in, const PoseRecord* __restrict__ P_d
         // the per-row interval slots start out empty; from then on the thread that consumes a row's interval empties it again (see the run list)
         s_lo[tid] = 1 << 28; s_hi[tid] = -(1 << 28); s_plo[tid] = 1 << 28; s_phi[tid] = -(1 << 28);
     }
-#else
-    {
-        unsigned long long* sb = reinterpret_cast<unsigned long long*>(s_zg);   // [2][64] best1 / best2 keys
-        int* sr = s_ring;                                                        // [2][64] their rings
-        if (wid == lead) {
-            float qx = 0.f, qy = 0.f, qz = 0.f;
-            if (active) {
-                // everything the set-up needs is requested at once (coalesced, no load behind another load's result)
-                const float4 psrc = qpts[qi];
-                const bool seeded = out.prev_a && !(DBG && (dbg & 512));
-                float4 sa = make_float4(0.f, 0.f, 0.f, __int_as_float(-1)), sb = sa;
-                int2 sr = make_int2(-1, -1);
-                if (seeded) { sa = out.prev_a[qi]; sb = out.prev_b[qi]; sr = out.prev_r[qi]; }
-                transform_query(P, psrc, &qx, &qy, &qz);
-                // Warm start: the two winners of the previous round (same source, same target, slightly different pose) are real
-                // candidates of this round, so entering them first changes nothing in the result (top-2 is idempotent) but starts the
-                // search with a tight second-best bound: almost every later candidate fails the cheap trip test and the per-query
-                // second phase is rarely needed.  Seeds beyond the current gate are dropped like any other candidate.
-                if (__float_as_int(sa.w) >= 0) {
-                    const float d = dist2_f(sa.x, sa.y, sa.z, qx, qy, qz);
-                    if (__float_as_uint(d) <= gate_bits) top2_update(t, ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)(__float_as_int(sa.w) + out.first_point), sr.x);
-                }
-                if (__float_as_int(sb.w) >= 0) {
-                    const float d = dist2_f(sb.x, sb.y, sb.z, qx, qy, qz);
-                    if (__float_as_uint(d) <= gate_bits) top2_update(t, ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)(__float_as_int(sb.w) + out.first_point), sr.y);
-                }
-            }
-            s_q[0][lane] = qx; s_q[1][lane] = qy; s_q[2][lane] = qz;
-            sb[lane] = t.b1; sb[64 + lane] = t.b2; sr[lane] = t.b1ring; sr[64 + lane] = t.b2ring;
-        }
-        __syncthreads();
-        if (wid != lead) {
-            t.b1 = sb[lane]; t.b2 = sb[64 + lane]; t.b1ring = sr[lane]; t.b2ring = sr[64 + lane];
-            t.b2d = __uint_as_float((unsigned)(t.b2 >> 32));
-        }
-        __syncthreads();                                                         // the tile may be overwritten from here on
-    }
-#endif
     VELO_STAMP(0);
     float* s_xy_f = reinterpret_cast<float*>(s_xy);
     float* s_zg_f = reinterpret_cast<float*>(s_zg);
@@ -1824,11 +1376,6 @@ assoc_search_v5_body(const PoseScalars& P_in, const PoseRecord* __restrict__ P_d
                     if (__ballot(hit) == 0ull) continue;
                 }
                 // ---- 0. per-row x-intervals ----
-#if !VELO_ASSOC_SYNC_LEAN
-                s_lo[tid] = big; s_hi[tid] = -big;
-                if (ph == 1) { s_plo[tid] = big; s_phi[tid] = -big; }
-                __syncthreads();
-#endif
                 if (asks) {                                            // the rows of this query's box: z-layers dealt over the waves
                     const int bx0 = s_box[ph][0][lane], bx1 = s_box[ph][1][lane], by0 = s_box[ph][2][lane], by1 = s_box[ph][3][lane];
                     const int bz0 = s_box[ph][4][lane], bz1 = s_box[ph][5][lane];
@@ -1858,13 +1405,9 @@ assoc_search_v5_body(const PoseScalars& P_in, const PoseRecord* __restrict__ P_d
                 // ---- 1. run list ----
                 int ja0 = 0, la = 0, jb0 = 0, lb = 0;
                 const int r = rbase + tid;
-#if VELO_ASSOC_SYNC_LEAN
                 const int lo_raw = s_lo[tid], hi_raw = s_hi[tid], plo_raw = s_plo[tid], phi_raw = s_phi[tid];
                 s_lo[tid] = big; s_hi[tid] = -big; s_plo[tid] = big; s_phi[tid] = -big;   // emptied by their consumer: the next chunk / phase / cluster needs no barrier to start filling
                                                                                           // (its atomics come behind the two barriers of the scan below)
-#else
-                const int lo_raw = s_lo[tid], hi_raw = s_hi[tid], plo_raw = (ph == 1) ? s_plo[tid] : big, phi_raw = (ph == 1) ? s_phi[tid] : -big;
-#endif
                 if (r < nrows) {
                     const int lo = max(lo_raw, 0), hi = min(hi_raw, g.nx - 1);
                     if (lo <= hi) {
@@ -1983,7 +1526,7 @@ assoc_search_v5_body(const PoseScalars& P_in, const PoseRecord* __restrict__ P_d
                 }
                 // (lean: the scratch aliases the tile, and every way from here to the next write into the tile -- the staging of a later phase or
                 //  cluster -- passes the barrier behind a box computation and the two of a scan; the query-by-query paths write it at once)
-                if (!VELO_ASSOC_SYNC_LEAN || ASKER != 0) __syncthreads();
+                if (ASKER != 0) __syncthreads();
             }
             VELO_STAMP(6);
         }
@@ -2113,7 +1656,7 @@ assoc_search_v5_body(const PoseScalars& P_in, const PoseRecord* __restrict__ P_d
         pending = pending && !member;
         // lean: a group of several clusters -- wave 0 of the next cluster publishes s_phase / s_box while a slow wave may still be reading this
         // cluster's (the barrier the merge used to end with kept them apart)
-        if (VELO_ASSOC_SYNC_LEAN && ASKER == 0 && __ballot(pending) != 0ull) __syncthreads();
+        if (ASKER == 0 && __ballot(pending) != 0ull) __syncthreads();
     }
     if (NW > 1 && wid != lead) return;
     VELO_Q(qx, qy, qz);
@@ -2318,11 +1861,7 @@ assoc_asker_batch_kernel(AssocBatch B)
 // (64-bit key: range^2 bits << 32 | local index; built with one atomicMin per target point).  seed_kernel looks the query's bucket and
 // its four neighbours up, adds the previous winners when there are any, and leaves the best two of different rings as the seeds.
 // Only a hash: for clouds that are no range images the seeds are merely poor.  Results never depend on it.
-#ifndef VELO_DIMG_W
-#define VELO_DIMG_W 1024
-#define VELO_DIMG_H 256
-#endif
-constexpr int kDimgW = VELO_DIMG_W, kDimgH = VELO_DIMG_H;       // 1024 x 256: 0.35 deg x 0.35 deg over +-45 deg of elevation, 2 MB (W: a power of two)
+constexpr int kDimgW = 1024, kDimgH = 256;       // 1024 x 256: 0.35 deg x 0.35 deg over +-45 deg of elevation, 2 MB (W: a power of two)
 __device__ __forceinline__ void dimg_bucket(float x, float y, float z, int* a, int* e) {
     // camera frame (x right, y down, z forward; kitti.h:100-107): azimuth about the y axis, elevation up positive
     const float az = atan2f(x, z), el = atan2f(-y, sqrtf(x * x + z * z));
@@ -2484,472 +2023,9 @@ assoc_direct_batch_kernel(AssocBatch B)
 ;
 #endif
 
-// ---- association search, lane variant: the rounds that start from seeds ------------------------------------------------------
-// The tube kernel shares every staged candidate among the 64 queries of a group: 350 candidates x 64 lanes per warm round, of
-// which a query needs the ~15 of its own bound sphere -- 9,400 lane-instructions per query.  A round that starts from the
-// previous round's winners knows a tight bound for (nearly) every query BEFORE it looks at a single cell, so sharing buys
-// nothing: here ONE LANE OWNS ONE QUERY and walks the cells of its own bound sphere straight from the cell-sorted copy in L2
-// (neighbouring lanes walk neighbouring cells, so the gathers share lines).  No tile, no run list of the group, no workgroup
-// barrier -- a workgroup is four independent waves.
-//   * easy query (bound box <= 3 x 3 rows, the rule whenever the bound is below one cell): the lane fetches the (start, end)
-//     of its <= 9 row runs at once, keeps the non-empty ones in its LDS column and then consumes them four candidates per trip
-//     (all four loads in flight together; entries behind the end of a run are real points of the next cells or the +inf
-//     sentinels behind the last point -- harmless extra candidates);
-//   * hard query (a query whose second ring is farther than a cell: no second seed, first iteration's gate = 4 cells): the
-//     wave turns all 64 lanes on that one query, as the tube kernel's asker phase does (rows over lanes -> wave prefix sum ->
-//     candidates over lanes -> xor-shuffle merge).
-// Candidate set = every point of every cell the bound sphere touches, keys and tie rules as everywhere else: the tables equal the
-// tube kernel's bit for bit (tests: warm rounds against cold rounds, against the oracle, lane against tube).
-// MEASURED (C2, one pair in flight): 88-90 us per second-iteration round against the tube kernel's 46-50, 440 us per seeded
-// first-iteration round (10-25 % hard queries, each a 9 x 9-row box) against 80.  The instruction count is what was hoped for, but
-// every lane-private 16-byte gather pulls a 128-byte line from L2 into a 16 KB L1 that 64 lanes x 8 gathers per trip thrash: the
-// kernel waits on L2->L1 line traffic (~0.8 MB per wave) that the tube kernel's coalesced staging never creates.  Kept as an
-// independent second implementation for the parity tests and as an A/B (VELO_ASSOC_LANE=1), NOT the default.
-template <bool DBG>
-__device__ __forceinline__ void
-assoc_lane_body(const PoseScalars& P_in, const PoseRecord* __restrict__ P_dev, int* __restrict__ chain_fail, const GridView& G, const float4* __restrict__ qpts, int q_begin, int q_end,
-                const float4* __restrict__ tgt_pad, const int* __restrict__ tgt_off, unsigned gate_bits, double norm_cond, const AssocOut& out, int want_aux, const int block_x) {
-    constexpr int kRows = 9;
-    __shared__ int s_j0[4][kRows][64];
-    __shared__ int s_j1[4][kRows][64];
-    __shared__ int s_cj0[4][66];
-    __shared__ int s_coff[4][66];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    if (chain_fail && *chain_fail) return;
-    if (P_dev && !P_dev->ready) { if (block_x == 0 && tid == 0) *chain_fail = 1; return; }
-    const PoseScalars& P = P_dev ? P_dev->P : P_in;
-    if (out.n_valid_next && block_x == 0 && tid == 0) *out.n_valid_next = 0;
-    const int group = block_x * 4 + wid;
-    if (group * 64 >= q_end - q_begin) return;                         // wave-uniform
-    const int qi = q_begin + group * 64 + lane;
-    const bool active = qi < q_end;
-    const unsigned long long key_inf = ((unsigned long long)gate_bits + 1ull) << 32;
-    Top2 t;
-    t.b1 = key_inf; t.b2 = key_inf; t.b1ring = -1; t.b2ring = -1; t.b2d = __uint_as_float(gate_bits + 1u);
-    const GridDesc g = G.d;
-    float qx = 0.f, qy = 0.f, qz = 0.f;
-    if (active) {
-        const float4 psrc = qpts[qi];
-        const float4 sa = out.prev_a[qi], sb = out.prev_b[qi];
-        const int2 sr = out.prev_r[qi];
-        transform_query(P, psrc, &qx, &qy, &qz);
-        if (__float_as_int(sa.w) >= 0) {
-            const float d = dist2_f(sa.x, sa.y, sa.z, qx, qy, qz);
-            if (__float_as_uint(d) <= gate_bits) top2_update(t, ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)(__float_as_int(sa.w) + out.first_point), sr.x);
-        }
-        if (__float_as_int(sb.w) >= 0) {
-            const float d = dist2_f(sb.x, sb.y, sb.z, qx, qy, qz);
-            if (__float_as_uint(d) <= gate_bits) top2_update(t, ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)(__float_as_int(sb.w) + out.first_point), sr.y);
-        }
-    }
-    // the cell box of the bound sphere (padded against rounding, like the tube kernel's)
-    const float r0 = sqrtf(t.b2d) * 1.0001f + 1e-6f;
-    int x0, x1, y0, y1, z0, z1;
-    {
-        const CellBox bb = query_box(g, qx, qy, qz, 0, 0, 0, r0, false);
-        x0 = max(bb.x0, 0); x1 = min(bb.x1, g.nx - 1); y0 = max(bb.y0, 0); y1 = min(bb.y1, g.ny - 1); z0 = max(bb.z0, 0); z1 = min(bb.z1, g.nz - 1);
-    }
-    const int nyb = y1 - y0 + 1, nzb = z1 - z0 + 1;
-    const bool some = active && x0 <= x1 && nyb > 0 && nzb > 0;        // else: the sphere lies outside the grid, nothing to look at
-    const bool easy = some && nyb <= 3 && nzb <= 3;
-    const bool hard = some && !easy;
-    // ---- easy lanes: own row runs -> LDS column -> four candidates per trip ----
-    int nrun = 0;
-    if (easy) {
-        int a[kRows], b[kRows];
-#pragma unroll
-        for (int zz = 0; zz < 3; zz++) {
-#pragma unroll
-            for (int yy = 0; yy < 3; yy++) {
-                const bool on = zz < nzb && yy < nyb;
-                const int row = on ? ((z0 + zz) * g.ny + (y0 + yy)) : 0;
-                a[zz * 3 + yy] = on ? grid_start(G, row, x0) : 0;
-                b[zz * 3 + yy] = on ? grid_start(G, row, x1 + 1) : 0;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < kRows; k++) {
-            if (b[k] > a[k]) { s_j0[wid][nrun][lane] = a[k]; s_j1[wid][nrun][lane] = b[k]; nrun++; }
-        }
-    }
-    {
-        int k = 0, j = 0, jend = 0;
-        for (;;) {
-            if (j >= jend && k < nrun) { j = s_j0[wid][k][lane]; jend = s_j1[wid][k][lane]; k++; }
-            const bool have = j < jend;
-            if (__ballot(have) == 0ull) break;
-            const int jj = have ? j : 0;
-            const float4 c0 = G.sorted[jj], c1 = G.sorted[jj + 1], c2 = G.sorted[jj + 2], c3 = G.sorted[jj + 3];
-            const int g0 = G.sring[jj], g1 = G.sring[jj + 1], g2 = G.sring[jj + 2], g3 = G.sring[jj + 3];
-            const float d0 = dist2_f(qx, qy, qz, c0.x, c0.y, c0.z), d1 = dist2_f(qx, qy, qz, c1.x, c1.y, c1.z);
-            const float d2 = dist2_f(qx, qy, qz, c2.x, c2.y, c2.z), d3 = dist2_f(qx, qy, qz, c3.x, c3.y, c3.z);
-            if (have && fminf(fminf(d0, d1), fminf(d2, d3)) <= t.b2d) {
-                if (d0 <= t.b2d) top2_update(t, ((unsigned long long)__float_as_uint(d0) << 32) | (unsigned)__float_as_int(c0.w), g0);
-                if (d1 <= t.b2d) top2_update(t, ((unsigned long long)__float_as_uint(d1) << 32) | (unsigned)__float_as_int(c1.w), g1);
-                if (d2 <= t.b2d) top2_update(t, ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)__float_as_int(c2.w), g2);
-                if (d3 <= t.b2d) top2_update(t, ((unsigned long long)__float_as_uint(d3) << 32) | (unsigned)__float_as_int(c3.w), g3);
-            }
-            j += 4;
-        }
-    }
-    // ---- hard lanes: the whole wave on one query at a time ----
-    unsigned long long hm = __ballot(hard);
-    while (hm != 0ull) {
-        const int la = (int)__ffsll((long long)hm) - 1;
-        hm &= hm - 1ull;
-        const float ax = __shfl(qx, la), ay = __shfl(qy, la), az = __shfl(qz, la);
-        Top2 tl;
-        tl.b1 = __shfl(t.b1, la); tl.b2 = __shfl(t.b2, la); tl.b1ring = __shfl(t.b1ring, la); tl.b2ring = __shfl(t.b2ring, la);
-        tl.b2d = __uint_as_float((unsigned)(tl.b2 >> 32));
-        const int bx0 = __shfl(x0, la), bx1 = __shfl(x1, la), by0 = __shfl(y0, la), bz0 = __shfl(z0, la);
-        const int ny = __shfl(nyb, la), nz = __shfl(nzb, la);
-        const int nrows_a = ny * nz;
-        const float rcp_ny = 1.0f / (float)ny;
-        for (int rb = 0; rb < nrows_a; rb += 64) {
-            const int r = rb + lane;
-            int j0 = 0, len = 0;
-            if (r < nrows_a) {
-                int zq = (int)((float)r * rcp_ny), yr = r - zq * ny;
-                if (yr < 0) { zq--; yr += ny; } else if (yr >= ny) { zq++; yr -= ny; }
-                const int row = ((bz0 + zq) * g.ny + (by0 + yr));
-                j0 = grid_start(G, row, bx0); len = grid_start(G, row, bx1 + 1) - j0;
-            }
-            int inc = len;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off); if (lane >= off) inc += v; }
-            const int total = __shfl(inc, 63);
-            s_cj0[wid][lane] = j0; s_coff[wid][lane] = inc - len;
-            if (lane == 0) s_coff[wid][64] = total;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            for (int slot = lane; slot < total; slot += 64) {
-                int lo = 0;                                            // largest i with s_coff[i] <= slot
-#pragma unroll
-                for (int step = 32; step > 0; step >>= 1) { if (s_coff[wid][lo + step] <= slot) lo += step; }
-                const int j = s_cj0[wid][lo] + (slot - s_coff[wid][lo]);
-                const float4 c = G.sorted[j];
-                const float d = dist2_f(ax, ay, az, c.x, c.y, c.z);
-                if (d <= tl.b2d) top2_update(tl, ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)__float_as_int(c.w), G.sring[j]);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();                           // the run list is rewritten by the next rows
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) top2_merge_xor(tl, m);
-        if (lane == la) { t.b1 = tl.b1; t.b2 = tl.b2; t.b1ring = tl.b1ring; t.b2ring = tl.b2ring; t.b2d = tl.b2d; }
-    }
-    if (active) finish_correspondence_pad(qi, qpts, qx, qy, qz, t.b1, t.b2, t.b1ring, t.b2ring, key_inf, tgt_pad, tgt_off, norm_cond, out, want_aux != 0);
-}
-
-__global__ void __launch_bounds__(256)
-assoc_lane_kernel(PoseScalars P, const PoseRecord* __restrict__ P_dev, int* __restrict__ chain_fail, GridView G, const float4* __restrict__ qpts, int q_begin, int q_end,
-                  const float4* __restrict__ tgt_pad, const int* __restrict__ tgt_off, unsigned gate_bits, double norm_cond, AssocOut out, int want_aux)
-#if VELO_DEF_ASSOC
-{
-    assoc_lane_body<false>(P, P_dev, chain_fail, G, qpts, q_begin, q_end, tgt_pad, tgt_off, gate_bits, norm_cond, out, want_aux, (int)blockIdx.x);
-}
-#else
-;
-#endif
-// the same round of several contexts in one launch (blockIdx.y = context)
-__global__ void __launch_bounds__(256)
-assoc_lane_batch_kernel(AssocBatch B)
-#if VELO_DEF_ASSOC
-{
-    const AssocArgs& a = B.item[blockIdx.y];
-    if ((int)blockIdx.x * 256 >= a.q_end - a.q_begin) return;
-    assoc_lane_body<false>(a.P, a.P_dev, a.chain_fail, a.G, a.qpts, a.q_begin, a.q_end, a.tgt_pad, a.tgt_off, a.gate_bits, a.norm_cond, a.out, a.want_aux, (int)blockIdx.x);
-}
-#else
-;
-#endif
-
-// ---- association as a balanced pipeline: prepare (clusters -> work items) + persistent per-cluster search -----------------
-// The monolithic kernel above walks a group's clusters one after the other, so a 64-query group with several clusters and
-// two phases each is a long latency chain while most workgroups have already left.  Here a cheap prepare kernel (one
-// wave per group) transforms the queries, forms the clusters and appends ONE WORK ITEM PER CLUSTER; a persistent kernel
-// then keeps every workgroup slot busy: workgroups pull items from a global queue, run that cluster's phases (same LDS
-// staged box walk) and finish the correspondences of the cluster's member lanes.
-struct AssocItem {            // 32 bytes
-    int group;                // 64-query group
-    unsigned mask_lo, mask_hi;
-    int bx, by, bz;           // cell bounding box of the members: lo | hi << 16
-    int pad0, pad1;
-};
-// The queue is split into kQShards sub-queues (one returning atomic on ONE word tops out near 90 per microsecond on
-// this chip): group g appends to shard g % kQShards with a single reservation, a workgroup pulls from shard
-// blockIdx % kQShards first and steals from the others when its own runs dry.  Counters sit on separate 128-byte lines.
-constexpr int kQShards = 8;
-constexpr int kQStride = 32;         // ints between counters
-struct AssocQueue {
-    AssocItem* __restrict__ items;   // kQShards regions of shard_cap items
-    int shard_cap;
-    int* __restrict__ counters;      // [s * kQStride] = items in shard s, [(kQShards + s) * kQStride] = dequeue head of shard s
-    float4* __restrict__ qpos;       // transformed query coordinates (float, as the reference rounds them) per query
-};
-
-__global__ void __launch_bounds__(64)
-assoc_prepare_kernel(PoseScalars P, GridDesc g, const float4* __restrict__ src, const int* __restrict__ q_src, int q_begin, int q_end,
-                     int cluster_w, AssocQueue Q)
-#if VELO_DEF_ASSOC
-{
-    const int lane = threadIdx.x;
-    const int group = blockIdx.x;
-    const int qi = q_begin + group * 64 + lane;
-    const bool active = qi < q_end;
-    float qx = 0.f, qy = 0.f, qz = 0.f;
-    int cx = 0, cy = 0, cz = 0;
-    if (active) {
-        const float4 psrc = src[q_src[qi]];
-        transform_query(P, psrc, &qx, &qy, &qz);
-        cx = cell_coord(qx, g.ox, g.inv_h, g.nx); cy = cell_coord(qy, g.oy, g.inv_h, g.ny); cz = cell_coord(qz, g.oz, g.inv_h, g.nz);
-        Q.qpos[qi] = make_float4(qx, qy, qz, 0.f);
-    }
-    // pass 1: count this group's clusters; one reservation per group in its shard
-    int n_clusters = 0;
-    {
-        bool pending = active;
-        for (;;) {
-            const unsigned long long pm = __ballot(pending);
-            if (pm == 0ull) break;
-            const int leader = (int)__ffsll((long long)pm) - 1;
-            const int scx = __builtin_amdgcn_readlane(cx, leader), scy = __builtin_amdgcn_readlane(cy, leader), scz = __builtin_amdgcn_readlane(cz, leader);
-            const bool member = pending && abs(cx - scx) <= cluster_w && abs(cy - scy) <= cluster_w && abs(cz - scz) <= cluster_w;
-            n_clusters++;
-            pending = pending && !member;
-        }
-    }
-    const int shard = group % kQShards;
-    int base = 0;
-    if (lane == 0 && n_clusters > 0) base = atomicAdd(&Q.counters[shard * kQStride], n_clusters);
-    base = __builtin_amdgcn_readfirstlane(base);
-    // pass 2: write the items
-    bool pending = active;
-    int k = 0;
-    for (;;) {
-        const unsigned long long pm = __ballot(pending);
-        if (pm == 0ull) break;
-        const int leader = (int)__ffsll((long long)pm) - 1;
-        const int scx = __builtin_amdgcn_readlane(cx, leader), scy = __builtin_amdgcn_readlane(cy, leader), scz = __builtin_amdgcn_readlane(cz, leader);
-        const bool member = pending && abs(cx - scx) <= cluster_w && abs(cy - scy) <= cluster_w && abs(cz - scz) <= cluster_w;
-        const unsigned long long mm = __ballot(member);
-        const int big = 1 << 28;
-        const int bx0 = wave_min_i(member ? cx : big), bx1 = wave_max_i(member ? cx : -big);
-        const int by0 = wave_min_i(member ? cy : big), by1 = wave_max_i(member ? cy : -big);
-        const int bz0 = wave_min_i(member ? cz : big), bz1 = wave_max_i(member ? cz : -big);
-        if (lane == 0) {
-            AssocItem it;
-            it.group = group; it.mask_lo = (unsigned)(mm & 0xffffffffull); it.mask_hi = (unsigned)(mm >> 32);
-            // cell coordinates live in [-2, n+1] with n <= 8192: bias by 2 and pack two 16-bit fields
-            it.bx = (bx0 + 2) | ((bx1 + 2) << 16); it.by = (by0 + 2) | ((by1 + 2) << 16); it.bz = (bz0 + 2) | ((bz1 + 2) << 16);
-            it.pad0 = 0; it.pad1 = 0;
-            Q.items[(size_t)shard * Q.shard_cap + base + k] = it;
-        }
-        k++;
-        pending = pending && !member;
-    }
-}
-#else
-;
-#endif
-
-template <int NW, int MINW>
-__global__ void __launch_bounds__(NW * 64, MINW)
-assoc_cluster_kernel(GridView G, AssocQueue Q, const float4* __restrict__ src, const int* __restrict__ q_src, int q_begin, int q_end,
-                     const float4* __restrict__ tgt, const int* __restrict__ tgt_off, const int* __restrict__ ring_of,
-                     unsigned gate_bits, double norm_cond, float h_safe, AssocOut out, int want_aux) {
-    constexpr int NT = NW * 64;
-    constexpr int NRUN = 2 * NT;
-    __shared__ float4 s_xy[kTileCap / 2];
-    __shared__ float4 s_zg[kTileCap / 2];
-    __shared__ int s_ring[kTileCap];
-    __shared__ int s_run_j0[NRUN];
-    __shared__ int s_run_off[NRUN + 1];
-    __shared__ int s_wave_tot[NW];
-    __shared__ unsigned long long m1[NW][64], m2[NW][64];
-    __shared__ int mr[NW][64];
-    __shared__ int s_item;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned long long key_inf = ((unsigned long long)gate_bits + 1ull) << 32;
-    const GridDesc g = G.d;
-    float* s_xy_f = reinterpret_cast<float*>(s_xy);
-    float* s_zg_f = reinterpret_cast<float*>(s_zg);
-    int shard = blockIdx.x % kQShards, tries = 0;
-
-    for (;;) {                                                         // persistent: pull the next cluster
-        if (tid == 0) {
-            int got = -1;
-            while (tries < kQShards) {
-                const int n = Q.counters[shard * kQStride];
-                int* head = &Q.counters[(kQShards + shard) * kQStride];
-                // plain peek first: an exhausted shard costs no atomic
-                if (__hip_atomic_load(head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < n) {
-                    const int h = atomicAdd(head, 1);
-                    if (h < n) { got = shard * Q.shard_cap + h; break; }
-                }
-                shard = (shard + 1) % kQShards; tries++;
-            }
-            s_item = got;
-        }
-        __syncthreads();
-        const int item = s_item;
-        __syncthreads();
-        if (item < 0) break;
-        const AssocItem it = Q.items[item];
-        const unsigned long long mm = ((unsigned long long)it.mask_hi << 32) | it.mask_lo;
-        const bool member = (mm >> lane) & 1ull;
-        const int qi = q_begin + it.group * 64 + lane;
-        const int bx0 = (it.bx & 0xffff) - 2, bx1 = (it.bx >> 16) - 2;
-        const int by0 = (it.by & 0xffff) - 2, by1 = (it.by >> 16) - 2;
-        const int bz0 = (it.bz & 0xffff) - 2, bz1 = (it.bz >> 16) - 2;
-        float qx = 0.f, qy = 0.f, qz = 0.f;
-        if (member) { const float4 qp = Q.qpos[qi]; qx = qp.x; qy = qp.y; qz = qp.z; }
-        const f32x2 qx2 = {qx, qx}, qy2 = {qy, qy}, qz2 = {qz, qz};
-        Top2 t;
-        t.b1 = key_inf; t.b2 = key_inf; t.b1ring = -1; t.b2ring = -1; t.b2d = __uint_as_float(gate_bits + 1u);
-        int e_prev = -1, e = 1;
-        for (;;) {                                                     // phases (see assoc_search_v3_kernel)
-            const int X0 = max(bx0 - e, 0), X1 = min(bx1 + e, g.nx - 1);
-            const int Y0 = max(by0 - e, 0), Y1 = min(by1 + e, g.ny - 1);
-            const int Z0 = max(bz0 - e, 0), Z1 = min(bz1 + e, g.nz - 1);
-            const int px0 = bx0 - e_prev, px1 = bx1 + e_prev, py0 = by0 - e_prev, py1 = by1 + e_prev, pz0 = bz0 - e_prev, pz1 = bz1 + e_prev;
-            const int nyb = Y1 - Y0 + 1, nzb = Z1 - Z0 + 1;
-            const int nrows = (X0 <= X1 && nyb > 0 && nzb > 0) ? nyb * nzb : 0;
-            const float inv_nyb = 1.0f / (float)max(nyb, 1);
-            for (int rbase = 0; rbase < nrows; rbase += NT) {
-                int ja0 = 0, la = 0, jb0 = 0, lb = 0;
-                const int r = rbase + tid;
-                if (r < nrows) {
-                    int zq = (int)(((float)r + 0.5f) * inv_nyb);      // r / nyb for small non-negative ints, fixed up below
-                    zq = (zq * nyb > r) ? zq - 1 : ((zq + 1) * nyb <= r ? zq + 1 : zq);
-                    const int y = Y0 + (r - zq * nyb), z = Z0 + zq;
-                    const int row = (z * g.ny + y);
-                    const bool fresh = e_prev < 0 || y < py0 || y > py1 || z < pz0 || z > pz1;
-                    if (fresh) {
-                        ja0 = grid_start(G, row, X0); la = grid_start(G, row, X1 + 1) - ja0;
-                    } else {
-                        const int a1 = min(px0 - 1, X1), b0 = max(px1 + 1, X0);
-                        if (X0 <= a1) { ja0 = grid_start(G, row, X0); la = grid_start(G, row, a1 + 1) - ja0; }
-                        if (b0 <= X1) { jb0 = grid_start(G, row, b0); lb = grid_start(G, row, X1 + 1) - jb0; }
-                    }
-                }
-                const int mine = la + lb;
-                int inc = mine;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off); if (lane >= off) inc += v; }
-                if (lane == 63) s_wave_tot[wid] = inc;
-                __syncthreads();
-                int wbase = 0, total = 0;
-#pragma unroll
-                for (int w = 0; w < NW; w++) { const int v = s_wave_tot[w]; if (w < wid) wbase += v; total += v; }
-                const int ex = wbase + inc - mine;
-                s_run_j0[2 * tid] = ja0; s_run_off[2 * tid] = ex;
-                s_run_j0[2 * tid + 1] = jb0; s_run_off[2 * tid + 1] = ex + la;
-                if (tid == 0) s_run_off[NRUN] = total;
-                __syncthreads();
-                for (int tbase = 0; tbase < total; tbase += kTileCap) {
-                    const int tn = min(total - tbase, kTileCap);
-                    const int tn8 = (tn + 7) & ~7;                     // the sweep consumes 4 pairs per trip
-                    for (int i = tid; i < tn8; i += NT) {
-                        float4 c = make_float4(__builtin_inff(), __builtin_inff(), __builtin_inff(), __int_as_float(0x7fffffff));
-                        int cr = 0x7fffffff;
-                        if (i < tn) {
-                            const int slot = tbase + i;
-                            int lo = 0;
-#pragma unroll
-                            for (int step = NRUN / 2; step > 0; step >>= 1) {
-                                if (s_run_off[lo + step] <= slot) lo += step;
-                            }
-                            const int j = s_run_j0[lo] + (slot - s_run_off[lo]);
-                            c = G.sorted[j];
-                            cr = G.sring[j];
-                        }
-                        const int pr = i >> 1, hb = i & 1;
-                        s_xy_f[4 * pr + hb] = c.x; s_xy_f[4 * pr + 2 + hb] = c.y;
-                        s_zg_f[4 * pr + hb] = c.z; s_zg_f[4 * pr + 2 + hb] = c.w;
-                        s_ring[i] = cr;
-                    }
-                    __syncthreads();
-                    const int nquads = tn8 >> 3;                       // groups of 4 pairs
-                    const int per = (nquads + NW - 1) / NW;
-                    const int g0 = wid * per, g1 = min(g0 + per, nquads);
-                    if (member) {
-                        for (int gq = g0; gq < g1; gq++) {
-                            const int pi = gq * 4;
-                            float4 a[4], bq[4];
-#pragma unroll
-                            for (int u = 0; u < 4; u++) { a[u] = s_xy[pi + u]; bq[u] = s_zg[pi + u]; }
-                            f32x2 d2[4];
-#pragma unroll
-                            for (int u = 0; u < 4; u++) {
-                                const f32x2 cxp = {a[u].x, a[u].y}, cyp = {a[u].z, a[u].w}, czp = {bq[u].x, bq[u].y};
-                                const f32x2 dx = qx2 - cxp, dy = qy2 - cyp, dz = qz2 - czp;
-                                f32x2 d = dx * dx;                     // x -> y -> z accumulation, no FMA (-ffp-contract=off)
-                                d = d + dy * dy;
-                                d = d + dz * dz;
-                                d2[u] = d;
-                            }
-                            const float dmin = fminf(fminf(fminf(d2[0].x, d2[0].y), fminf(d2[1].x, d2[1].y)), fminf(fminf(d2[2].x, d2[2].y), fminf(d2[3].x, d2[3].y)));
-                            if (dmin <= t.b2d) {
-#pragma unroll
-                                for (int u = 0; u < 4; u++) {
-                                    if (d2[u].x <= t.b2d) {
-                                        const unsigned long long key = ((unsigned long long)__float_as_uint(d2[u].x) << 32) | (unsigned)__float_as_int(bq[u].z);
-                                        top2_update(t, key, s_ring[2 * (pi + u)]);
-                                    }
-                                    if (d2[u].y <= t.b2d) {
-                                        const unsigned long long key = ((unsigned long long)__float_as_uint(d2[u].y) << 32) | (unsigned)__float_as_int(bq[u].w);
-                                        top2_update(t, key, s_ring[2 * (pi + u) + 1]);
-                                    }
-                                }
-                            }
-                        }
-                    }
-                    __syncthreads();
-                }
-            }
-            if (NW > 1) {
-                m1[wid][lane] = t.b1; m2[wid][lane] = t.b2; mr[wid][lane] = t.b1ring;
-                __syncthreads();
-#pragma unroll
-                for (int w = 0; w < NW; w++) {
-                    if (w == wid) continue;
-                    const unsigned long long c1 = m1[w][lane], c2 = m2[w][lane];
-                    if (c1 < t.b2) top2_update(t, c1, mr[w][lane]);
-                    if (c2 < t.b2) top2_update(t, c2, ring_of[(int)(unsigned)(c2 & 0xffffffffull) - out.first_point]);
-                }
-                __syncthreads();
-            }
-            const float rw = __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane(wave_max_i(member ? (int)__float_as_uint(t.b2d) : 0)));
-            const float reach = (float)e * h_safe;
-            if (reach * reach > rw) break;
-            e_prev = e;
-            e = max(e + 1, (int)ceilf(sqrtf(rw) / h_safe));
-            if ((float)e * h_safe * ((float)e * h_safe) <= rw) e++;
-        }
-        // rows A3-A6 for the member lanes of this cluster (wave 0 holds the merged state like every other wave)
-        if (wid == 0 && member && qi < q_end) {
-            const float4 psrc = src[q_src[qi]];
-            finish_correspondence(qi, psrc, qx, qy, qz, t.b1, t.b2, key_inf, tgt, tgt_off, ring_of, norm_cond, out, want_aux != 0);
-        }
-    }
-}
-
 #endif  // VELO_UNIT_LM_ONLY
 // ---- visual blocks (rows G1, R2-R5) ------------------------------------------------------------------------------------
-// One record per match, three block slots: slot 0 = 3D3D or 2D2D, slot 1 = 3D2D, slot 2 = 2D3D (velo.h order).
-struct VisualMatch {      // device copy of velo_match, floats kept as floats and widened at use (costfunctions.h ctors)
-    float p3_1[3], p3_2[3], p2_1[2], p2_2[2], t_cam[3];
-    int cam, point1, point2;
-    unsigned char d1, d2, pad[2];
-};
+// (the match record, VisualMatch, is in velo_scan_types.h)
 struct VisualParams {
     double w_3d2d, w_2d2d;
     double th_3d2d, th_2d2d, th_3d3d;
@@ -3342,39 +2418,6 @@ __device__ __forceinline__ void accumulate_row(double acc[kNumAcc], double r, co
 // 8-byte stores), eight threads per accumulator add 8 values each, one thread per accumulator adds those eight and stores.
 // Two barriers; 14 KB of LDS, so that a sweep workgroup fits next to four association workgroups.  Fixed order -> deterministic.
 constexpr int kScratchDoubles = 128 * kNumAcc;                    // 28,672 bytes: the sweep's reduction and the step's chunk of partial rows share it
-#ifndef VELO_REDUCE_LDS
-#define VELO_REDUCE_LDS 1
-#endif
-#if !VELO_REDUCE_LDS
-// A/B: the halving butterfly (1 KB of LDS)
-__device__ __forceinline__ void block_reduce_store(double acc[kNumAcc], double* __restrict__ dst /* [28] */, double* __restrict__) {
-    __shared__ double red[kEvalThreads / kWave][32];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    double v[32];
-#pragma unroll
-    for (int k = 0; k < 32; k++) v[k] = (k < kNumAcc) ? acc[k] : 0.0;
-#pragma unroll
-    for (int n = 16, mask = 32; n >= 1; n >>= 1, mask >>= 1) {
-        const bool hi = (lane & mask) != 0;
-#pragma unroll
-        for (int i = 0; i < n; i++) {
-            const double mine = hi ? v[i + n] : v[i];
-            const double send = hi ? v[i] : v[i + n];
-            v[i] = mine + __shfl_xor(send, mask);
-        }
-    }
-    v[0] += __shfl_xor(v[0], 1);
-    const int idx = ((lane >> 5) & 1) * 16 + ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
-    if ((lane & 1) == 0) red[wid][idx] = v[0];
-    __syncthreads();
-    if (threadIdx.x < kNumAcc) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < kEvalThreads / kWave; w++) t += red[w][threadIdx.x];
-        dst[threadIdx.x] = t;
-    }
-}
-#else
 // Agent-scope accesses for data one workgroup hands to another INSIDE a launch (the partial rows of the fused sweep + step): the
 // store is written through to where every XCD sees it, the load does not stop at an L2 line another XCD's store has made stale.
 // No release/acquire fence anywhere on that path -- on this chip an agent-scope fence writes back / invalidates a whole L2.
@@ -3414,7 +2457,6 @@ __device__ __forceinline__ void block_reduce_store(double acc[kNumAcc], double* 
         if (COHERENT) store_agent(dst + t, v); else dst[t] = v;
     }
 }
-#endif
 
 // The eval point into LDS: one cooperative copy of the block the LM step left (or, for an explicit x, built here by four
 // lanes).  Returns false when the solve is already done (every thread of the workgroup gets the same answer).
@@ -3557,11 +2599,7 @@ __device__ __forceinline__ void eval_icp_body(const EvalArgs& A, const int bx, c
     double acc[kNumAcc];
     sweep_rows<true>(A, f, s_pt, bx, nbx, acc);
     VELO_LM_TRACE(A.trace, A.trace_eval, 2);
-#if VELO_REDUCE_LDS
     __shared__ double s_scratch[kScratchDoubles / 2];            // 64 columns x 28: 14 KB (the sweep must fit next to association workgroups)
-#else
-    double* s_scratch = nullptr;
-#endif
     block_reduce_store(acc, A.partials + (size_t)bx * kNumAcc, s_scratch);
     VELO_LM_TRACE(A.trace, A.trace_eval, 3);
 }
@@ -3708,11 +2746,7 @@ __device__ __forceinline__ void eval_visual_body(const EvalArgs& A, const int bx
     if (!eval_point_load(A, &s_pt)) return;
     double acc[kNumAcc];
     visual_sweep_acc(A, s_pt, bx, nbx, acc);
-#if VELO_REDUCE_LDS
     __shared__ double s_scratch[kScratchDoubles / 2];
-#else
-    double* s_scratch = nullptr;
-#endif
     block_reduce_store(acc, A.partials + (size_t)(A.vis_row0 + bx) * kNumAcc, s_scratch);
 }
 
@@ -4123,9 +3157,7 @@ __device__ __forceinline__ void lm_advance(const LMParams& Q, const LMState* __r
         __syncthreads();
         if (comm) peer_allreduce28(*comm, E);                // query-sharded: every rank continues with the same 28 sums
         VELO_LM_TRACE(trace, trace_eval, 6);
-#ifndef VELO_X1
         if (t < 64) lm_transition_wave(Q, sL, E, t);
-#endif
         if (t == 0 && sL->done && writer) {                  // the solve has just finished: what the host and the next round need
             if (log) {
                 for (int i = 0; i < 6; i++) log->x[i] = sL->x[i];
@@ -4136,9 +3168,7 @@ __device__ __forceinline__ void lm_advance(const LMParams& Q, const LMState* __r
                 double xf[6];
                 for (int i = 0; i < 6; i++) xf[i] = sL->x[i];
                 PoseScalars S;
-#ifndef VELO_X2
                 pose_scalars_compute(xf, &S);
-#endif
                 pose_out->P = S;
                 __threadfence();
                 pose_out->ready = 1;
@@ -4152,9 +3182,7 @@ __device__ __forceinline__ void lm_advance(const LMParams& Q, const LMState* __r
         const bool cand = sL->phase == PHASE_CAND;
 #pragma unroll
         for (int k = 0; k < 6; k++) x[k] = cand ? sL->xc[k] : sL->x[k];
-#ifndef VELO_X3
         eval_point_column(x, sL->done, t, s_pt);
-#endif
     }
     __syncthreads();
     VELO_LM_TRACE(trace, trace_eval, 8);
@@ -4472,9 +3500,6 @@ template <bool M_LDS, int PRE, int CHUNK, bool VIS = false, bool ROWS_TOGETHER =
 __device__ __forceinline__ void eval_step_batch_body(const LMParams& Q, const LMBatchItem& it, int* __restrict__ tickets, const int first) {
     const int bx = blockIdx.x, nbx = it.nb_icp, nb_all = VIS ? it.nb_icp + it.nb_vis : it.nb_icp;
     if (bx >= nb_all) return;
-#ifdef VELO_LM_SETPRIO
-    __builtin_amdgcn_s_setprio(VELO_LM_SETPRIO);                      // A/B: the LM chain's waves ahead of other groups' association waves in a SIMD's issue arbitration
-#endif
     const EvalArgs& A = it.A;
     const RowPrefetchT<PRE> f = prefetch_rows<PRE>(A, (VIS && bx >= nbx) ? 0 : bx, nbx);   // (a visual workgroup: block 0's rows, unused)
     __shared__ LMEvalPoint s_pt;
@@ -4524,17 +3549,15 @@ eval_step_batch_kernel(LMParams Q, const LMBatchItem* __restrict__ items, int* _
 ;
 #endif
 // The LEAN instantiation, for launches that share the chip with other lock-step groups' association kernels: matrices read from LDS,
-// VELO_LEAN_PRE prefetched rows, the step's partial rows 64 at a time -- few enough registers and LDS (<= 152 VGPRs, < 25 KB) that a
+// kLeanPre prefetched rows, the step's partial rows 64 at a time -- few enough registers and LDS (<= 152 VGPRs, < 25 KB) that a
 // workgroup fits on a CU beside FIVE association workgroups (5 x 72 VGPRs of 512 per SIMD, 5 x 27 KB of 160 KB with the pad the batch
 // driver gives them), so an LM launch never waits for association workgroups to drain.  Same arithmetic, same order: bit-identical.
-#ifndef VELO_LEAN_PRE
-#define VELO_LEAN_PRE 1
-#endif
+constexpr int kLeanPre = 1;
 __global__ void __launch_bounds__(kEvalThreads) __attribute__((amdgpu_num_vgpr(152)))
 eval_step_batch_lean_kernel(LMParams Q, const LMBatchItem* __restrict__ items, int* __restrict__ tickets, int first)
 #if VELO_DEF_LMB
 {
-    eval_step_batch_body<true, VELO_LEAN_PRE, 64>(Q, items[blockIdx.y], tickets, first);
+    eval_step_batch_body<true, kLeanPre, 64>(Q, items[blockIdx.y], tickets, first);
 }
 #else
 ;
@@ -4543,7 +3566,7 @@ __global__ void __launch_bounds__(kEvalThreads) __attribute__((amdgpu_num_vgpr(1
 eval_step_batch_lean_vis_kernel(LMParams Q, const LMBatchItem* __restrict__ items, int* __restrict__ tickets, int first)
 #if VELO_DEF_LMB
 {
-    eval_step_batch_body<true, VELO_LEAN_PRE, 64, true>(Q, items[blockIdx.y], tickets, first);
+    eval_step_batch_body<true, kLeanPre, 64, true>(Q, items[blockIdx.y], tickets, first);
 }
 #else
 ;
@@ -4573,7 +3596,7 @@ __global__ void __launch_bounds__(kEvalThreads) __attribute__((amdgpu_num_vgpr(1
 eval_step_batch_lean_v_kernel(LMParams Q, LMBatchPackV P, int* __restrict__ tickets, int first)
 #if VELO_DEF_LMB
 {
-    eval_step_batch_body<true, VELO_LEAN_PRE, 64>(Q, P.item[blockIdx.y], tickets, first);
+    eval_step_batch_body<true, kLeanPre, 64>(Q, P.item[blockIdx.y], tickets, first);
 }
 #else
 ;
@@ -4584,7 +3607,7 @@ __global__ void __launch_bounds__(kEvalThreads) __attribute__((amdgpu_num_vgpr(1
 eval_step_batch_lean_v_slim_kernel(LMParams Q, LMBatchPackV P, int* __restrict__ tickets, int first)
 #if VELO_DEF_LMB
 {
-    eval_step_batch_body<true, VELO_LEAN_PRE, 64, false, false>(Q, P.item[blockIdx.y], tickets, first);
+    eval_step_batch_body<true, kLeanPre, 64, false, false>(Q, P.item[blockIdx.y], tickets, first);
 }
 #else
 ;
@@ -4593,7 +3616,7 @@ __global__ void __launch_bounds__(kEvalThreads) __attribute__((amdgpu_num_vgpr(1
 eval_step_batch_lean_vis_v_kernel(LMParams Q, LMBatchPackV P, int* __restrict__ tickets, int first)
 #if VELO_DEF_LMB
 {
-    eval_step_batch_body<true, VELO_LEAN_PRE, 64, true>(Q, P.item[blockIdx.y], tickets, first);
+    eval_step_batch_body<true, kLeanPre, 64, true>(Q, P.item[blockIdx.y], tickets, first);
 }
 #else
 ;
@@ -4627,7 +3650,7 @@ lm_iter_batch_lean_kernel(LMParams Q, LMBatchPackV P, int parity, int first, siz
 {
     const LMBatchItem& it = P.item[blockIdx.y];
     if ((int)blockIdx.x >= it.nb_icp) return;
-    lm_iter_lean_body<true, VELO_LEAN_PRE, 64>(it.A, Q, it.S + parity, it.S + (parity ^ 1), it.A.partials + (size_t)parity * half, it.nb_icp,
+    lm_iter_lean_body<true, kLeanPre, 64>(it.A, Q, it.S + parity, it.S + (parity ^ 1), it.A.partials + (size_t)parity * half, it.nb_icp,
                                                it.A.partials + (size_t)(parity ^ 1) * half, first, it.xd, it.n_valid, blockIdx.x, it.nb_icp, it.pose_out, it.log);
 }
 #else
@@ -4636,9 +3659,6 @@ lm_iter_batch_lean_kernel(LMParams Q, LMBatchPackV P, int parity, int first, siz
 // (the all-gather solve, lm_solve_ag_batch_kernel, lives in velo_lm_ag_kernels.h / velo_lm_ag.hip: a translation unit of its own)
 __device__ __forceinline__ int ctl_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void ctl_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-#ifndef VELO_TEST_ATTR
-#define VELO_TEST_ATTR __attribute__((amdgpu_num_vgpr(152)))
-#endif
 struct AgCtl { int epoch, abort, pad[30]; int flag[2][kMaxEvalBlocks]; };
 
 // ---- a whole solve of a lock-step group in ONE launch ---------------------------------------------------------------------------------
@@ -4684,11 +3704,7 @@ __device__ __forceinline__ int persist_sweep(const EvalArgs& A, SolveCtl* __rest
         reinterpret_cast<unsigned long long*>(s_pt)[t] = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(pt) + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     double acc[kNumAcc];
-#ifndef VELO_T2
     sweep_rows<true, PRE, false>(A, f, *s_pt, bx, nb, acc);
-#else
-    for (int q = 0; q < kNumAcc; q++) acc[q] = f.p[0].x;
-#endif
     block_reduce_store<true>(acc, A.partials + (size_t)bx * kNumAcc, s_scratch);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                      // this thread's row entries have been written through
     __syncthreads();
@@ -4736,9 +3752,7 @@ __device__ __forceinline__ void lm_solve_persist_body(const LMParams& Q, const L
         if (advance) {                                                    // (workgroup-uniform)
             if (advance == 2 && t == 0) ctl_store(&ctl->arrived, 0);
             // start: what lm_begin_kernel does (state reset, eval point 0); else the transition over this iteration's partial rows
-#ifndef VELO_T1
             persist_advance(&Q, itp, advance == 1 ? 1 : 0, s_scratch, &sL, &s_pt);
-#endif
             if (t < (int)(sizeof(LMState) / 8)) __hip_atomic_store(reinterpret_cast<unsigned long long*>(it.S) + t, reinterpret_cast<const unsigned long long*>(&sL)[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             else if (t >= 64 && t < 64 + (int)(sizeof(LMEvalPoint) / 8)) __hip_atomic_store(reinterpret_cast<unsigned long long*>(pt) + (t - 64), reinterpret_cast<const unsigned long long*>(&s_pt)[t - 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -4757,7 +3771,7 @@ __global__ void __launch_bounds__(kEvalThreads, 3)                    // <= 168 
 lm_solve_persist_batch_kernel(LMParams Q, const LMBatchItem* __restrict__ items, SolveCtl* __restrict__ ctl, int kmax)
 #if VELO_DEF_LMB
 {
-    lm_solve_persist_body<VELO_LEAN_PRE>(Q, items + blockIdx.y, ctl + blockIdx.y, kmax, (int)gridDim.x);
+    lm_solve_persist_body<kLeanPre>(Q, items + blockIdx.y, ctl + blockIdx.y, kmax, (int)gridDim.x);
 }
 #else
 ;
@@ -4882,9 +3896,7 @@ lm_solve_small_body(const EvalArgs& A, const LMParams& Q, LMState* Sg, const dou
                 double xf[6];
                 for (int i = 0; i < 6; i++) xf[i] = sL.x[i];
                 PoseScalars S;
-#ifndef VELO_X2
                 pose_scalars_compute(xf, &S);
-#endif
                 pose_out->P = S;
                 __threadfence();
                 pose_out->ready = 1;
@@ -5002,8 +4014,6 @@ VELO_INST_LOAD __global__ void scan_lookback_kernel<kLbItemsLarge>(int*, int, un
 VELO_INST_LOAD __global__ void advance_scan_kernel<kLbItemsSmall>(AdvBatch);
 VELO_INST_LOAD __global__ void advance_scan_kernel<kLbItemsLarge>(AdvBatch);
 #define VELO_V5_ARGS (PoseScalars, const PoseRecord*, int*, GridView, const float4*, int, int, const float4*, const int*, unsigned, double, int, float, AssocOut, int, const int*, int, int)
-#define VELO_V3_ARGS (PoseScalars, GridView, const float4*, const int*, int, int, const float4*, const int*, const int*, unsigned, double, int, float, AssocOut, int, int, int)
-#define VELO_CLUSTER_ARGS (GridView, AssocQueue, const float4*, const int*, int, int, const float4*, const int*, const int*, unsigned, double, float, AssocOut, int)
 VELO_INST_ASSOC __global__ void assoc_search_v5_kernel<4, 5, false, 2, 0> VELO_V5_ARGS;
 VELO_INST_ASSOC __global__ void assoc_search_v5_kernel<4, 5, false, 2, 1> VELO_V5_ARGS;
 VELO_INST_ASSOC __global__ void assoc_search_v5_batch_kernel<4, 5, false, 2, 0>(AssocBatch);
@@ -5016,27 +4026,8 @@ VELO_INST_ASSOC __global__ void assoc_search_v5_kernel<4, 6, false, 2, 1> VELO_V
 VELO_INST_ASSOC __global__ void assoc_search_v5_kernel<4, 6, false, 2, 0> VELO_V5_ARGS;
 VELO_INST_ASSOC __global__ void assoc_search_v5_kernel<4, 7, false, 2, 0> VELO_V5_ARGS;
 VELO_INST_ASSOC __global__ void assoc_search_v5_kernel<4, 8, false, 2, 0> VELO_V5_ARGS;
-VELO_INST_ASSOC __global__ void assoc_search_v3_kernel<1, 1, false> VELO_V3_ARGS;
-VELO_INST_ASSOC __global__ void assoc_search_v3_kernel<1, 1, true> VELO_V3_ARGS;
-VELO_INST_ASSOC __global__ void assoc_search_v3_kernel<2, 1, false> VELO_V3_ARGS;
-VELO_INST_ASSOC __global__ void assoc_search_v3_kernel<2, 1, true> VELO_V3_ARGS;
-VELO_INST_ASSOC __global__ void assoc_search_v3_kernel<4, 5, false> VELO_V3_ARGS;
-VELO_INST_ASSOC __global__ void assoc_search_v3_kernel<4, 5, true> VELO_V3_ARGS;
-VELO_INST_ASSOC __global__ void assoc_search_v3_kernel<4, 6, false> VELO_V3_ARGS;
-VELO_INST_ASSOC __global__ void assoc_search_v3_kernel<4, 6, true> VELO_V3_ARGS;
-VELO_INST_ASSOC __global__ void assoc_search_v3_kernel<4, 7, false> VELO_V3_ARGS;
-VELO_INST_ASSOC __global__ void assoc_search_v3_kernel<4, 7, true> VELO_V3_ARGS;
-VELO_INST_ASSOC __global__ void assoc_search_v3_kernel<4, 8, false> VELO_V3_ARGS;
-VELO_INST_ASSOC __global__ void assoc_search_v3_kernel<4, 8, true> VELO_V3_ARGS;
-VELO_INST_ASSOC __global__ void assoc_search_v3_kernel<8, 8, false> VELO_V3_ARGS;
-VELO_INST_ASSOC __global__ void assoc_search_v3_kernel<8, 8, true> VELO_V3_ARGS;
-VELO_INST_ASSOC __global__ void assoc_cluster_kernel<2, 1> VELO_CLUSTER_ARGS;
-VELO_INST_ASSOC __global__ void assoc_cluster_kernel<4, 6> VELO_CLUSTER_ARGS;
-VELO_INST_ASSOC __global__ void assoc_cluster_kernel<8, 6> VELO_CLUSTER_ARGS;
 #endif
 #undef VELO_V5_ARGS
-#undef VELO_V3_ARGS
-#undef VELO_CLUSTER_ARGS
 #endif  // VELO_UNIT_LM_ONLY
 
 }  // namespace velo

@@ -31,9 +31,7 @@ namespace velo {
 #ifndef VELO_AG_KATTR
 #define VELO_AG_KATTR
 #endif
-#ifndef VELO_AG_PRE
-#define VELO_AG_PRE VELO_LEAN_PRE
-#endif
+constexpr int kAgPre = kLeanPre;
 #ifndef VELO_AG_WAVES
 #define VELO_AG_WAVES 3
 #endif
@@ -110,7 +108,7 @@ __device__ __forceinline__ void lm_solve_ag_body(const LMParams& Q, const LMBatc
 }
 __global__ void __launch_bounds__(kEvalThreads, VELO_AG_WAVES) VELO_AG_KATTR
 lm_solve_ag_batch_kernel(LMParams Q, LMBatchPackV P, AgCtl* __restrict__ ctl, int kmax, size_t half) {
-    lm_solve_ag_body<true, VELO_AG_PRE, 64>(Q, P.item[blockIdx.y], ctl + blockIdx.y, kmax, half);
+    lm_solve_ag_body<true, kAgPre, 64>(Q, P.item[blockIdx.y], ctl + blockIdx.y, kmax, half);
 }
 
 

@@ -1,5 +1,5 @@
 // velo_tri_kernels.h -- SURVEY.md 8(f) row 4: batched triangulatePoint (reference velo.h:1027-1130, functors
-// costfunctions.h:288-375).  Included by velo_hip.hip after velo_kernels.h (LMParams, loss functions); gfx950 only.
+// costfunctions.h:288-375).  Its kernels belong to the VELO_DEF_LOAD family (velo_unit_load.hip defines them); gfx950 only.
 //
 // Every landmark is an independent 3-unknown Levenberg-Marquardt problem over a handful of observations (3..30), thousands per
 // frame.  Two kernels with identical results: one WAVE per landmark (default, see triangulate_wave_kernel below) and one thread
@@ -14,7 +14,12 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/velo_hip.h"
-#include "velo_device_math.h"
+#include "velo_device_math.h"   // loss functions
+#include "velo_trust_region.h"   // LMParams
+
+#ifndef VELO_DEF_LOAD
+#define VELO_DEF_LOAD 0
+#endif
 
 namespace velo {
 

@@ -9,3 +9,6 @@
 
 #define VELO_DEF_ASSOC 1
 #include "velo_kernels.h"
+#ifdef VELO_DIAGNOSTICS
+#include "velo_assoc_ab_kernels.h"   // the A/B kernels exist in the diagnostics build only
+#endif
