@@ -863,6 +863,28 @@ int velo_graph_order(int32_t n_nodes, int32_t n_edges, const int32_t* a, const i
  * nodes with a pose that are not fixed, ascending: cost, J^T r (gradient [n_free][6]) and the diagonal blocks of J^T J (diag_blocks
  * [n_free][36], row-major), unscaled.  Each output may be NULL. */
 int velo_graph_system(velo_ctx* ctx, const int32_t* fixed, int32_t n_fixed, double* cost, double* gradient, double* diag_blocks);
+/* Marginal and joint covariances of the poses (what iSAM offers as slam.covariances()), evaluated at the stored state; nothing in the
+ * store changes.  The free nodes are those of velo_graph_optimize with the same `fixed`.  H = J^T J is the UNDAMPED normal matrix of
+ * the problem the solvers see: the Jacobian whitened by sqrt(info) or by the Cholesky factor of W, corrected by the robust loss where
+ * an edge has one.  Sigma = H^-1, in the coordinates the solver steps in (the 6 doubles of a node): Ceres' Covariance convention for
+ * cost = sum |r|^2 / 2.  Pair p returns Cov(frame_a[p], frame_b[p]) as cov36[p], row-major 6 x 6: the marginal for a == b, the cross
+ * block Sigma_ab (not its transpose) otherwise; a pair that names a fixed frame returns 36 zeros (a constant has no uncertainty).
+ * (a, b) and (b, a) are transposes of one another to the bit, a marginal is symmetric to the bit, and two identical calls give
+ * identical bytes.
+ *   method    the Jacobi-scaled H is factored by the envelope Cholesky in the order of velo_graph_order; the entries of its inverse
+ *             inside the envelope follow from the factor by the Takahashi recursion (one workgroup, the factorisation's block-product
+ *             count): every marginal and the pair of every edge between free nodes lie there.  A pair outside the envelope costs a
+ *             column solve of its own (forward and back substitution with 6 right-hand sides) over a work vector of n_free x 36
+ *             doubles; pairs in different components of the free graph return an exact zero block.
+ *   params    only reserved[1], the envelope's work cap, is read (NULL, or 0 there: VELO_GRAPH_DEFAULT_MAX_WORK); the other members
+ *             are validated as velo_graph_optimize validates them.
+ * Refused before anything is written to cov36: what velo_graph_optimize refuses; VELO_ERR_INVALID for n_pairs < 0, a NULL array with
+ * n_pairs > 0, a frame out of range, an order whose work exceeds the cap (the envelope solver's message), pairs outside the envelope
+ * whose work vectors exceed VELO_GRAPH_MAX_COLUMN_DOUBLES in all, and an H that is not positive definite -- the message names the frame
+ * of the failing pivot; a free node without edges is the case; VELO_ERR_STATE for a frame without a pose. */
+#define VELO_GRAPH_MAX_COLUMN_DOUBLES (1 << 27)  /* work vectors of one call's pairs outside the envelope: pairs x n_free x 36 doubles (1 GiB) */
+int velo_graph_covariance(velo_ctx* ctx, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params,
+                          int32_t n_pairs, const int32_t* frame_a, const int32_t* frame_b, double* cov36 /* [n_pairs][36] row-major */);
 
 /* --- resident keypoint frames and the visual matches assembled from them (velo.h:562-590, velo.h:627-654, main.cpp:366-405) ---
  * Every context can hold one frame store: for every (frame, camera) put so far keypoints[cam][frame], keypoint_ids[cam][frame],

@@ -10,6 +10,8 @@
 //     graph.optimize(fixed);                                         // fixed = {0}: the reference's prior on the first node
 //     graph.optimize(fixed, &summary, 0, VELO_GRAPH_SOLVER_ENVELOPE); // the same with the exact envelope solver: a whole drive
 //     graph.poses(0, n, &flat);                                      // n x 6, for velo_landmarks_set_pose / velo_map_set_pose
+//     graph.covariance(frames, fixed, &cov36);                       // how well each pose is determined: 6 x 6 marginals
+//     graph.jointCovariance(loop_from, frame, fixed, joint144);      // 12 x 12, for a Mahalanobis loop-closure gate
 #ifndef VELO_POSE_GRAPH_HPP_
 #define VELO_POSE_GRAPH_HPP_
 
@@ -97,6 +99,29 @@ public:
         flat->swap(out);
         return VELO_OK;
     }
+    // the marginal covariance of every frame of `frames` at the stored poses (velo_graph_covariance): 36 doubles each, row-major, in the
+    // coordinates of a node's 6 doubles; zeros for a fixed frame.  fixed: as for optimize; max_work: the envelope's cap (0: the default)
+    int covariance(const std::vector<int>& frames, const std::vector<int>& fixed, std::vector<double>* cov36, int max_work = 0) const {
+        std::vector<int32_t> a(frames.begin(), frames.end());
+        return covariancePairs(a, a, fixed, cov36, max_work);
+    }
+    // the 12 x 12 joint covariance of frames a and b, row-major, from the three blocks of one call: [Saa Sab; Sab^T Sbb]
+    int jointCovariance(int a, int b, const std::vector<int>& fixed, double joint144[144], int max_work = 0) const {
+        std::vector<int32_t> fa(3, (int32_t)a), fb(3, (int32_t)b);
+        fb[0] = a; fa[2] = b;                                          // (a, a), (a, b), (b, b)
+        std::vector<double> blk;
+        const int st = covariancePairs(fa, fb, fixed, &blk, max_work);
+        if (st != VELO_OK) return st;
+        for (int r = 0; r < 6; r++)
+            for (int c = 0; c < 6; c++) {
+                joint144[r * 12 + c] = blk[(size_t)(r * 6 + c)];
+                joint144[r * 12 + 6 + c] = blk[(size_t)(36 + r * 6 + c)];
+                joint144[(6 + c) * 12 + r] = blk[(size_t)(36 + r * 6 + c)];
+                joint144[(6 + r) * 12 + 6 + c] = blk[(size_t)(72 + r * 6 + c)];
+            }
+        return VELO_OK;
+    }
+
     int info(Info* out) const {
         int32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         const int st = velo_graph_info(ctx_, v);
@@ -106,6 +131,19 @@ public:
     }
 
 private:
+    int covariancePairs(const std::vector<int32_t>& a, const std::vector<int32_t>& b, const std::vector<int>& fixed, std::vector<double>* cov36, int max_work) const {
+        std::vector<int32_t> f(fixed.begin(), fixed.end());
+        velo_graph_params own;
+        const int ps = velo_default_graph_params(&own);
+        if (ps != VELO_OK) return ps;
+        own.reserved[1] = max_work;
+        std::vector<double> out(36 * a.size() + 36);
+        const int st = velo_graph_covariance(ctx_, f.empty() ? 0 : &f[0], (int32_t)f.size(), &own, (int32_t)a.size(), a.empty() ? 0 : &a[0], b.empty() ? 0 : &b[0], &out[0]);
+        if (st != VELO_OK) return st;
+        out.resize(36 * a.size());
+        cov36->swap(out);
+        return VELO_OK;
+    }
     PoseGraph(const PoseGraph&);                           // one owner of the context's store
     PoseGraph& operator=(const PoseGraph&);
     velo_ctx* ctx_;

@@ -387,6 +387,7 @@ SIGNATURES = {
     "velo_graph_info": (C.c_int, [_ctx, C.c_void_p]),
     "velo_graph_order": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "velo_graph_system": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _dp, C.c_void_p, C.c_void_p]),
+    "velo_graph_covariance": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(VeloGraphParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "velo_frames_reset": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_int32]),
     "velo_frames_put": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "velo_frames_drop": (C.c_int, [_ctx, C.c_int32]),
@@ -975,6 +976,38 @@ class Context:
         self._check(self._lib.velo_graph_system(self._h, C.c_void_p(fx.ctypes.data) if len(fx) else None, len(fx), C.byref(cost),
                                                 C.c_void_p(g.ctypes.data), C.c_void_p(H.ctypes.data)))
         return cost.value, g, H
+
+    def graph_covariance(self, pairs_or_frames, fixed=(0,), max_work=None) -> np.ndarray:
+        """Covariances of the poses at the stored state (nothing changes): blocks of (J^T J)^-1 of the problem graph_optimize would
+        solve, in the coordinates of a node's 6 doubles.  A 1-D list of frames asks for their marginals, an [n, 2] array for
+        Cov(a, b) per row (a == b: the marginal; otherwise the cross block, not its transpose); returns [n, 6, 6].  A fixed frame's
+        block is zero.  max_work caps the envelope factorisation's block products (None: the library's default).  Refused: what
+        graph_optimize refuses, a frame without a pose, and a J^T J that is not positive definite (a free node without edges)."""
+        q = np.asarray(pairs_or_frames)
+        if q.size and not np.issubdtype(q.dtype, np.integer):
+            raise ValueError("graph_covariance: frames are integers")
+        if q.ndim == 1:
+            q = np.stack([q, q], axis=1) if q.size else np.zeros((0, 2), dtype=np.int32)
+        elif q.ndim != 2 or q.shape[1] != 2:
+            raise ValueError("graph_covariance: a 1-D list of frames (marginals) or an [n, 2] array of pairs")
+        a = np.ascontiguousarray(q[:, 0], dtype=np.int32)
+        b = np.ascontiguousarray(q[:, 1], dtype=np.int32)
+        fx = np.ascontiguousarray(np.asarray(fixed, dtype=np.int32).reshape(-1))
+        out = np.zeros((max(len(a), 1), 6, 6), dtype=np.float64)
+        params = None
+        if max_work is not None:
+            params = self._graph_params(None, None, "cg", max_work)
+        vp = lambda v: C.c_void_p(v.ctypes.data) if len(v) else None  # noqa: E731
+        self._check(self._lib.velo_graph_covariance(self._h, vp(fx), len(fx), params, len(a), vp(a), vp(b), C.c_void_p(out.ctypes.data)))
+        return out[:len(a)]
+
+    def graph_joint_covariance(self, a: int, b: int, fixed=(0,)) -> np.ndarray:
+        """The 12 x 12 joint covariance of frames a and b, from the three blocks of one graph_covariance call; symmetric by construction:
+        its (b, a) block is the transpose of the returned (a, b) block."""
+        blk = self.graph_covariance([[a, a], [a, b], [b, b]], fixed)
+        J = np.empty((12, 12), dtype=np.float64)
+        J[:6, :6], J[:6, 6:], J[6:, :6], J[6:, 6:] = blk[0], blk[1], blk[1].T, blk[2]
+        return J
 
     # -- resident keypoint frames and the visual matches assembled from them (velo.h:562-590, velo.h:627-654) ---------------
     def frames_reset(self, cam_trans, arena_capacity: int = 0):

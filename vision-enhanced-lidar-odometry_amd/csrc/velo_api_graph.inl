@@ -34,6 +34,10 @@ struct GraphStore {
     DevBuf<int> env_idx;
     DevBuf<double> env;
     int env_widest = 0, env_blocks = 0;                  // of the last envelope solve (velo_graph_info)
+    // velo_graph_covariance: the selected inverse (a second skyline), the column solves' work vectors, the pairs' ints, and the record
+    // with the pairs' blocks behind it (one copy to the host)
+    DevBuf<double> cov_z, cov_work, cov_out;
+    DevBuf<int> cov_pair;
 };
 
 namespace {
@@ -59,6 +63,8 @@ struct GraphCall {
     int n_free = 0, E = 0;
     bool envelope = false;                               // set by the caller: graph_begin then orders the free nodes and checks the work
     int64_t max_work = 0, env_stats[4] = {0, 0, 0, 0};
+    const char* who = "velo_graph_optimize";             // the entry a refusal names
+    std::vector<int32_t> env_ints;                       // of an envelope call: perm [n], pos [n], first [n], rowptr [n + 1], last [n]
 };
 
 // velo_graph_order's rule (include/velo_hip.h), on checked arguments
@@ -212,7 +218,8 @@ int graph_begin(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
     }
     // the envelope solver's order of the free nodes (velo_graph_order on the edges between two of them), refused here -- before anything is
     // sent -- when its work exceeds the cap; ints: perm, pos, first, rowptr, last
-    std::vector<int32_t> env_ints;
+    std::vector<int32_t>& env_ints = call->env_ints;
+    env_ints.clear();
     if (call->envelope && n) {
         std::vector<int32_t> ea, eb, perm(n), first(n);
         for (size_t e = 0; e < E; e++) {
@@ -221,9 +228,9 @@ int graph_begin(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
         }
         graph_order((int32_t)n, (int32_t)ea.size(), ea.data(), eb.data(), perm.data(), first.data(), call->env_stats);
         if (call->env_stats[2] > call->max_work)
-            return fail(VELO_ERR_INVALID, "velo_graph_optimize: the envelope solver's work is %lld block products, over the cap of %lld (widest row %lld blocks, %lld free nodes); "
-                        "raise reserved[1] or use the CG solver", (long long)call->env_stats[2], (long long)call->max_work, (long long)call->env_stats[0], (long long)n);
-        if (call->env_stats[1] > (int64_t)1 << 30) return fail(VELO_ERR_INVALID, "velo_graph_optimize: an envelope of %lld blocks; at most 2^30", (long long)call->env_stats[1]);
+            return fail(VELO_ERR_INVALID, "%s: the envelope solver's work is %lld block products, over the cap of %lld (widest row %lld blocks, %lld free nodes); "
+                        "raise reserved[1] or use the CG solver", call->who, (long long)call->env_stats[2], (long long)call->max_work, (long long)call->env_stats[0], (long long)n);
+        if (call->env_stats[1] > (int64_t)1 << 30) return fail(VELO_ERR_INVALID, "%s: an envelope of %lld blocks; at most 2^30", call->who, (long long)call->env_stats[1]);
         env_ints.resize(5 * n + 1);
         int32_t* pos = env_ints.data() + n;
         int32_t* rowptr = env_ints.data() + 3 * n;
@@ -618,6 +625,109 @@ int velo_graph_system(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, double
     if (cost) *cost = rec->red[0];
     const double* nd = (const double*)tail;
     for (size_t i = 0; i < n; i++) expand_upper6(nd + i * kGrNode, gradient ? gradient + 6 * i : nullptr, diag_blocks ? diag_blocks + 36 * i : nullptr);
+    return VELO_OK;
+}
+
+int velo_graph_covariance(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, int32_t n_pairs,
+                          const int32_t* frame_a, const int32_t* frame_b, double* cov36) {
+    const char* who = "velo_graph_covariance";
+    VELO_TRY(graph_check(c, fixed, n_fixed, params, who));
+    if (n_pairs < 0) return fail(VELO_ERR_INVALID, "%s: negative pair count", who);
+    if (n_pairs > 0 && (!frame_a || !frame_b || !cov36)) return fail(VELO_ERR_INVALID, "%s: null pair array or output", who);
+    GraphStore& S = *c->graph;
+    for (int p = 0; p < n_pairs; p++) {
+        const int32_t ends[2] = {frame_a[p], frame_b[p]};
+        for (int k = 0; k < 2; k++) {
+            VELO_TRY(check_frame(ends[k], who, p));
+            if ((size_t)ends[k] >= S.pose_set.size() || !S.pose_set[(size_t)ends[k]]) return fail(VELO_ERR_STATE, "%s: pair %d names frame %d, which has no pose", who, p, ends[k]);
+        }
+    }
+    if (n_pairs == 0) return VELO_OK;
+    GraphCall call;
+    call.envelope = true;
+    call.who = who;
+    call.max_work = params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
+    VELO_TRY(graph_begin(c, fixed, n_fixed, graph_params(nullptr), &call));
+    const size_t n = (size_t)call.n_free, np = (size_t)n_pairs;
+    // per pair: the free indices of its ends (-1: a constant) and, for a pair outside the envelope, the slot of its column solve
+    const int32_t* pos = call.env_ints.data() + n;
+    const int32_t* first = call.env_ints.data() + 2 * n;
+    const int32_t* perm = call.env_ints.data();
+    std::vector<int32_t> pr(3 * np);
+    size_t n_out = 0;
+    for (size_t p = 0; p < np; p++) {
+        int32_t idx[2];
+        const int32_t ends[2] = {frame_a[p], frame_b[p]};
+        for (int k = 0; k < 2; k++) {
+            const auto it = std::lower_bound(call.free_nodes.begin(), call.free_nodes.end(), ends[k]);
+            idx[k] = it != call.free_nodes.end() && *it == ends[k] ? (int32_t)(it - call.free_nodes.begin()) : -1;
+        }
+        int32_t slot = -1;
+        if (idx[0] >= 0 && idx[1] >= 0) {
+            const int32_t pa = pos[(size_t)idx[0]], pb = pos[(size_t)idx[1]], hi = std::max(pa, pb), lo = std::min(pa, pb);
+            if (first[(size_t)hi] > lo) slot = (int32_t)n_out++;
+        }
+        pr[3 * p] = idx[0]; pr[3 * p + 1] = idx[1]; pr[3 * p + 2] = slot;
+    }
+    if (n_out * n * 36 > (size_t)VELO_GRAPH_MAX_COLUMN_DOUBLES) {
+        HIP_TRY(hipStreamSynchronize(c->stream));                      // (graph_begin's copies out of the staging are done before the next call fills it)
+        return fail(VELO_ERR_INVALID, "%s: %zu pairs outside the envelope need %zu doubles of work vectors (%zu free nodes x 36 each), over the cap of %lld; ask in smaller batches",
+                    who, n_out, n_out * n * 36, n, (long long)VELO_GRAPH_MAX_COLUMN_DOUBLES);
+    }
+    constexpr size_t kRec = sizeof(GraphRecord) / sizeof(double);
+    static_assert(sizeof(GraphRecord) % sizeof(double) == 0, "the pairs' blocks follow the record");
+    VELO_TRY(S.cov_out.reserve(kRec + 36 * np));
+    VELO_TRY(S.cov_pair.reserve(3 * np));
+    VELO_TRY(S.h_out.reserve(sizeof(double) * (kRec + 36 * np) + 64));
+    if (n) {
+        VELO_TRY(S.cov_z.reserve((size_t)call.env_stats[1] * 36));
+        VELO_TRY(S.cov_work.reserve(n_out * n * 36 + 1));
+    }
+    VELO_TRY(S.in_ev.wait_or_create());
+    VELO_TRY(S.h_in.reserve(sizeof(int32_t) * 3 * np));
+    std::memcpy(S.h_in.p, pr.data(), sizeof(int32_t) * 3 * np);
+    HIP_TRY(hipMemcpyAsync(S.cov_pair.p, S.h_in.p, sizeof(int32_t) * 3 * np, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(S.in_ev, c->stream));
+    GraphArgs A = call.A;
+    A.rec = (GraphRecord*)S.cov_out.p;                                 // this call's record, the blocks behind it
+    GraphCov V;
+    V.zenv = S.cov_z.p; V.work = S.cov_work.p; V.pair = S.cov_pair.p; V.out = S.cov_out.p + kRec; V.n_pairs = n_pairs;
+    const auto factor = [&](int rows) -> int {                         // H~ of the stored state and the factor of its leading `rows` rows
+        GraphArgs B = A;
+        B.n_free = rows;
+        HIP_TRY(hipMemsetAsync(A.rec, 0, sizeof(GraphRecord), c->stream));
+        hipLaunchKernelGGL(graph_env_fill_undamped_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, A);
+        hipLaunchKernelGGL(graph_env_factor_kernel, dim3(1), dim3(kGrEnvFactorThreads), 0, c->stream, B);
+        HIP_TRY(hipGetLastError());
+        return VELO_OK;
+    };
+    HIP_TRY(hipMemsetAsync(A.rec, 0, sizeof(GraphRecord), c->stream));
+    if (n) {
+        VELO_TRY(factor((int)n));
+        hipLaunchKernelGGL(graph_env_selinv_kernel, dim3(1), dim3(kGrEnvSelinvThreads), 0, c->stream, A, V);
+        if (n_out) hipLaunchKernelGGL(graph_env_column_kernel, dim3((unsigned)n_out), dim3(kGrEnvColumnThreads), 0, c->stream, A, V);
+    }
+    hipLaunchKernelGGL(graph_cov_gather_kernel, dim3((unsigned)np), dim3(64), 0, c->stream, A, V);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(S.h_out.p, S.cov_out.p, sizeof(double) * (kRec + 36 * np), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (((const GraphRecord*)S.h_out.p)->bad != 0) {
+        // which pivot: the factor of the leading k rows fails exactly when k exceeds the first bad pivot's position, so bisect on k.  A
+        // refusal's path only: each probe fills and factors again.
+        int lo = 0, hi = (int)n;
+        while (hi - lo > 1) {
+            const int mid = lo + (hi - lo) / 2;
+            VELO_TRY(factor(mid));
+            GraphRecord* rec = nullptr;
+            HIP_TRY(hipMemcpyAsync(S.h_out.p, A.rec, sizeof(GraphRecord), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            rec = (GraphRecord*)S.h_out.p;
+            if (rec->bad != 0) hi = mid; else lo = mid;
+        }
+        return fail(VELO_ERR_INVALID, "%s: J^T J is not positive definite: the factorisation's pivot at frame %d (position %d of the order) is not positive and finite; "
+                    "every free node needs edges that determine it", who, call.free_nodes[(size_t)perm[(size_t)hi - 1]], hi - 1);
+    }
+    std::memcpy(cov36, S.h_out.p + sizeof(GraphRecord), sizeof(double) * 36 * np);
     return VELO_OK;
 }
 

@@ -24,6 +24,8 @@
 // iterations in batches and reads one GraphRecord per batch, and one per LM iteration, from which it takes the LM decision.
 // A call may select the envelope solver for the linear step instead (velo_graph_params.reserved[0]): the same system, assembled as a
 // block skyline and factored exactly -- graph_env_fill_kernel, graph_env_factor_kernel, graph_env_solve_kernel at the end of this file.
+// velo_graph_covariance reads blocks of (J^T J)^-1 off the same factor of the undamped system: graph_env_fill_undamped_kernel,
+// graph_env_selinv_kernel, graph_env_column_kernel, graph_cov_gather_kernel behind them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -988,6 +990,322 @@ graph_env_solve_kernel(GraphArgs G, int cur)
     }
     for (int u = t; u < n * 6; u += kGrEnvSolveThreads)               // the step y, by free index, where graph_step_kernel reads it
         G.y[(size_t)G.env_perm[u / 6] * 6 + u % 6] = v[u];
+}
+#else
+;
+#endif
+
+// ---- covariances of the poses: blocks of (J^T J)^-1 from the envelope factor (velo_graph_covariance) ---------------------------------
+// H~ = c H c is the UNDAMPED Jacobi-scaled normal matrix (c = G.scale, which graph_assemble_kernel sets from this call's H in every
+// graph_begin: no history of G.diag in it), L its envelope Cholesky factor, Z = H~^-1.  Sigma_ab = c_a Z_ab c_b.  On one stream:
+//     graph_env_fill_undamped_kernel  graph_env_fill_kernel's fill of buffer 0 without the D / mu term; G.diag is not touched
+//     graph_env_factor_kernel         as above; a pivot that is not positive sets the record's `bad` and ends what follows
+//     graph_env_selinv_kernel         ONE workgroup: the entries of Z inside the envelope (the selected inverse), lower triangle, into a
+//                                     second skyline with the same rowptr, by the Takahashi recursion.  Columns j = n - 1 .. 0 over
+//                                     S_j = { i in (j, last(j)] : first(i) <= j }.  The envelope is closed under it: for i, k in S_j, k > i,
+//                                     first(k) <= j < i, so (k, i) is stored.  Per column: thread 0 inverts L(j,j) into LDS; the panel
+//                                     Z(i,j) = -(sum_{k in S_j} Z(i,k) L(k,j)) L(j,j)^-1, a thread per block row, Z(i,k) = Z(k,i)^T for k > i;
+//                                     the diagonal Z(j,j) = (L(j,j)^-T - sum_k Z(k,j)^T L(k,j)) L(j,j)^-1, a thread per entry, the lower
+//                                     triangle computed and mirrored, so the block is symmetric to the bit.  A __syncthreads after each.
+//                                     A row's sum over k is dealt to as many threads as the workgroup has for it (chunk c takes k = j + 1 + c,
+//                                     j + 1 + c + chunks, ..., ascending, into LDS) and the row's thread adds the chunks in order; likewise
+//                                     the 36 entries of the diagonal's sum, 28 chunks each.  Where a column reaches more than 85 rows a thread
+//                                     carries its row's whole sum.  The split depends on the column alone, so every entry is one fixed-order expression;
+//                                     no atomics.  The panel reads columns > j of Z only and writes column j only.
+//     graph_env_column_kernel         one workgroup per pair OUTSIDE the envelope, independent of one another: with positions hi > lo the
+//                                     6 columns of Z that belong to lo, as far as row hi: forward substitution of E_lo from row lo on, back
+//                                     substitution from row n - 1 down to hi.  The work vector ([n][36], a 6 x 6 per row) is the
+//                                     workgroup's slice of a scratch buffer.  Two components of the free graph occupy disjoint position
+//                                     ranges, so across them every term of the forward sum is zero and the block is an exact zero.
+//     graph_cov_gather_kernel         one workgroup per pair: Z or Z^T from the skyline or from a column's row hi, times c_a c_b, into
+//                                     the output staging behind the record; zeros for a pair that names a constant.
+// The rows of a 6 x 6 are short dependent fp64 chains; as in the factor kernel a thread owns a block row and requests its loads together.
+constexpr int kGrEnvSelinvThreads = 1024;
+constexpr int kGrEnvSelinvChunks = kGrEnvSelinvThreads / 36;   // partial sums of an entry of the diagonal block
+constexpr int kGrEnvColumnThreads = 256;
+constexpr int kGrEnvColumnChunks = kGrEnvColumnThreads / 36;   // partial sums of a row's forward substitution
+
+struct GraphCov {
+    double* zenv;                                // [blocks][36]: Z inside the envelope, lower triangle, rows as in G.env
+    double* work;                                // [n_out][n_free][36]: the column kernel's work vectors
+    const int* pair;                             // [n_pairs][3]: free index of a, of b (-1: a constant), column slot (-1: inside the envelope)
+    double* out;                                 // [n_pairs][36]
+    int n_pairs;
+};
+
+__global__ void __launch_bounds__(64)
+graph_env_fill_undamped_kernel(GraphArgs G)
+#if VELO_DEF_GRAPH
+{
+    const int i = blockIdx.x, l = threadIdx.x;
+    if (i >= G.n_free || l >= 36) return;
+    const int a = l / 6, b = l % 6;
+    const int node = G.env_perm[i], first = G.env_first[i], w = i - first;
+    double* row = G.env + (size_t)G.env_rowptr[i] * 36;
+    for (int k = 0; k < w; k++) row[(size_t)k * 36 + l] = 0.0;
+    const double* nd = G.nd + (size_t)node * kGrNode;                  // the stored state is buffer 0
+    const double ca = G.scale[(size_t)node * 6 + a], cb = G.scale[(size_t)node * 6 + b];
+    row[(size_t)w * 36 + l] = nd[upper6(a < b ? a : b, a < b ? b : a)] * ca * cb;
+    const int end = G.inc_start[node + 1];
+    for (int m = G.inc_start[node]; m < end; m++) {
+        const int j = G.inc_other[m];
+        if (j < 0) continue;                                           // the other end is a constant
+        const int pj = G.env_pos[j];
+        if (pj >= i) continue;                                         // the later end's row holds this block
+        const int code = G.inc[m];
+        const double* W = G.blk + (size_t)(code >> 1) * kGrBlk + kGrAtB;
+        const double v = (code & 1) ? W[b * 6 + a] : W[a * 6 + b];    // transposed on the `to` side
+        row[(size_t)(pj - first) * 36 + l] += (ca * v) * G.scale[(size_t)j * 6 + b];
+    }
+}
+#else
+;
+#endif
+
+// X = L^-1 for the lower triangle of a 6 x 6 block, column by column; the strict upper triangle of X is zero
+// (L: packed, row-major; X: 36 doubles in LDS, written and read back by the one calling thread)
+__device__ __forceinline__ void graph_env_inv6(const double L[21], double* X) {
+    double d[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) d[i] = 1.0 / L[graph_lower6(i, i)];
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+        double x[6];                                                   // column c
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            double s = 0.0;
+#pragma unroll
+            for (int q = c; q < i; q++) s -= L[graph_lower6(i, q)] * x[q];
+            x[i] = i < c ? 0.0 : (i == c ? d[i] : s * d[i]);
+            X[i * 6 + c] = x[i];
+        }
+    }
+}
+
+// the part k = k0, k0 + step, ... <= j + m of row r of sum_{k in S_j} Z(i,k) L(k,j), k ascending
+__device__ __forceinline__ void graph_env_selinv_row(const GraphArgs& G, const GraphCov& V, int i, int r, int fi, int j, int m, int k0, int step, double s[6]) {
+    const size_t zi = (size_t)G.env_rowptr[i];
+    for (int k = k0; k <= j + m; k += step) {
+        const int fk = G.env_first[k];
+        if (fk > j) continue;
+        const double* Lk = G.env + ((size_t)G.env_rowptr[k] + (size_t)(j - fk)) * 36;
+        double z[6];
+        if (k <= i) {
+            const double* Z = V.zenv + (zi + (size_t)(k - fi)) * 36 + r * 6;
+#pragma unroll
+            for (int c = 0; c < 6; c++) z[c] = Z[c];
+        } else {                                                       // first(k) <= j < i: (k,i) is stored, read transposed
+            const double* Z = V.zenv + ((size_t)G.env_rowptr[k] + (size_t)(i - fk)) * 36 + r;
+#pragma unroll
+            for (int c = 0; c < 6; c++) z[c] = Z[c * 6];
+        }
+#pragma unroll
+        for (int c = 0; c < 6; c++) {                                  // a row of L(k,j) at a time: 36 doubles of it in registers spill
+            double lk[6];
+#pragma unroll
+            for (int b = 0; b < 6; b++) lk[b] = Lk[c * 6 + b];
+#pragma unroll
+            for (int b = 0; b < 6; b++) s[b] += z[c] * lk[b];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kGrEnvSelinvThreads)
+graph_env_selinv_kernel(GraphArgs G, GraphCov V)
+#if VELO_DEF_GRAPH
+{
+    __shared__ double linv[36];                                        // L(j,j)^-1, the upper triangle zero
+    __shared__ double part[kGrEnvSelinvThreads * 6];                   // chunk sums: of the panel's rows, then of the diagonal's entries
+    if (G.rec->bad != 0) return;                                       // (the same word for every thread: the factorisation's launch wrote it)
+    const int t = threadIdx.x, n = G.n_free;
+    for (int j = n - 1; j >= 0; j--) {
+        const int fj = G.env_first[j];
+        const int m = G.env_last[j] - j;                               // the rows j + 1 .. j + m can hold a block in column j
+        const int rows = m * 6;
+        // a panel row's sum over k is dealt to `chunks` threads (k = j + 1 + c, j + 1 + c + chunks, ...) when the workgroup has them
+        int chunks = rows > 0 ? kGrEnvSelinvThreads / rows : 0;
+        if (chunks > m) chunks = m;
+        if (t == kGrEnvSelinvThreads - 1) {                            // (the thread least likely to hold a chunk)
+            double Lb[21];
+            const double* D = G.env + ((size_t)G.env_rowptr[j] + (size_t)(j - fj)) * 36;
+#pragma unroll
+            for (int r = 0; r < 6; r++) {
+#pragma unroll
+                for (int c = 0; c <= r; c++) Lb[graph_lower6(r, c)] = D[r * 6 + c];
+            }
+            graph_env_inv6(Lb, linv);
+        }
+        if (chunks >= 2 && t < rows * chunks) {
+            const int u = t % rows, ch = t / rows;
+            const int i = j + 1 + u / 6, r = u % 6, fi = G.env_first[i];
+            double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            if (fi <= j) graph_env_selinv_row(G, V, i, r, fi, j, m, j + 1 + ch, chunks, s);
+#pragma unroll
+            for (int b = 0; b < 6; b++) part[(size_t)t * 6 + b] = s[b];
+        }
+        __syncthreads();
+        for (int u = t; u < rows; u += kGrEnvSelinvThreads) {          // the panel: row r of Z(i,j) = -(the sum) L(j,j)^-1
+            const int i = j + 1 + u / 6, r = u % 6, fi = G.env_first[i];
+            if (fi > j) continue;
+            double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            if (chunks >= 2) {                                         // (then rows <= 512: one trip, u == t)
+                for (int ch = 0; ch < chunks; ch++) {
+#pragma unroll
+                    for (int b = 0; b < 6; b++) s[b] += part[((size_t)ch * rows + u) * 6 + b];
+                }
+            } else graph_env_selinv_row(G, V, i, r, fi, j, m, j + 1, 1, s);
+            double* out = V.zenv + ((size_t)G.env_rowptr[i] + (size_t)(j - fi)) * 36 + r * 6;
+#pragma unroll
+            for (int c = 0; c < 6; c++) {
+                double v = 0.0;
+#pragma unroll
+                for (int b = c; b < 6; b++) v -= s[b] * linv[b * 6 + c];
+                out[c] = v;
+            }
+        }
+        __syncthreads();
+        const int dch = m < kGrEnvSelinvChunks ? m : kGrEnvSelinvChunks;
+        if (t < 36 * dch) {                                            // entry (r, c) of sum_k Z(k,j)^T L(k,j): a chunk of the k
+            const int e = t % 36, ch = t / 36, r = e / 6, c = e % 6;
+            double s = 0.0;
+            for (int k = j + 1 + ch; k <= j + m; k += dch) {
+                const int fk = G.env_first[k];
+                if (fk > j) continue;
+                const size_t o = ((size_t)G.env_rowptr[k] + (size_t)(j - fk)) * 36;
+                const double* Lk = G.env + o;
+                const double* Zk = V.zenv + o;
+#pragma unroll
+                for (int q = 0; q < 6; q++) s += Zk[q * 6 + r] * Lk[q * 6 + c];
+            }
+            part[t] = s;
+        }
+        __syncthreads();
+        if (t < 36) {                                                  // Z(j,j) = (L(j,j)^-T - the sum) L(j,j)^-1: the lower triangle, mirrored
+            const int r = t / 6, c = t % 6;
+            if (c <= r) {
+                double v = 0.0;
+#pragma unroll
+                for (int b = 0; b < 6; b++) {
+                    double w = linv[b * 6 + r];
+                    for (int ch = 0; ch < dch; ch++) w -= part[ch * 36 + r * 6 + b];
+                    v += w * linv[b * 6 + c];
+                }
+                double* Zj = V.zenv + ((size_t)G.env_rowptr[j] + (size_t)(j - fj)) * 36;
+                Zj[r * 6 + c] = v;
+                Zj[c * 6 + r] = v;
+            }
+        }
+        __syncthreads();
+    }
+}
+#else
+;
+#endif
+
+__global__ void __launch_bounds__(kGrEnvColumnThreads)
+graph_env_column_kernel(GraphArgs G, GraphCov V)
+#if VELO_DEF_GRAPH
+{
+    __shared__ double part[kGrEnvColumnChunks * 36];
+    __shared__ double xs[36];
+    __shared__ int pair_s[2];
+    if (G.rec->bad != 0) return;
+    const int t = threadIdx.x, n = G.n_free;
+    if (t == 0) {                                                      // the pair that holds this workgroup's slot
+        int pa = 0, pb = 0;
+        for (int p = 0; p < V.n_pairs; p++)
+            if (V.pair[p * 3 + 2] == (int)blockIdx.x) { pa = G.env_pos[V.pair[p * 3]]; pb = G.env_pos[V.pair[p * 3 + 1]]; break; }
+        pair_s[0] = pa > pb ? pa : pb;
+        pair_s[1] = pa > pb ? pb : pa;
+    }
+    __syncthreads();
+    const int hi = pair_s[0], lo = pair_s[1];
+    double* v = V.work + (size_t)blockIdx.x * (size_t)n * 36;          // row i: the 6 x 6 of the 6 right-hand sides
+    const int e = t % 36, ch = t / 36, er = e / 6, ec = e % 6;
+    for (int i = lo; i < n; i++) {                                     // forward, by rows: Y_i = L(i,i)^-1 (E_i - sum_j L(i,j) Y_j), Y_j = 0 for j < lo
+        const int fi = G.env_first[i];
+        const int j0 = fi > lo ? fi : lo;
+        const double* row = G.env + (size_t)G.env_rowptr[i] * 36;
+        if (ch < kGrEnvColumnChunks) {
+            double s = 0.0;
+            for (int j = j0 + ch; j < i; j += kGrEnvColumnChunks) {
+                const double* L = row + (size_t)(j - fi) * 36 + er * 6;
+                const double* y = v + (size_t)j * 36 + ec;
+#pragma unroll
+                for (int q = 0; q < 6; q++) s += L[q] * y[q * 6];
+            }
+            part[ch * 36 + e] = s;
+        }
+        __syncthreads();
+        if (t < 6) {                                                   // thread c: column c of the block, the chunks in order, then the triangle
+            const double* D = row + (size_t)(i - fi) * 36;
+            const int w = i - j0;
+            const int nc = w < kGrEnvColumnChunks ? w : kGrEnvColumnChunks;
+            double x[6];
+#pragma unroll
+            for (int r = 0; r < 6; r++) {
+                double q = (i == lo && r == t) ? 1.0 : 0.0;
+                for (int c = 0; c < nc; c++) q -= part[c * 36 + r * 6 + t];
+#pragma unroll
+                for (int c = 0; c < r; c++) q -= D[r * 6 + c] * x[c];
+                x[r] = q / D[r * 6 + r];
+            }
+#pragma unroll
+            for (int r = 0; r < 6; r++) v[(size_t)i * 36 + r * 6 + t] = x[r];
+        }
+        __syncthreads();
+    }
+    for (int i = n - 1; i >= hi; i--) {                                // back, by columns: X_i = L(i,i)^-T Y_i, then Y_j -= L(i,j)^T X_i for hi <= j < i
+        const int fi = G.env_first[i];
+        const int j0 = fi > hi ? fi : hi;
+        const double* row = G.env + (size_t)G.env_rowptr[i] * 36;
+        if (t < 6) {
+            const double* D = row + (size_t)(i - fi) * 36;
+            double x[6];
+#pragma unroll
+            for (int r = 5; r >= 0; r--) {
+                double q = v[(size_t)i * 36 + r * 6 + t];
+#pragma unroll
+                for (int c = r + 1; c < 6; c++) q -= D[c * 6 + r] * x[c];
+                x[r] = q / D[r * 6 + r];
+            }
+#pragma unroll
+            for (int r = 0; r < 6; r++) { v[(size_t)i * 36 + r * 6 + t] = x[r]; xs[r * 6 + t] = x[r]; }
+        }
+        __syncthreads();
+        for (int u = t; u < (i - j0) * 36; u += kGrEnvColumnThreads) {
+            const int j = j0 + u / 36, r = (u % 36) / 6, c = u % 6;
+            const double* L = row + (size_t)(j - fi) * 36;
+            double s = v[(size_t)j * 36 + r * 6 + c];
+#pragma unroll
+            for (int q = 0; q < 6; q++) s -= L[q * 6 + r] * xs[q * 6 + c];
+            v[(size_t)j * 36 + r * 6 + c] = s;
+        }
+        __syncthreads();
+    }
+}
+#else
+;
+#endif
+
+__global__ void __launch_bounds__(64)
+graph_cov_gather_kernel(GraphArgs G, GraphCov V)
+#if VELO_DEF_GRAPH
+{
+    const int p = blockIdx.x, l = threadIdx.x;
+    if (p >= V.n_pairs || l >= 36) return;
+    const int r = l / 6, c = l % 6;
+    const int ia = V.pair[p * 3], ib = V.pair[p * 3 + 1], slot = V.pair[p * 3 + 2];
+    double out = 0.0;                                                  // a constant has no uncertainty
+    if (ia >= 0 && ib >= 0 && G.rec->bad == 0) {
+        const int pa = G.env_pos[ia], pb = G.env_pos[ib];
+        const int hi = pa > pb ? pa : pb, lo = pa > pb ? pb : pa;
+        const double* B = slot >= 0 ? V.work + ((size_t)slot * (size_t)G.n_free + (size_t)hi) * 36
+                                    : V.zenv + ((size_t)G.env_rowptr[hi] + (size_t)(lo - G.env_first[hi])) * 36;
+        const double z = pa >= pb ? B[r * 6 + c] : B[c * 6 + r];      // the stored block is Z(hi, lo)
+        out = z * (G.scale[(size_t)ia * 6 + r] * G.scale[(size_t)ib * 6 + c]);
+    }
+    V.out[(size_t)p * 36 + l] = out;
 }
 #else
 ;
