@@ -20,7 +20,7 @@ LIB = os.path.join(CSRC, "libvelo_hip.so")
 LIB_DIAG = os.path.join(CSRC, "libvelo_hip_diag.so")     # the tools' build: -DVELO_DIAGNOSTICS (stamps, counters, VELO_DEBUG_SKIP)
 # Translation units, each with the flags only it gets, compiled side by side and linked into ONE shared library (round 6: ~10 s instead of
 # 27 s for the product build).  velo_hip.hip is the host side of the C-ABI and defines no kernel; every kernel family is defined -- its device
-# code generated -- in exactly one velo_unit_*.hip (velo_kernels.h, "translation units"; the A/B association kernels of
+# code generated -- in exactly one velo_unit_*.hip (velo_hip.hip, "translation units"; the A/B association kernels of
 # velo_assoc_ab_kernels.h only with -DVELO_DIAGNOSTICS); velo_lm_ag.hip is the one-launch Levenberg-Marquardt solve, built without
 # machine-level loop-invariant code motion (velo_lm_ag_kernels.h says why).
 SOURCES = {"velo_hip.hip": [], "velo_unit_load.hip": [], "velo_unit_assoc.hip": [], "velo_unit_lm_a.hip": [], "velo_unit_lm_b.hip": [],

@@ -33,6 +33,19 @@
 #include <chrono>
 
 #include "../../include/velo_hip.h"
+
+// ---- translation units (round 6) ---------------------------------------------------------------------------------------------------------
+// The library is built from several units compiled side by side (build.py): velo_hip.hip holds the host side of the C-ABI and DEFINES NO
+// KERNEL; each kernel family is defined -- its device code generated -- in exactly one unit, the one that sets the family's VELO_DEF_* flag to 1.
+// The scan-matching core:
+//     VELO_DEF_LOAD   velo_unit_load.hip    velo_load_kernels.h: scan ingestion, index build, the group loaders (+ the widened rows: projection, depth, triangulation)
+//     VELO_DEF_ASSOC  velo_unit_assoc.hip   velo_kernels.h: the association family (tube / direct / asker kernels, seeds, merge; with -DVELO_DIAGNOSTICS also velo_assoc_ab_kernels.h)
+//     VELO_DEF_LMA    velo_unit_lm_a.hip    velo_kernels.h: visual gate, residual statistics, the sweep and step kernels, one-launch iterations, peer exchange
+//     VELO_DEF_LMB    velo_unit_lm_b.hip    velo_kernels.h: the fused sweep + step family of the lock-step groups, single-launch solves, chain finish, functors
+// Every other unit sees a kernel's DECLARATION (the `#else ;` branch behind its signature) and launches it through the host stub the
+// defining unit exports; template kernels are instantiated explicitly in their unit and declared `extern template` elsewhere (the list
+// at the end of the family's header).  Device functions and data layouts stay visible to every unit.
+#include "velo_load_kernels.h"
 #include "velo_kernels.h"
 #ifdef VELO_DIAGNOSTICS
 #include "velo_assoc_ab_kernels.h"   // the A/B association kernels: launched by the tools' build only
@@ -58,7 +71,7 @@ extern "C" int velo_launch_lm_solve_ag(int nb_max, int n, void* stream, const vo
 
 // ---- the host side, in parts (round 6: one 4,700-line file before) ---------------------------------------------------------------------
 // ONE translation unit: the parts share unnamed-namespace helpers and static functions, and their order is the order of definition.
-// The kernels live elsewhere: every family is defined in a velo_unit_*.hip of its own (velo_kernels.h, "translation units").
+// The kernels live elsewhere: every family is defined in a velo_unit_*.hip of its own ("translation units" above).
 #include "velo_host_types.inl"   // error state, device and pinned buffers, staging pairs, the search index, TargetData and velo_ctx: what one context holds; what calls over a list of contexts share
 #include "velo_host_index.inl"   // launch timing, uploads, the index build (build_grid), the query list in patch order
 #include "velo_host_assoc.inl"   // pose scalars, parameter blocks, evaluation plan, seeds and askers, the association driver of one context (do_associate)

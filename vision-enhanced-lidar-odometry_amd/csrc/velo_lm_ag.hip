@@ -1,6 +1,10 @@
 // velo_lm_ag.hip -- the all-gather Levenberg-Marquardt solve (velo_lm_ag_kernels.h) as a translation unit of its own, compiled with
-// -mllvm -disable-machine-licm (see that header).  It exports ONE host function, the launcher; the shared kernel header is included
-// inside an unnamed namespace, so every kernel it defines has internal linkage here and nothing of it collides with velo_hip.hip's copies.
+// -mllvm -disable-machine-licm (see that header).  It exports ONE host function, the launcher.  The solver half of the shared kernel header
+// is included inside an unnamed namespace (VELO_UNIT_LM_ONLY hides the association half, whose `extern template` list cannot be declared
+// there; the macro goes when that family has a header of its own): the one kernel this unit defines, lm_solve_ag_batch_kernel, has internal
+// linkage, and so has whatever it instantiates of the shared device functions under this unit's flags.  The other kernels of that half
+// are declarations here (no VELO_DEF_* flag is set) and generate no code.  The namespace stays because the kernel's symbol carries it,
+// and recorded traces and tools/kernel_digest.py know the kernel by that symbol.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>

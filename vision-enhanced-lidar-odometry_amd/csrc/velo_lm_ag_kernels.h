@@ -28,16 +28,8 @@ namespace velo {
 // Every wait is bounded (kAgTimeoutTicks of the 100 MHz clock): a workgroup that waits longer -- its peers never became resident, e.g.
 // beside other processes' kernels -- raises the context's abort word, everybody leaves, the state stays "not done" and the pose record
 // "not ready": the chained call fails like a call whose launch prediction fell short and is repeated host-driven (same results).
-#ifndef VELO_AG_KATTR
-#define VELO_AG_KATTR
-#endif
 constexpr int kAgPre = kLeanPre;
-#ifndef VELO_AG_WAVES
-#define VELO_AG_WAVES 3
-#endif
-#ifndef VELO_AG_NOINLINE
-#define VELO_AG_NOINLINE __forceinline__
-#endif
+constexpr int kAgWaves = 3;                                                 // launch bound: waves per SIMD
 constexpr unsigned long long kAgTimeoutTicks = 2000000ull;                 // 20 ms
 __device__ __forceinline__ bool ag_wait(AgCtl* __restrict__ ctl, const int parity, const int nb, const int tag, const int abort_tag, const int tid) {
     bool ok = true;
@@ -53,11 +45,10 @@ __device__ __forceinline__ bool ag_wait(AgCtl* __restrict__ ctl, const int parit
     if (!all && tid == 0) ctl_store(&ctl->abort, abort_tag);
     return all != 0;
 }
-// the transition as a real function: inlined into the loop it drives the kernel to 260 registers (one wave per SIMD: it could not sit beside
-// association workgroups)
+// the transition with the arguments the solve loop has, inlined into the loop
 template <int CHUNK>
-__device__ VELO_AG_NOINLINE void ag_advance(const LMParams* Q, const LMState* S, const double* xd, const int* n_valid, PoseRecord* pose_out, SolveLog* log,
-                                                    const double* partials, int nb, int first, double* s_scratch, LMState* sL, LMEvalPoint* s_pt, bool writer, int tid) {
+__device__ __forceinline__ void ag_advance(const LMParams* Q, const LMState* S, const double* xd, const int* n_valid, PoseRecord* pose_out, SolveLog* log,
+                                           const double* partials, int nb, int first, double* s_scratch, LMState* sL, LMEvalPoint* s_pt, bool writer, int tid) {
     lm_advance<true, CHUNK, false, true>(*Q, S, partials, nb, first ? 2 : 0, xd, n_valid, s_scratch, sL, s_pt, nullptr, 0, nullptr, pose_out, log, writer, first != 0, tid);
 }
 template <bool M_LDS, int PRE, int CHUNK>
@@ -91,25 +82,19 @@ __device__ __forceinline__ void lm_solve_ag_body(const LMParams& Q, const LMBatc
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // this thread's row entries have been written through
         __syncthreads();
         if (tt == 0) ctl_store(&ctl->flag[k & 1][bx], epoch + k + 1);
-#ifdef VELO_AG_PREFETCH
-        f = prefetch_rows<PRE>(A, bx, nb, tt);                            // the rows do not depend on the pose: the next sweep's first ones are requested ahead of the wait
-#endif
         if (!ag_wait(ctl, k & 1, nb, epoch + k + 1, epoch + 1, tt)) break;    // (the abort word carries the launch's own tag: nothing to reset)
         ag_advance<CHUNK>(&Q, it.S, it.xd, it.n_valid, it.pose_out, it.log, A.partials + (size_t)(k & 1) * half, nb, k == 0 ? 1 : 0, s_scratch, &sL, &s_pt, bx == 0, tt);
         if (sL.done) { finished = true; break; }
-#ifndef VELO_AG_PREFETCH
         f = prefetch_rows<PRE>(A, bx, nb, tt);
-#endif
     }
     if (bx == 0) {
         if (finished && t < (int)(sizeof(LMState) / 8)) reinterpret_cast<unsigned long long*>(it.S)[t] = reinterpret_cast<const unsigned long long*>(&sL)[t];
         if (t == 0) ctl->epoch = epoch + kmax + 4;
     }
 }
-__global__ void __launch_bounds__(kEvalThreads, VELO_AG_WAVES) VELO_AG_KATTR
+__global__ void __launch_bounds__(kEvalThreads, kAgWaves)
 lm_solve_ag_batch_kernel(LMParams Q, LMBatchPackV P, AgCtl* __restrict__ ctl, int kmax, size_t half) {
     lm_solve_ag_body<true, kAgPre, 64>(Q, P.item[blockIdx.y], ctl + blockIdx.y, kmax, half);
 }
-
 
 }  // namespace velo

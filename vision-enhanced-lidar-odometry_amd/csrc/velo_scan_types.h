@@ -1,6 +1,6 @@
 // velo_scan_types.h -- constants and device data layouts that more than one kernel family reads (gfx950 / CDNA4 only): the search grid,
-// the pose scalars of an association round, the hand-over records of chain mode, the visual match record, the workgroup scan.  No kernel lives here.
-// velo_kernels.h (the scan-matching core) builds on it; the bundle adjustment, pose graph, landmark and frame headers include it
+// the pose scalars of an association round, the hand-over records of chain mode and of the target-sharded mode, the visual match record, the workgroup scan.  No kernel lives here.
+// velo_load_kernels.h and velo_kernels.h (the scan-matching core) build on it; the bundle adjustment, pose graph, landmark and frame headers include it
 // instead of the core's kernels.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -93,6 +93,17 @@ struct SolveLog {
     double x[6];
     double initial_cost, final_cost;
     int termination, iter, evals, n_valid;
+};
+// Target-sharded mode (BASELINE config 5): what one rank knows about a query after searching ITS rings.
+// Rings are disjoint across ranks, so the global winners are: best1 = min key1 over ranks (rank w*), best2 = the smaller
+// of { min key1 over the other ranks, key2 of rank w* }.  The record carries the points the plane needs, so the owner of
+// the query can finish without touching any other rank's cloud.  Same layout as velo_partial in include/velo_hip.h.
+struct PartialRec {
+    unsigned long long key1, key2;     // (d^2 bits << 32 | global index); >= key_inf when absent
+    int ring1, ring2;                  // global ring ids, -1 when absent
+    int idx1, idx_k, idx2, pad;        // np_i, np_k (in ring1), np_j (in ring2)
+    float v0[3], v2[3], v1[3];         // best point, its chosen ring neighbour, second-best point
+    float pad2;
 };
 
 __device__ __forceinline__ int cell_coord(float p, float o, float inv_h, int n) {

@@ -1,4 +1,4 @@
-// velo_unit_assoc.hip -- the translation unit that DEFINES the kernels of the VELO_DEF_ASSOC family (velo_kernels.h, "translation units"): their
+// velo_unit_assoc.hip -- the translation unit that DEFINES the kernels of the VELO_DEF_ASSOC family (velo_hip.hip, "translation units"): their
 // device code is generated here and nowhere else; velo_hip.hip (the host side of the C-ABI) and the other units see declarations and launch
 // through the host stubs this unit exports.  No host logic lives here.
 #include <hip/hip_runtime.h>
