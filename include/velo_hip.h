@@ -885,6 +885,54 @@ int velo_graph_system(velo_ctx* ctx, const int32_t* fixed, int32_t n_fixed, doub
 #define VELO_GRAPH_MAX_COLUMN_DOUBLES (1 << 27)  /* work vectors of one call's pairs outside the envelope: pairs x n_free x 36 doubles (1 GiB) */
 int velo_graph_covariance(velo_ctx* ctx, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params,
                           int32_t n_pairs, const int32_t* frame_a, const int32_t* frame_b, double* cov36 /* [n_pairs][36] row-major */);
+/* The covariance of a relative pose in an edge's tangent space, and the test of a proposed edge BEFORE it enters the graph (the
+ * reference's agreement check, main.cpp:415-437, has no statistics behind it).  Evaluated at the stored state; nothing in the store
+ * changes.  Free nodes, H, params (only reserved[1] is read) and the factorisation are velo_graph_covariance's.  For pair p, with
+ * a = from[p], b = to[p] and the stored poses:
+ *   rel6    pose_vec(T_a^-1 T_b);
+ *   z       the measurement Z_p; NULL: every pair takes its own rel6, formed on the device;
+ *   r6      the unweighted edge residual pose_vec(Z_p^-1 T_a^-1 T_b) -- evaluated, not assumed zero;
+ *   cov36   S = Sigma_rel + W^-1, row-major, symmetric to the bit.  Sigma_rel = A S_aa A^T + A S_ab B^T + B S_ba A^T + B S_bb B^T with A, B
+ *           the Jacobians of r in the 6 doubles of a and b and the S blocks exactly what velo_graph_covariance returns (zero for a fixed
+ *           frame): to first order the covariance of r, which -- unlike the marginals -- does not depend on which frame is fixed.  W is
+ *           info21[p] (the upper triangle row by row, as velo_graph_add_edges_weighted takes it); NULL: S = Sigma_rel;
+ *   chi2    r^T S^-1 r through the Cholesky factor of S in double; -1.0 where a pivot of S is not positive and finite (both ends fixed
+ *           and no info21 is the case).
+ * Every output may be NULL.  What a caller should know:
+ *   - the result belongs to the estimate H describes: Sigma is the covariance AT THE OPTIMUM, so optimise first.  At a dead-reckoned
+ *     start a true closing edge gates at chi2 in the hundreds;
+ *   - chi2 means something only if the edges' informations are inverse covariances (velo_graph_edge_information), not weights;
+ *   - chi2 is compared with a quantile of the chi-square distribution with 6 degrees of freedom (16.8 at 99 %, 22.5 at 99.9 %); the
+ *     threshold and what to do with the edge are the caller's.
+ *   cost    blocks inside the envelope come from the selected inverse.  The pairs outside it are grouped by their `to` frame and ONE
+ *           full block column of the inverse is solved per distinct such frame (n_free x 36 doubles of work vector each, under
+ *           VELO_GRAPH_MAX_COLUMN_DOUBLES in all): 32 candidates against one query frame cost one column, not 32.
+ * Refused before anything is written: what velo_graph_covariance refuses (and, as there, a call with n == 0 returns VELO_OK after the
+ * argument checks alone: no order is formed and nothing is factored, so neither the work cap nor H is tested); VELO_ERR_INVALID for
+ * n < 0, a NULL from or to with n > 0, a
+ * frame out of range, from == to, a z that is not finite, an info21 that velo_graph_add_edges_weighted would refuse (the message names
+ * the pair); VELO_ERR_STATE for a frame without a pose. */
+int velo_graph_edge_gate(velo_ctx* ctx, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params,
+                         int32_t n, const int32_t* from, const int32_t* to, const double* z /* [n][6] | NULL */, const double* info21 /* [n][21] | NULL */,
+                         double* rel6 /* [n][6] */, double* r6 /* [n][6] */, double* cov36 /* [n][36] */, double* chi2 /* [n] */);
+/* Loop-closure candidates for one query frame, proposed from the graph (the reference tries fixed offsets and divides the vertical
+ * component by 20 by hand because height drifts, main.cpp:328-345; the graph knows how uncertain each relative position is).  Considers
+ * every frame i that has a pose with |i - query| >= min_gap:
+ *   dist    |t(T_i^-1 T_query)| at the stored poses;
+ *   sigma   sqrt(trace(Sigma_rel(i, query)[3:, 3:])) in the tangent at the stored relative pose: the total standard deviation of the
+ *           relative position (the trace does not depend on the frame it is written in);
+ * and selects i when dist <= radius + k_sigma . sigma.  The selected frames are returned in ascending order: the first `capacity` are
+ * written to frames_out, dist_out, sigma_out (each [capacity], each may be NULL), *n_found is the total -- ask again with more room when
+ * it exceeds capacity.  What velo_match_frames then screens.  Work: one factorisation, one selected inverse, ONE full block column
+ * for the query (none when it is fixed), a thread per frame and an ordered compaction.  Frames in another component of the free graph
+ * have a zero cross-covariance, exactly.  k_sigma == 0 is the reference's test without its /20: no factorisation runs, sigma is
+ * written as 0, and a graph whose H is singular is served.  As for velo_graph_edge_gate, sigma belongs to the optimum.
+ * Refused before anything is written: what velo_graph_covariance refuses (with k_sigma == 0: what its argument checks refuse);
+ * VELO_ERR_INVALID for a query out of range, min_gap < 1, a radius or k_sigma that is negative or not finite, capacity < 0, a NULL
+ * n_found; VELO_ERR_STATE for a query without a pose. */
+int velo_graph_loop_candidates(velo_ctx* ctx, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params,
+                               int32_t query, int32_t min_gap /* >= 1 */, double radius /* >= 0 */, double k_sigma /* >= 0 */,
+                               int32_t capacity, int32_t* frames_out, double* dist_out, double* sigma_out, int32_t* n_found);
 
 /* --- resident keypoint frames and the visual matches assembled from them (velo.h:562-590, velo.h:627-654, main.cpp:366-405) ---
  * Every context can hold one frame store: for every (frame, camera) put so far keypoints[cam][frame], keypoint_ids[cam][frame],

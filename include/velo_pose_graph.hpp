@@ -11,7 +11,9 @@
 //     graph.optimize(fixed, &summary, 0, VELO_GRAPH_SOLVER_ENVELOPE); // the same with the exact envelope solver: a whole drive
 //     graph.poses(0, n, &flat);                                      // n x 6, for velo_landmarks_set_pose / velo_map_set_pose
 //     graph.covariance(frames, fixed, &cov36);                       // how well each pose is determined: 6 x 6 marginals
-//     graph.jointCovariance(loop_from, frame, fixed, joint144);      // 12 x 12, for a Mahalanobis loop-closure gate
+//     graph.jointCovariance(loop_from, frame, fixed, joint144);      // 12 x 12, the material of the gate below
+//     graph.loopCandidates(frame, 50, 3.0, 3.0, fixed, &cand, 0, 0);  // frames within 3 m + 3 sigma of `frame`: what to try to close against
+//     graph.gateEdges(from, to, z, info21, fixed, 0, 0, 0, &chi2);    // a proposed edge against the graph BEFORE it is added: chi2 with 6 dof
 #ifndef VELO_POSE_GRAPH_HPP_
 #define VELO_POSE_GRAPH_HPP_
 
@@ -120,6 +122,65 @@ public:
                 joint144[(6 + r) * 12 + 6 + c] = blk[(size_t)(72 + r * 6 + c)];
             }
         return VELO_OK;
+    }
+
+    // proposed edges tested against the graph BEFORE they enter it (velo_graph_edge_gate), at the stored poses -- optimise first.  z: 6
+    // doubles per pair, or empty (every pair's own stored relative pose); info21: 21 per pair, or empty (S = Sigma_rel).  Per pair:
+    // rel6 (6), r6 (6), cov36 = Sigma_rel + W^-1 (36), chi2 = r^T S^-1 r (-1 where S is not positive definite), to be compared with a
+    // chi-square quantile of 6 degrees of freedom.  Every output may be null.
+    int gateEdges(const std::vector<int>& from, const std::vector<int>& to, const std::vector<double>& z, const std::vector<double>& info21,
+                  const std::vector<int>& fixed, std::vector<double>* rel6, std::vector<double>* r6, std::vector<double>* cov36, std::vector<double>* chi2,
+                  int max_work = 0) const {
+        const size_t n = from.size();
+        if (to.size() != n || (!z.empty() && z.size() != 6 * n) || (!info21.empty() && info21.size() != 21 * n)) return VELO_ERR_INVALID;
+        std::vector<int32_t> a(from.begin(), from.end()), b(to.begin(), to.end()), f(fixed.begin(), fixed.end());
+        velo_graph_params own;
+        const int ps = velo_default_graph_params(&own);
+        if (ps != VELO_OK) return ps;
+        own.reserved[1] = max_work;
+        std::vector<double> rel(6 * n + 6), r(6 * n + 6), cov(36 * n + 36), c2(n + 1);
+        const int st = velo_graph_edge_gate(ctx_, f.empty() ? 0 : &f[0], (int32_t)f.size(), &own, (int32_t)n, n ? &a[0] : 0, n ? &b[0] : 0,
+                                            z.empty() ? 0 : &z[0], info21.empty() ? 0 : &info21[0], &rel[0], &r[0], &cov[0], &c2[0]);
+        if (st != VELO_OK) return st;
+        rel.resize(6 * n); r.resize(6 * n); cov.resize(36 * n); c2.resize(n);
+        if (rel6) rel6->swap(rel);
+        if (r6) r6->swap(r);
+        if (cov36) cov36->swap(cov);
+        if (chi2) chi2->swap(c2);
+        return VELO_OK;
+    }
+    // the stored relative pose of every pair (a, b) and its covariance in the tangent at that pose: gateEdges without a measurement and
+    // without an information.  Unlike the marginals it does not depend on which frame is fixed.
+    int relativeCovariance(const std::vector<int>& a, const std::vector<int>& b, const std::vector<int>& fixed, std::vector<double>* rel6,
+                           std::vector<double>* cov36, int max_work = 0) const {
+        return gateEdges(a, b, std::vector<double>(), std::vector<double>(), fixed, rel6, 0, cov36, 0, max_work);
+    }
+    // loop-closure candidates of `query` (velo_graph_loop_candidates): the frames i with |i - query| >= min_gap whose stored distance to
+    // the query is at most radius + k_sigma . sigma_i, ascending, with that distance and sigma_i (0 for k_sigma == 0, which runs no
+    // factorisation); asks again when the first room was too small -- a second whole call, factorisation included, so where more than
+    // `capacity` candidates can be expected (a long drive, a wide radius) give the room at once.  max_work: the envelope's cap (0: the
+    // default).  Every output may be null.
+    int loopCandidates(int query, int min_gap, double radius, double k_sigma, const std::vector<int>& fixed, std::vector<int>* frames,
+                       std::vector<double>* dist, std::vector<double>* sigma, int capacity = 64, int max_work = 0) const {
+        std::vector<int32_t> f(fixed.begin(), fixed.end());
+        velo_graph_params own;
+        const int ps = velo_default_graph_params(&own);
+        if (ps != VELO_OK) return ps;
+        own.reserved[1] = max_work;
+        int32_t cap = capacity > 0 ? capacity : 1;
+        for (;;) {
+            std::vector<int32_t> fr((size_t)cap);
+            std::vector<double> d((size_t)cap), s((size_t)cap);
+            int32_t found = 0;
+            const int st = velo_graph_loop_candidates(ctx_, f.empty() ? 0 : &f[0], (int32_t)f.size(), &own, query, min_gap, radius, k_sigma, cap, &fr[0], &d[0], &s[0], &found);
+            if (st != VELO_OK) return st;
+            if (found > cap) { cap = found; continue; }
+            d.resize((size_t)found); s.resize((size_t)found);
+            if (frames) frames->assign(fr.begin(), fr.begin() + found);
+            if (dist) dist->swap(d);
+            if (sigma) sigma->swap(s);
+            return VELO_OK;
+        }
     }
 
     int info(Info* out) const {

@@ -388,6 +388,10 @@ SIGNATURES = {
     "velo_graph_order": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "velo_graph_system": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _dp, C.c_void_p, C.c_void_p]),
     "velo_graph_covariance": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(VeloGraphParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "velo_graph_edge_gate": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(VeloGraphParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "velo_graph_loop_candidates": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(VeloGraphParams), C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
     "velo_frames_reset": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_int32]),
     "velo_frames_put": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "velo_frames_drop": (C.c_int, [_ctx, C.c_int32]),
@@ -1008,6 +1012,71 @@ class Context:
         J = np.empty((12, 12), dtype=np.float64)
         J[:6, :6], J[:6, 6:], J[6:, :6], J[6:, 6:] = blk[0], blk[1], blk[1].T, blk[2]
         return J
+
+    def graph_edge_gate(self, frm, to, z=None, info=None, fixed=(0,), max_work=None):
+        """velo_graph_edge_gate: proposed edges (frm[k], to[k], z[k], info[k]) tested against the graph BEFORE they enter it, at the
+        stored state (nothing changes; optimise first: the covariance belongs to the optimum).  Returns (rel [n, 6], r [n, 6],
+        cov [n, 6, 6], chi2 [n]): the stored relative pose, the unweighted edge residual, S = Sigma_rel + W^-1 and r^T S^-1 r (-1 where
+        S is not positive definite), to be compared with a chi-square quantile of 6 degrees of freedom.  z None: every pair's own
+        relative pose (r is then zero to rounding); info: [n, 6, 6] or [n, 21] as in graph_add_edges_weighted, None: S = Sigma_rel."""
+        a = np.ascontiguousarray(np.asarray(frm, dtype=np.int32).reshape(-1))
+        b = np.ascontiguousarray(np.asarray(to, dtype=np.int32).reshape(-1))
+        zz = None if z is None else np.ascontiguousarray(np.asarray(z, dtype=np.float64).reshape(-1, 6))
+        w = None
+        if info is not None:
+            w = np.asarray(info, dtype=np.float64)
+            if w.ndim == 3 and w.shape[1:] == (6, 6):
+                if not np.array_equal(w, np.transpose(w, (0, 2, 1))):
+                    raise ValueError("graph_edge_gate: an information matrix is not symmetric")
+                w = w[:, np.triu_indices(6)[0], np.triu_indices(6)[1]]
+            elif not (w.ndim == 2 and w.shape[1] == 21):
+                raise ValueError("graph_edge_gate: info is [n, 6, 6] or [n, 21]")
+            w = np.ascontiguousarray(w)
+        if len(a) != len(b) or (zz is not None and len(zz) != len(a)) or (w is not None and len(w) != len(a)):
+            raise ValueError("graph_edge_gate: one from, to, z and info per pair")
+        fx = np.ascontiguousarray(np.asarray(fixed, dtype=np.int32).reshape(-1))
+        n = len(a)
+        rel, r = np.zeros((max(n, 1), 6)), np.zeros((max(n, 1), 6))
+        cov, chi2 = np.zeros((max(n, 1), 6, 6)), np.zeros(max(n, 1))
+        params = None if max_work is None else self._graph_params(None, None, "cg", max_work)
+        vp = lambda v: C.c_void_p(v.ctypes.data) if v is not None and v.size else None   # noqa: E731
+        self._check(self._lib.velo_graph_edge_gate(self._h, vp(fx), len(fx), params, n, vp(a), vp(b), vp(zz), vp(w), vp(rel), vp(r), vp(cov), vp(chi2)))
+        return rel[:n], r[:n], cov[:n], chi2[:n]
+
+    def graph_relative_covariance(self, pairs, fixed=(0,)):
+        """(rel [n, 6], cov [n, 6, 6]) for an [n, 2] array of frames (a, b): the stored relative pose pose_vec(T_a^-1 T_b) and its
+        covariance in the tangent at that pose -- graph_edge_gate without a measurement and without an information.  Unlike the
+        marginals of graph_covariance it does not depend on which frame is fixed."""
+        q = np.asarray(pairs)
+        if q.size and not np.issubdtype(q.dtype, np.integer):
+            raise ValueError("graph_relative_covariance: frames are integers")
+        if q.size == 0:
+            q = np.zeros((0, 2), dtype=np.int32)
+        if q.ndim != 2 or q.shape[1] != 2:
+            raise ValueError("graph_relative_covariance: an [n, 2] array of pairs")
+        rel, _, cov, _ = self.graph_edge_gate(q[:, 0], q[:, 1], None, None, fixed)
+        return rel, cov
+
+    def graph_loop_candidates(self, query: int, min_gap: int, radius: float, k_sigma: float = 0.0, fixed=(0,), capacity: Optional[int] = None,
+                              max_work=None):
+        """velo_graph_loop_candidates: (frames, dist, sigma) of the frames i with |i - query| >= min_gap whose stored distance to the
+        query is at most radius + k_sigma . sigma_i, ascending; sigma_i is the standard deviation of the relative position from the
+        graph (0 with k_sigma == 0, which runs no factorisation).  capacity: the room of the first call (None: 64); a call that finds
+        more is repeated with that room -- a second whole call, factorisation included, so give the room at once where more can be
+        expected.  max_work caps the envelope factorisation's block products (None: the library's default)."""
+        fx = np.ascontiguousarray(np.asarray(fixed, dtype=np.int32).reshape(-1))
+        cap = 64 if capacity is None else int(capacity)
+        params = None if max_work is None else self._graph_params(None, None, "cg", max_work)
+        vp = lambda v: C.c_void_p(v.ctypes.data) if v.size else None   # noqa: E731
+        while True:
+            frames = np.zeros(max(cap, 1), dtype=np.int32)
+            dist, sigma = np.zeros(max(cap, 1)), np.zeros(max(cap, 1))
+            found = C.c_int32(0)
+            self._check(self._lib.velo_graph_loop_candidates(self._h, vp(fx), len(fx), params, int(query), int(min_gap), float(radius), float(k_sigma), cap,
+                                                             vp(frames), vp(dist), vp(sigma), C.byref(found)))
+            if found.value <= cap:
+                return frames[:found.value], dist[:found.value], sigma[:found.value]
+            cap = found.value
 
     # -- resident keypoint frames and the visual matches assembled from them (velo.h:562-590, velo.h:627-654) ---------------
     def frames_reset(self, cam_trans, arena_capacity: int = 0):

@@ -38,6 +38,10 @@ struct GraphStore {
     // with the pairs' blocks behind it (one copy to the host)
     DevBuf<double> cov_z, cov_work, cov_out;
     DevBuf<int> cov_pair;
+    // velo_graph_edge_gate, velo_graph_loop_candidates: the pairs' (the frames') ints and doubles; the factor, the selected inverse, the
+    // work vectors and the record are the covariance's
+    DevBuf<double> rel_d;
+    DevBuf<int> rel_i;
 };
 
 namespace {
@@ -440,6 +444,50 @@ int graph_append(velo_ctx* c, int32_t n, const int32_t* from, const int32_t* to,
     return VELO_OK;
 }
 
+// ---- what velo_graph_covariance, velo_graph_edge_gate and velo_graph_loop_candidates share behind graph_begin -----------------------------
+constexpr size_t kGraphRecDoubles = sizeof(GraphRecord) / sizeof(double);     // a call's record heads S.cov_out, its results follow
+static_assert(sizeof(GraphRecord) % sizeof(double) == 0, "a call's results follow its record");
+
+// H~ of the stored state (all of A's rows) and the factor of its leading `rows` rows, A's record cleared before
+int graph_cov_factor(velo_ctx* c, const GraphArgs& A, int rows) {
+    GraphArgs B = A;
+    B.n_free = rows;
+    HIP_TRY(hipMemsetAsync(A.rec, 0, sizeof(GraphRecord), c->stream));
+    hipLaunchKernelGGL(graph_env_fill_undamped_kernel, dim3((unsigned)A.n_free), dim3(64), 0, c->stream, A);
+    hipLaunchKernelGGL(graph_env_factor_kernel, dim3(1), dim3(kGrEnvFactorThreads), 0, c->stream, B);
+    HIP_TRY(hipGetLastError());
+    return VELO_OK;
+}
+
+// The refusal of a call whose factor met a pivot that is not positive and finite.  Which pivot: the factor of the leading k rows fails exactly
+// when k exceeds the first bad pivot's position, so bisect on k.  A refusal's path only: each probe fills and factors again.
+int graph_cov_refuse(velo_ctx* c, const GraphCall& call, const GraphArgs& A, const char* who) {
+    GraphStore& S = *c->graph;
+    int lo = 0, hi = call.n_free;
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        VELO_TRY(graph_cov_factor(c, A, mid));
+        HIP_TRY(hipMemcpyAsync(S.h_out.p, A.rec, sizeof(GraphRecord), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (((const GraphRecord*)S.h_out.p)->bad != 0) hi = mid; else lo = mid;
+    }
+    return fail(VELO_ERR_INVALID, "%s: J^T J is not positive definite: the factorisation's pivot at frame %d (position %d of the order) is not positive and finite; "
+                "every free node needs edges that determine it", who, call.free_nodes[(size_t)call.env_ints[(size_t)hi - 1]], hi - 1);
+}
+
+int graph_free_index(const GraphCall& call, int32_t frame) {          // -1: a constant
+    const auto it = std::lower_bound(call.free_nodes.begin(), call.free_nodes.end(), frame);
+    return it != call.free_nodes.end() && *it == frame ? (int)(it - call.free_nodes.begin()) : -1;
+}
+
+// the cap on a call's column work vectors; what: what a column is solved for, in the refusal's words
+int graph_column_cap(velo_ctx* c, const char* who, const char* what, size_t n_cols, size_t n) {
+    if (n_cols * n * 36 <= (size_t)VELO_GRAPH_MAX_COLUMN_DOUBLES) return VELO_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));                          // (graph_begin's copies out of the staging are done before the next call fills it)
+    return fail(VELO_ERR_INVALID, "%s: %zu %s need %zu doubles of work vectors (%zu free nodes x 36 each), over the cap of %lld; ask in smaller batches",
+                who, n_cols, what, n_cols * n * 36, n, (long long)VELO_GRAPH_MAX_COLUMN_DOUBLES);
+}
+
 }  // namespace
 
 extern "C" {   // (continued from the previous part)
@@ -652,16 +700,10 @@ int velo_graph_covariance(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, co
     // per pair: the free indices of its ends (-1: a constant) and, for a pair outside the envelope, the slot of its column solve
     const int32_t* pos = call.env_ints.data() + n;
     const int32_t* first = call.env_ints.data() + 2 * n;
-    const int32_t* perm = call.env_ints.data();
     std::vector<int32_t> pr(3 * np);
     size_t n_out = 0;
     for (size_t p = 0; p < np; p++) {
-        int32_t idx[2];
-        const int32_t ends[2] = {frame_a[p], frame_b[p]};
-        for (int k = 0; k < 2; k++) {
-            const auto it = std::lower_bound(call.free_nodes.begin(), call.free_nodes.end(), ends[k]);
-            idx[k] = it != call.free_nodes.end() && *it == ends[k] ? (int32_t)(it - call.free_nodes.begin()) : -1;
-        }
+        const int32_t idx[2] = {graph_free_index(call, frame_a[p]), graph_free_index(call, frame_b[p])};
         int32_t slot = -1;
         if (idx[0] >= 0 && idx[1] >= 0) {
             const int32_t pa = pos[(size_t)idx[0]], pb = pos[(size_t)idx[1]], hi = std::max(pa, pb), lo = std::min(pa, pb);
@@ -669,13 +711,8 @@ int velo_graph_covariance(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, co
         }
         pr[3 * p] = idx[0]; pr[3 * p + 1] = idx[1]; pr[3 * p + 2] = slot;
     }
-    if (n_out * n * 36 > (size_t)VELO_GRAPH_MAX_COLUMN_DOUBLES) {
-        HIP_TRY(hipStreamSynchronize(c->stream));                      // (graph_begin's copies out of the staging are done before the next call fills it)
-        return fail(VELO_ERR_INVALID, "%s: %zu pairs outside the envelope need %zu doubles of work vectors (%zu free nodes x 36 each), over the cap of %lld; ask in smaller batches",
-                    who, n_out, n_out * n * 36, n, (long long)VELO_GRAPH_MAX_COLUMN_DOUBLES);
-    }
-    constexpr size_t kRec = sizeof(GraphRecord) / sizeof(double);
-    static_assert(sizeof(GraphRecord) % sizeof(double) == 0, "the pairs' blocks follow the record");
+    VELO_TRY(graph_column_cap(c, who, "pairs outside the envelope", n_out, n));
+    constexpr size_t kRec = kGraphRecDoubles;
     VELO_TRY(S.cov_out.reserve(kRec + 36 * np));
     VELO_TRY(S.cov_pair.reserve(3 * np));
     VELO_TRY(S.h_out.reserve(sizeof(double) * (kRec + 36 * np) + 64));
@@ -692,18 +729,9 @@ int velo_graph_covariance(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, co
     A.rec = (GraphRecord*)S.cov_out.p;                                 // this call's record, the blocks behind it
     GraphCov V;
     V.zenv = S.cov_z.p; V.work = S.cov_work.p; V.pair = S.cov_pair.p; V.out = S.cov_out.p + kRec; V.n_pairs = n_pairs;
-    const auto factor = [&](int rows) -> int {                         // H~ of the stored state and the factor of its leading `rows` rows
-        GraphArgs B = A;
-        B.n_free = rows;
-        HIP_TRY(hipMemsetAsync(A.rec, 0, sizeof(GraphRecord), c->stream));
-        hipLaunchKernelGGL(graph_env_fill_undamped_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, A);
-        hipLaunchKernelGGL(graph_env_factor_kernel, dim3(1), dim3(kGrEnvFactorThreads), 0, c->stream, B);
-        HIP_TRY(hipGetLastError());
-        return VELO_OK;
-    };
     HIP_TRY(hipMemsetAsync(A.rec, 0, sizeof(GraphRecord), c->stream));
     if (n) {
-        VELO_TRY(factor((int)n));
+        VELO_TRY(graph_cov_factor(c, A, (int)n));
         hipLaunchKernelGGL(graph_env_selinv_kernel, dim3(1), dim3(kGrEnvSelinvThreads), 0, c->stream, A, V);
         if (n_out) hipLaunchKernelGGL(graph_env_column_kernel, dim3((unsigned)n_out), dim3(kGrEnvColumnThreads), 0, c->stream, A, V);
     }
@@ -711,23 +739,196 @@ int velo_graph_covariance(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, co
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(S.h_out.p, S.cov_out.p, sizeof(double) * (kRec + 36 * np), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (((const GraphRecord*)S.h_out.p)->bad != 0) {
-        // which pivot: the factor of the leading k rows fails exactly when k exceeds the first bad pivot's position, so bisect on k.  A
-        // refusal's path only: each probe fills and factors again.
-        int lo = 0, hi = (int)n;
-        while (hi - lo > 1) {
-            const int mid = lo + (hi - lo) / 2;
-            VELO_TRY(factor(mid));
-            GraphRecord* rec = nullptr;
-            HIP_TRY(hipMemcpyAsync(S.h_out.p, A.rec, sizeof(GraphRecord), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            rec = (GraphRecord*)S.h_out.p;
-            if (rec->bad != 0) hi = mid; else lo = mid;
-        }
-        return fail(VELO_ERR_INVALID, "%s: J^T J is not positive definite: the factorisation's pivot at frame %d (position %d of the order) is not positive and finite; "
-                    "every free node needs edges that determine it", who, call.free_nodes[(size_t)perm[(size_t)hi - 1]], hi - 1);
-    }
+    if (((const GraphRecord*)S.h_out.p)->bad != 0) return graph_cov_refuse(c, call, A, who);
     std::memcpy(cov36, S.h_out.p + sizeof(GraphRecord), sizeof(double) * 36 * np);
+    return VELO_OK;
+}
+
+int velo_graph_edge_gate(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, int32_t n_pairs,
+                         const int32_t* from, const int32_t* to, const double* z, const double* info21,
+                         double* rel6, double* r6, double* cov36, double* chi2) {
+    const char* who = "velo_graph_edge_gate";
+    VELO_TRY(graph_check(c, fixed, n_fixed, params, who));
+    if (n_pairs < 0) return fail(VELO_ERR_INVALID, "%s: negative pair count", who);
+    if (n_pairs > 0 && (!from || !to)) return fail(VELO_ERR_INVALID, "%s: null pair array", who);
+    GraphStore& S = *c->graph;
+    const size_t np = (size_t)std::max(n_pairs, 0);
+    std::vector<double> L(info21 ? 21 * np : 0);
+    for (int p = 0; p < n_pairs; p++) {
+        if (from[p] < 0 || from[p] >= kLmMaxFrame || to[p] < 0 || to[p] >= kLmMaxFrame) return fail(VELO_ERR_INVALID, "%s: pair %d: frames %d -> %d; 0..%d", who, p, from[p], to[p], kLmMaxFrame - 1);
+        if (from[p] == to[p]) return fail(VELO_ERR_INVALID, "%s: pair %d: from == to (%d)", who, p, from[p]);
+        const int32_t ends[2] = {from[p], to[p]};
+        for (int k = 0; k < 2; k++)
+            if ((size_t)ends[k] >= S.pose_set.size() || !S.pose_set[(size_t)ends[k]]) return fail(VELO_ERR_STATE, "%s: pair %d names frame %d, which has no pose", who, p, ends[k]);
+        for (int k = 0; z && k < 6; k++) if (!std::isfinite(z[6 * (size_t)p + k])) return fail(VELO_ERR_INVALID, "%s: pair %d: z[%d] is not finite", who, p, k);
+        if (info21) {                                                  // as velo_graph_add_edges_weighted validates an edge's
+            const double* u = info21 + 21 * (size_t)p;
+            for (int k = 0; k < 21; k++) if (!std::isfinite(u[k])) return fail(VELO_ERR_INVALID, "%s: pair %d: info21[%d] is not finite", who, p, k);
+            if (!graph_host_chol6(u, L.data() + 21 * (size_t)p))
+                return fail(VELO_ERR_INVALID, "%s: pair %d: its information matrix is not positive definite (the Cholesky factorisation met a pivot that is not positive and finite)", who, p);
+        }
+    }
+    if (n_pairs == 0) return VELO_OK;
+    GraphCall call;
+    call.envelope = true;
+    call.who = who;
+    call.max_work = params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
+    VELO_TRY(graph_begin(c, fixed, n_fixed, graph_params(nullptr), &call));
+    const size_t n = (size_t)call.n_free;
+    // per pair: its frames, their free indices and, for a pair outside the envelope, the slot of the full column of one end -- `to`'s; the
+    // pairs that share that frame share the column
+    const int32_t* pos = call.env_ints.data() + n;
+    const int32_t* first = call.env_ints.data() + 2 * n;
+    std::vector<int32_t> pr(5 * np), col_of(n, -1), cols;
+    for (size_t p = 0; p < np; p++) {
+        const int32_t ia = graph_free_index(call, from[p]), ib = graph_free_index(call, to[p]);
+        int32_t slot = -1;
+        if (ia >= 0 && ib >= 0) {
+            const int32_t pa = pos[(size_t)ia], pb = pos[(size_t)ib], hi = std::max(pa, pb), lo = std::min(pa, pb);
+            if (first[(size_t)hi] > lo) {
+                if (col_of[(size_t)ib] < 0) { col_of[(size_t)ib] = (int32_t)cols.size(); cols.push_back(pb); }
+                slot = col_of[(size_t)ib];
+            }
+        }
+        int32_t* q = pr.data() + 5 * p;
+        q[0] = from[p]; q[1] = to[p]; q[2] = ia; q[3] = ib; q[4] = slot;
+    }
+    const size_t nc = cols.size();
+    VELO_TRY(graph_column_cap(c, who, "block columns", nc, n));
+    const size_t n_ints = 5 * np + nc, n_dbl = (z ? 6 * np : 0) + 21 * (info21 ? np : 0), n_res = kGraphRecDoubles + kGrRelOut * np;
+    VELO_TRY(S.cov_out.reserve(n_res));
+    VELO_TRY(S.rel_i.reserve(n_ints));
+    VELO_TRY(S.rel_d.reserve(n_dbl + 1));
+    VELO_TRY(S.h_out.reserve(sizeof(double) * n_res + 64));
+    if (n) {
+        VELO_TRY(S.cov_z.reserve((size_t)call.env_stats[1] * 36));
+        VELO_TRY(S.cov_work.reserve(nc * n * 36 + 1));
+    }
+    VELO_TRY(S.in_ev.wait_or_create());
+    VELO_TRY(S.h_in.reserve(sizeof(double) * n_dbl + sizeof(int32_t) * n_ints));
+    double* hd = (double*)S.h_in.p;                                    // z, then L, then the ints
+    int32_t* hi = (int32_t*)(hd + n_dbl);
+    if (z) std::memcpy(hd, z, sizeof(double) * 6 * np);
+    if (info21) std::memcpy(hd + (z ? 6 * np : 0), L.data(), sizeof(double) * 21 * np);
+    std::memcpy(hi, pr.data(), sizeof(int32_t) * 5 * np);
+    if (nc) std::memcpy(hi + 5 * np, cols.data(), sizeof(int32_t) * nc);
+    if (n_dbl) HIP_TRY(hipMemcpyAsync(S.rel_d.p, hd, sizeof(double) * n_dbl, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(S.rel_i.p, hi, sizeof(int32_t) * n_ints, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(S.in_ev, c->stream));
+    GraphArgs A = call.A;
+    A.rec = (GraphRecord*)S.cov_out.p;                                 // this call's record, the pairs' results behind it
+    GraphCov V;
+    V.zenv = S.cov_z.p; V.work = nullptr; V.pair = nullptr; V.out = nullptr; V.n_pairs = 0;
+    GraphRel R;
+    R.zenv = S.cov_z.p; R.work = S.cov_work.p; R.col_pos = S.rel_i.p + 5 * np; R.pair = S.rel_i.p;
+    R.z = z ? S.rel_d.p : nullptr; R.linfo = info21 ? S.rel_d.p + (z ? 6 * np : 0) : nullptr;
+    R.out = S.cov_out.p + kGraphRecDoubles; R.n_pairs = n_pairs;
+    HIP_TRY(hipMemsetAsync(A.rec, 0, sizeof(GraphRecord), c->stream));
+    if (n) {
+        VELO_TRY(graph_cov_factor(c, A, (int)n));
+        hipLaunchKernelGGL(graph_env_selinv_kernel, dim3(1), dim3(kGrEnvSelinvThreads), 0, c->stream, A, V);
+        if (nc) hipLaunchKernelGGL(graph_env_column_full_kernel, dim3((unsigned)nc), dim3(kGrEnvColumnThreads), 0, c->stream, A, R);
+    }
+    hipLaunchKernelGGL(graph_relcov_kernel, dim3((unsigned)np), dim3(64), 0, c->stream, A, R);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(S.h_out.p, S.cov_out.p, sizeof(double) * n_res, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (((const GraphRecord*)S.h_out.p)->bad != 0) return graph_cov_refuse(c, call, A, who);
+    const double* res = (const double*)S.h_out.p + kGraphRecDoubles;
+    for (size_t p = 0; p < np; p++) {
+        const double* o = res + kGrRelOut * p;
+        if (rel6) std::memcpy(rel6 + 6 * p, o, sizeof(double) * 6);
+        if (r6) std::memcpy(r6 + 6 * p, o + 6, sizeof(double) * 6);
+        if (cov36) std::memcpy(cov36 + 36 * p, o + 12, sizeof(double) * 36);
+        if (chi2) chi2[p] = o[48];
+    }
+    return VELO_OK;
+}
+
+int velo_graph_loop_candidates(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, int32_t query, int32_t min_gap,
+                               double radius, double k_sigma, int32_t capacity, int32_t* frames_out, double* dist_out, double* sigma_out, int32_t* n_found) {
+    const char* who = "velo_graph_loop_candidates";
+    VELO_TRY(graph_check(c, fixed, n_fixed, params, who));
+    VELO_TRY(check_frame(query, who));
+    if (min_gap < 1) return fail(VELO_ERR_INVALID, "%s: min_gap %d; at least 1", who, min_gap);
+    if (!(radius >= 0.0) || !std::isfinite(radius)) return fail(VELO_ERR_INVALID, "%s: radius must be non-negative and finite", who);
+    if (!(k_sigma >= 0.0) || !std::isfinite(k_sigma)) return fail(VELO_ERR_INVALID, "%s: k_sigma must be non-negative and finite", who);
+    if (capacity < 0) return fail(VELO_ERR_INVALID, "%s: negative capacity", who);
+    if (!n_found) return fail(VELO_ERR_INVALID, "%s: null n_found", who);
+    GraphStore& S = *c->graph;
+    if ((size_t)query >= S.pose_set.size() || !S.pose_set[(size_t)query]) return fail(VELO_ERR_STATE, "%s: the query frame %d has no pose", who, query);
+    const size_t F = S.frame_cap;
+    const bool with_sigma = k_sigma > 0.0;
+    GraphCall call;
+    GraphArgs A;
+    std::memset(&A, 0, sizeof(A));
+    if (with_sigma) {
+        call.envelope = true;
+        call.who = who;
+        call.max_work = params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
+        VELO_TRY(graph_begin(c, fixed, n_fixed, graph_params(nullptr), &call));
+        A = call.A;
+    } else {                                                           // distances alone: the stored poses to buffer 0, no system
+        HIP_TRY(hipSetDevice(c->device));
+        VELO_TRY(S.x.reserve(2 * F * 6 + 1));
+        HIP_TRY(hipMemcpyAsync(S.x.p, S.h_x.p, sizeof(double) * F * 6, hipMemcpyHostToDevice, c->stream));
+        A.x = S.x.p; A.x_stride = F * 6;
+    }
+    const size_t n = (size_t)call.n_free;
+    // per frame: -2 = no pose, -1 = a constant, otherwise the free index; without sigma only `no pose` matters
+    std::vector<int32_t> slot(F, -2);
+    for (size_t f = 0; f < F; f++) if (S.pose_set[f]) slot[f] = -1;
+    for (size_t i = 0; i < n; i++) slot[(size_t)call.free_nodes[i]] = (int32_t)i;
+    const int32_t iq = with_sigma ? slot[(size_t)query] : -1;
+    const size_t nc = iq >= 0 ? 1 : 0;
+    VELO_TRY(graph_column_cap(c, who, "block columns", nc, n));
+    const size_t cap = std::min((size_t)capacity, F), n_res = kGraphRecDoubles + 1 + 3 * cap;
+    VELO_TRY(S.cov_out.reserve(n_res));
+    VELO_TRY(S.rel_i.reserve(2 * F + 1));
+    VELO_TRY(S.rel_d.reserve(2 * F + 1));
+    VELO_TRY(S.h_out.reserve(sizeof(double) * n_res + 64));
+    if (n) {
+        VELO_TRY(S.cov_z.reserve((size_t)call.env_stats[1] * 36));
+        VELO_TRY(S.cov_work.reserve(nc * n * 36 + 1));
+    }
+    VELO_TRY(S.in_ev.wait_or_create());
+    VELO_TRY(S.h_in.reserve(sizeof(int32_t) * (F + 1)));
+    int32_t* hi = (int32_t*)S.h_in.p;                                  // the slots, then the position of the query's column
+    std::memcpy(hi, slot.data(), sizeof(int32_t) * F);
+    hi[F] = nc ? call.env_ints[n + (size_t)iq] : 0;
+    HIP_TRY(hipMemcpyAsync(S.rel_i.p, hi, sizeof(int32_t) * (F + 1), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(S.in_ev, c->stream));
+    A.rec = (GraphRecord*)S.cov_out.p;
+    GraphCov V;
+    V.zenv = S.cov_z.p; V.work = nullptr; V.pair = nullptr; V.out = nullptr; V.n_pairs = 0;
+    GraphRel R;
+    std::memset(&R, 0, sizeof(R));
+    R.zenv = S.cov_z.p; R.work = S.cov_work.p; R.col_pos = S.rel_i.p + F;
+    GraphCand K;
+    K.zenv = S.cov_z.p; K.work = S.cov_work.p; K.slot = S.rel_i.p; K.flag = S.rel_i.p + F + 1; K.rec = S.rel_d.p;
+    K.out = S.cov_out.p + kGraphRecDoubles;
+    K.n_frames = (int)F; K.query = query; K.min_gap = min_gap; K.capacity = (int)cap; K.with_sigma = with_sigma ? 1 : 0;
+    K.radius = radius; K.k_sigma = k_sigma;
+    HIP_TRY(hipMemsetAsync(A.rec, 0, sizeof(GraphRecord), c->stream));
+    if (n) {
+        VELO_TRY(graph_cov_factor(c, A, (int)n));
+        hipLaunchKernelGGL(graph_env_selinv_kernel, dim3(1), dim3(kGrEnvSelinvThreads), 0, c->stream, A, V);
+        if (nc) hipLaunchKernelGGL(graph_env_column_full_kernel, dim3(1), dim3(kGrEnvColumnThreads), 0, c->stream, A, R);
+    }
+    hipLaunchKernelGGL(graph_loop_candidates_kernel, dim3((unsigned)cdiv((int)F, kGrThreads)), dim3(kGrThreads), 0, c->stream, A, K);
+    hipLaunchKernelGGL(graph_loop_compact_kernel, dim3(1), dim3(kGrCompactThreads), 0, c->stream, K);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(S.h_out.p, S.cov_out.p, sizeof(double) * n_res, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (((const GraphRecord*)S.h_out.p)->bad != 0) return graph_cov_refuse(c, call, A, who);
+    const double* res = (const double*)S.h_out.p + kGraphRecDoubles;
+    const size_t found = (size_t)res[0];
+    for (size_t k = 0; k < std::min(found, cap); k++) {
+        if (frames_out) frames_out[k] = (int32_t)res[1 + 3 * k];
+        if (dist_out) dist_out[k] = res[2 + 3 * k];
+        if (sigma_out) sigma_out[k] = res[3 + 3 * k];
+    }
+    *n_found = (int32_t)found;
     return VELO_OK;
 }
 

@@ -25,7 +25,9 @@
 // A call may select the envelope solver for the linear step instead (velo_graph_params.reserved[0]): the same system, assembled as a
 // block skyline and factored exactly -- graph_env_fill_kernel, graph_env_factor_kernel, graph_env_solve_kernel at the end of this file.
 // velo_graph_covariance reads blocks of (J^T J)^-1 off the same factor of the undamped system: graph_env_fill_undamped_kernel,
-// graph_env_selinv_kernel, graph_env_column_kernel, graph_cov_gather_kernel behind them.
+// graph_env_selinv_kernel, graph_env_column_kernel, graph_cov_gather_kernel behind them.  velo_graph_edge_gate and
+// velo_graph_loop_candidates turn those blocks into the covariance of a relative pose in an edge's tangent space: graph_env_column_full_kernel,
+// graph_relcov_kernel, graph_loop_candidates_kernel, graph_loop_compact_kernel at the very end.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -213,11 +215,8 @@ __device__ __forceinline__ void graph_mul3_tt(const double A[9], const double B[
 
 // ---- linearise: one thread per edge, at the poses of buffer `which` -------------------------------------------------------------
 // the unweighted residual r = pose_vec(Z^-1 T_from^-1 T_to) of edge e and its Jacobians A (from), B (to), row-major 6 x 6: the text both
-// linearise kernels share
-__device__ __forceinline__ void graph_edge_terms(const GraphArgs& G, int e, int which, double r[6], double A[36], double B[36]) {
-    const double* xf = G.x + (size_t)which * G.x_stride + (size_t)G.from[e] * 6;
-    const double* xt = G.x + (size_t)which * G.x_stride + (size_t)G.to[e] * 6;
-    const double* zz = G.z + (size_t)e * 6;
+// linearise kernels share, and graph_relcov_kernel and graph_loop_candidates_kernel with them.  xf, xt: the 6 doubles of the two poses; zz: of Z
+__device__ __forceinline__ void graph_edge_terms_at(const double* xf, const double* xt, const double* zz, double r[6], double A[36], double B[36]) {
     const double wf[3] = {xf[0], xf[1], xf[2]}, wt[3] = {xt[0], xt[1], xt[2]}, wz[3] = {zz[0], zz[1], zz[2]};
     double Rf[9], Jlf[9], Rt[9], Jlt[9], Rz[9];
     graph_rot(wf, Rf, Jlf);
@@ -258,6 +257,11 @@ __device__ __forceinline__ void graph_edge_terms(const GraphArgs& G, int e, int 
 #pragma unroll
         for (int j = 0; j < 3; j++) { B[i * 6 + j] = U[i * 3 + j]; B[i * 6 + 3 + j] = 0.0; B[(3 + i) * 6 + j] = 0.0; B[(3 + i) * 6 + 3 + j] = Q[i * 3 + j]; }
     }
+}
+// edge e of the store at the poses of buffer `which`
+__device__ __forceinline__ void graph_edge_terms(const GraphArgs& G, int e, int which, double r[6], double A[36], double B[36]) {
+    graph_edge_terms_at(G.x + (size_t)which * G.x_stride + (size_t)G.from[e] * 6, G.x + (size_t)which * G.x_stride + (size_t)G.to[e] * 6,
+                        G.z + (size_t)e * 6, r, A, B);
 }
 
 // w A^T A, w B^T B (upper), w A^T B, w A^T r, w B^T r into the edge's block
@@ -1202,10 +1206,12 @@ graph_env_selinv_kernel(GraphArgs G, GraphCov V)
 ;
 #endif
 
-__global__ void __launch_bounds__(kGrEnvColumnThreads)
-graph_env_column_kernel(GraphArgs G, GraphCov V)
-#if VELO_DEF_GRAPH
-{
+// The 6 columns of Z that belong to position lo, rows hi .. n - 1, into the work vector v (row i: the 6 x 6 of the 6 right-hand sides): the
+// text graph_env_column_kernel (one pair: as far as row hi) and graph_env_column_full_kernel (hi = 0: the whole block column) share.  The
+// back substitution reads the rows [hi, lo) as zeros, which the full kernel writes there first.  ints: the pairs ([n_pairs][3], as
+// GraphCov::pair), or for the full kernel the position of every slot's column.
+template <bool kFull>
+__device__ __forceinline__ void graph_env_column_body(const GraphArgs& G, double* work, const int* ints, int n_pairs) {
     __shared__ double part[kGrEnvColumnChunks * 36];
     __shared__ double xs[36];
     __shared__ int pair_s[2];
@@ -1213,14 +1219,18 @@ graph_env_column_kernel(GraphArgs G, GraphCov V)
     const int t = threadIdx.x, n = G.n_free;
     if (t == 0) {                                                      // the pair that holds this workgroup's slot
         int pa = 0, pb = 0;
-        for (int p = 0; p < V.n_pairs; p++)
-            if (V.pair[p * 3 + 2] == (int)blockIdx.x) { pa = G.env_pos[V.pair[p * 3]]; pb = G.env_pos[V.pair[p * 3 + 1]]; break; }
-        pair_s[0] = pa > pb ? pa : pb;
-        pair_s[1] = pa > pb ? pb : pa;
+        for (int p = 0; !kFull && p < n_pairs; p++)
+            if (ints[p * 3 + 2] == (int)blockIdx.x) { pa = G.env_pos[ints[p * 3]]; pb = G.env_pos[ints[p * 3 + 1]]; break; }
+        pair_s[0] = kFull ? 0 : pa > pb ? pa : pb;
+        pair_s[1] = kFull ? ints[blockIdx.x] : pa > pb ? pb : pa;
     }
     __syncthreads();
     const int hi = pair_s[0], lo = pair_s[1];
-    double* v = V.work + (size_t)blockIdx.x * (size_t)n * 36;          // row i: the 6 x 6 of the 6 right-hand sides
+    double* v = work + (size_t)blockIdx.x * (size_t)n * 36;            // row i: the 6 x 6 of the 6 right-hand sides
+    if (kFull) {
+        for (int u = t; u < lo * 36; u += kGrEnvColumnThreads) v[u] = 0.0;
+        __syncthreads();
+    }
     const int e = t % 36, ch = t / 36, er = e / 6, ec = e % 6;
     for (int i = lo; i < n; i++) {                                     // forward, by rows: Y_i = L(i,i)^-1 (E_i - sum_j L(i,j) Y_j), Y_j = 0 for j < lo
         const int fi = G.env_first[i];
@@ -1284,6 +1294,13 @@ graph_env_column_kernel(GraphArgs G, GraphCov V)
         __syncthreads();
     }
 }
+
+__global__ void __launch_bounds__(kGrEnvColumnThreads)
+graph_env_column_kernel(GraphArgs G, GraphCov V)
+#if VELO_DEF_GRAPH
+{
+    graph_env_column_body<false>(G, V.work, V.pair, V.n_pairs);
+}
 #else
 ;
 #endif
@@ -1306,6 +1323,261 @@ graph_cov_gather_kernel(GraphArgs G, GraphCov V)
         out = z * (G.scale[(size_t)ia * 6 + r] * G.scale[(size_t)ib * 6 + c]);
     }
     V.out[(size_t)p * 36 + l] = out;
+}
+#else
+;
+#endif
+
+// ---- the covariance of a relative pose in an edge's tangent space (velo_graph_edge_gate, velo_graph_loop_candidates) -------------------
+// For a pair (a, b) and a measurement Z the unweighted edge residual r = pose_vec(Z^-1 T_a^-1 T_b) has the Jacobians A, B of
+// graph_edge_terms_at, and to first order Cov(r) = Sigma_rel = A S_aa A^T + A S_ab B^T + B S_ba A^T + B S_bb B^T with the blocks S of
+// velo_graph_covariance -- which, unlike them, does not depend on the frame that is fixed.  Behind the factor and the selected inverse
+// of velo_graph_covariance, on the same stream:
+//     graph_env_column_full_kernel   one workgroup per DISTINCT frame that a pair outside the envelope needs a column of: the whole block
+//                                    column of Z at its position q, rows 0 .. n - 1 (graph_env_column_body with hi = 0, the rows above q
+//                                    cleared first), so that every pair that shares the frame reads its cross block off one solve
+//     graph_relcov_kernel            one workgroup per pair: thread 0 forms rel = pose_vec(T_a^-1 T_b), takes Z (the caller's, or rel itself),
+//                                    r, A, B and, where the pair has an information W = L L^T, L^-1; the three blocks are gathered with the
+//                                    Jacobi scales as graph_cov_gather_kernel gathers them (zeros for a constant); T1 = S_aa A^T + S_ab B^T and
+//                                    T2 = S_ba A^T + S_bb B^T, a thread per entry; then S = A T1 + B T2 + W^-1, a thread per entry of the lower
+//                                    triangle, mirrored, so S is symmetric to the bit; thread 0 factors S and writes chi2 = r^T S^-1 r, or -1
+//                                    where a pivot is not positive and finite.  Every entry is one fixed-order expression.
+//     graph_loop_candidates_kernel   one thread per frame i of the node table against ONE query q: dist = |t(T_i^-1 T_q)| and, unless the call
+//                                    asks for distances only, sigma = sqrt(trace(Sigma_rel(i, q)[3:, 3:])) in the tangent at the stored relative
+//                                    pose (rows 3 .. 5 of A and B alone), S_iq from the query's full column; the flag dist <= radius + k sigma
+//     graph_loop_compact_kernel      ONE workgroup: the flagged frames in ascending order, by a prefix sum over 256 frames at a time; the first
+//                                    `capacity` are written, the count is the total
+struct GraphRel {
+    const double* zenv;                          // as GraphCov
+    double* work;                                // [n_cols][n_free][36]: the full columns
+    const int* col_pos;                          // [n_cols]: the position whose block column a slot holds
+    const int* pair;                             // [n_pairs][5]: frame a, frame b, free index of a, of b (-1: a constant), the slot of b's full column
+                                                 // (-1: the cross block lies inside the envelope, or is zero)
+    const double* z;                             // [n_pairs][6], or null: the stored relative pose
+    const double* linfo;                         // [n_pairs][21], or null: the Cholesky factor of the pair's information, as GraphWeights::winfo
+    double* out;                                 // [n_pairs][kGrRelOut]: rel (6), r (6), S (36), chi2
+    int n_pairs;
+};
+constexpr int kGrRelOut = 49;
+
+struct GraphCand {
+    const double* zenv;
+    const double* work;                          // [n_free][36]: the query's full column (not read for a constant query)
+    const int* slot;                             // [n_frames]: -2 = no pose, -1 = a constant, otherwise the free index
+    int* flag;                                   // [n_frames]
+    double* rec;                                 // [n_frames][2]: dist, sigma
+    double* out;                                 // the count, then per written candidate: frame, dist, sigma
+    int n_frames, query, min_gap, capacity, with_sigma;
+    double radius, k_sigma;
+};
+
+__global__ void __launch_bounds__(kGrEnvColumnThreads)
+graph_env_column_full_kernel(GraphArgs G, GraphRel V)
+#if VELO_DEF_GRAPH
+{
+    graph_env_column_body<true>(G, V.work, V.col_pos, 0);
+}
+#else
+;
+#endif
+
+// entry (r, c) of Z_ab c_a c_b for the free indices ia, ib: off the skyline, or (col not null) off the full column of b's position
+__device__ __forceinline__ double graph_rel_sigma(const GraphArgs& G, const double* zenv, const double* col, int ia, int ib, int r, int c) {
+    const int pa = G.env_pos[ia], pb = G.env_pos[ib];
+    double z;
+    if (col) z = col[(size_t)pa * 36 + r * 6 + c];                    // row o of the column of q is Z(o, q)
+    else {
+        const int hi = pa > pb ? pa : pb, lo = pa > pb ? pb : pa;
+        const double* B = zenv + ((size_t)G.env_rowptr[hi] + (size_t)(lo - G.env_first[hi])) * 36;
+        z = pa >= pb ? B[r * 6 + c] : B[c * 6 + r];
+    }
+    return z * (G.scale[(size_t)ia * 6 + r] * G.scale[(size_t)ib * 6 + c]);
+}
+
+// rel = pose_vec(T_a^-1 T_b) from the 6 doubles of the two poses
+__device__ __forceinline__ void graph_relative(const double* xa, const double* xb, double rel[6]) {
+    const double wa[3] = {xa[0], xa[1], xa[2]}, wb[3] = {xb[0], xb[1], xb[2]};
+    double Ra[9], Rb[9], Q[9];
+    graph_rot_value(wa, Ra);
+    graph_rot_value(wb, Rb);
+    graph_mul3_tn(Ra, Rb, Q);
+    graph_log(Q, rel);
+    const double d[3] = {xb[3] - xa[3], xb[4] - xa[4], xb[5] - xa[5]};
+#pragma unroll
+    for (int i = 0; i < 3; i++) rel[3 + i] = Ra[i] * d[0] + Ra[3 + i] * d[1] + Ra[6 + i] * d[2];
+}
+
+__global__ void __launch_bounds__(64)
+graph_relcov_kernel(GraphArgs G, GraphRel V)
+#if VELO_DEF_GRAPH
+{
+    __shared__ double As[36], Bs[36], rs[6], Xs[36], Saa[36], Sab[36], Sbb[36], T1[36], T2[36], Ss[36];
+    const int p = blockIdx.x, l = threadIdx.x;
+    if (p >= V.n_pairs) return;
+    const int* pr = V.pair + (size_t)p * 5;
+    const int fa = pr[0], fb = pr[1], ia = pr[2], ib = pr[3], slot = pr[4];
+    double* out = V.out + (size_t)p * kGrRelOut;
+    if (l == 0) {                                                      // the stored state is buffer 0
+        const double* xa = G.x + (size_t)fa * 6;
+        const double* xb = G.x + (size_t)fb * 6;
+        double rel[6], zz[6], r[6], A[36], B[36];
+        graph_relative(xa, xb, rel);
+#pragma unroll
+        for (int k = 0; k < 6; k++) { zz[k] = V.z ? V.z[(size_t)p * 6 + k] : rel[k]; out[k] = rel[k]; }
+        graph_edge_terms_at(xa, xb, zz, r, A, B);
+#pragma unroll
+        for (int k = 0; k < 36; k++) { As[k] = A[k]; Bs[k] = B[k]; }
+#pragma unroll
+        for (int k = 0; k < 6; k++) { rs[k] = r[k]; out[6 + k] = r[k]; }
+    }
+    if (l == 63) {                                                     // L^-1 of the pair's information; zero without one
+        if (V.linfo) {
+            double L[21];
+#pragma unroll
+            for (int k = 0; k < 21; k++) L[k] = V.linfo[(size_t)p * 21 + k];
+            graph_env_inv6(L, Xs);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 36; k++) Xs[k] = 0.0;
+        }
+    }
+    const int r = l / 6, c = l % 6;
+    if (l < 36) {
+        const bool ok = G.rec->bad == 0;
+        Saa[l] = ia >= 0 && ok ? graph_rel_sigma(G, V.zenv, nullptr, ia, ia, r, c) : 0.0;
+        Sbb[l] = ib >= 0 && ok ? graph_rel_sigma(G, V.zenv, nullptr, ib, ib, r, c) : 0.0;
+        Sab[l] = ia >= 0 && ib >= 0 && ok ? graph_rel_sigma(G, V.zenv, slot >= 0 ? V.work + (size_t)slot * (size_t)G.n_free * 36 : nullptr, ia, ib, r, c) : 0.0;
+    }
+    __syncthreads();
+    if (l < 36) {                                                      // T1 = S_aa A^T + S_ab B^T, T2 = S_ba A^T + S_bb B^T: entry (r, c)
+        double t1 = 0.0, t2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; k++) t1 += Saa[r * 6 + k] * As[c * 6 + k];
+#pragma unroll
+        for (int k = 0; k < 6; k++) t1 += Sab[r * 6 + k] * Bs[c * 6 + k];
+#pragma unroll
+        for (int k = 0; k < 6; k++) t2 += Sab[k * 6 + r] * As[c * 6 + k];
+#pragma unroll
+        for (int k = 0; k < 6; k++) t2 += Sbb[r * 6 + k] * Bs[c * 6 + k];
+        T1[l] = t1;
+        T2[l] = t2;
+    }
+    __syncthreads();
+    if (l < 36 && c <= r) {                                            // S = A T1 + B T2 + L^-T L^-1: the lower triangle, mirrored
+        double s = 0.0, w = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; k++) s += As[r * 6 + k] * T1[k * 6 + c];
+#pragma unroll
+        for (int k = 0; k < 6; k++) s += Bs[r * 6 + k] * T2[k * 6 + c];
+#pragma unroll
+        for (int k = 0; k < 6; k++) w += Xs[k * 6 + r] * Xs[k * 6 + c];
+        s += w;
+        Ss[r * 6 + c] = s;
+        Ss[c * 6 + r] = s;
+        out[12 + r * 6 + c] = s;
+        out[12 + c * 6 + r] = s;
+    }
+    __syncthreads();
+    if (l == 0) {                                                      // chi2 = |L_S^-1 r|^2
+        double M[36], y[6];
+#pragma unroll
+        for (int k = 0; k < 36; k++) M[k] = Ss[k];
+        const bool ok = graph_chol6(M);
+        double chi2 = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            double s = rs[i];
+#pragma unroll
+            for (int k = 0; k < i; k++) s -= M[i * 6 + k] * y[k];
+            y[i] = s / M[i * 6 + i];
+            chi2 += y[i] * y[i];
+        }
+        out[48] = ok ? chi2 : -1.0;
+    }
+}
+#else
+;
+#endif
+
+__global__ void __launch_bounds__(kGrThreads)
+graph_loop_candidates_kernel(GraphArgs G, GraphCand V)
+#if VELO_DEF_GRAPH
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= V.n_frames) return;
+    const int q = V.query, si = V.slot[i], sq = V.slot[q];
+    const int gap = i > q ? i - q : q - i;
+    double dist = 0.0, sigma = 0.0;
+    int flag = 0;
+    if (si != -2 && gap >= V.min_gap) {
+        const double* xa = G.x + (size_t)i * 6;                        // the stored state is buffer 0
+        const double* xb = G.x + (size_t)q * 6;
+        double rel[6];
+        graph_relative(xa, xb, rel);
+        dist = sqrt(rel[3] * rel[3] + rel[4] * rel[4] + rel[5] * rel[5]);
+        if (V.with_sigma) {
+            double r[6], A[36], B[36];
+            graph_edge_terms_at(xa, xb, rel, r, A, B);
+            double tr = 0.0;
+#pragma unroll
+            for (int row = 3; row < 6; row++) {                        // a S_aa a^T + 2 a S_ab b^T + b S_bb b^T for the rows a, b of A, B
+                double aa = 0.0, ab = 0.0, bb = 0.0;
+#pragma unroll
+                for (int k = 0; k < 6; k++) {
+                    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+#pragma unroll
+                    for (int m = 0; m < 6; m++) {
+                        if (si >= 0) s1 += graph_rel_sigma(G, V.zenv, nullptr, si, si, k, m) * A[row * 6 + m];
+                        if (si >= 0 && sq >= 0) s2 += graph_rel_sigma(G, V.zenv, V.work, si, sq, k, m) * B[row * 6 + m];
+                        if (sq >= 0) s3 += graph_rel_sigma(G, V.zenv, nullptr, sq, sq, k, m) * B[row * 6 + m];
+                    }
+                    aa += A[row * 6 + k] * s1;
+                    ab += A[row * 6 + k] * s2;
+                    bb += B[row * 6 + k] * s3;
+                }
+                tr += (aa + 2.0 * ab) + bb;
+            }
+            sigma = sqrt(fmax(tr, 0.0));
+        }
+        flag = dist <= V.radius + V.k_sigma * sigma ? 1 : 0;
+    }
+    V.flag[i] = flag;
+    V.rec[(size_t)i * 2] = dist;
+    V.rec[(size_t)i * 2 + 1] = sigma;
+}
+#else
+;
+#endif
+
+constexpr int kGrCompactThreads = 256;
+__global__ void __launch_bounds__(kGrCompactThreads)
+graph_loop_compact_kernel(GraphCand V)
+#if VELO_DEF_GRAPH
+{
+    __shared__ int cnt[kGrCompactThreads];
+    const int t = threadIdx.x;
+    int base = 0;
+    for (int start = 0; start < V.n_frames; start += kGrCompactThreads) {
+        const int i = start + t;
+        const int f = i < V.n_frames ? V.flag[i] : 0;
+        cnt[t] = f;
+        __syncthreads();
+        for (int off = 1; off < kGrCompactThreads; off <<= 1) {        // an inclusive prefix sum of the flags
+            const int v = t >= off ? cnt[t - off] : 0;
+            __syncthreads();
+            cnt[t] += v;
+            __syncthreads();
+        }
+        const int at = base + cnt[t] - f;
+        if (f && at < V.capacity) {
+            V.out[1 + (size_t)at * 3] = (double)i;
+            V.out[2 + (size_t)at * 3] = V.rec[(size_t)i * 2];
+            V.out[3 + (size_t)at * 3] = V.rec[(size_t)i * 2 + 1];
+        }
+        base += cnt[kGrCompactThreads - 1];
+        __syncthreads();
+    }
+    if (t == 0) V.out[0] = (double)base;
 }
 #else
 ;
