@@ -859,6 +859,33 @@ int velo_graph_info(velo_ctx* ctx, int32_t* info);
  * A node without a neighbour is a component of its own and a row of width 0.  VELO_ERR_INVALID: a NULL argument (a and b may be NULL
  * when n_edges is 0), a negative count, an end out of range, a[e] == b[e]. */
 int velo_graph_order(int32_t n_nodes, int32_t n_edges, const int32_t* a, const int32_t* b, int32_t* perm, int32_t* first, int64_t* stats);
+/* The order of a graph that has GROWN since an order of it was kept (velo_graph_retain); a pure host function: no context, no GPU.
+ * perm_old [n_old] is the kept order of the nodes 0 .. n_old - 1; the nodes n_old .. n_nodes - 1 are new; a, b are ALL edges, of which
+ * those from first_new_edge on are new (an edge before it joins two old nodes).  Writes perm [n_nodes], first [n_nodes] and stats[8].
+ * The rule, to the letter:
+ *   extended order   perm_old, then the new nodes in ascending number;
+ *   first dirty row  p = the smallest position, in the extended order, among the ends of the new edges and the new nodes; p = n_nodes
+ *                    when there is nothing new.  A Cholesky factor in the extended order keeps every row before p;
+ *   rows before p    keep their `first`: no new edge touches them.  The function checks it (VELO_ERR_STATE if not: cannot happen);
+ *   rows >= p        `first` as velo_graph_order defines it, over all edges;
+ *   fresh order      velo_graph_order's order of the whole graph, ORIENTED: it is reversed as a whole when both hold: the reversal moves
+ *                    the highest-numbered node from the first half of the positions to the second (2 pos < n_nodes before and
+ *                    2 (n_nodes - 1 - pos) >= n_nodes after), and the reversed order's work is <= VELO_GRAPH_RETAIN_REBUILD_RATIO times the
+ *                    unreversed one's.  (A chain's newest frame must sit near the end of the order, or every later append dirties row 0);
+ *   rebuild          the extended order is the result iff its work sum w (w + 1) / 2 is <= max_work AND <=
+ *                    VELO_GRAPH_RETAIN_REBUILD_RATIO times the fresh order's; otherwise the result is the fresh order and p = 0.  A fresh
+ *                    order over max_work is still returned: the caller compares stats[2];
+ *   stats            [0] widest row, [1] blocks, [2] work, [3] components, all of the result; [4] p; [5] 1 if the result is the fresh
+ *                    order (a rebuild); [6] 1 if it is the fresh order reversed; [7] the fresh order's work.
+ * With n_old == 0 the extended order is 0, 1, .. n_nodes - 1: what velo_graph_retain starts from without a caller's order.
+ * VELO_GRAPH_RETAIN_REBUILD_RATIO is a policy constant: how much factorisation work an append may cost over a fresh order before the
+ * order is built anew.  It is NOT measured or tuned; profiles/ records what it costs where it was tried.
+ * VELO_ERR_INVALID: a NULL argument (perm_old may be NULL when n_old is 0, a and b when n_edges is 0), a negative count or max_work,
+ * n_nodes < n_old, first_new_edge outside 0 .. n_edges, a perm_old that is not a permutation of 0 .. n_old - 1, an end out of range,
+ * a[e] == b[e], an edge before first_new_edge that ends at a new node. */
+#define VELO_GRAPH_RETAIN_REBUILD_RATIO 2
+int velo_graph_order_extend(int32_t n_old, const int32_t* perm_old, int32_t n_nodes, int32_t n_edges, const int32_t* a, const int32_t* b,
+                            int32_t first_new_edge, int64_t max_work, int32_t* perm, int32_t* first, int64_t* stats);
 /* Diagnostics: the problem velo_graph_optimize would solve, evaluated at the stored state; nothing changes.  The free nodes are the
  * nodes with a pose that are not fixed, ascending: cost, J^T r (gradient [n_free][6]) and the diagonal blocks of J^T J (diag_blocks
  * [n_free][36], row-major), unscaled.  Each output may be NULL. */
@@ -933,6 +960,43 @@ int velo_graph_edge_gate(velo_ctx* ctx, const int32_t* fixed, int32_t n_fixed, c
 int velo_graph_loop_candidates(velo_ctx* ctx, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params,
                                int32_t query, int32_t min_gap /* >= 1 */, double radius /* >= 0 */, double k_sigma /* >= 0 */,
                                int32_t capacity, int32_t* frames_out, double* dist_out, double* sigma_out, int32_t* n_found);
+/* Retains the factorisation the three entries above build -- velo_graph_covariance's problem for the stored state and this `fixed` set:
+ * the same free nodes, the same undamped H, the same Jacobi scales, the work cap of params->reserved[1] -- so that they stop building it
+ * per call.  Kept, in buffers of its own: the order's ints, the skyline of L, the scales, the poses; on first need the skyline of Z (the
+ * selected inverse, at most once per generation) and the LAST full block column solved, with its position: a candidates call for frame q
+ * followed by gates whose `to` is q solves one column.  A context retains one state; retaining again replaces it.
+ *   perm     the order to factor in: a permutation of the free nodes' indices, n_perm == n_free; with velo_graph_order's order the
+ *            factorisation, and so every answer, is to the bit the one an un-retained call computes.  NULL: velo_graph_order_extend's
+ *            rule with n_old == 0 (frame order, unless that costs more than VELO_GRAPH_RETAIN_REBUILD_RATIO times the fresh order);
+ *   queries  velo_graph_covariance, velo_graph_edge_gate and velo_graph_loop_candidates with k_sigma > 0 use the state when their
+ *            `fixed` equals the retained one and their cap is not below the retained one; otherwise they run as without it and leave it
+ *            alone.  On a current state they build no order, fill and factor nothing;
+ *   append   frames posed for the first time whose numbers lie above every retained free frame, and new edges, leave the state BEHIND.
+ *            The next such query, or the next velo_graph_retain with perm == NULL, extends it: the order of velo_graph_order_extend, the
+ *            system linearised and assembled again, the rows from the first dirty row on filled and factored -- the rows before keep
+ *            their bits, and the rows after get the bits of a full factorisation in that order.  Z and the kept column go stale.  Where
+ *            the rule says rebuild, everything is rebuilt in the fresh order.  An extension that fails (the cap; a pivot that is not
+ *            positive, as of a new frame that has no edge yet) leaves the state behind at its last good generation -- the rows it
+ *            touched are filled again by the next extension -- and the call is answered, or refused, as without a state;
+ *            an extension over the cap fails again, after forming the system, on every such query until velo_graph_release or a
+ *            velo_graph_retain under a larger cap.  The extension runs BEFORE the query's own later checks: a query that is then
+ *            refused (its column work vectors over VELO_GRAPH_MAX_COLUMN_DOUBLES) has written nothing to its outputs and nothing to
+ *            the store, but may have moved the retained state on by a generation, counters included;
+ *   dropped  by velo_graph_set_pose[s] on a frame that has a pose, a newly posed frame numbered below a retained free frame,
+ *            velo_graph_optimize once it runs (whatever its outcome: retain again after a solve), velo_graph_reset, and the store's
+ *            promotion to weighted edges.  The queries then run as without a state.
+ * Refused: what velo_graph_covariance refuses; VELO_ERR_INVALID for a perm that is not a permutation, work over the cap (both leave a
+ * state retained before as it was) and an H that is not positive definite (the message names the frame; nothing is retained then).
+ * velo_graph_release forgets the state and frees its buffers; without one it returns VELO_OK.  velo_graph_retained reports:
+ *   info[0] state: 0 none, 1 current, 2 behind     [1] free nodes in the retained order   [2] widest row   [3] blocks   [4] work
+ *   counters since velo_graph_reset or velo_graph_release:  [5] full builds   [6] extensions   [7] of them rebuilds forced by the order's
+ *   rule   [8] selected-inverse runs   [9] full columns solved   [10] queries served from the state
+ *   [11] the first dirty row of the last extension   [12] the rows it refactored   [13..15] 0
+ * and the first min(capacity, info[1]) entries of the order in perm_out (NULL with capacity 0).  velo_graph_info is unchanged. */
+int velo_graph_retain(velo_ctx* ctx, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params,
+                      const int32_t* perm /* [n_perm] | NULL */, int32_t n_perm);
+int velo_graph_release(velo_ctx* ctx);
+int velo_graph_retained(velo_ctx* ctx, int64_t info[16], int32_t* perm_out, int32_t capacity);
 
 /* --- resident keypoint frames and the visual matches assembled from them (velo.h:562-590, velo.h:627-654, main.cpp:366-405) ---
  * Every context can hold one frame store: for every (frame, camera) put so far keypoints[cam][frame], keypoint_ids[cam][frame],

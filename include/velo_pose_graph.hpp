@@ -183,6 +183,38 @@ public:
         }
     }
 
+    // Keeps the factorisation covariance, gateEdges and loopCandidates (k_sigma > 0) build for this `fixed` set (velo_graph_retain), so that
+    // they stop building it per call; setPose of a NEW frame above every retained free one and addEdge leave it behind, and the next query
+    // extends it from the first row they touch.  perm: the order of the free nodes' indices to factor in, or empty (frame order, unless
+    // that costs more than VELO_GRAPH_RETAIN_REBUILD_RATIO times velo_graph_order's).  optimize drops it: retain again after a solve.
+    int retain(const std::vector<int>& fixed, const std::vector<int>& perm = std::vector<int>(), int max_work = 0) {
+        std::vector<int32_t> f(fixed.begin(), fixed.end()), p(perm.begin(), perm.end());
+        velo_graph_params own;
+        const int ps = velo_default_graph_params(&own);
+        if (ps != VELO_OK) return ps;
+        own.reserved[1] = max_work;
+        return velo_graph_retain(ctx_, f.empty() ? 0 : &f[0], (int32_t)f.size(), &own, p.empty() ? 0 : &p[0], (int32_t)p.size());
+    }
+    int release() { return velo_graph_release(ctx_); }
+    struct Retained {
+        int state;                                         // 0 none, 1 current, 2 behind
+        long long free_nodes, widest_row, blocks, work, builds, extensions, rebuilds, selected_inverses, columns, served, first_dirty_row, rows_refactored;
+        std::vector<int> perm;                             // the retained order: free indices by position
+    };
+    int retained(Retained* out) const {
+        int64_t v[16];
+        int st = velo_graph_retained(ctx_, v, 0, 0);
+        if (st != VELO_OK) return st;
+        std::vector<int32_t> p((size_t)v[1] + 1);
+        st = velo_graph_retained(ctx_, v, &p[0], (int32_t)v[1]);
+        if (st != VELO_OK) return st;
+        out->state = (int)v[0]; out->free_nodes = v[1]; out->widest_row = v[2]; out->blocks = v[3]; out->work = v[4]; out->builds = v[5];
+        out->extensions = v[6]; out->rebuilds = v[7]; out->selected_inverses = v[8]; out->columns = v[9]; out->served = v[10];
+        out->first_dirty_row = v[11]; out->rows_refactored = v[12];
+        out->perm.assign(p.begin(), p.begin() + (size_t)v[1]);
+        return VELO_OK;
+    }
+
     int info(Info* out) const {
         int32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         const int st = velo_graph_info(ctx_, v);

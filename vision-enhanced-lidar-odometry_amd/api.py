@@ -386,7 +386,12 @@ SIGNATURES = {
     "velo_graph_get_poses": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p]),
     "velo_graph_info": (C.c_int, [_ctx, C.c_void_p]),
     "velo_graph_order": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "velo_graph_order_extend": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "velo_graph_system": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _dp, C.c_void_p, C.c_void_p]),
+    "velo_graph_retain": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(VeloGraphParams), C.c_void_p, C.c_int32]),
+    "velo_graph_release": (C.c_int, [_ctx]),
+    "velo_graph_retained": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32]),
     "velo_graph_covariance": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(VeloGraphParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "velo_graph_edge_gate": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _P(VeloGraphParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1077,6 +1082,35 @@ class Context:
             if found.value <= cap:
                 return frames[:found.value], dist[:found.value], sigma[:found.value]
             cap = found.value
+
+    def graph_retain(self, fixed=(0,), max_work=None, perm=None):
+        """velo_graph_retain: keeps the factorisation graph_covariance, graph_edge_gate and graph_loop_candidates (k_sigma > 0) build for
+        this `fixed` set, so that they stop building it per call; appended frames and edges extend it from the first row they touch.
+        perm: the order of the free nodes' indices to factor in (with api.graph_order's the answers are an un-retained call's to the
+        bit); None: frame order unless that costs more than twice the fresh order.  Retain again after graph_optimize."""
+        fx = np.ascontiguousarray(np.asarray(fixed, dtype=np.int32).reshape(-1))
+        pm = None if perm is None else np.ascontiguousarray(np.asarray(perm, dtype=np.int32).reshape(-1))
+        params = None if max_work is None else self._graph_params(None, None, "cg", max_work)
+        one = np.zeros(1, dtype=np.int32)                              # (an empty order is still an order: not NULL)
+        self._check(self._lib.velo_graph_retain(self._h, C.c_void_p(fx.ctypes.data) if len(fx) else None, len(fx), params,
+                                                None if pm is None else C.c_void_p((pm if len(pm) else one).ctypes.data), 0 if pm is None else len(pm)))
+
+    def graph_release(self):
+        """velo_graph_release: forgets the retained factorisation (none is fine)"""
+        self._check(self._lib.velo_graph_release(self._h))
+
+    def graph_retained(self) -> dict:
+        """velo_graph_retained: the retained factorisation's state ("none", "current", "behind" as state 0, 1, 2), its size, the counters
+        that show what work was skipped, and its order `perm` (free indices by position)."""
+        info = np.zeros(16, dtype=np.int64)
+        self._check(self._lib.velo_graph_retained(self._h, C.c_void_p(info.ctypes.data), None, 0))
+        perm = np.zeros(max(int(info[1]), 1), dtype=np.int32)
+        self._check(self._lib.velo_graph_retained(self._h, C.c_void_p(info.ctypes.data), C.c_void_p(perm.ctypes.data), int(info[1])))
+        keys = ("state", "n_free", "widest_row", "blocks", "work", "builds", "extensions", "rebuilds", "selected_inverses", "columns", "served",
+                "first_dirty_row", "rows_refactored")
+        out = {k: int(info[i]) for i, k in enumerate(keys)}
+        out["perm"] = perm[:int(info[1])]
+        return out
 
     # -- resident keypoint frames and the visual matches assembled from them (velo.h:562-590, velo.h:627-654) ---------------
     def frames_reset(self, cam_trans, arena_capacity: int = 0):
@@ -2068,3 +2102,26 @@ def graph_order(n_nodes: int, a, b):
         msg = lib.velo_last_error()
         raise VeloError(f"velo status {st}: {msg.decode() if msg else ''}")
     return perm[:n], first[:n], dict(widest_row=int(stats[0]), envelope_blocks=int(stats[1]), work=int(stats[2]), components=int(stats[3]))
+
+
+def graph_order_extend(n_old: int, perm_old, n_nodes: int, a, b, first_new_edge: int, max_work: int = 1 << 24):
+    """velo_graph_order_extend: the order of a graph that has grown since the order perm_old of its first n_old nodes was kept (a host
+    function: no context, no GPU).  a, b: all edges, new from first_new_edge on.  Returns (perm, first, stats: dict(widest_row,
+    envelope_blocks, work, components, first_dirty_row, rebuilt, reversed, fresh_work))."""
+    lib = load_library()
+    po = np.ascontiguousarray(np.asarray(perm_old, dtype=np.int32).reshape(-1))
+    ea = np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))
+    eb = np.ascontiguousarray(np.asarray(b, dtype=np.int32).reshape(-1))
+    if len(ea) != len(eb):
+        raise ValueError("graph_order_extend: one a and one b per edge")
+    if len(po) != int(n_old):
+        raise ValueError("graph_order_extend: perm_old has n_old entries")
+    n = max(int(n_nodes), 0)
+    perm, first, stats = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32), np.zeros(8, dtype=np.int64)
+    vp = lambda v: C.c_void_p(v.ctypes.data) if v.size else None   # noqa: E731
+    st = lib.velo_graph_order_extend(int(n_old), vp(po), int(n_nodes), len(ea), vp(ea), vp(eb), int(first_new_edge), int(max_work), vp(perm), vp(first), vp(stats))
+    if st != 0:
+        msg = lib.velo_last_error()
+        raise VeloError(f"velo status {st}: {msg.decode() if msg else ''}")
+    keys = ("widest_row", "envelope_blocks", "work", "components", "first_dirty_row", "rebuilt", "reversed", "fresh_work")
+    return perm[:n], first[:n], {k: int(stats[i]) for i, k in enumerate(keys)}

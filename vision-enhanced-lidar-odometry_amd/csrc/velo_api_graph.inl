@@ -6,7 +6,30 @@
 // The HOST keeps the ints of the edges -- enough to refuse a call and to build the incidence lists -- and a pinned mirror of the poses:
 // a pose arrives from the host (velo_graph_set_pose) and leaves to it (velo_graph_get_poses), so the mirror is the one copy both
 // directions share, and a solve starts by sending it.  The LM decision is taken here, from one GraphRecord per iteration.
+// velo_graph_retain: the factorisation of velo_graph_covariance's problem, kept between calls.  It owns every buffer a query on it reads
+// -- the order's ints, the skyline of L, the Jacobi scales, the poses it was linearised at, the skyline of Z, the full columns -- so a
+// call that does not use it cannot disturb it; the work buffers of a build or an extension (graph_begin's) are the store's.
+struct GraphRetained {
+    int state = 0;                                       // 0 none, 1 current, 2 behind (the store has been appended to since)
+    std::vector<int32_t> fixed, free_nodes;
+    std::vector<int32_t> ints;                           // of the generation: perm [n], pos [n], first [n], rowptr [n + 1], last [n]
+    int64_t max_work = 0, stats[4] = {0, 0, 0, 0};       // the cap it was retained under; widest row, blocks, work, components
+    size_t edges_seen = 0, frames = 0;                   // the store's edges the generation covers; the node table's rows in x
+    // The device rows < valid_rows hold the generation's L (less than n after an extension failed).  INVARIANT: a state that is behind is never
+    // served.  After a failed extension idx, scale and x on the device hold the ATTEMPTED generation while ints and free_nodes here hold the
+    // old one; that is safe only because every extension uploads all three again before anything reads them.
+    int valid_rows = 0;
+    bool z_valid = false;                                // zenv holds the generation's selected inverse
+    int col_pos = -1;                                    // the position whose full column slot 0 of `col` holds; -1: none
+    int64_t counters[6] = {0, 0, 0, 0, 0, 0};            // full builds, extensions, rebuilds, selected inverses, full columns, queries served
+    int64_t last_p = 0, last_rows = 0;                   // of the last extension: its first dirty row, the rows it refactored
+    DevBuf<int> idx;
+    DevBuf<double> env, zenv, scale, x, col;
+    PinBuf<> h_idx;
+};
+
 struct GraphStore {
+    GraphRetained ret;
     // device: the edges
     DevBuf<int> from, to;
     DevBuf<double> z, info;
@@ -70,6 +93,25 @@ struct GraphCall {
     const char* who = "velo_graph_optimize";             // the entry a refusal names
     std::vector<int32_t> env_ints;                       // of an envelope call: perm [n], pos [n], first [n], rowptr [n + 1], last [n]
 };
+
+// What moves a retained factorisation on (include/velo_hip.h, velo_graph_retain): an append leaves it behind, everything else drops it.
+// The buffers and the counters stay with the store.
+void graph_ret_drop(GraphStore& S) { S.ret.state = 0; S.ret.z_valid = false; S.ret.col_pos = -1; S.ret.valid_rows = 0; }
+void graph_ret_behind(GraphStore& S) { if (S.ret.state == 1) S.ret.state = 2; }
+
+// an order's ints as the kernels take them: perm [n], pos [n], first [n], rowptr [n + 1], last [n]
+void graph_env_ints(size_t n, const int32_t* perm, const int32_t* first, std::vector<int32_t>* out) {
+    out->resize(5 * n + 1);
+    int32_t* pos = out->data() + n;
+    int32_t* rowptr = out->data() + 3 * n;
+    int32_t* last = out->data() + 4 * n + 1;
+    std::memcpy(out->data(), perm, sizeof(int32_t) * n);
+    std::memcpy(out->data() + 2 * n, first, sizeof(int32_t) * n);
+    rowptr[0] = 0;
+    for (size_t k = 0; k < n; k++) { pos[(size_t)perm[k]] = (int32_t)k; rowptr[k + 1] = rowptr[k] + ((int32_t)k - first[k] + 1); last[k] = (int32_t)k; }
+    for (size_t k = 0; k < n; k++) last[(size_t)first[k]] = std::max(last[(size_t)first[k]], (int32_t)k);
+    for (size_t k = 1; k < n; k++) last[k] = std::max(last[k], last[k - 1]);      // the last row whose first column is <= k
+}
 
 // velo_graph_order's rule (include/velo_hip.h), on checked arguments
 void graph_order(int32_t n, int32_t m, const int32_t* ea, const int32_t* eb, int32_t* perm, int32_t* first, int64_t* stats) {
@@ -156,6 +198,67 @@ void graph_order(int32_t n, int32_t m, const int32_t* ea, const int32_t* eb, int
     stats[0] = widest; stats[1] = blocks; stats[2] = work; stats[3] = components;
 }
 
+// first[k] = the smallest position among k and the neighbours of perm[k], by definition, over the edges [0, m); widest row, blocks, work
+void graph_first_of(int32_t n, int32_t m, const int32_t* ea, const int32_t* eb, const int32_t* perm, int32_t* first, int64_t* stats3) {
+    std::vector<int32_t> pos((size_t)n);
+    for (int32_t k = 0; k < n; k++) { pos[(size_t)perm[k]] = k; first[k] = k; }
+    for (int32_t e = 0; e < m; e++) {
+        const int32_t pa = pos[(size_t)ea[e]], pb = pos[(size_t)eb[e]];
+        first[std::max(pa, pb)] = std::min(first[std::max(pa, pb)], std::min(pa, pb));
+    }
+    int64_t widest = 0, blocks = 0, work = 0;
+    for (int32_t k = 0; k < n; k++) {
+        const int64_t w = (int64_t)k - first[k];
+        widest = std::max(widest, w); blocks += w + 1; work += w * (w + 1) / 2;
+    }
+    stats3[0] = widest; stats3[1] = blocks; stats3[2] = work;
+}
+
+// velo_graph_order_extend's rule (include/velo_hip.h), on checked arguments (perm_old a permutation, the old edges among the old nodes).
+// False when a row before the first dirty one does not keep its `first`: cannot happen, and is checked.
+bool graph_order_extend(int32_t n_old, const int32_t* perm_old, int32_t n, int32_t m, const int32_t* ea, const int32_t* eb, int32_t first_new,
+                        int64_t max_work, int32_t* perm, int32_t* first, int64_t* stats) {
+    const size_t N = (size_t)n;
+    // the fresh order, oriented
+    std::vector<int32_t> fperm(N), ffirst(N);
+    int64_t fs[4] = {0, 0, 0, 0};
+    graph_order(n, m, ea, eb, fperm.data(), ffirst.data(), fs);
+    bool reversed = false;
+    if (n > 0) {
+        int32_t at = 0;
+        for (int32_t k = 0; k < n; k++) if (fperm[(size_t)k] == n - 1) at = k;
+        if (2 * (int64_t)at < n && 2 * (int64_t)(n - 1 - at) >= n) {
+            std::vector<int32_t> rperm(fperm.rbegin(), fperm.rend()), rfirst(N);
+            int64_t rs[3];
+            graph_first_of(n, m, ea, eb, rperm.data(), rfirst.data(), rs);
+            if (rs[2] <= (int64_t)VELO_GRAPH_RETAIN_REBUILD_RATIO * fs[2]) {
+                reversed = true;
+                fperm.swap(rperm); ffirst.swap(rfirst);
+                fs[0] = rs[0]; fs[1] = rs[1]; fs[2] = rs[2];
+            }
+        }
+    }
+    // the extended order and its first dirty row
+    std::vector<int32_t> pos(N), old_first((size_t)n_old);
+    for (int32_t k = 0; k < n; k++) { perm[k] = k < n_old ? perm_old[k] : k; pos[(size_t)perm[k]] = k; }
+    int32_t p = n_old < n ? n_old : n;
+    for (int32_t e = first_new; e < m; e++) p = std::min(p, std::min(pos[(size_t)ea[e]], pos[(size_t)eb[e]]));
+    int64_t os[3], es[3];
+    if (n_old > 0) graph_first_of(n_old, first_new, ea, eb, perm_old, old_first.data(), os);
+    graph_first_of(n, m, ea, eb, perm, first, es);
+    for (int32_t k = 0; k < std::min(p, n_old); k++) if (first[k] != old_first[(size_t)k]) return false;
+    const bool keep = es[2] <= max_work && es[2] <= (int64_t)VELO_GRAPH_RETAIN_REBUILD_RATIO * fs[2];
+    if (keep) { stats[0] = es[0]; stats[1] = es[1]; stats[2] = es[2]; }
+    else {
+        std::memcpy(perm, fperm.data(), sizeof(int32_t) * N);
+        std::memcpy(first, ffirst.data(), sizeof(int32_t) * N);
+        stats[0] = fs[0]; stats[1] = fs[1]; stats[2] = fs[2];
+        p = 0;
+    }
+    stats[3] = fs[3]; stats[4] = p; stats[5] = keep ? 0 : 1; stats[6] = !keep && reversed ? 1 : 0; stats[7] = fs[2];
+    return true;
+}
+
 int graph_check(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, const char* who) {
     if (!c) return fail(VELO_ERR_INVALID, "null ctx");
     if (n_fixed < 1) return fail(VELO_ERR_INVALID, "%s: %d fixed nodes; at least 1 fixes the gauge", who, n_fixed);
@@ -235,16 +338,7 @@ int graph_begin(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
             return fail(VELO_ERR_INVALID, "%s: the envelope solver's work is %lld block products, over the cap of %lld (widest row %lld blocks, %lld free nodes); "
                         "raise reserved[1] or use the CG solver", call->who, (long long)call->env_stats[2], (long long)call->max_work, (long long)call->env_stats[0], (long long)n);
         if (call->env_stats[1] > (int64_t)1 << 30) return fail(VELO_ERR_INVALID, "%s: an envelope of %lld blocks; at most 2^30", call->who, (long long)call->env_stats[1]);
-        env_ints.resize(5 * n + 1);
-        int32_t* pos = env_ints.data() + n;
-        int32_t* rowptr = env_ints.data() + 3 * n;
-        int32_t* last = env_ints.data() + 4 * n + 1;
-        std::memcpy(env_ints.data(), perm.data(), sizeof(int32_t) * n);
-        std::memcpy(env_ints.data() + 2 * n, first.data(), sizeof(int32_t) * n);
-        rowptr[0] = 0;
-        for (size_t k = 0; k < n; k++) { pos[(size_t)perm[k]] = (int32_t)k; rowptr[k + 1] = rowptr[k] + ((int32_t)k - first[k] + 1); last[k] = (int32_t)k; }
-        for (size_t k = 0; k < n; k++) last[(size_t)first[k]] = std::max(last[(size_t)first[k]], (int32_t)k);
-        for (size_t k = 1; k < n; k++) last[k] = std::max(last[k], last[k - 1]);      // the last row whose first column is <= k
+        graph_env_ints(n, perm.data(), first.data(), &env_ints);
     }
     const int nb = std::max(1, cdiv((int)n, kGrThreads));
     call->n_free = (int)n; call->E = (int)E;
@@ -336,7 +430,12 @@ int graph_put_poses(velo_ctx* c, int32_t first, int32_t n, const double* poses, 
     GraphStore& S = *c->graph;
     HIP_TRY(hipSetDevice(c->device));
     const size_t last = (size_t)first + (size_t)n;
-    if (last > S.frame_cap) {                                          // the table grows geometrically: a new pinned mirror, filled from the old one
+    for (size_t f = (size_t)first; f < last && S.ret.state != 0; f++) {   // a retained factorisation: a frame that has a pose moves, or a new one
+        const bool posed = f < S.pose_set.size() && S.pose_set[f];     // below a retained free frame shifts the free indices: dropped
+        if (posed || (!S.ret.free_nodes.empty() && (int64_t)f < S.ret.free_nodes.back())) graph_ret_drop(S);
+        else graph_ret_behind(S);
+    }
+    if (last > S.frame_cap) {                                         // the table grows geometrically: a new pinned mirror, filled from the old one
         const size_t cap = std::max<size_t>({last, 2 * S.frame_cap, 256});
         PinBuf<double> nh;
         VELO_TRY(nh.reserve(sizeof(double) * cap * 6));
@@ -389,6 +488,8 @@ int graph_append(velo_ctx* c, int32_t n, const int32_t* from, const int32_t* to,
     GraphStore& S = *c->graph;
     if (S.n_edges + (size_t)n > (size_t)(1 << 30)) return fail(VELO_ERR_INVALID, "more than 2^30 edges");
     HIP_TRY(hipSetDevice(c->device));
+    if (L && !S.weighted) graph_ret_drop(S);                           // the promotion restates every edge
+    else graph_ret_behind(S);
     if (L && !S.weighted) {
         VELO_TRY(S.winfo.reserve(S.edge_cap * 21));
         VELO_TRY(S.wloss.reserve(S.edge_cap));
@@ -486,6 +587,184 @@ int graph_column_cap(velo_ctx* c, const char* who, const char* what, size_t n_co
     HIP_TRY(hipStreamSynchronize(c->stream));                          // (graph_begin's copies out of the staging are done before the next call fills it)
     return fail(VELO_ERR_INVALID, "%s: %zu %s need %zu doubles of work vectors (%zu free nodes x 36 each), over the cap of %lld; ask in smaller batches",
                 who, n_cols, what, n_cols * n * 36, n, (long long)VELO_GRAPH_MAX_COLUMN_DOUBLES);
+}
+
+// ---- the retained factorisation (velo_graph_retain) ----------------------------------------------------------------------------------------
+// the edges between two free nodes in free indices, in the store's order, and how many of them lie among the store's first `seen` edges
+void graph_free_edges(const GraphStore& S, const std::vector<int32_t>& free_nodes, size_t seen, std::vector<int32_t>* ea, std::vector<int32_t>* eb, size_t* n_seen,
+                      std::vector<int32_t>* slot_out) {
+    std::vector<int32_t>& slot = *slot_out;
+    slot.assign(S.frame_cap, -1);
+    for (size_t i = 0; i < free_nodes.size(); i++) slot[(size_t)free_nodes[i]] = (int32_t)i;
+    ea->clear(); eb->clear();
+    *n_seen = 0;
+    for (size_t e = 0; e < S.n_edges; e++) {
+        const int32_t sf = slot[(size_t)S.h_from[e]], st = slot[(size_t)S.h_to[e]];
+        if (sf >= 0 && st >= 0) { ea->push_back(sf); eb->push_back(st); if (e < seen) ++*n_seen; }
+    }
+}
+
+// the kernels' arguments over the retained buffers: what the selected inverse, the columns and the pairs' kernels read
+GraphArgs graph_ret_args(const GraphRetained& R) {
+    GraphArgs A;
+    std::memset(&A, 0, sizeof(A));
+    const size_t n = R.free_nodes.size();
+    A.x = R.x.p; A.x_stride = R.frames * 6;
+    A.scale = R.scale.p; A.n_free = (int)n;
+    A.env_perm = R.idx.p; A.env_pos = R.idx.p + n; A.env_first = R.idx.p + 2 * n; A.env_rowptr = R.idx.p + 3 * n; A.env_last = R.idx.p + 4 * n + 1;
+    A.env = R.env.p;
+    return A;
+}
+
+// Builds (p_rule < 0: every row, in the order `ints`) or extends (rows >= p) the retained factor from the system graph_begin has just formed
+// in the store's work buffers.  *bad: a pivot was not positive and finite; the rows >= p are then not valid.  Nothing of R's host state moves.
+int graph_ret_factor(velo_ctx* c, GraphRetained& R, const GraphCall& call, const std::vector<int32_t>& ints, int64_t blocks, int p, size_t keep_blocks, bool* bad, GraphArgs* out) {
+    GraphStore& S = *c->graph;
+    const size_t n = (size_t)call.n_free, F = S.frame_cap;
+    VELO_TRY(R.idx.reserve(ints.size() + 1));
+    VELO_TRY(R.scale.reserve(n * 6 + 1));
+    VELO_TRY(R.x.reserve(F * 6 + 1));
+    if ((size_t)blocks * 36 + 1 > R.env.cap) {                         // (DevBuf::reserve frees on growth: the rows that keep their factor are carried over)
+        if (keep_blocks) VELO_TRY(lm_regrow(c, &R.env, keep_blocks * 36, (size_t)blocks * 36 + 1, 0));
+        else VELO_TRY(R.env.reserve((size_t)blocks * 36 + 1));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));                          // (the last copy out of h_idx is done)
+    VELO_TRY(R.h_idx.reserve(sizeof(int32_t) * (ints.size() + 1)));
+    std::memcpy(R.h_idx.p, ints.data(), sizeof(int32_t) * ints.size());
+    HIP_TRY(hipMemcpyAsync(R.idx.p, R.h_idx.p, sizeof(int32_t) * ints.size(), hipMemcpyHostToDevice, c->stream));
+    if (n) HIP_TRY(hipMemcpyAsync(R.scale.p, call.A.scale, sizeof(double) * n * 6, hipMemcpyDeviceToDevice, c->stream));
+    if (F) HIP_TRY(hipMemcpyAsync(R.x.p, call.A.x, sizeof(double) * F * 6, hipMemcpyDeviceToDevice, c->stream));
+    GraphArgs A = call.A;                                              // the system (blk, nd, inc) is the store's, the skyline and its ints are R's
+    A.scale = R.scale.p;
+    A.env_perm = R.idx.p; A.env_pos = R.idx.p + n; A.env_first = R.idx.p + 2 * n; A.env_rowptr = R.idx.p + 3 * n; A.env_last = R.idx.p + 4 * n + 1;
+    A.env = R.env.p;
+    *out = A;
+    *bad = false;
+    if (n == 0 || p >= (int)n) return VELO_OK;
+    if (p <= 0) VELO_TRY(graph_cov_factor(c, A, (int)n));
+    else {
+        int k0 = p;
+        for (size_t i = (size_t)p; i < n; i++) k0 = std::min(k0, ints[2 * n + i]);
+        HIP_TRY(hipMemsetAsync(A.rec, 0, sizeof(GraphRecord), c->stream));
+        hipLaunchKernelGGL(graph_env_fill_undamped_rows_kernel, dim3((unsigned)(n - (size_t)p)), dim3(64), 0, c->stream, A, p);
+        hipLaunchKernelGGL(graph_env_factor_rows_kernel, dim3(1), dim3(kGrEnvFactorThreads), 0, c->stream, A, p, k0);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(S.h_out.p, A.rec, sizeof(GraphRecord), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *bad = ((const GraphRecord*)S.h_out.p)->bad != 0;
+    return VELO_OK;
+}
+
+void graph_ret_commit(GraphStore& S, GraphRetained& R, const GraphCall& call, std::vector<int32_t>& ints, const int64_t* stats) {
+    R.free_nodes = call.free_nodes;
+    R.ints.swap(ints);
+    for (int k = 0; k < 4; k++) R.stats[k] = stats[k];
+    R.edges_seen = S.n_edges; R.frames = S.frame_cap;
+    R.valid_rows = call.n_free;
+    R.z_valid = false; R.col_pos = -1;
+    R.state = 1;
+}
+
+// a state that is behind: the order of velo_graph_order_extend, the system again, the rows from the first dirty one on.  *ok false: the
+// extension failed (the cap, a pivot) and the state stays behind at its last generation; the caller answers by the un-retained path.
+int graph_ret_extend(velo_ctx* c, bool* ok) {
+    GraphStore& S = *c->graph;
+    GraphRetained& R = S.ret;
+    *ok = false;
+    GraphCall call;
+    call.who = "velo_graph_retain";
+    VELO_TRY(graph_begin(c, R.fixed.data(), (int32_t)R.fixed.size(), graph_params(nullptr), &call));
+    const size_t n_old = R.free_nodes.size(), n = (size_t)call.n_free;
+    if (n < n_old || !std::equal(R.free_nodes.begin(), R.free_nodes.end(), call.free_nodes.begin())) {      // (the hooks keep this from happening)
+        graph_ret_drop(S);
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return VELO_OK;
+    }
+    std::vector<int32_t> ea, eb, slot, perm(n), first(n), ints;
+    size_t m_old = 0;
+    graph_free_edges(S, call.free_nodes, R.edges_seen, &ea, &eb, &m_old, &slot);
+    int64_t st[8];
+    if (!graph_order_extend((int32_t)n_old, R.ints.data(), (int32_t)n, (int32_t)ea.size(), ea.data(), eb.data(), (int32_t)m_old, R.max_work, perm.data(), first.data(), st)) {
+        graph_ret_drop(S);
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return VELO_OK;
+    }
+    if (st[2] > R.max_work || st[1] > (int64_t)1 << 30) { HIP_TRY(hipStreamSynchronize(c->stream)); return VELO_OK; }
+    graph_env_ints(n, perm.data(), first.data(), &ints);
+    int p = (int)st[4];
+    for (size_t e = R.edges_seen; e < S.n_edges; e++) {                // a new edge to a constant changes its free end's diagonal block
+        const int32_t sf = slot[(size_t)S.h_from[e]], sb = slot[(size_t)S.h_to[e]];
+        if ((sf >= 0) != (sb >= 0)) p = std::min(p, ints[n + (size_t)(sf >= 0 ? sf : sb)]);
+    }
+    const bool rebuilt = st[5] != 0;
+    if (!rebuilt) p = std::min(p, R.valid_rows);
+    bool bad = false;
+    GraphArgs A;
+    VELO_TRY(graph_ret_factor(c, R, call, ints, st[1], p, !rebuilt && p > 0 ? (size_t)ints[3 * n + (size_t)p] : 0, &bad, &A));
+    if (bad) { R.valid_rows = rebuilt ? 0 : std::min(R.valid_rows, p); return VELO_OK; }
+    graph_ret_commit(S, R, call, ints, st);
+    R.counters[1]++;
+    if (rebuilt) R.counters[2]++;
+    R.last_p = p; R.last_rows = (int64_t)n - p;
+    *ok = true;
+    return VELO_OK;
+}
+
+// The retained state a query with this `fixed` set and these params is served from, extended first where it is behind; null: the query
+// runs as it does without one.  call: what the queries read of a GraphCall.
+int graph_ret_serve(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, GraphCall* call, GraphRetained** out) {
+    GraphStore& S = *c->graph;
+    GraphRetained& R = S.ret;
+    *out = nullptr;
+    if (R.state == 0 || R.fixed.size() != (size_t)n_fixed || !std::equal(R.fixed.begin(), R.fixed.end(), fixed)) return VELO_OK;
+    const int64_t cap = params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
+    if (cap < R.max_work) return VELO_OK;                              // a tighter cap than the state was retained under: the un-retained path decides
+    HIP_TRY(hipSetDevice(c->device));
+    if (R.state == 2) {
+        bool ok = false;
+        VELO_TRY(graph_ret_extend(c, &ok));
+        if (!ok) return VELO_OK;
+    }
+    call->free_nodes = R.free_nodes;
+    call->env_ints = R.ints;
+    call->n_free = (int)R.free_nodes.size(); call->E = (int)S.n_edges;
+    for (int k = 0; k < 4; k++) call->env_stats[k] = R.stats[k];
+    call->A = graph_ret_args(R);
+    *out = &R;
+    return VELO_OK;
+}
+
+// the selected inverse of the generation, once: enqueued behind a cleared record A.rec
+int graph_ret_selinv(velo_ctx* c, GraphRetained& R, const GraphArgs& A, bool* ran) {
+    *ran = false;
+    if (R.z_valid || A.n_free == 0) return VELO_OK;
+    VELO_TRY(R.zenv.reserve((size_t)R.stats[1] * 36 + 1));
+    GraphCov V;
+    V.zenv = R.zenv.p; V.work = nullptr; V.pair = nullptr; V.out = nullptr; V.n_pairs = 0;
+    hipLaunchKernelGGL(graph_env_selinv_kernel, dim3(1), dim3(kGrEnvSelinvThreads), 0, c->stream, A, V);
+    *ran = true;
+    return VELO_OK;
+}
+
+// Room for nc full columns in R.col, the kept one staying in slot 0.  cols: the positions the call needs; on return cols[0] is the kept
+// column when the call needs it (*first_new = 1: solve the slots from 1 on), otherwise the call's last one (*first_new = 0).  remap:
+// the slot of each entry of the caller's numbering.
+int graph_ret_columns(velo_ctx* c, GraphRetained& R, std::vector<int32_t>& cols, std::vector<int32_t>* remap, int* first_new) {
+    const size_t nc = cols.size(), n = R.free_nodes.size();
+    remap->resize(nc);
+    for (size_t k = 0; k < nc; k++) (*remap)[k] = (int32_t)k;
+    *first_new = 0;
+    if (nc == 0) return VELO_OK;
+    size_t at = nc - 1;
+    for (size_t k = 0; k < nc; k++) if (R.col_pos >= 0 && cols[k] == R.col_pos) { at = k; *first_new = 1; }
+    std::swap(cols[0], cols[at]);
+    (*remap)[0] = (int32_t)at; (*remap)[at] = 0;
+    if (nc * n * 36 + 1 > R.col.cap) {
+        if (*first_new) VELO_TRY(lm_regrow(c, &R.col, n * 36, nc * n * 36 + 1, 0));
+        else { R.col_pos = -1; VELO_TRY(R.col.reserve(nc * n * 36 + 1)); }
+    }
+    return VELO_OK;
 }
 
 }  // namespace
@@ -660,6 +939,115 @@ int velo_graph_order(int32_t n_nodes, int32_t n_edges, const int32_t* a, const i
     return VELO_OK;
 }
 
+int velo_graph_order_extend(int32_t n_old, const int32_t* perm_old, int32_t n_nodes, int32_t n_edges, const int32_t* a, const int32_t* b, int32_t first_new_edge,
+                            int64_t max_work, int32_t* perm, int32_t* first, int64_t* stats) {
+    const char* who = "velo_graph_order_extend";
+    if (n_old < 0 || n_nodes < n_old || n_edges < 0) return fail(VELO_ERR_INVALID, "%s: counts must satisfy 0 <= n_old <= n_nodes and 0 <= n_edges", who);
+    if (first_new_edge < 0 || first_new_edge > n_edges) return fail(VELO_ERR_INVALID, "%s: first_new_edge %d; 0..%d", who, first_new_edge, n_edges);
+    if (max_work < 0) return fail(VELO_ERR_INVALID, "%s: negative max_work", who);
+    if (!perm || !first || !stats || (n_old > 0 && !perm_old) || (n_edges > 0 && (!a || !b))) return fail(VELO_ERR_INVALID, "%s: null argument", who);
+    std::vector<unsigned char> seen((size_t)n_old, 0);
+    for (int32_t k = 0; k < n_old; k++) {
+        if (perm_old[k] < 0 || perm_old[k] >= n_old || seen[(size_t)perm_old[k]]) return fail(VELO_ERR_INVALID, "%s: perm_old is not a permutation of 0..%d (entry %d is %d)", who, n_old - 1, k, perm_old[k]);
+        seen[(size_t)perm_old[k]] = 1;
+    }
+    for (int32_t e = 0; e < n_edges; e++) {
+        if (a[e] < 0 || a[e] >= n_nodes || b[e] < 0 || b[e] >= n_nodes) return fail(VELO_ERR_INVALID, "%s: edge %d joins %d and %d; nodes 0..%d", who, e, a[e], b[e], n_nodes - 1);
+        if (a[e] == b[e]) return fail(VELO_ERR_INVALID, "%s: edge %d: a == b (%d)", who, e, a[e]);
+        if (e < first_new_edge && (a[e] >= n_old || b[e] >= n_old)) return fail(VELO_ERR_INVALID, "%s: edge %d is not new (first_new_edge %d) and ends at a new node (%d, %d; n_old %d)", who, e, first_new_edge, a[e], b[e], n_old);
+    }
+    if (!graph_order_extend(n_old, perm_old, n_nodes, n_edges, a, b, first_new_edge, max_work, perm, first, stats))
+        return fail(VELO_ERR_STATE, "%s: a row before the first dirty row does not keep its first column", who);
+    return VELO_OK;
+}
+
+int velo_graph_retain(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, const int32_t* perm, int32_t n_perm) {
+    const char* who = "velo_graph_retain";
+    VELO_TRY(graph_check(c, fixed, n_fixed, params, who));
+    if (perm && n_perm < 0) return fail(VELO_ERR_INVALID, "%s: negative n_perm", who);
+    GraphStore& S = *c->graph;
+    GraphRetained& R = S.ret;
+    const int64_t max_work = params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool same = R.state != 0 && R.max_work == max_work && R.fixed.size() == (size_t)n_fixed && std::equal(R.fixed.begin(), R.fixed.end(), fixed);
+    if (!perm && same && R.state == 1) return VELO_OK;                 // retained and current
+    if (!perm && same) {                                               // behind: extended, as the next query would
+        bool ok = false;
+        VELO_TRY(graph_ret_extend(c, &ok));
+        if (ok) return VELO_OK;
+    }
+    GraphCall call;
+    call.who = who;
+    VELO_TRY(graph_begin(c, fixed, n_fixed, graph_params(nullptr), &call));
+    const size_t n = (size_t)call.n_free;
+    // every refusal from here on leaves nothing retained; the order's arguments are checked before the state goes
+    std::vector<int32_t> ea, eb, slot, order(n), first(n), ints;
+    size_t m_seen = 0;
+    graph_free_edges(S, call.free_nodes, S.n_edges, &ea, &eb, &m_seen, &slot);
+    int64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int status = VELO_OK;
+    if (perm) {
+        std::vector<unsigned char> seen(n, 0);
+        if ((size_t)n_perm != n) status = fail(VELO_ERR_INVALID, "%s: perm has %d entries; the graph has %zu free nodes", who, n_perm, n);
+        for (size_t k = 0; k < n && status == VELO_OK; k++) {
+            if (perm[k] < 0 || (size_t)perm[k] >= n || seen[(size_t)perm[k]]) status = fail(VELO_ERR_INVALID, "%s: perm is not a permutation of the free nodes' indices 0..%zu (entry %zu is %d)", who, n - 1, k, perm[k]);
+            else seen[(size_t)perm[k]] = 1;
+        }
+        if (status == VELO_OK) {
+            std::memcpy(order.data(), perm, sizeof(int32_t) * n);
+            graph_first_of((int32_t)n, (int32_t)ea.size(), ea.data(), eb.data(), order.data(), first.data(), st);
+        }
+    } else if (!graph_order_extend(0, nullptr, (int32_t)n, (int32_t)ea.size(), ea.data(), eb.data(), 0, max_work, order.data(), first.data(), st))
+        status = fail(VELO_ERR_STATE, "%s: the order's rule failed", who);
+    if (status == VELO_OK && st[2] > max_work)
+        status = fail(VELO_ERR_INVALID, "%s: the envelope solver's work is %lld block products, over the cap of %lld (widest row %lld blocks, %lld free nodes); raise reserved[1]",
+                      who, (long long)st[2], (long long)max_work, (long long)st[0], (long long)n);
+    if (status == VELO_OK && st[1] > (int64_t)1 << 30) status = fail(VELO_ERR_INVALID, "%s: an envelope of %lld blocks; at most 2^30", who, (long long)st[1]);
+    if (status != VELO_OK) { (void)hipStreamSynchronize(c->stream); return status; }      // (refused on the host: a state retained before stays)
+    graph_ret_drop(S);                                                 // the buffers are written from here on
+    graph_env_ints(n, order.data(), first.data(), &ints);
+    bool bad = false;
+    GraphArgs A;
+    VELO_TRY(graph_ret_factor(c, R, call, ints, st[1], -1, 0, &bad, &A));
+    if (bad) {
+        call.env_ints = ints;
+        return graph_cov_refuse(c, call, A, who);
+    }
+    R.fixed.assign(fixed, fixed + n_fixed);
+    R.max_work = max_work;
+    graph_ret_commit(S, R, call, ints, st);
+    R.counters[0]++;
+    R.last_p = 0; R.last_rows = 0;
+    return VELO_OK;
+}
+
+int velo_graph_release(velo_ctx* c) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (!c->graph) return VELO_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));           // nothing of the state is in flight when its buffers go
+    c->graph->ret = GraphRetained();
+    return VELO_OK;
+}
+
+int velo_graph_retained(velo_ctx* c, int64_t info[16], int32_t* perm_out, int32_t capacity) {
+    if (!c) return fail(VELO_ERR_INVALID, "null ctx");
+    if (!info) return fail(VELO_ERR_INVALID, "velo_graph_retained: null info");
+    if (capacity < 0 || (capacity > 0 && !perm_out)) return fail(VELO_ERR_INVALID, "velo_graph_retained: a negative capacity, or a null perm_out with a positive one");
+    for (int k = 0; k < 16; k++) info[k] = 0;
+    if (!c->graph) return VELO_OK;
+    const GraphRetained& R = c->graph->ret;
+    info[0] = R.state;
+    if (R.state != 0) {
+        info[1] = (int64_t)R.free_nodes.size(); info[2] = R.stats[0]; info[3] = R.stats[1]; info[4] = R.stats[2];
+        const size_t m = std::min((size_t)capacity, R.free_nodes.size());
+        if (m) std::memcpy(perm_out, R.ints.data(), sizeof(int32_t) * m);
+    }
+    for (int k = 0; k < 6; k++) info[5 + k] = R.counters[k];
+    info[11] = R.last_p; info[12] = R.last_rows;
+    return VELO_OK;
+}
+
 int velo_graph_system(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, double* cost, double* gradient, double* diag_blocks) {
     VELO_TRY(graph_check(c, fixed, n_fixed, nullptr, "velo_graph_system"));
     GraphStore& S = *c->graph;
@@ -695,7 +1083,9 @@ int velo_graph_covariance(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, co
     call.envelope = true;
     call.who = who;
     call.max_work = params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
-    VELO_TRY(graph_begin(c, fixed, n_fixed, graph_params(nullptr), &call));
+    GraphRetained* kept = nullptr;                                     // a retained factorisation of this problem: no order, no fill, no factor
+    VELO_TRY(graph_ret_serve(c, fixed, n_fixed, params, &call, &kept));
+    if (!kept) VELO_TRY(graph_begin(c, fixed, n_fixed, graph_params(nullptr), &call));
     const size_t n = (size_t)call.n_free, np = (size_t)n_pairs;
     // per pair: the free indices of its ends (-1: a constant) and, for a pair outside the envelope, the slot of its column solve
     const int32_t* pos = call.env_ints.data() + n;
@@ -717,7 +1107,7 @@ int velo_graph_covariance(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, co
     VELO_TRY(S.cov_pair.reserve(3 * np));
     VELO_TRY(S.h_out.reserve(sizeof(double) * (kRec + 36 * np) + 64));
     if (n) {
-        VELO_TRY(S.cov_z.reserve((size_t)call.env_stats[1] * 36));
+        if (!kept) VELO_TRY(S.cov_z.reserve((size_t)call.env_stats[1] * 36));
         VELO_TRY(S.cov_work.reserve(n_out * n * 36 + 1));
     }
     VELO_TRY(S.in_ev.wait_or_create());
@@ -730,16 +1120,24 @@ int velo_graph_covariance(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, co
     GraphCov V;
     V.zenv = S.cov_z.p; V.work = S.cov_work.p; V.pair = S.cov_pair.p; V.out = S.cov_out.p + kRec; V.n_pairs = n_pairs;
     HIP_TRY(hipMemsetAsync(A.rec, 0, sizeof(GraphRecord), c->stream));
+    bool ran_selinv = false;
+    if (kept) {
+        VELO_TRY(graph_ret_selinv(c, *kept, A, &ran_selinv));
+        V.zenv = kept->zenv.p;
+    }
     if (n) {
-        VELO_TRY(graph_cov_factor(c, A, (int)n));
-        hipLaunchKernelGGL(graph_env_selinv_kernel, dim3(1), dim3(kGrEnvSelinvThreads), 0, c->stream, A, V);
+        if (!kept) {
+            VELO_TRY(graph_cov_factor(c, A, (int)n));
+            hipLaunchKernelGGL(graph_env_selinv_kernel, dim3(1), dim3(kGrEnvSelinvThreads), 0, c->stream, A, V);
+        }
         if (n_out) hipLaunchKernelGGL(graph_env_column_kernel, dim3((unsigned)n_out), dim3(kGrEnvColumnThreads), 0, c->stream, A, V);
     }
     hipLaunchKernelGGL(graph_cov_gather_kernel, dim3((unsigned)np), dim3(64), 0, c->stream, A, V);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(S.h_out.p, S.cov_out.p, sizeof(double) * (kRec + 36 * np), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (((const GraphRecord*)S.h_out.p)->bad != 0) return graph_cov_refuse(c, call, A, who);
+    if (kept) { kept->z_valid = kept->z_valid || ran_selinv; kept->counters[3] += ran_selinv; kept->counters[5]++; }
+    else if (((const GraphRecord*)S.h_out.p)->bad != 0) return graph_cov_refuse(c, call, A, who);
     std::memcpy(cov36, S.h_out.p + sizeof(GraphRecord), sizeof(double) * 36 * np);
     return VELO_OK;
 }
@@ -773,7 +1171,9 @@ int velo_graph_edge_gate(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, con
     call.envelope = true;
     call.who = who;
     call.max_work = params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
-    VELO_TRY(graph_begin(c, fixed, n_fixed, graph_params(nullptr), &call));
+    GraphRetained* kept = nullptr;                                     // as in velo_graph_covariance
+    VELO_TRY(graph_ret_serve(c, fixed, n_fixed, params, &call, &kept));
+    if (!kept) VELO_TRY(graph_begin(c, fixed, n_fixed, graph_params(nullptr), &call));
     const size_t n = (size_t)call.n_free;
     // per pair: its frames, their free indices and, for a pair outside the envelope, the slot of the full column of one end -- `to`'s; the
     // pairs that share that frame share the column
@@ -795,12 +1195,18 @@ int velo_graph_edge_gate(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, con
     }
     const size_t nc = cols.size();
     VELO_TRY(graph_column_cap(c, who, "block columns", nc, n));
+    int first_new = 0;                                                 // a retained state keeps the last full column in slot 0 and does not solve it again
+    if (kept) {
+        std::vector<int32_t> remap;
+        VELO_TRY(graph_ret_columns(c, *kept, cols, &remap, &first_new));
+        for (size_t p = 0; p < np; p++) if (pr[5 * p + 4] >= 0) pr[5 * p + 4] = remap[(size_t)pr[5 * p + 4]];
+    }
     const size_t n_ints = 5 * np + nc, n_dbl = (z ? 6 * np : 0) + 21 * (info21 ? np : 0), n_res = kGraphRecDoubles + kGrRelOut * np;
     VELO_TRY(S.cov_out.reserve(n_res));
     VELO_TRY(S.rel_i.reserve(n_ints));
     VELO_TRY(S.rel_d.reserve(n_dbl + 1));
     VELO_TRY(S.h_out.reserve(sizeof(double) * n_res + 64));
-    if (n) {
+    if (n && !kept) {
         VELO_TRY(S.cov_z.reserve((size_t)call.env_stats[1] * 36));
         VELO_TRY(S.cov_work.reserve(nc * n * 36 + 1));
     }
@@ -824,7 +1230,16 @@ int velo_graph_edge_gate(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, con
     R.z = z ? S.rel_d.p : nullptr; R.linfo = info21 ? S.rel_d.p + (z ? 6 * np : 0) : nullptr;
     R.out = S.cov_out.p + kGraphRecDoubles; R.n_pairs = n_pairs;
     HIP_TRY(hipMemsetAsync(A.rec, 0, sizeof(GraphRecord), c->stream));
-    if (n) {
+    bool ran_selinv = false;
+    if (kept) {
+        VELO_TRY(graph_ret_selinv(c, *kept, A, &ran_selinv));
+        R.zenv = kept->zenv.p; R.work = kept->col.p;
+        if (nc > (size_t)first_new) {                                  // the columns the state does not hold
+            GraphRel R2 = R;
+            R2.work += (size_t)first_new * n * 36; R2.col_pos += first_new;
+            hipLaunchKernelGGL(graph_env_column_full_kernel, dim3((unsigned)(nc - (size_t)first_new)), dim3(kGrEnvColumnThreads), 0, c->stream, A, R2);
+        }
+    } else if (n) {
         VELO_TRY(graph_cov_factor(c, A, (int)n));
         hipLaunchKernelGGL(graph_env_selinv_kernel, dim3(1), dim3(kGrEnvSelinvThreads), 0, c->stream, A, V);
         if (nc) hipLaunchKernelGGL(graph_env_column_full_kernel, dim3((unsigned)nc), dim3(kGrEnvColumnThreads), 0, c->stream, A, R);
@@ -833,7 +1248,11 @@ int velo_graph_edge_gate(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, con
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(S.h_out.p, S.cov_out.p, sizeof(double) * n_res, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (((const GraphRecord*)S.h_out.p)->bad != 0) return graph_cov_refuse(c, call, A, who);
+    if (kept) {
+        kept->z_valid = kept->z_valid || ran_selinv; kept->counters[3] += ran_selinv; kept->counters[5]++;
+        kept->counters[4] += (int64_t)nc - first_new;
+        if (nc) kept->col_pos = cols[0];
+    } else if (((const GraphRecord*)S.h_out.p)->bad != 0) return graph_cov_refuse(c, call, A, who);
     const double* res = (const double*)S.h_out.p + kGraphRecDoubles;
     for (size_t p = 0; p < np; p++) {
         const double* o = res + kGrRelOut * p;
@@ -861,12 +1280,14 @@ int velo_graph_loop_candidates(velo_ctx* c, const int32_t* fixed, int32_t n_fixe
     const bool with_sigma = k_sigma > 0.0;
     GraphCall call;
     GraphArgs A;
+    GraphRetained* kept = nullptr;
     std::memset(&A, 0, sizeof(A));
     if (with_sigma) {
         call.envelope = true;
         call.who = who;
         call.max_work = params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
-        VELO_TRY(graph_begin(c, fixed, n_fixed, graph_params(nullptr), &call));
+        VELO_TRY(graph_ret_serve(c, fixed, n_fixed, params, &call, &kept));      // as in velo_graph_covariance
+        if (!kept) VELO_TRY(graph_begin(c, fixed, n_fixed, graph_params(nullptr), &call));
         A = call.A;
     } else {                                                           // distances alone: the stored poses to buffer 0, no system
         HIP_TRY(hipSetDevice(c->device));
@@ -887,7 +1308,11 @@ int velo_graph_loop_candidates(velo_ctx* c, const int32_t* fixed, int32_t n_fixe
     VELO_TRY(S.rel_i.reserve(2 * F + 1));
     VELO_TRY(S.rel_d.reserve(2 * F + 1));
     VELO_TRY(S.h_out.reserve(sizeof(double) * n_res + 64));
-    if (n) {
+    int first_new = 0;
+    if (kept) {
+        std::vector<int32_t> cols(nc, nc ? call.env_ints[n + (size_t)iq] : 0), remap;
+        VELO_TRY(graph_ret_columns(c, *kept, cols, &remap, &first_new));
+    } else if (n) {
         VELO_TRY(S.cov_z.reserve((size_t)call.env_stats[1] * 36));
         VELO_TRY(S.cov_work.reserve(nc * n * 36 + 1));
     }
@@ -910,7 +1335,13 @@ int velo_graph_loop_candidates(velo_ctx* c, const int32_t* fixed, int32_t n_fixe
     K.n_frames = (int)F; K.query = query; K.min_gap = min_gap; K.capacity = (int)cap; K.with_sigma = with_sigma ? 1 : 0;
     K.radius = radius; K.k_sigma = k_sigma;
     HIP_TRY(hipMemsetAsync(A.rec, 0, sizeof(GraphRecord), c->stream));
-    if (n) {
+    bool ran_selinv = false;
+    if (kept) {
+        VELO_TRY(graph_ret_selinv(c, *kept, A, &ran_selinv));
+        R.zenv = kept->zenv.p; R.work = kept->col.p;
+        K.zenv = kept->zenv.p; K.work = kept->col.p;
+        if (nc > (size_t)first_new) hipLaunchKernelGGL(graph_env_column_full_kernel, dim3(1), dim3(kGrEnvColumnThreads), 0, c->stream, A, R);
+    } else if (n) {
         VELO_TRY(graph_cov_factor(c, A, (int)n));
         hipLaunchKernelGGL(graph_env_selinv_kernel, dim3(1), dim3(kGrEnvSelinvThreads), 0, c->stream, A, V);
         if (nc) hipLaunchKernelGGL(graph_env_column_full_kernel, dim3(1), dim3(kGrEnvColumnThreads), 0, c->stream, A, R);
@@ -920,7 +1351,11 @@ int velo_graph_loop_candidates(velo_ctx* c, const int32_t* fixed, int32_t n_fixe
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(S.h_out.p, S.cov_out.p, sizeof(double) * n_res, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (((const GraphRecord*)S.h_out.p)->bad != 0) return graph_cov_refuse(c, call, A, who);
+    if (kept) {
+        kept->z_valid = kept->z_valid || ran_selinv; kept->counters[3] += ran_selinv; kept->counters[5]++;
+        kept->counters[4] += (int64_t)nc - first_new;
+        if (nc) kept->col_pos = call.env_ints[n + (size_t)iq];
+    } else if (((const GraphRecord*)S.h_out.p)->bad != 0) return graph_cov_refuse(c, call, A, who);
     const double* res = (const double*)S.h_out.p + kGraphRecDoubles;
     const size_t found = (size_t)res[0];
     for (size_t k = 0; k < std::min(found, cap); k++) {
@@ -940,6 +1375,7 @@ int velo_graph_optimize(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, cons
     call.envelope = P.reserved[0] == VELO_GRAPH_SOLVER_ENVELOPE;
     call.max_work = P.reserved[1] > 0 ? P.reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
     VELO_TRY(graph_begin(c, fixed, n_fixed, P, &call));
+    graph_ret_drop(S);                                                 // a solve that runs ends a retained factorisation, whatever its outcome
     const GraphArgs& A = call.A;
     const LMParams Q = A.lm;
     const int n = call.n_free, E = call.E, nb = A.nb;

@@ -901,6 +901,107 @@ graph_env_factor_kernel(GraphArgs G)
 ;
 #endif
 
+// graph_env_factor_kernel for an APPEND to a retained factor (velo_graph_retain): the rows < row_begin of the skyline hold their final L,
+// the rows >= row_begin hold H~ fresh from the fill.  It starts at step k0 = min first(i) over i >= row_begin (the host's); for
+// k < row_begin the pivot is read back from the stored diagonal block (pinv = 1.0 / l, as graph_env_chol6 forms it) and the panel and
+// the update touch the block rows i >= row_begin alone, in all their columns j in (k, i]; from k = row_begin on it is the full step.
+// Every entry of the rows >= row_begin so receives exactly the operations of a full factorisation in the same order, in the same
+// sequence: an entry is written by one thread per step, the steps are separated by barriers, and which thread it is does not enter the
+// expression.  The row test guards work, never a barrier: every __syncthreads is reached by every thread of the workgroup (the return
+// on a bad pivot is taken by all of them: bad_s is read behind the barrier).
+// Its text repeats graph_env_factor_kernel's, which stays as it is: as two instances of one template body the full factorisation's
+// instance came out with other instructions than before, and that kernel is what every solve is measured on.
+__global__ void __launch_bounds__(kGrEnvFactorThreads)
+graph_env_factor_rows_kernel(GraphArgs G, int row_begin, int k0)
+#if VELO_DEF_GRAPH
+{
+    __shared__ double piv[36];                                         // L(k,k), lower triangle
+    __shared__ double pinv[6];                                         // 1 / its diagonal
+    __shared__ int bad_s;
+    const int t = threadIdx.x, n = G.n_free;
+    const int ea = t % 6, g = t / 6;
+    if (t == 0) { bad_s = 0; G.rec->cg_done = 1; }                     // no CG ran: the record keeps cg_iters = 0, cg_rel = 0
+    for (int k = k0; k < n; k++) {
+        const int fk = G.env_first[k];
+        if (t == 0) {
+            double* D = G.env + ((size_t)G.env_rowptr[k] + (size_t)(k - fk)) * 36;
+            if (k < row_begin) {                                       // a row that keeps its factor: L(k,k) as it was stored
+#pragma unroll
+                for (int r = 0; r < 6; r++) {
+#pragma unroll
+                    for (int c = 0; c <= r; c++) piv[r * 6 + c] = D[r * 6 + c];
+                    pinv[r] = 1.0 / D[r * 6 + r];
+                }
+            } else {
+                double M[36];
+#pragma unroll
+                for (int x = 0; x < 36; x++) M[x] = D[x];
+                double inv[6];
+                if (!graph_env_chol6(M, inv)) bad_s = 1;
+#pragma unroll
+                for (int r = 0; r < 6; r++) {
+#pragma unroll
+                    for (int c = 0; c <= r; c++) { D[r * 6 + c] = M[r * 6 + c]; piv[r * 6 + c] = M[r * 6 + c]; }
+                    pinv[r] = inv[r];
+                }
+            }
+        }
+        __syncthreads();
+        if (bad_s) {                                                   // a pivot that is not positive and finite: an invalid step
+            if (t == 0) G.rec->bad = 1;
+            return;
+        }
+        const int m = G.env_last[k] - k;                               // the rows k + 1 .. k + m can hold a block in column k
+        const int skip = row_begin > k + 1 ? row_begin - k - 1 : 0;    // of them the first `skip` keep their factor
+        for (int u = skip * 6 + t; u < m * 6; u += kGrEnvFactorThreads) {      // the panel: row r of L(i,k) = A(i,k) L(k,k)^-T
+            const int i = k + 1 + u / 6, r = u % 6, fi = G.env_first[i];
+            if (fi > k) continue;
+            double* A = G.env + ((size_t)G.env_rowptr[i] + (size_t)(k - fi)) * 36 + r * 6;
+            double x[6];
+#pragma unroll
+            for (int c = 0; c < 6; c++) {
+                double s = A[c];
+#pragma unroll
+                for (int q = 0; q < c; q++) s -= x[q] * piv[c * 6 + q];
+                x[c] = s * pinv[c];
+            }
+#pragma unroll
+            for (int c = 0; c < 6; c++) A[c] = x[c];
+        }
+        __syncthreads();
+        if (g < kGrEnvGroups) {                                        // the update: row ea of A(i,j) -= L(i,k) L(j,k)^T, i >= j > k
+            int ii = skip, jj = g;                                     // pair number p = ii (ii + 1) / 2 + jj, p = g, g + groups, ... (from row `skip` on)
+            for (;;) {
+                while (jj > ii) { jj -= ii + 1; ii++; }
+                if (ii >= m) break;
+                const int i = k + 1 + ii, j = k + 1 + jj, fi = G.env_first[i], fj = G.env_first[j];
+                if (fi <= k && fj <= k) {                              // then first(i) <= k < j: (i,j) lies inside the envelope
+                    const double* Li = G.env + ((size_t)G.env_rowptr[i] + (size_t)(k - fi)) * 36 + ea * 6;
+                    const double* Lj = G.env + ((size_t)G.env_rowptr[j] + (size_t)(k - fj)) * 36;
+                    double* A = G.env + ((size_t)G.env_rowptr[i] + (size_t)(j - fi)) * 36 + ea * 6;
+                    double li[6], lj[36], s[6];                        // every load of the pair is requested before its first store
+#pragma unroll
+                    for (int c = 0; c < 6; c++) { li[c] = Li[c]; s[c] = A[c]; }
+#pragma unroll
+                    for (int x = 0; x < 36; x++) lj[x] = Lj[x];
+#pragma unroll
+                    for (int b = 0; b < 6; b++) {
+#pragma unroll
+                        for (int c = 0; c < 6; c++) s[b] -= li[c] * lj[b * 6 + c];
+                    }
+#pragma unroll
+                    for (int b = 0; b < 6; b++) A[b] = s[b];
+                }
+                jj += kGrEnvGroups;
+            }
+        }
+        __syncthreads();
+    }
+}
+#else
+;
+#endif
+
 __global__ void __launch_bounds__(kGrEnvSolveThreads)
 graph_env_solve_kernel(GraphArgs G, int cur)
 #if VELO_DEF_GRAPH
@@ -1042,6 +1143,37 @@ graph_env_fill_undamped_kernel(GraphArgs G)
 #if VELO_DEF_GRAPH
 {
     const int i = blockIdx.x, l = threadIdx.x;
+    if (i >= G.n_free || l >= 36) return;
+    const int a = l / 6, b = l % 6;
+    const int node = G.env_perm[i], first = G.env_first[i], w = i - first;
+    double* row = G.env + (size_t)G.env_rowptr[i] * 36;
+    for (int k = 0; k < w; k++) row[(size_t)k * 36 + l] = 0.0;
+    const double* nd = G.nd + (size_t)node * kGrNode;                  // the stored state is buffer 0
+    const double ca = G.scale[(size_t)node * 6 + a], cb = G.scale[(size_t)node * 6 + b];
+    row[(size_t)w * 36 + l] = nd[upper6(a < b ? a : b, a < b ? b : a)] * ca * cb;
+    const int end = G.inc_start[node + 1];
+    for (int m = G.inc_start[node]; m < end; m++) {
+        const int j = G.inc_other[m];
+        if (j < 0) continue;                                           // the other end is a constant
+        const int pj = G.env_pos[j];
+        if (pj >= i) continue;                                         // the later end's row holds this block
+        const int code = G.inc[m];
+        const double* W = G.blk + (size_t)(code >> 1) * kGrBlk + kGrAtB;
+        const double v = (code & 1) ? W[b * 6 + a] : W[a * 6 + b];    // transposed on the `to` side
+        row[(size_t)(pj - first) * 36 + l] += (ca * v) * G.scale[(size_t)j * 6 + b];
+    }
+}
+#else
+;
+#endif
+
+// graph_env_fill_undamped_kernel for the rows row_begin .. n_free - 1 alone (workgroup w: row row_begin + w): what an append to a
+// retained factor refills; the rows before keep their L
+__global__ void __launch_bounds__(64)
+graph_env_fill_undamped_rows_kernel(GraphArgs G, int row_begin)
+#if VELO_DEF_GRAPH
+{
+    const int i = row_begin + (int)blockIdx.x, l = threadIdx.x;
     if (i >= G.n_free || l >= 36) return;
     const int a = l / 6, b = l % 6;
     const int node = G.env_perm[i], first = G.env_first[i], w = i - first;
