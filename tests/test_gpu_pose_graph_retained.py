@@ -9,6 +9,7 @@ calls and extended on append.  What is held to what:
   (d) ring70_open's closing edge (an extension: its other end is fixed), closing edges between free frames (a rebuild); the held edges
       gate as tests/test_gpu_pose_graph_gate.py records
   (e) what drops the state, (f) a new frame without an edge, (g) asking changes nothing a solve sees
+  (h) the three kinds of query in another order, with sizes that shrink and grow between them: every answer a fresh context's
 """
 import numpy as np
 import pytest
@@ -338,3 +339,46 @@ def test_g_asking_changes_nothing_a_solve_sees():
     assert out[:2] == out[2:] and asked.graph_info() == plain.graph_info()
     asked.close()
     plain.close()
+
+
+def test_h_queries_of_every_kind_in_any_order_share_the_buffers():
+    """The tests above ask covariance, gate, candidates, always in that order.  Here a retained and a never-retaining context are asked
+    gate, candidates, covariance, candidates without sigma, a gate of three columns (the column buffer grows, the kept column survives),
+    the first gate again: sizes shrink and grow between kinds, and every answer is a fresh never-retaining context's asked that alone."""
+    gk = K.final("ring70_open")
+    fx = gk["fixed"]
+    pairs, frm, to, query = K.requests(gk)
+    far_from, far_to = np.array([5, 60, 10], np.int32), np.array([query, 20, 50], np.int32)     # three distinct free `to` frames, each pair 40 and more apart
+    questions = [lambda c: c.graph_edge_gate(frm, to, None, None, fx),
+                 lambda c: c.graph_loop_candidates(query, K.CAND["min_gap"], K.CAND["radius"], K.CAND["k_sigma"], fx, capacity=512),
+                 lambda c: (c.graph_covariance(pairs, fx),),
+                 lambda c: c.graph_loop_candidates(query, K.CAND["min_gap"], K.CAND["radius"], 0.0, fx, capacity=512),
+                 lambda c: c.graph_edge_gate(far_from, far_to, None, None, fx),
+                 lambda c: c.graph_edge_gate(frm, to, None, None, fx)]
+    as_b = lambda ans: b"".join(np.asarray(x).tobytes() for x in ans)  # noqa: E731
+    want = []
+    for q in questions:
+        alone = api.Context(0)
+        load(alone, gk)
+        want.append(as_b(q(alone)))
+        alone.close()
+    kept, never = api.Context(0), api.Context(0)
+    load(kept, gk)
+    load(never, gk)
+    kept.graph_retain(fx, perm=library_perm("ring70_open", gk))       # (a): the bytes are an un-retained context's in the library's own order
+    columns = [0]
+    for k, q in enumerate(questions):
+        assert as_b(q(never)) == want[k], k
+        assert as_b(q(kept)) == want[k], k
+        columns.append(kept.graph_retained()["columns"])
+    solved = np.diff(columns).tolist()
+    info = kept.graph_retained()
+    print(f"ring70_open: full columns solved per question {solved}; {info}")
+    # the precondition, from the state's own counters: the three-column gate keeps the query's column (the candidates' before it) and solves two,
+    # the first gate asked again keeps it too and solves the other `to` frame's: columns were solved and columns were reused
+    needed = [len(set(to.tolist())), 1, 0, 0, 3, len(set(to.tolist()))]
+    reused = [n - s for n, s in zip(needed, solved)]
+    assert solved[4] == 2 and reused[4] == 1 and solved[5] >= 1 and reused[5] >= 1, (solved, needed)
+    assert info["state"] == 1 and info["served"] == 5 and info["selected_inverses"] == 1 and info["builds"] == 1 and never.graph_retained()["state"] == 0
+    kept.close()
+    never.close()

@@ -11,8 +11,9 @@ same calls on a second context that retains nothing, in the same process, interl
   the newest frame       where velo_graph_order puts it, and where velo_graph_order_extend's orientation does
   the first append       after velo_graph_retain, and again after the rebuild: the state is in velo_graph_order's (oriented) order, in which the newest
                          frame does NOT sit at the end, so the first append dirties from that frame's row on; the appends behind it from the end
-  --hash                 SHA-256 of velo_graph_optimize's summary and poses, of all marginals and of the 96-block covariance call on a context
-                         that never retains, and nothing else
+  --hash                 SHA-256 of velo_graph_optimize's summary and poses, of all marginals, of the 96-block covariance call, of one 32-pair gate
+                         and one k_sigma 3 candidates call before anything is retained; of that gate and those candidates asked twice once
+                         the state is retained, and of velo_graph_retained's info after them; and nothing else
   --parent-record FILE   the --hash --out FILE lines of the PARENT commit's library, to be stated beside this library's and compared.  The parent's
                          tree has no such tool: check the parent commit out beside this tree, build it, copy this file into its tools/ and run it
                          there with --hash --out FILE (it imports the tree it lies in; --hash uses no entry the parent lacks)
@@ -58,7 +59,8 @@ def gate_frames(query):
 
 
 def hashes(api, g):
-    """the un-retained bytes of optimize, all marginals and the 96 blocks of 32 pairs against the last frame"""
+    """the un-retained bytes of optimize, all marginals, the 96 blocks of 32 pairs against the last frame, their gate and the last frame's
+    candidates; the gate's and the candidates' again, twice, once that state is retained, and velo_graph_retained's info after them"""
     N = B.N
     ctx = load(api, g)
     s = ctx.graph_optimize(g["fixed"], linear_solver="envelope")
@@ -67,10 +69,19 @@ def hashes(api, g):
     frm, to = gate_frames(N - 1)
     blocks = np.array([q for f in frm for q in ((f, f), (f, N - 1), (N - 1, N - 1))], dtype=np.int32)
     cov96 = ctx.graph_covariance(blocks, g["fixed"])
-    ctx.close()
     sha = lambda b: hashlib.sha256(b).hexdigest()                      # noqa: E731
-    return [f"sha256 optimize (summary, poses)  {sha(C.string_at(C.addressof(s), C.sizeof(s)) + poses.tobytes())}",
-            f"sha256 covariance, {N} marginals   {sha(marg.tobytes())}", f"sha256 covariance, 96 blocks        {sha(cov96.tobytes())}"]
+    ans = lambda x: b"".join(np.asarray(v).tobytes() for v in x)       # noqa: E731
+    gate = lambda c: ans(c.graph_edge_gate(frm, to, None, None, g["fixed"]))                                                  # noqa: E731
+    cand = lambda c: ans(c.graph_loop_candidates(N - 1, 50, B.LOOP_CLOSE_THRESH, 3.0, g["fixed"], capacity=N + 64))           # noqa: E731
+    out = [f"sha256 optimize (summary, poses)  {sha(C.string_at(C.addressof(s), C.sizeof(s)) + poses.tobytes())}",
+           f"sha256 covariance, {N} marginals   {sha(marg.tobytes())}", f"sha256 covariance, 96 blocks        {sha(cov96.tobytes())}",
+           f"sha256 gate, 32 pairs, un-retained   {sha(gate(ctx))}", f"sha256 candidates, un-retained      {sha(cand(ctx))}"]
+    ctx.graph_retain(g["fixed"])                                       # the same state retained, each asked twice, and what the state counts
+    out += [f"sha256 {what}, retained, {nth}   {sha(fn(ctx))}" for nth in ("1st", "2nd") for what, fn in (("gate, 32 pairs", gate), ("candidates", cand))]
+    info = ctx.graph_retained()
+    out.append("sha256 velo_graph_retained's info    " + sha(repr(sorted((k, np.asarray(v).tolist()) for k, v in info.items())).encode()))
+    ctx.close()
+    return out
 
 
 def main():
@@ -87,8 +98,9 @@ def main():
     if a.parent_record:
         with open(a.parent_record) as f:
             parent = [line.rstrip("\n") for line in f if line.startswith("sha256 ")]
+        same = parent == lines
         lines += ["parent  " + line for line in parent]
-        lines.append("the parent commit's library, a process of its own: " + ("the SAME three digests" if parent == lines[:3] else "DIFFERENT digests"))
+        lines.append("the parent commit's library, a process of its own: " + (f"the SAME {len(parent)} digests" if same else "DIFFERENT digests"))
     if not a.hash:
         kept, plain = load(api, g), load(api, g)
         for ctx in (kept, plain):

@@ -15,10 +15,7 @@ struct GraphRetained {
     std::vector<int32_t> ints;                           // of the generation: perm [n], pos [n], first [n], rowptr [n + 1], last [n]
     int64_t max_work = 0, stats[4] = {0, 0, 0, 0};       // the cap it was retained under; widest row, blocks, work, components
     size_t edges_seen = 0, frames = 0;                   // the store's edges the generation covers; the node table's rows in x
-    // The device rows < valid_rows hold the generation's L (less than n after an extension failed).  INVARIANT: a state that is behind is never
-    // served.  After a failed extension idx, scale and x on the device hold the ATTEMPTED generation while ints and free_nodes here hold the
-    // old one; that is safe only because every extension uploads all three again before anything reads them.
-    int valid_rows = 0;
+    int valid_rows = 0;                                  // the device rows < valid_rows hold the generation's L (less than n after an extension failed)
     bool z_valid = false;                                // zenv holds the generation's selected inverse
     int col_pos = -1;                                    // the position whose full column slot 0 of `col` holds; -1: none
     int64_t counters[6] = {0, 0, 0, 0, 0, 0};            // full builds, extensions, rebuilds, selected inverses, full columns, queries served
@@ -83,6 +80,12 @@ velo_graph_params graph_params(const velo_graph_params* params) {     // a call'
     return params ? *params : p;
 }
 
+int64_t graph_work_cap(const velo_graph_params* params) {            // a call's cap on the envelope solver's work
+    return params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
+}
+
+bool graph_has_pose(const GraphStore& S, int64_t frame) { return (size_t)frame < S.pose_set.size() && S.pose_set[(size_t)frame]; }
+
 struct GraphCall {
     GraphArgs A;
     GraphWeights W = {nullptr, nullptr, nullptr};        // of a weighted store
@@ -111,6 +114,21 @@ void graph_env_ints(size_t n, const int32_t* perm, const int32_t* first, std::ve
     for (size_t k = 0; k < n; k++) { pos[(size_t)perm[k]] = (int32_t)k; rowptr[k + 1] = rowptr[k] + ((int32_t)k - first[k] + 1); last[k] = (int32_t)k; }
     for (size_t k = 0; k < n; k++) last[(size_t)first[k]] = std::max(last[(size_t)first[k]], (int32_t)k);
     for (size_t k = 1; k < n; k++) last[k] = std::max(last[k], last[k - 1]);      // the last row whose first column is <= k
+}
+
+// that layout on the device, and the skyline it indexes, as a kernel's arguments
+void graph_env_bind(GraphArgs* A, const int* idx, size_t n, double* env) {
+    A->env_perm = idx; A->env_pos = idx + n; A->env_first = idx + 2 * n; A->env_rowptr = idx + 3 * n; A->env_last = idx + 4 * n + 1;
+    A->env = env;
+}
+
+// what an order may not exceed, refused before anything is sent; advice: what the entry's caller can do about the cap
+int graph_env_refusal(const char* who, const int64_t* stats, int64_t max_work, size_t n, const char* advice) {
+    if (stats[2] > max_work)
+        return fail(VELO_ERR_INVALID, "%s: the envelope solver's work is %lld block products, over the cap of %lld (widest row %lld blocks, %lld free nodes); %s",
+                    who, (long long)stats[2], (long long)max_work, (long long)stats[0], (long long)n, advice);
+    if (stats[1] > (int64_t)1 << 30) return fail(VELO_ERR_INVALID, "%s: an envelope of %lld blocks; at most 2^30", who, (long long)stats[1]);
+    return VELO_OK;
 }
 
 // velo_graph_order's rule (include/velo_hip.h), on checked arguments
@@ -277,11 +295,11 @@ int graph_check(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
     VELO_TRY(graph_need_store(c, who));
     const GraphStore& S = *c->graph;
     for (int i = 0; i < n_fixed; i++)
-        if ((size_t)fixed[i] >= S.pose_set.size() || !S.pose_set[(size_t)fixed[i]]) return fail(VELO_ERR_STATE, "%s: fixed frame %d has no pose: velo_graph_set_pose", who, fixed[i]);
+        if (!graph_has_pose(S, fixed[i])) return fail(VELO_ERR_STATE, "%s: fixed frame %d has no pose: velo_graph_set_pose", who, fixed[i]);
     for (size_t e = 0; e < S.n_edges; e++) {
         const int32_t ends[2] = {S.h_from[e], S.h_to[e]};
         for (int k = 0; k < 2; k++)
-            if ((size_t)ends[k] >= S.pose_set.size() || !S.pose_set[(size_t)ends[k]]) return fail(VELO_ERR_STATE, "%s: edge %zu ends at frame %d, which has no pose", who, e, ends[k]);
+            if (!graph_has_pose(S, ends[k])) return fail(VELO_ERR_STATE, "%s: edge %zu ends at frame %d, which has no pose", who, e, ends[k]);
     }
     return VELO_OK;
 }
@@ -334,10 +352,7 @@ int graph_begin(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
             if (sf >= 0 && st >= 0) { ea.push_back(sf); eb.push_back(st); }
         }
         graph_order((int32_t)n, (int32_t)ea.size(), ea.data(), eb.data(), perm.data(), first.data(), call->env_stats);
-        if (call->env_stats[2] > call->max_work)
-            return fail(VELO_ERR_INVALID, "%s: the envelope solver's work is %lld block products, over the cap of %lld (widest row %lld blocks, %lld free nodes); "
-                        "raise reserved[1] or use the CG solver", call->who, (long long)call->env_stats[2], (long long)call->max_work, (long long)call->env_stats[0], (long long)n);
-        if (call->env_stats[1] > (int64_t)1 << 30) return fail(VELO_ERR_INVALID, "%s: an envelope of %lld blocks; at most 2^30", call->who, (long long)call->env_stats[1]);
+        VELO_TRY(graph_env_refusal(call->who, call->env_stats, call->max_work, n, "raise reserved[1] or use the CG solver"));
         graph_env_ints(n, perm.data(), first.data(), &env_ints);
     }
     const int nb = std::max(1, cdiv((int)n, kGrThreads));
@@ -398,10 +413,7 @@ int graph_begin(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_g
     A.part_rho0 = S.part.p; A.part_rho = S.part.p + nb; A.part_sigma = S.part.p + 3 * (size_t)nb;
     A.nterm = S.nterm.p; A.rec = S.rec.p;
     A.E = (int)E; A.n_free = (int)n; A.nb = nb;
-    if (!env_ints.empty()) {
-        A.env_perm = S.env_idx.p; A.env_pos = S.env_idx.p + n; A.env_first = S.env_idx.p + 2 * n; A.env_rowptr = S.env_idx.p + 3 * n;
-        A.env_last = S.env_idx.p + 4 * n + 1; A.env = S.env.p;
-    }
+    if (!env_ints.empty()) graph_env_bind(&A, S.env_idx.p, n, S.env.p);
     if (S.weighted) { call->W.winfo = S.winfo.p; call->W.loss = S.wloss.p; call->W.estat = S.estat.p; }
     A.cg_tol2 = params.cg_tolerance * params.cg_tolerance;
     A.lm = lm_params(c->P);
@@ -431,7 +443,7 @@ int graph_put_poses(velo_ctx* c, int32_t first, int32_t n, const double* poses, 
     HIP_TRY(hipSetDevice(c->device));
     const size_t last = (size_t)first + (size_t)n;
     for (size_t f = (size_t)first; f < last && S.ret.state != 0; f++) {   // a retained factorisation: a frame that has a pose moves, or a new one
-        const bool posed = f < S.pose_set.size() && S.pose_set[f];     // below a retained free frame shifts the free indices: dropped
+        const bool posed = graph_has_pose(S, (int64_t)f);              // below a retained free frame shifts the free indices: dropped
         if (posed || (!S.ret.free_nodes.empty() && (int64_t)f < S.ret.free_nodes.back())) graph_ret_drop(S);
         else graph_ret_behind(S);
     }
@@ -562,9 +574,9 @@ int graph_cov_factor(velo_ctx* c, const GraphArgs& A, int rows) {
 
 // The refusal of a call whose factor met a pivot that is not positive and finite.  Which pivot: the factor of the leading k rows fails exactly
 // when k exceeds the first bad pivot's position, so bisect on k.  A refusal's path only: each probe fills and factors again.
-int graph_cov_refuse(velo_ctx* c, const GraphCall& call, const GraphArgs& A, const char* who) {
+int graph_cov_refuse(velo_ctx* c, const std::vector<int32_t>& free_nodes, const int32_t* perm, const GraphArgs& A, const char* who) {
     GraphStore& S = *c->graph;
-    int lo = 0, hi = call.n_free;
+    int lo = 0, hi = (int)free_nodes.size();
     while (hi - lo > 1) {
         const int mid = lo + (hi - lo) / 2;
         VELO_TRY(graph_cov_factor(c, A, mid));
@@ -573,12 +585,7 @@ int graph_cov_refuse(velo_ctx* c, const GraphCall& call, const GraphArgs& A, con
         if (((const GraphRecord*)S.h_out.p)->bad != 0) hi = mid; else lo = mid;
     }
     return fail(VELO_ERR_INVALID, "%s: J^T J is not positive definite: the factorisation's pivot at frame %d (position %d of the order) is not positive and finite; "
-                "every free node needs edges that determine it", who, call.free_nodes[(size_t)call.env_ints[(size_t)hi - 1]], hi - 1);
-}
-
-int graph_free_index(const GraphCall& call, int32_t frame) {          // -1: a constant
-    const auto it = std::lower_bound(call.free_nodes.begin(), call.free_nodes.end(), frame);
-    return it != call.free_nodes.end() && *it == frame ? (int)(it - call.free_nodes.begin()) : -1;
+                "every free node needs edges that determine it", who, free_nodes[(size_t)perm[(size_t)hi - 1]], hi - 1);
 }
 
 // the cap on a call's column work vectors; what: what a column is solved for, in the refusal's words
@@ -611,8 +618,7 @@ GraphArgs graph_ret_args(const GraphRetained& R) {
     const size_t n = R.free_nodes.size();
     A.x = R.x.p; A.x_stride = R.frames * 6;
     A.scale = R.scale.p; A.n_free = (int)n;
-    A.env_perm = R.idx.p; A.env_pos = R.idx.p + n; A.env_first = R.idx.p + 2 * n; A.env_rowptr = R.idx.p + 3 * n; A.env_last = R.idx.p + 4 * n + 1;
-    A.env = R.env.p;
+    graph_env_bind(&A, R.idx.p, n, R.env.p);
     return A;
 }
 
@@ -631,13 +637,15 @@ int graph_ret_factor(velo_ctx* c, GraphRetained& R, const GraphCall& call, const
     HIP_TRY(hipStreamSynchronize(c->stream));                          // (the last copy out of h_idx is done)
     VELO_TRY(R.h_idx.reserve(sizeof(int32_t) * (ints.size() + 1)));
     std::memcpy(R.h_idx.p, ints.data(), sizeof(int32_t) * ints.size());
+    // INVARIANT: idx, scale and x on the device are the ATTEMPTED generation's from here on, while R.ints and R.free_nodes stay the old one's
+    // until graph_ret_commit.  A failed extension leaves them apart.  That is safe because a state that is behind is never served
+    // (graph_query_open) and every build or extension passes here, uploading all three again before anything reads them.
     HIP_TRY(hipMemcpyAsync(R.idx.p, R.h_idx.p, sizeof(int32_t) * ints.size(), hipMemcpyHostToDevice, c->stream));
     if (n) HIP_TRY(hipMemcpyAsync(R.scale.p, call.A.scale, sizeof(double) * n * 6, hipMemcpyDeviceToDevice, c->stream));
     if (F) HIP_TRY(hipMemcpyAsync(R.x.p, call.A.x, sizeof(double) * F * 6, hipMemcpyDeviceToDevice, c->stream));
     GraphArgs A = call.A;                                              // the system (blk, nd, inc) is the store's, the skyline and its ints are R's
     A.scale = R.scale.p;
-    A.env_perm = R.idx.p; A.env_pos = R.idx.p + n; A.env_first = R.idx.p + 2 * n; A.env_rowptr = R.idx.p + 3 * n; A.env_last = R.idx.p + 4 * n + 1;
-    A.env = R.env.p;
+    graph_env_bind(&A, R.idx.p, n, R.env.p);
     *out = A;
     *bad = false;
     if (n == 0 || p >= (int)n) return VELO_OK;
@@ -711,49 +719,11 @@ int graph_ret_extend(velo_ctx* c, bool* ok) {
     return VELO_OK;
 }
 
-// The retained state a query with this `fixed` set and these params is served from, extended first where it is behind; null: the query
-// runs as it does without one.  call: what the queries read of a GraphCall.
-int graph_ret_serve(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, GraphCall* call, GraphRetained** out) {
-    GraphStore& S = *c->graph;
-    GraphRetained& R = S.ret;
-    *out = nullptr;
-    if (R.state == 0 || R.fixed.size() != (size_t)n_fixed || !std::equal(R.fixed.begin(), R.fixed.end(), fixed)) return VELO_OK;
-    const int64_t cap = params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
-    if (cap < R.max_work) return VELO_OK;                              // a tighter cap than the state was retained under: the un-retained path decides
-    HIP_TRY(hipSetDevice(c->device));
-    if (R.state == 2) {
-        bool ok = false;
-        VELO_TRY(graph_ret_extend(c, &ok));
-        if (!ok) return VELO_OK;
-    }
-    call->free_nodes = R.free_nodes;
-    call->env_ints = R.ints;
-    call->n_free = (int)R.free_nodes.size(); call->E = (int)S.n_edges;
-    for (int k = 0; k < 4; k++) call->env_stats[k] = R.stats[k];
-    call->A = graph_ret_args(R);
-    *out = &R;
-    return VELO_OK;
-}
-
-// the selected inverse of the generation, once: enqueued behind a cleared record A.rec
-int graph_ret_selinv(velo_ctx* c, GraphRetained& R, const GraphArgs& A, bool* ran) {
-    *ran = false;
-    if (R.z_valid || A.n_free == 0) return VELO_OK;
-    VELO_TRY(R.zenv.reserve((size_t)R.stats[1] * 36 + 1));
-    GraphCov V;
-    V.zenv = R.zenv.p; V.work = nullptr; V.pair = nullptr; V.out = nullptr; V.n_pairs = 0;
-    hipLaunchKernelGGL(graph_env_selinv_kernel, dim3(1), dim3(kGrEnvSelinvThreads), 0, c->stream, A, V);
-    *ran = true;
-    return VELO_OK;
-}
-
 // Room for nc full columns in R.col, the kept one staying in slot 0.  cols: the positions the call needs; on return cols[0] is the kept
 // column when the call needs it (*first_new = 1: solve the slots from 1 on), otherwise the call's last one (*first_new = 0).  remap:
-// the slot of each entry of the caller's numbering.
+// the slot of each entry of the caller's numbering, the identity on entry.
 int graph_ret_columns(velo_ctx* c, GraphRetained& R, std::vector<int32_t>& cols, std::vector<int32_t>* remap, int* first_new) {
     const size_t nc = cols.size(), n = R.free_nodes.size();
-    remap->resize(nc);
-    for (size_t k = 0; k < nc; k++) (*remap)[k] = (int32_t)k;
     *first_new = 0;
     if (nc == 0) return VELO_OK;
     size_t at = nc - 1;
@@ -764,6 +734,117 @@ int graph_ret_columns(velo_ctx* c, GraphRetained& R, std::vector<int32_t>& cols,
         if (*first_new) VELO_TRY(lm_regrow(c, &R.col, n * 36, nc * n * 36 + 1, 0));
         else { R.col_pos = -1; VELO_TRY(R.col.reserve(nc * n * 36 + 1)); }
     }
+    return VELO_OK;
+}
+
+// ---- the factor a query reads: velo_graph_covariance, velo_graph_edge_gate and velo_graph_loop_candidates between their own packing and kernel ----
+// What a query needs of the factorisation and nothing about where it lives.  Two producers (graph_query_open): the retained state, whose
+// ints and free nodes it refers to, or a build for this call in the store's buffers (`built` holds its host side).  As declared it is the
+// factor of no system (n = 0), which is what velo_graph_loop_candidates without sigma asks with.
+struct GraphFactor {
+    GraphArgs A;                                         // over the buffers of either home; rec: the call's record (graph_query_reserve)
+    GraphRetained* kept = nullptr;                       // the retained state, or null: built for this call
+    GraphCall built;
+    size_t n = 0;                                        // free nodes
+    const std::vector<int32_t>* free_nodes = &built.free_nodes;
+    const int32_t *perm = nullptr, *pos = nullptr, *first = nullptr;      // of the order: position -> free index, its inverse, a row's first column
+    const int64_t* stats = built.env_stats;              // widest row, blocks, work, components
+    // from graph_query_reserve on
+    double *zenv = nullptr, *work = nullptr;             // the selected inverse's skyline; the base of the columns' work vectors
+    size_t n_res = 0, n_full = 0;                        // doubles of the record and the results; full columns the call needs
+    int first_new = 0, col_pos = -1;                     // the slot from which they are solved (those before are held); the position of slot 0's
+    bool run_selinv = false;                             // (retained) the generation's selected inverse is not there yet
+    GraphFactor() { std::memset(&A, 0, sizeof(A)); }
+    GraphFactor(const GraphFactor&) = delete;            // (it points into itself)
+    int free_index(int32_t frame) const {                // -1: a constant
+        const auto it = std::lower_bound(free_nodes->begin(), free_nodes->end(), frame);
+        return it != free_nodes->end() && *it == frame ? (int)(it - free_nodes->begin()) : -1;
+    }
+    // the block of two free nodes lies outside the envelope: Z does not hold it, a column solve does
+    bool outside(int32_t ia, int32_t ib) const { return first[(size_t)std::max(pos[(size_t)ia], pos[(size_t)ib])] > std::min(pos[(size_t)ia], pos[(size_t)ib]); }
+};
+
+// Open: the retained state where it is of this `fixed` set and no tighter cap is asked (a tighter one: the per-call path decides), extended
+// first where it is behind -- a state that stays behind is never served; otherwise graph_begin's system and order for this call.
+int graph_query_open(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const velo_graph_params* params, const char* who, GraphFactor* Q) {
+    GraphRetained& R = c->graph->ret;
+    const int64_t cap = graph_work_cap(params);
+    bool serve = R.state != 0 && R.fixed.size() == (size_t)n_fixed && std::equal(R.fixed.begin(), R.fixed.end(), fixed) && cap >= R.max_work;
+    if (serve) {
+        HIP_TRY(hipSetDevice(c->device));
+        if (R.state == 2) VELO_TRY(graph_ret_extend(c, &serve));
+    }
+    const int32_t* ints = R.ints.data();
+    if (serve) { Q->kept = &R; Q->A = graph_ret_args(R); Q->free_nodes = &R.free_nodes; Q->stats = R.stats; }
+    else {
+        Q->built.envelope = true; Q->built.who = who; Q->built.max_work = cap;
+        VELO_TRY(graph_begin(c, fixed, n_fixed, graph_params(nullptr), &Q->built));
+        Q->A = Q->built.A;
+        ints = Q->built.env_ints.data();
+    }
+    Q->n = Q->free_nodes->size();
+    Q->perm = ints; Q->pos = ints + Q->n; Q->first = ints + 2 * Q->n;
+    return VELO_OK;
+}
+
+// Plan and reserve: the call's record with n_res - kGraphRecDoubles results behind it (one copy to the host), the selected inverse, the
+// columns.  cols: the positions of the full columns the call needs -- the retained state's own, the kept one staying in slot 0 (remap: the
+// slot of each entry of the caller's numbering) -- or null: n_pair pair columns, which are the store's on either path.
+int graph_query_reserve(velo_ctx* c, GraphFactor* Q, const char* who, const char* what, size_t n_res, size_t n_pair, std::vector<int32_t>* cols, std::vector<int32_t>* remap) {
+    GraphStore& S = *c->graph;
+    const size_t n = Q->n, nc = cols ? cols->size() : n_pair;
+    VELO_TRY(graph_column_cap(c, who, what, nc, n));
+    if (cols) { remap->resize(nc); for (size_t k = 0; k < nc; k++) (*remap)[k] = (int32_t)k; }
+    if (cols && Q->kept) VELO_TRY(graph_ret_columns(c, *Q->kept, *cols, remap, &Q->first_new));
+    else if (n) VELO_TRY(S.cov_work.reserve(nc * n * 36 + 1));
+    Q->work = cols && Q->kept ? Q->kept->col.p : S.cov_work.p;
+    if (cols && nc) { Q->n_full = nc; Q->col_pos = (*cols)[0]; }
+    if (Q->kept) {
+        Q->run_selinv = !Q->kept->z_valid && n != 0;
+        if (Q->run_selinv) VELO_TRY(Q->kept->zenv.reserve((size_t)Q->stats[1] * 36 + 1));
+    } else if (n) VELO_TRY(S.cov_z.reserve((size_t)Q->stats[1] * 36));
+    Q->zenv = Q->kept ? Q->kept->zenv.p : S.cov_z.p;
+    VELO_TRY(S.cov_out.reserve(n_res));
+    VELO_TRY(S.h_out.reserve(sizeof(double) * n_res + 64));
+    Q->A.rec = (GraphRecord*)S.cov_out.p;
+    Q->n_res = n_res;
+    return VELO_OK;
+}
+
+// Enqueue the factor side behind a cleared record: the selected inverse, once per generation, or the fill, the factor and the selected
+// inverse; then the full columns the state does not hold (full; null: the caller solves its own kind).  pairs: velo_graph_covariance's,
+// which its per-call selected inverse is launched with (the kernel reads zenv alone).
+int graph_query_enqueue(velo_ctx* c, const GraphFactor& Q, const GraphCov* pairs, const GraphRel* full) {
+    GraphCov Z;
+    Z.zenv = Q.zenv; Z.work = nullptr; Z.pair = nullptr; Z.out = nullptr; Z.n_pairs = 0;
+    HIP_TRY(hipMemsetAsync(Q.A.rec, 0, sizeof(GraphRecord), c->stream));
+    if (Q.kept) {
+        if (Q.run_selinv) hipLaunchKernelGGL(graph_env_selinv_kernel, dim3(1), dim3(kGrEnvSelinvThreads), 0, c->stream, Q.A, Z);
+    } else if (Q.n) {
+        VELO_TRY(graph_cov_factor(c, Q.A, (int)Q.n));
+        hipLaunchKernelGGL(graph_env_selinv_kernel, dim3(1), dim3(kGrEnvSelinvThreads), 0, c->stream, Q.A, pairs ? *pairs : Z);
+    }
+    if (full && Q.n_full > (size_t)Q.first_new) {
+        GraphRel R = *full;
+        R.work += (size_t)Q.first_new * Q.n * 36; R.col_pos += Q.first_new;
+        hipLaunchKernelGGL(graph_env_column_full_kernel, dim3((unsigned)(Q.n_full - (size_t)Q.first_new)), dim3(kGrEnvColumnThreads), 0, c->stream, Q.A, R);
+    }
+    return VELO_OK;
+}
+
+// Finish: the record and the results to S.h_out, the synchronisation, and what the call leaves behind -- on the retained state the selected
+// inverse, the column in slot 0 and the counters; of a build for this call the refusal of a pivot that was not positive and finite.
+int graph_query_finish(velo_ctx* c, const GraphFactor& Q, const char* who) {
+    GraphStore& S = *c->graph;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(S.h_out.p, S.cov_out.p, sizeof(double) * Q.n_res, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (Q.kept) {
+        GraphRetained& R = *Q.kept;
+        R.z_valid = R.z_valid || Q.run_selinv; R.counters[3] += Q.run_selinv; R.counters[5]++;
+        R.counters[4] += (int64_t)Q.n_full - Q.first_new;
+        if (Q.n_full) R.col_pos = Q.col_pos;
+    } else if (((const GraphRecord*)S.h_out.p)->bad != 0) return graph_cov_refuse(c, *Q.free_nodes, Q.perm, Q.A, who);
     return VELO_OK;
 }
 
@@ -841,7 +922,7 @@ int velo_graph_edge_stats(velo_ctx* c, int32_t first, int32_t n, double* chi2, d
     for (size_t e = (size_t)first; e < (size_t)first + (size_t)n; e++) {
         const int32_t ends[2] = {S.h_from[e], S.h_to[e]};
         for (int k = 0; k < 2; k++)
-            if ((size_t)ends[k] >= S.pose_set.size() || !S.pose_set[(size_t)ends[k]]) return fail(VELO_ERR_STATE, "velo_graph_edge_stats: edge %zu ends at frame %d, which has no pose", e, ends[k]);
+            if (!graph_has_pose(S, ends[k])) return fail(VELO_ERR_STATE, "velo_graph_edge_stats: edge %zu ends at frame %d, which has no pose", e, ends[k]);
     }
     if (n == 0) return VELO_OK;
     HIP_TRY(hipSetDevice(c->device));
@@ -913,7 +994,7 @@ int velo_graph_get_poses(velo_ctx* c, int32_t first, int32_t n, double* out) {
     VELO_TRY(graph_need_store(c, "velo_graph_get_poses"));
     const GraphStore& S = *c->graph;
     for (int64_t f = first; f < (int64_t)first + n; f++)
-        if ((size_t)f >= S.pose_set.size() || !S.pose_set[(size_t)f]) return fail(VELO_ERR_STATE, "velo_graph_get_poses: frame %lld has no pose", (long long)f);
+        if (!graph_has_pose(S, f)) return fail(VELO_ERR_STATE, "velo_graph_get_poses: frame %lld has no pose", (long long)f);
     if (n > 0) std::memcpy(out, S.h_x.p + (size_t)first * 6, sizeof(double) * 6 * (size_t)n);
     return VELO_OK;
 }
@@ -967,7 +1048,7 @@ int velo_graph_retain(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const 
     if (perm && n_perm < 0) return fail(VELO_ERR_INVALID, "%s: negative n_perm", who);
     GraphStore& S = *c->graph;
     GraphRetained& R = S.ret;
-    const int64_t max_work = params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
+    const int64_t max_work = graph_work_cap(params);
     HIP_TRY(hipSetDevice(c->device));
     const bool same = R.state != 0 && R.max_work == max_work && R.fixed.size() == (size_t)n_fixed && std::equal(R.fixed.begin(), R.fixed.end(), fixed);
     if (!perm && same && R.state == 1) return VELO_OK;                 // retained and current
@@ -999,20 +1080,14 @@ int velo_graph_retain(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, const 
         }
     } else if (!graph_order_extend(0, nullptr, (int32_t)n, (int32_t)ea.size(), ea.data(), eb.data(), 0, max_work, order.data(), first.data(), st))
         status = fail(VELO_ERR_STATE, "%s: the order's rule failed", who);
-    if (status == VELO_OK && st[2] > max_work)
-        status = fail(VELO_ERR_INVALID, "%s: the envelope solver's work is %lld block products, over the cap of %lld (widest row %lld blocks, %lld free nodes); raise reserved[1]",
-                      who, (long long)st[2], (long long)max_work, (long long)st[0], (long long)n);
-    if (status == VELO_OK && st[1] > (int64_t)1 << 30) status = fail(VELO_ERR_INVALID, "%s: an envelope of %lld blocks; at most 2^30", who, (long long)st[1]);
+    if (status == VELO_OK) status = graph_env_refusal(who, st, max_work, n, "raise reserved[1]");
     if (status != VELO_OK) { (void)hipStreamSynchronize(c->stream); return status; }      // (refused on the host: a state retained before stays)
     graph_ret_drop(S);                                                 // the buffers are written from here on
     graph_env_ints(n, order.data(), first.data(), &ints);
     bool bad = false;
     GraphArgs A;
     VELO_TRY(graph_ret_factor(c, R, call, ints, st[1], -1, 0, &bad, &A));
-    if (bad) {
-        call.env_ints = ints;
-        return graph_cov_refuse(c, call, A, who);
-    }
+    if (bad) return graph_cov_refuse(c, call.free_nodes, ints.data(), A, who);
     R.fixed.assign(fixed, fixed + n_fixed);
     R.max_work = max_work;
     graph_ret_commit(S, R, call, ints, st);
@@ -1075,69 +1150,33 @@ int velo_graph_covariance(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, co
         const int32_t ends[2] = {frame_a[p], frame_b[p]};
         for (int k = 0; k < 2; k++) {
             VELO_TRY(check_frame(ends[k], who, p));
-            if ((size_t)ends[k] >= S.pose_set.size() || !S.pose_set[(size_t)ends[k]]) return fail(VELO_ERR_STATE, "%s: pair %d names frame %d, which has no pose", who, p, ends[k]);
+            if (!graph_has_pose(S, ends[k])) return fail(VELO_ERR_STATE, "%s: pair %d names frame %d, which has no pose", who, p, ends[k]);
         }
     }
     if (n_pairs == 0) return VELO_OK;
-    GraphCall call;
-    call.envelope = true;
-    call.who = who;
-    call.max_work = params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
-    GraphRetained* kept = nullptr;                                     // a retained factorisation of this problem: no order, no fill, no factor
-    VELO_TRY(graph_ret_serve(c, fixed, n_fixed, params, &call, &kept));
-    if (!kept) VELO_TRY(graph_begin(c, fixed, n_fixed, graph_params(nullptr), &call));
-    const size_t n = (size_t)call.n_free, np = (size_t)n_pairs;
+    GraphFactor Q;
+    VELO_TRY(graph_query_open(c, fixed, n_fixed, params, who, &Q));
+    const size_t np = (size_t)n_pairs;
     // per pair: the free indices of its ends (-1: a constant) and, for a pair outside the envelope, the slot of its column solve
-    const int32_t* pos = call.env_ints.data() + n;
-    const int32_t* first = call.env_ints.data() + 2 * n;
     std::vector<int32_t> pr(3 * np);
     size_t n_out = 0;
     for (size_t p = 0; p < np; p++) {
-        const int32_t idx[2] = {graph_free_index(call, frame_a[p]), graph_free_index(call, frame_b[p])};
-        int32_t slot = -1;
-        if (idx[0] >= 0 && idx[1] >= 0) {
-            const int32_t pa = pos[(size_t)idx[0]], pb = pos[(size_t)idx[1]], hi = std::max(pa, pb), lo = std::min(pa, pb);
-            if (first[(size_t)hi] > lo) slot = (int32_t)n_out++;
-        }
-        pr[3 * p] = idx[0]; pr[3 * p + 1] = idx[1]; pr[3 * p + 2] = slot;
+        const int32_t ia = Q.free_index(frame_a[p]), ib = Q.free_index(frame_b[p]);
+        pr[3 * p] = ia; pr[3 * p + 1] = ib; pr[3 * p + 2] = ia >= 0 && ib >= 0 && Q.outside(ia, ib) ? (int32_t)n_out++ : -1;
     }
-    VELO_TRY(graph_column_cap(c, who, "pairs outside the envelope", n_out, n));
-    constexpr size_t kRec = kGraphRecDoubles;
-    VELO_TRY(S.cov_out.reserve(kRec + 36 * np));
+    VELO_TRY(graph_query_reserve(c, &Q, who, "pairs outside the envelope", kGraphRecDoubles + 36 * np, n_out, nullptr, nullptr));
     VELO_TRY(S.cov_pair.reserve(3 * np));
-    VELO_TRY(S.h_out.reserve(sizeof(double) * (kRec + 36 * np) + 64));
-    if (n) {
-        if (!kept) VELO_TRY(S.cov_z.reserve((size_t)call.env_stats[1] * 36));
-        VELO_TRY(S.cov_work.reserve(n_out * n * 36 + 1));
-    }
     VELO_TRY(S.in_ev.wait_or_create());
     VELO_TRY(S.h_in.reserve(sizeof(int32_t) * 3 * np));
     std::memcpy(S.h_in.p, pr.data(), sizeof(int32_t) * 3 * np);
     HIP_TRY(hipMemcpyAsync(S.cov_pair.p, S.h_in.p, sizeof(int32_t) * 3 * np, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipEventRecord(S.in_ev, c->stream));
-    GraphArgs A = call.A;
-    A.rec = (GraphRecord*)S.cov_out.p;                                 // this call's record, the blocks behind it
     GraphCov V;
-    V.zenv = S.cov_z.p; V.work = S.cov_work.p; V.pair = S.cov_pair.p; V.out = S.cov_out.p + kRec; V.n_pairs = n_pairs;
-    HIP_TRY(hipMemsetAsync(A.rec, 0, sizeof(GraphRecord), c->stream));
-    bool ran_selinv = false;
-    if (kept) {
-        VELO_TRY(graph_ret_selinv(c, *kept, A, &ran_selinv));
-        V.zenv = kept->zenv.p;
-    }
-    if (n) {
-        if (!kept) {
-            VELO_TRY(graph_cov_factor(c, A, (int)n));
-            hipLaunchKernelGGL(graph_env_selinv_kernel, dim3(1), dim3(kGrEnvSelinvThreads), 0, c->stream, A, V);
-        }
-        if (n_out) hipLaunchKernelGGL(graph_env_column_kernel, dim3((unsigned)n_out), dim3(kGrEnvColumnThreads), 0, c->stream, A, V);
-    }
-    hipLaunchKernelGGL(graph_cov_gather_kernel, dim3((unsigned)np), dim3(64), 0, c->stream, A, V);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(S.h_out.p, S.cov_out.p, sizeof(double) * (kRec + 36 * np), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (kept) { kept->z_valid = kept->z_valid || ran_selinv; kept->counters[3] += ran_selinv; kept->counters[5]++; }
-    else if (((const GraphRecord*)S.h_out.p)->bad != 0) return graph_cov_refuse(c, call, A, who);
+    V.zenv = Q.zenv; V.work = Q.work; V.pair = S.cov_pair.p; V.out = S.cov_out.p + kGraphRecDoubles; V.n_pairs = n_pairs;
+    VELO_TRY(graph_query_enqueue(c, Q, &V, nullptr));
+    if (n_out) hipLaunchKernelGGL(graph_env_column_kernel, dim3((unsigned)n_out), dim3(kGrEnvColumnThreads), 0, c->stream, Q.A, V);
+    hipLaunchKernelGGL(graph_cov_gather_kernel, dim3((unsigned)np), dim3(64), 0, c->stream, Q.A, V);
+    VELO_TRY(graph_query_finish(c, Q, who));
     std::memcpy(cov36, S.h_out.p + sizeof(GraphRecord), sizeof(double) * 36 * np);
     return VELO_OK;
 }
@@ -1157,7 +1196,7 @@ int velo_graph_edge_gate(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, con
         if (from[p] == to[p]) return fail(VELO_ERR_INVALID, "%s: pair %d: from == to (%d)", who, p, from[p]);
         const int32_t ends[2] = {from[p], to[p]};
         for (int k = 0; k < 2; k++)
-            if ((size_t)ends[k] >= S.pose_set.size() || !S.pose_set[(size_t)ends[k]]) return fail(VELO_ERR_STATE, "%s: pair %d names frame %d, which has no pose", who, p, ends[k]);
+            if (!graph_has_pose(S, ends[k])) return fail(VELO_ERR_STATE, "%s: pair %d names frame %d, which has no pose", who, p, ends[k]);
         for (int k = 0; z && k < 6; k++) if (!std::isfinite(z[6 * (size_t)p + k])) return fail(VELO_ERR_INVALID, "%s: pair %d: z[%d] is not finite", who, p, k);
         if (info21) {                                                  // as velo_graph_add_edges_weighted validates an edge's
             const double* u = info21 + 21 * (size_t)p;
@@ -1167,49 +1206,26 @@ int velo_graph_edge_gate(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, con
         }
     }
     if (n_pairs == 0) return VELO_OK;
-    GraphCall call;
-    call.envelope = true;
-    call.who = who;
-    call.max_work = params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
-    GraphRetained* kept = nullptr;                                     // as in velo_graph_covariance
-    VELO_TRY(graph_ret_serve(c, fixed, n_fixed, params, &call, &kept));
-    if (!kept) VELO_TRY(graph_begin(c, fixed, n_fixed, graph_params(nullptr), &call));
-    const size_t n = (size_t)call.n_free;
+    GraphFactor Q;
+    VELO_TRY(graph_query_open(c, fixed, n_fixed, params, who, &Q));
     // per pair: its frames, their free indices and, for a pair outside the envelope, the slot of the full column of one end -- `to`'s; the
     // pairs that share that frame share the column
-    const int32_t* pos = call.env_ints.data() + n;
-    const int32_t* first = call.env_ints.data() + 2 * n;
-    std::vector<int32_t> pr(5 * np), col_of(n, -1), cols;
+    std::vector<int32_t> pr(5 * np), col_of(Q.n, -1), cols, remap;
     for (size_t p = 0; p < np; p++) {
-        const int32_t ia = graph_free_index(call, from[p]), ib = graph_free_index(call, to[p]);
+        const int32_t ia = Q.free_index(from[p]), ib = Q.free_index(to[p]);
         int32_t slot = -1;
-        if (ia >= 0 && ib >= 0) {
-            const int32_t pa = pos[(size_t)ia], pb = pos[(size_t)ib], hi = std::max(pa, pb), lo = std::min(pa, pb);
-            if (first[(size_t)hi] > lo) {
-                if (col_of[(size_t)ib] < 0) { col_of[(size_t)ib] = (int32_t)cols.size(); cols.push_back(pb); }
-                slot = col_of[(size_t)ib];
-            }
+        if (ia >= 0 && ib >= 0 && Q.outside(ia, ib)) {
+            if (col_of[(size_t)ib] < 0) { col_of[(size_t)ib] = (int32_t)cols.size(); cols.push_back(Q.pos[(size_t)ib]); }
+            slot = col_of[(size_t)ib];
         }
         int32_t* q = pr.data() + 5 * p;
         q[0] = from[p]; q[1] = to[p]; q[2] = ia; q[3] = ib; q[4] = slot;
     }
-    const size_t nc = cols.size();
-    VELO_TRY(graph_column_cap(c, who, "block columns", nc, n));
-    int first_new = 0;                                                 // a retained state keeps the last full column in slot 0 and does not solve it again
-    if (kept) {
-        std::vector<int32_t> remap;
-        VELO_TRY(graph_ret_columns(c, *kept, cols, &remap, &first_new));
-        for (size_t p = 0; p < np; p++) if (pr[5 * p + 4] >= 0) pr[5 * p + 4] = remap[(size_t)pr[5 * p + 4]];
-    }
-    const size_t n_ints = 5 * np + nc, n_dbl = (z ? 6 * np : 0) + 21 * (info21 ? np : 0), n_res = kGraphRecDoubles + kGrRelOut * np;
-    VELO_TRY(S.cov_out.reserve(n_res));
+    const size_t nc = cols.size(), n_ints = 5 * np + nc, n_dbl = (z ? 6 * np : 0) + 21 * (info21 ? np : 0);
+    VELO_TRY(graph_query_reserve(c, &Q, who, "block columns", kGraphRecDoubles + kGrRelOut * np, 0, &cols, &remap));
+    for (size_t p = 0; p < np; p++) if (pr[5 * p + 4] >= 0) pr[5 * p + 4] = remap[(size_t)pr[5 * p + 4]];      // (a retained state keeps its column in slot 0)
     VELO_TRY(S.rel_i.reserve(n_ints));
     VELO_TRY(S.rel_d.reserve(n_dbl + 1));
-    VELO_TRY(S.h_out.reserve(sizeof(double) * n_res + 64));
-    if (n && !kept) {
-        VELO_TRY(S.cov_z.reserve((size_t)call.env_stats[1] * 36));
-        VELO_TRY(S.cov_work.reserve(nc * n * 36 + 1));
-    }
     VELO_TRY(S.in_ev.wait_or_create());
     VELO_TRY(S.h_in.reserve(sizeof(double) * n_dbl + sizeof(int32_t) * n_ints));
     double* hd = (double*)S.h_in.p;                                    // z, then L, then the ints
@@ -1221,38 +1237,13 @@ int velo_graph_edge_gate(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, con
     if (n_dbl) HIP_TRY(hipMemcpyAsync(S.rel_d.p, hd, sizeof(double) * n_dbl, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(S.rel_i.p, hi, sizeof(int32_t) * n_ints, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipEventRecord(S.in_ev, c->stream));
-    GraphArgs A = call.A;
-    A.rec = (GraphRecord*)S.cov_out.p;                                 // this call's record, the pairs' results behind it
-    GraphCov V;
-    V.zenv = S.cov_z.p; V.work = nullptr; V.pair = nullptr; V.out = nullptr; V.n_pairs = 0;
     GraphRel R;
-    R.zenv = S.cov_z.p; R.work = S.cov_work.p; R.col_pos = S.rel_i.p + 5 * np; R.pair = S.rel_i.p;
+    R.zenv = Q.zenv; R.work = Q.work; R.col_pos = S.rel_i.p + 5 * np; R.pair = S.rel_i.p;
     R.z = z ? S.rel_d.p : nullptr; R.linfo = info21 ? S.rel_d.p + (z ? 6 * np : 0) : nullptr;
     R.out = S.cov_out.p + kGraphRecDoubles; R.n_pairs = n_pairs;
-    HIP_TRY(hipMemsetAsync(A.rec, 0, sizeof(GraphRecord), c->stream));
-    bool ran_selinv = false;
-    if (kept) {
-        VELO_TRY(graph_ret_selinv(c, *kept, A, &ran_selinv));
-        R.zenv = kept->zenv.p; R.work = kept->col.p;
-        if (nc > (size_t)first_new) {                                  // the columns the state does not hold
-            GraphRel R2 = R;
-            R2.work += (size_t)first_new * n * 36; R2.col_pos += first_new;
-            hipLaunchKernelGGL(graph_env_column_full_kernel, dim3((unsigned)(nc - (size_t)first_new)), dim3(kGrEnvColumnThreads), 0, c->stream, A, R2);
-        }
-    } else if (n) {
-        VELO_TRY(graph_cov_factor(c, A, (int)n));
-        hipLaunchKernelGGL(graph_env_selinv_kernel, dim3(1), dim3(kGrEnvSelinvThreads), 0, c->stream, A, V);
-        if (nc) hipLaunchKernelGGL(graph_env_column_full_kernel, dim3((unsigned)nc), dim3(kGrEnvColumnThreads), 0, c->stream, A, R);
-    }
-    hipLaunchKernelGGL(graph_relcov_kernel, dim3((unsigned)np), dim3(64), 0, c->stream, A, R);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(S.h_out.p, S.cov_out.p, sizeof(double) * n_res, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (kept) {
-        kept->z_valid = kept->z_valid || ran_selinv; kept->counters[3] += ran_selinv; kept->counters[5]++;
-        kept->counters[4] += (int64_t)nc - first_new;
-        if (nc) kept->col_pos = cols[0];
-    } else if (((const GraphRecord*)S.h_out.p)->bad != 0) return graph_cov_refuse(c, call, A, who);
+    VELO_TRY(graph_query_enqueue(c, Q, nullptr, &R));
+    hipLaunchKernelGGL(graph_relcov_kernel, dim3((unsigned)np), dim3(64), 0, c->stream, Q.A, R);
+    VELO_TRY(graph_query_finish(c, Q, who));
     const double* res = (const double*)S.h_out.p + kGraphRecDoubles;
     for (size_t p = 0; p < np; p++) {
         const double* o = res + kGrRelOut * p;
@@ -1275,87 +1266,46 @@ int velo_graph_loop_candidates(velo_ctx* c, const int32_t* fixed, int32_t n_fixe
     if (capacity < 0) return fail(VELO_ERR_INVALID, "%s: negative capacity", who);
     if (!n_found) return fail(VELO_ERR_INVALID, "%s: null n_found", who);
     GraphStore& S = *c->graph;
-    if ((size_t)query >= S.pose_set.size() || !S.pose_set[(size_t)query]) return fail(VELO_ERR_STATE, "%s: the query frame %d has no pose", who, query);
+    if (!graph_has_pose(S, query)) return fail(VELO_ERR_STATE, "%s: the query frame %d has no pose", who, query);
     const size_t F = S.frame_cap;
     const bool with_sigma = k_sigma > 0.0;
-    GraphCall call;
-    GraphArgs A;
-    GraphRetained* kept = nullptr;
-    std::memset(&A, 0, sizeof(A));
-    if (with_sigma) {
-        call.envelope = true;
-        call.who = who;
-        call.max_work = params && params->reserved[1] > 0 ? params->reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
-        VELO_TRY(graph_ret_serve(c, fixed, n_fixed, params, &call, &kept));      // as in velo_graph_covariance
-        if (!kept) VELO_TRY(graph_begin(c, fixed, n_fixed, graph_params(nullptr), &call));
-        A = call.A;
-    } else {                                                           // distances alone: the stored poses to buffer 0, no system
+    GraphFactor Q;
+    if (with_sigma) VELO_TRY(graph_query_open(c, fixed, n_fixed, params, who, &Q));
+    else {                                                             // distances alone: the stored poses to buffer 0, no system
         HIP_TRY(hipSetDevice(c->device));
         VELO_TRY(S.x.reserve(2 * F * 6 + 1));
         HIP_TRY(hipMemcpyAsync(S.x.p, S.h_x.p, sizeof(double) * F * 6, hipMemcpyHostToDevice, c->stream));
-        A.x = S.x.p; A.x_stride = F * 6;
+        Q.A.x = S.x.p; Q.A.x_stride = F * 6;
     }
-    const size_t n = (size_t)call.n_free;
     // per frame: -2 = no pose, -1 = a constant, otherwise the free index; without sigma only `no pose` matters
     std::vector<int32_t> slot(F, -2);
     for (size_t f = 0; f < F; f++) if (S.pose_set[f]) slot[f] = -1;
-    for (size_t i = 0; i < n; i++) slot[(size_t)call.free_nodes[i]] = (int32_t)i;
+    for (size_t i = 0; i < Q.n; i++) slot[(size_t)(*Q.free_nodes)[i]] = (int32_t)i;
     const int32_t iq = with_sigma ? slot[(size_t)query] : -1;
-    const size_t nc = iq >= 0 ? 1 : 0;
-    VELO_TRY(graph_column_cap(c, who, "block columns", nc, n));
-    const size_t cap = std::min((size_t)capacity, F), n_res = kGraphRecDoubles + 1 + 3 * cap;
-    VELO_TRY(S.cov_out.reserve(n_res));
+    std::vector<int32_t> cols(iq >= 0 ? 1 : 0, iq >= 0 ? Q.pos[(size_t)iq] : 0), remap;      // the query's full column
+    const size_t cap = std::min((size_t)capacity, F);
+    VELO_TRY(graph_query_reserve(c, &Q, who, "block columns", kGraphRecDoubles + 1 + 3 * cap, 0, &cols, &remap));
     VELO_TRY(S.rel_i.reserve(2 * F + 1));
     VELO_TRY(S.rel_d.reserve(2 * F + 1));
-    VELO_TRY(S.h_out.reserve(sizeof(double) * n_res + 64));
-    int first_new = 0;
-    if (kept) {
-        std::vector<int32_t> cols(nc, nc ? call.env_ints[n + (size_t)iq] : 0), remap;
-        VELO_TRY(graph_ret_columns(c, *kept, cols, &remap, &first_new));
-    } else if (n) {
-        VELO_TRY(S.cov_z.reserve((size_t)call.env_stats[1] * 36));
-        VELO_TRY(S.cov_work.reserve(nc * n * 36 + 1));
-    }
     VELO_TRY(S.in_ev.wait_or_create());
     VELO_TRY(S.h_in.reserve(sizeof(int32_t) * (F + 1)));
     int32_t* hi = (int32_t*)S.h_in.p;                                  // the slots, then the position of the query's column
     std::memcpy(hi, slot.data(), sizeof(int32_t) * F);
-    hi[F] = nc ? call.env_ints[n + (size_t)iq] : 0;
+    hi[F] = cols.empty() ? 0 : cols[0];
     HIP_TRY(hipMemcpyAsync(S.rel_i.p, hi, sizeof(int32_t) * (F + 1), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipEventRecord(S.in_ev, c->stream));
-    A.rec = (GraphRecord*)S.cov_out.p;
-    GraphCov V;
-    V.zenv = S.cov_z.p; V.work = nullptr; V.pair = nullptr; V.out = nullptr; V.n_pairs = 0;
     GraphRel R;
     std::memset(&R, 0, sizeof(R));
-    R.zenv = S.cov_z.p; R.work = S.cov_work.p; R.col_pos = S.rel_i.p + F;
+    R.zenv = Q.zenv; R.work = Q.work; R.col_pos = S.rel_i.p + F;
     GraphCand K;
-    K.zenv = S.cov_z.p; K.work = S.cov_work.p; K.slot = S.rel_i.p; K.flag = S.rel_i.p + F + 1; K.rec = S.rel_d.p;
+    K.zenv = Q.zenv; K.work = Q.work; K.slot = S.rel_i.p; K.flag = S.rel_i.p + F + 1; K.rec = S.rel_d.p;
     K.out = S.cov_out.p + kGraphRecDoubles;
     K.n_frames = (int)F; K.query = query; K.min_gap = min_gap; K.capacity = (int)cap; K.with_sigma = with_sigma ? 1 : 0;
     K.radius = radius; K.k_sigma = k_sigma;
-    HIP_TRY(hipMemsetAsync(A.rec, 0, sizeof(GraphRecord), c->stream));
-    bool ran_selinv = false;
-    if (kept) {
-        VELO_TRY(graph_ret_selinv(c, *kept, A, &ran_selinv));
-        R.zenv = kept->zenv.p; R.work = kept->col.p;
-        K.zenv = kept->zenv.p; K.work = kept->col.p;
-        if (nc > (size_t)first_new) hipLaunchKernelGGL(graph_env_column_full_kernel, dim3(1), dim3(kGrEnvColumnThreads), 0, c->stream, A, R);
-    } else if (n) {
-        VELO_TRY(graph_cov_factor(c, A, (int)n));
-        hipLaunchKernelGGL(graph_env_selinv_kernel, dim3(1), dim3(kGrEnvSelinvThreads), 0, c->stream, A, V);
-        if (nc) hipLaunchKernelGGL(graph_env_column_full_kernel, dim3(1), dim3(kGrEnvColumnThreads), 0, c->stream, A, R);
-    }
-    hipLaunchKernelGGL(graph_loop_candidates_kernel, dim3((unsigned)cdiv((int)F, kGrThreads)), dim3(kGrThreads), 0, c->stream, A, K);
+    VELO_TRY(graph_query_enqueue(c, Q, nullptr, &R));
+    hipLaunchKernelGGL(graph_loop_candidates_kernel, dim3((unsigned)cdiv((int)F, kGrThreads)), dim3(kGrThreads), 0, c->stream, Q.A, K);
     hipLaunchKernelGGL(graph_loop_compact_kernel, dim3(1), dim3(kGrCompactThreads), 0, c->stream, K);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(S.h_out.p, S.cov_out.p, sizeof(double) * n_res, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (kept) {
-        kept->z_valid = kept->z_valid || ran_selinv; kept->counters[3] += ran_selinv; kept->counters[5]++;
-        kept->counters[4] += (int64_t)nc - first_new;
-        if (nc) kept->col_pos = call.env_ints[n + (size_t)iq];
-    } else if (((const GraphRecord*)S.h_out.p)->bad != 0) return graph_cov_refuse(c, call, A, who);
+    VELO_TRY(graph_query_finish(c, Q, who));
     const double* res = (const double*)S.h_out.p + kGraphRecDoubles;
     const size_t found = (size_t)res[0];
     for (size_t k = 0; k < std::min(found, cap); k++) {
@@ -1373,7 +1323,7 @@ int velo_graph_optimize(velo_ctx* c, const int32_t* fixed, int32_t n_fixed, cons
     const velo_graph_params P = graph_params(params);
     GraphCall call;
     call.envelope = P.reserved[0] == VELO_GRAPH_SOLVER_ENVELOPE;
-    call.max_work = P.reserved[1] > 0 ? P.reserved[1] : VELO_GRAPH_DEFAULT_MAX_WORK;
+    call.max_work = graph_work_cap(&P);
     VELO_TRY(graph_begin(c, fixed, n_fixed, P, &call));
     graph_ret_drop(S);                                                 // a solve that runs ends a retained factorisation, whatever its outcome
     const GraphArgs& A = call.A;
