@@ -1591,9 +1591,28 @@ __device__ __forceinline__ void accumulate_row(double acc[kNumAcc], double r, co
     for (int i = 0; i < 6; i++) acc[21 + i] += J[i] * rk;
 }
 
-// Workgroup reduction of the 28 accumulators, laid out for latency (the LM chain waits for it): exchanges with the lanes 32 and 16
-// away (2 x 28 independent shuffles), the 16 x 4 partial sums of every accumulator through LDS ([accumulator][64], conflict-free
-// 8-byte stores), eight threads per accumulator add 8 values each, one thread per accumulator adds those eight and stores.
+// The two lane exchanges of the reduction below as gfx950 lane swaps: VALU instructions, where __shfl_xor on a double is two
+// ds_bpermute_b32 on the LDS pipe the association workgroups of the same CU live on.  A swap exchanges halves of TWO registers, so one
+// serves two accumulators: v_permlane32_swap a, b leaves a = (a's lanes 0-31, b's lanes 0-31), b = (a's lanes 32-63, b's lanes 32-63), and
+// a + b holds a[l] + a[l + 32] in lanes 0-31 and b[l - 32] + b[l] in lanes 32-63 -- each the sum the shuffle gave (a two-operand add
+// commutes: same bits).  v_permlane16_swap a, b exchanges a's odd rows of 16 lanes with b's even rows: a + b then holds, row by row,
+// a.row0 + a.row1, b.row0 + b.row1, a.row2 + a.row3, b.row2 + b.row3.
+__device__ __forceinline__ double swap32_add(const double a, const double b) {
+    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
+    return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
+}
+__device__ __forceinline__ double swap16_add(const double a, const double b) {
+    const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
+    return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
+}
+
+// Workgroup reduction of the 28 accumulators, laid out for latency (the LM chain waits for it): the sums over the lanes 32 and 16 apart
+// by lane swaps, four accumulators at a time (21 exchanges of two v_permlane each; afterwards every 16-lane row of a wave holds one accumulator's 16 partial
+// sums: 7 full-wave stores instead of 28 from a quarter of the lanes), the 16 x 4 partial sums of every accumulator through LDS
+// ([accumulator][64], 8-byte stores, each row of lanes to 128 consecutive bytes), eight threads per accumulator add 8 values each, one
+// thread per accumulator adds those eight and stores.
 // Two barriers; 14 KB of LDS, so that a sweep workgroup fits next to four association workgroups.  Fixed order -> deterministic.
 constexpr int kScratchDoubles = 128 * kNumAcc;                    // 28,672 bytes: the sweep's reduction and the step's chunk of partial rows share it
 // Agent-scope accesses for data one workgroup hands to another INSIDE a launch (the partial rows of the fused sweep + step): the
@@ -1611,13 +1630,12 @@ __device__ __forceinline__ void block_reduce_store(double acc[kNumAcc], double* 
     double (*red)[kCols] = reinterpret_cast<double (*)[kCols]>(scratch);
     __shared__ double red2[kNumAcc][8];
     const int t = tid_in < 0 ? (int)threadIdx.x : tid_in, lane = t & 63, wid = t >> 6;
+    static_assert(kNumAcc % 4 == 0, "the lane swaps take the accumulators four at a time");
 #pragma unroll
-    for (int k = 0; k < kNumAcc; k++) acc[k] += __shfl_xor(acc[k], 32);
-#pragma unroll
-    for (int k = 0; k < kNumAcc; k++) acc[k] += __shfl_xor(acc[k], 16);
-    if (lane < 16) {
-#pragma unroll
-        for (int k = 0; k < kNumAcc; k++) red[k][wid * 16 + lane] = acc[k];
+    for (int q = 0; q < kNumAcc / 4; q++) {
+        const double v = swap16_add(swap32_add(acc[4 * q], acc[4 * q + 1]), swap32_add(acc[4 * q + 2], acc[4 * q + 3]));
+        const int row = lane >> 4;                                // rows 0..3 of the wave hold accumulators 4q, 4q + 2, 4q + 1, 4q + 3
+        red[4 * q + ((row & 1) << 1) + (row >> 1)][wid * 16 + (lane & 15)] = v;
     }
     __syncthreads();
     if (t < kNumAcc * 8) {
